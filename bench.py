@@ -19,11 +19,14 @@ of the count table per query (strong scaling); the line then also carries the am
 ONE batch of 100 filter + Mutations / AminoAcidMutations queries with an all-reduce per count table — and the filter
 queries / s on those shards.  At N = 1 configs[4] runs whole on the one GPU.
 
-metric = positions x sequences / s (whole job).  roofline: the dominant kernel of the scan (by HIP events on the stream it
-is launched on): the bytes that launch has to read / its duration, against the 8 TB/s HBM peak and against a measured
-plain stream-read ceiling; the layout-independent algorithmic figure of SURVEY.md section 8(d) beside it.  cpu_baseline:
-oracle/roaring_port.c (the reference's algorithm over roaring-format containers, OpenMP) on a bounded sample of the same
-store, rank 0 / N = 1 only.
+metric = positions x sequences / s (whole job).  A plain run builds the headline database, warms up, times the K steps,
+writes the last step's rows if `--dump-outputs DIR` is given and prints the line: nothing else.  Everything below and the
+side legs described above run only with `--full`.
+
+roofline (`--full`): the dominant kernel of the scan (by HIP events on the stream it is launched on): the bytes that launch
+has to read / its duration, against the 8 TB/s HBM peak and against a measured plain stream-read ceiling; the
+layout-independent algorithmic figure of SURVEY.md section 8(d) beside it.  cpu_baseline (`--full`): oracle/roaring_port.c
+(the reference's algorithm over roaring-format containers, OpenMP) on a bounded sample of the same store, rank 0 / N = 1 only.
 """
 import argparse
 import json
@@ -36,7 +39,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "lapis-silo_amd")]
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak
 QUERY_LINEAGE = "B.1"
 N_LINEAGES = 2000
 
@@ -708,6 +711,32 @@ def run_steps(engine, query, steps, warmup, sync):
     return elapsed, json.loads(body.decode())["queryResult"]
 
 
+def dump_outputs(directory, rows):
+    """The last timed step's response as arrays, one per field of its rows, in the order the engine returned them:
+    count, proportion, position (1-based), from_symbol / to_symbol (nucleotide symbol ids) and sequence (index of the
+    row's sequenceName among the database's nucleotide sequences).  float64, so every count is exact."""
+    import re
+
+    from silo_amd import alphabet
+
+    names = [g["name"] for g in load_reference_genomes(False)["nucleotideSequences"]]
+    parsed = [re.fullmatch(r"(.)([0-9]+)(.)", row["mutation"]) for row in rows]
+    if not all(parsed):
+        raise ValueError("dump-outputs: a mutation is not of the form <from><position><to>")
+    symbol = alphabet.NUCLEOTIDE.char_to_symbol
+    arrays = {
+        "count": [row["count"] for row in rows],
+        "proportion": [row["proportion"] for row in rows],
+        "position": [int(m.group(2)) for m in parsed],
+        "from_symbol": [symbol[m.group(1)] for m in parsed],
+        "to_symbol": [symbol[m.group(3)] for m in parsed],
+        "sequence": [names.index(row["sequenceName"]) for row in rows],
+    }
+    os.makedirs(directory, exist_ok=True)
+    for name, values in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(values, dtype=np.float64))
+
+
 def launch_ranks(n_gpus):
     """Runs this script under `python -m torch.distributed.run --nproc-per-node N` as a child process."""
     import socket
@@ -736,8 +765,13 @@ def main():
                     help="N > 1: the headline database sharded by position range (the north star's split; always measured, it is `value`), "
                          "BASELINE.json configs[4] sharded by sequence id, or both (default)")
     ap.add_argument("--config4-sequences", type=int, default=50_000_000, help="sequences of the configs[4] database (all ranks together)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="the headline measurement only: no further legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the CPU baseline and the side legs (other sizes, queries, layouts, configs[4]); "
+                         "a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the rows of the last timed step to DIR/<field>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full without the side legs: headline, roofline and CPU baseline")
     ap.add_argument("--no-client-threads", action="store_true",
                     help="skip the config-2 filter-query legs (8 / 16 client threads; > 100 000 launches make a kernel trace large)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
@@ -746,6 +780,9 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="use the torch.distributed / RCCL path even with one rank (testing)")
     ap.add_argument("--cpu-positions", type=int, default=0, help="positions in the CPU baseline sample (0 = sized to ~10-30 s of CPU work)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    also = args.full and not args.no_also
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks as CHILD processes (one per GPU, the same launcher the
@@ -852,11 +889,10 @@ def main():
     filter_us, action_us = engine.last_timings()
     ms_per_step = elapsed / args.steps * 1e3
     value = args.sequences * positions / (elapsed / args.steps)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, rows)
 
-    # roofline of the dominant kernel, on this rank's window
     w8 = 8 * ((args.sequences + 63) // 64)
-    kernel_ms, kernel_name, store, filt, counts_dev = time_kernel(engine, tree, window, reps=max(5, args.steps))
-    ceiling = stream_ceiling(lib) if rank == 0 else None
     result = {
         "metric": "Mutations-scan positions*sequences/s",
         "value": value,
@@ -878,11 +914,18 @@ def main():
             "mutation_rows": len(rows),
             "sharding": "none" if not use_dist else f"position-range x{world}, all-reduce of counts[{positions}][5] " + collective,
             "reference_phases_us": {"filter": filter_us, "action": action_us},
+            "database": (f"one database: nucleotide genome + 12 genes + the runs of the missing symbol, "
+                         f"{engine.partition_store(0).device_bytes / 1e9:.1f} GB of HBM" + (" on this rank" if use_dist else " on one GPU")),
         },
-        "roofline": roofline_of(lib, store, window, args.sequences, kernel_ms, ceiling),
     }
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        # roofline of the dominant kernel, on this rank's window
+        kernel_ms, kernel_name, store, filt, counts_dev = time_kernel(engine, tree, window, reps=max(5, args.steps))
+        ceiling = stream_ceiling(lib) if rank == 0 else None
+        result["roofline"] = roofline_of(lib, store, window, args.sequences, kernel_ms, ceiling)
+
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # ~10-30 s of CPU work in all (build + 6 passes): one partition, one 300-position grain per thread
         try:
             result["cpu_baseline"] = cpu_baseline(model, tree, lineage, args.sequences, store, filt, args.cpu_positions)
@@ -903,7 +946,7 @@ def main():
                 total[key] += part[key]
         return total, per_gene
 
-    if not args.no_also:
+    if also:
         # BASELINE.json configs[3], amino-acid leg, on the SAME database (N > 1: on its position shards, one all-reduce per query)
         elapsed_aa, rows_aa = run_steps(engine, aa_query, args.steps, args.warmup, sync)
         elapsed_aa = reduce_max(elapsed_aa)
@@ -920,19 +963,18 @@ def main():
             "physical_GBps_whole_query_this_rank": physical_aa["bytes"] / (elapsed_aa / args.steps) / 1e9,
             "mutation_rows": len(rows_aa),
         }
-        result["config"]["database"] = (f"one database: nucleotide genome + 12 genes + the runs of the missing symbol, "
-                                        f"{engine.partition_store(0).device_bytes / 1e9:.1f} GB of HBM" + (" on this rank" if use_dist else " on one GPU"))
-    if rank == 0 and world == 1 and not use_dist and not args.no_also:
+    if rank == 0 and world == 1 and not use_dist and also:
         if not args.no_client_threads:
             result["filter_queries"] = filter_workload(engine, model, tree, args.sequences, sync)
         result["batched_queries"] = batch_workload(engine, positions, args.sequences, sync)
         result["selective_queries"] = selective_workload(engine, lib, tree, lineage, positions, args.sequences, sync)
-    lib.silo_gpu_free(filt)
-    lib.silo_gpu_free(counts_dev)
+    if args.full:
+        lib.silo_gpu_free(filt)
+        lib.silo_gpu_free(counts_dev)
     engine.close()
 
     reference_text = load_reference_genomes(False)["nucleotideSequences"][0]["sequence"]
-    if not args.no_also and (world == 1 or args.shard in ("both", "sequence")):
+    if also and (world == 1 or args.shard in ("both", "sequence")):
         # BASELINE.json configs[4]: the big database, sharded by sequence id (each rank generates ITS rows), built in two passes
         per_rank = args.config4_sequences // world
         t_build = time.perf_counter()
@@ -970,7 +1012,7 @@ def main():
             }
         engine4.close()
 
-    if rank == 0 and world == 1 and not use_dist and not args.no_also and args.sequences != 1_000_000:
+    if rank == 0 and world == 1 and not use_dist and also and args.sequences != 1_000_000:
         # BASELINE.json configs[1]: 1 M sequences, same query
         engine1, model1, tree1, lineage1, window1 = build_engine(1_000_000, 0, 1, None, local_rank, with_genes=True, with_metadata=True)  # no collective
         elapsed1, rows1 = run_steps(engine1, query, args.steps, args.warmup, sync)

@@ -95,24 +95,34 @@ def test_hundred_query_batch_on_sequence_shards_matches_oracle_gpu(built):
 
 
 @pytest.mark.gpu
-def test_bench_rccl_path_on_one_gpu(built):
+def test_bench_rccl_path_on_one_gpu(built, tmp_path):
     """bench.py --force-dist: the multi-rank code path with ONE rank — gloo for the control plane, the engine's own
     RCCL communicator (silo_gpu_comm_create -> ncclCommInitRank) for the data path: the count table of every query is
     all-reduced by silo_gpu_allreduce_counts (ncclAllReduce, ncclUint32) on the engine's stream, with torch's HIP
-    runtime and RCCL serving the process.  Must give the same rows as the plain single-process run."""
+    runtime and RCCL serving the process.  Must give the same rows as the plain single-process run, whose line is the
+    headline alone (no roofline without --full); --dump-outputs writes the same arrays both ways."""
+    import numpy as np
+
     root = os.path.dirname(HERE)
-    common = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--sequences", "200000", "--steps", "2", "--warmup", "1",
-              "--no-also", "--no-cpu-baseline"]
+    common = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--sequences", "200000", "--steps", "2", "--warmup", "1"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    plain = subprocess.run(common, capture_output=True, text=True, env=env, timeout=900)
+    plain = subprocess.run(common + ["--dump-outputs", str(tmp_path / "plain")], capture_output=True, text=True, env=env, timeout=900)
     assert plain.returncode == 0, plain.stderr[-2000:]
-    forced = subprocess.run(common + ["--force-dist"], capture_output=True, text=True, env=env, timeout=900)
+    forced = subprocess.run(common + ["--full", "--no-also", "--no-cpu-baseline", "--force-dist", "--dump-outputs", str(tmp_path / "forced")],
+                            capture_output=True, text=True, env=env, timeout=900)
     assert forced.returncode == 0, forced.stderr[-2000:]
     # exactly ONE line on stdout, the JSON line — RCCL's version banner and the like go to stderr
     assert len(plain.stdout.strip().splitlines()) == 1 and len(forced.stdout.strip().splitlines()) == 1, forced.stdout[:500]
     a = json.loads(plain.stdout.strip().splitlines()[-1])
     b = json.loads(forced.stdout.strip().splitlines()[-1])
     assert a["config"]["mutation_rows"] == b["config"]["mutation_rows"] > 0
+    assert a["steps"] == 2 and a["ms_per_step"] > 0 and "roofline" not in a and "cpu_baseline" not in a
+    names = ("count", "proportion", "position", "from_symbol", "to_symbol", "sequence")
+    dumped = {side: {name: np.load(tmp_path / side / (name + ".npy")) for name in names} for side in ("plain", "forced")}
+    for name in names:
+        assert dumped["plain"][name].dtype == np.float64 and len(dumped["plain"][name]) == a["config"]["mutation_rows"]
+        assert np.array_equal(dumped["plain"][name], dumped["forced"][name]), name
+    assert (dumped["plain"]["count"] > 0).all() and ((dumped["plain"]["proportion"] > 0) & (dumped["plain"]["proportion"] <= 1)).all()
     assert b["config"]["sharding"].startswith("position-range x1") and "silo_gpu_allreduce_counts" in b["config"]["sharding"]
     assert 0 < b["roofline"]["frac"] <= 1.0  # the dominant launch's bytes / its time / peak: a fraction (small at 200 000 rows)
     assert b["roofline"]["kernel"] in {entry["kernel"] for entry in b["roofline"]["launches_per_scan"]} and b["roofline"]["stream_ceiling_GBps"] > 1000
@@ -192,11 +202,11 @@ def test_bench_two_rank_path_rehearsed_on_one_gpu(built, launcher):
 
 @pytest.mark.gpu
 def test_bench_two_rank_line_carries_every_leg_of_the_metric(built):
-    """`bench.py --gpus 2` without --no-also (rehearsed on one GPU): beside the position-sharded headline the line carries the
+    """`bench.py --gpus 2 --full` without --no-also (rehearsed on one GPU): beside the position-sharded headline the line carries the
     amino-acid leg on the position shards, BASELINE.json configs[4] on sequence-id shards (ONE batch of 200 queries, an
     all-reduce per count table) and the filter queries / s on those shards — the same answers as one rank gives."""
     root = os.path.dirname(HERE)
-    options = ["--sequences", "200000", "--config4-sequences", "300000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    options = ["--sequences", "200000", "--config4-sequences", "300000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for name in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(name, None)

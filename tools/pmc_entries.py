@@ -1,4 +1,4 @@
-"""HBM traffic per launch from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of bench.py, for the launches that bench line
+"""HBM traffic per launch from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of bench.py --full, for the launches that bench line
 lists in roofline.launches_per_scan: entries `kernel@blocks` with `sequences` and `bytes` in profiles/pmc_traffic.json, which
 bench.py reads for roofline.traffic.  Counter handling follows /opt/skills/guides/MI355X_MICROARCH.md (HBM / rocprofv3):
 FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports half of the bytes of a wide coalesced streaming read, so it
@@ -50,7 +50,7 @@ def main():
                  "sequences": sequences, "bytes": launch["bytes"], "plane_rows": launch["plane_rows"], "round": tag}
         doc["kernels"][f"{launch['kernel']}@{launch['blocks']}"] = entry
         rows.append((launch["kernel"], launch["blocks"], launch["bytes"], entry["hbm_bytes"], entry["hbm_read_bytes"], entry["hbm_write_bytes"], launches))
-    doc["source"] = (doc.get("source", "") + f"; {tag}: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of bench.py --no-also "
+    doc["source"] = (doc.get("source", "") + f"; {tag}: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of bench.py --full --no-also "
                      "--no-cpu-baseline --steps 3 --warmup 1 (tools/profile_round3.sh, tools/pmc_entries.py)")
     json.dump(doc, open(path, "w"), indent=1)
     out = [f"# {tag}: HBM traffic per launch of the headline scan (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes)", "",
