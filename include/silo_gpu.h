@@ -442,6 +442,32 @@ int silo_gpu_mutations_scan_ranges(
    uint32_t* const* counts_out_dev, void* stream
 );
 
+/* ---- K7: grouped mutation counts (MutationsOverTime) -------------------------------------------------
+ * For each of n_mutations listed cells (positions[m] 0-based in the store, symbols[m] a VALID mutation symbol id of the
+ * store's alphabet) and each of n_ranges date ranges (range_bounds[2r], range_bounds[2r + 1] = from, to, encoded dates
+ * as in K5, BOTH ends inclusive, 0 / 0xFFFFFFFF where unbounded; pairwise disjoint; rows whose date is NULL (0) fall in no
+ * range), over the rows selected by filter_dev (NULL = all rows) whose date_column_dev value lies in the range:
+ *     out_dev[(m * n_ranges + r) * 2 + 0] += rows whose symbol at positions[m] is symbols[m]            (count)
+ *     out_dev[(m * n_ranges + r) * 2 + 1] += rows with any valid mutation symbol at positions[m]        (coverage)
+ * exactly K1's cell counts[p][s] and its sum over the valid symbols under the filter And(filter, date in range), for every
+ * store layout (identity / code planes with escape keys, one-hot rows with a derived symbol, runs of the missing symbol,
+ * sparse or extra ambiguity planes).  ACCUMULATED into, like K1: partitions add up in one table.
+ * group_scratch_dev: device memory of SILO_GPU_GROUPED_SCRATCH_BYTES(row_words, n_ranges, n_mutations) bytes, 16-byte
+ * aligned; its first row_words * 64 uint16 hold each row's range (0xFFFF = none) after the call.  Uploads its small host
+ * tables and waits for them (one stream synchronisation), then launches K7 on `stream` without waiting.
+ * Fails with SILO_GPU_ERR_INVALID_ARGUMENT for more than SILO_GPU_MAX_DATE_RANGES ranges or SILO_GPU_MAX_GROUPED_MUTATIONS
+ * cells, a position out of bounds, a symbol that is not a valid mutation symbol, from > to, or overlapping ranges. */
+#define SILO_GPU_MAX_DATE_RANGES 1024
+#define SILO_GPU_MAX_GROUPED_MUTATIONS 4096
+#define SILO_GPU_GROUPED_SCRATCH_BYTES(row_words, n_ranges, n_mutations)                                                    \
+   ((size_t)(row_words) * 128u + (size_t)(n_mutations) * 32u + (size_t)(n_ranges) * 16u +                                   \
+    (size_t)(n_ranges) * 4u * (1u + 3u * (size_t)(n_mutations)) + 1024u)
+int silo_gpu_mutations_grouped(
+   const silo_gpu_store* store, uint32_t seqstore_id, const uint64_t* filter_dev, const uint32_t* date_column_dev, const uint32_t* range_bounds,
+   uint32_t n_ranges, const uint32_t* positions, const uint32_t* symbols, uint32_t n_mutations, void* group_scratch_dev, uint32_t* out_dev,
+   void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

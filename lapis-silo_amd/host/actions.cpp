@@ -1,4 +1,4 @@
-// actions.cpp — Action base (ordering / limit / offset), Aggregated (count) and Mutations<SymbolType>.
+// actions.cpp — Action base (ordering / limit / offset), Aggregated (count), Mutations<SymbolType> and MutationsOverTime<SymbolType>.
 // Reference: src/silo/query_engine/actions/{action,aggregated,mutations}.cpp.
 #include <algorithm>
 #include <charconv>
@@ -670,6 +670,167 @@ QueryResult Mutations<SymbolType>::execute(const Database& database, std::vector
 template class Mutations<Nucleotide>;
 template class Mutations<AminoAcid>;
 
+// ---- MutationsOverTime ---------------------------------------------------------------------------------
+namespace {
+const std::string OVER_TIME_FIELDS[] = {"mutation", "sequenceName", "dateFrom", "dateTo", "count", "coverage"};
+}
+
+template <typename SymbolType>
+void MutationsOverTime<SymbolType>::validateOrderByFields(const Database& /*database*/) const {
+   for (const OrderByField& field : order_by_fields) {
+      const bool known = std::find(std::begin(OVER_TIME_FIELDS), std::end(OVER_TIME_FIELDS), field.name) != std::end(OVER_TIME_FIELDS);
+      CHECK_SILO_QUERY(known, "OrderByField " + field.name + " is not contained in the result of this operation.")
+   }
+}
+
+template <typename SymbolType>
+QueryResult MutationsOverTime<SymbolType>::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string action_name = std::is_same_v<SymbolType, Nucleotide> ? "MutationsOverTime" : "AminoAcidMutationsOverTime";
+   CHECK_SILO_QUERY(
+      database.shard_world <= 1, action_name + " is not supported on a sharded database yet: its counts are not all-reduced across ranks"
+   )
+   const std::optional<storage::ColumnMetadata> column = database.database_config.getMetadata(date_field);
+   CHECK_SILO_QUERY(
+      column.has_value() && column->type == config::ColumnType::DATE, "The field dateField of " + action_name + " ('" + date_field + "') is not a date column"
+   )
+
+   // resolve every mutation against its sequence store: the name, the 0-based position, the reference symbol
+   struct Resolved {
+      std::string sequence_name;
+      const SequenceStore<SymbolType>* store;
+      uint32_t position;  // 0-based
+   };
+   std::vector<Resolved> resolved;
+   resolved.reserve(mutations.size());
+   for (const Mutation& mutation : mutations) {
+      const std::string name = mutation.sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+      const auto found = database.getSequenceStores<SymbolType>().find(name);
+      CHECK_SILO_QUERY(
+         found != database.getSequenceStores<SymbolType>().end(),
+         "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + name + "'"
+      )
+      const auto& reference = found->second.reference_sequence;
+      CHECK_SILO_QUERY(
+         mutation.position >= 1 && mutation.position <= reference.size(),
+         "The position " + std::to_string(mutation.position) + " of a mutation of " + action_name + " is outside the sequence '" + name + "' (1 to " +
+            std::to_string(reference.size()) + ")"
+      )
+      const auto reference_symbol = reference[mutation.position - 1];
+      if (mutation.reference_symbol.has_value()) {
+         CHECK_SILO_QUERY(
+            SymbolType::charToSymbol(*mutation.reference_symbol) == reference_symbol,
+            std::string("The reference symbol '") + *mutation.reference_symbol + "' of a mutation of " + action_name + " does not match the reference genome ('" +
+               SymbolType::symbolToChar(reference_symbol) + "' at position " + std::to_string(mutation.position) + " of '" + name + "')"
+         )
+      }
+      resolved.push_back({name, &found->second, mutation.position - 1});
+   }
+
+   // the table: one block of rows per sequence store touched, the store's mutations in request order within it
+   const auto n_ranges = static_cast<uint32_t>(date_ranges.size());
+   std::vector<std::string> store_names;
+   std::vector<std::vector<uint32_t>> members;  // request indices per store
+   for (uint32_t m = 0; m < resolved.size(); ++m) {
+      const auto s = static_cast<size_t>(std::find(store_names.begin(), store_names.end(), resolved[m].sequence_name) - store_names.begin());
+      if (s == store_names.size()) {
+         store_names.push_back(resolved[m].sequence_name);
+         members.emplace_back();
+      }
+      members[s].push_back(m);
+   }
+   std::vector<uint32_t> row_of(resolved.size());  // request index -> row of the table
+   std::vector<uint32_t> first_row(store_names.size());
+   uint32_t rows = 0;
+   for (size_t s = 0; s < store_names.size(); ++s) {
+      first_row[s] = rows;
+      for (const uint32_t m : members[s]) {
+         row_of[m] = rows++;
+      }
+   }
+   std::vector<uint32_t> bounds(2u * n_ranges);
+   for (uint32_t r = 0; r < n_ranges; ++r) {
+      bounds[2u * r] = date_ranges[r].from.value_or(common::Date{1});
+      bounds[2u * r + 1u] = date_ranges[r].to.value_or(common::Date{UINT32_MAX});
+   }
+
+   std::vector<uint32_t> table;
+   const size_t table_words = static_cast<size_t>(rows) * n_ranges * 2u;
+   if (table_words != 0 && !database.partitions.empty()) {
+      DeviceBuffer device_table = database.partitions.front().pool.acquire(table_words * sizeof(uint32_t));
+      std::vector<DeviceBuffer> scratch;  // kept until the table has landed: the launches read them
+      checkGpu(silo_gpu_memset_async(device_table.get(), 0, table_words * sizeof(uint32_t), queryStream()), "silo_gpu_memset_async");
+      HostFetch fetch;
+      try {
+         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+            const DatabasePartition& partition = database.partitions[partition_id];
+            const OperatorResult& filter = bitmap_filter[partition_id];
+            const uint32_t selected = partition.sequence_count == 0 ? 0 : filter.cardinality();
+            if (selected == 0) {
+               continue;
+            }
+            // a filter that selects every row is passed as NULL (no all-ones bitset is made for it)
+            const uint64_t* filter_bits = selected == partition.sequence_count ? nullptr : filter.bitset();
+            const auto* dates = partition.columns.find(date_field, config::ColumnType::DATE);
+            CHECK_SILO_QUERY(dates != nullptr, "The field dateField of " + action_name + " ('" + date_field + "') is not a date column")
+            for (size_t s = 0; s < store_names.size(); ++s) {
+               const SequenceStorePartition<SymbolType>& store = partition.getSequenceStores<SymbolType>().at(store_names[s]);
+               std::vector<uint32_t> positions, symbols;
+               for (const uint32_t m : members[s]) {
+                  positions.push_back(resolved[m].position);
+                  symbols.push_back(static_cast<uint32_t>(mutations[m].symbol));
+               }
+               const auto n = static_cast<uint32_t>(positions.size());
+               scratch.push_back(partition.pool.acquire(SILO_GPU_GROUPED_SCRATCH_BYTES(partition.rowWords(), n_ranges, n)));
+               checkGpu(
+                  silo_gpu_mutations_grouped(
+                     store.store, store.seqstore_id, filter_bits, static_cast<const uint32_t*>(dates->deviceValues()), bounds.data(), n_ranges,
+                     positions.data(), symbols.data(), n, scratch.back().get(), device_table.as<uint32_t>() + static_cast<size_t>(first_row[s]) * n_ranges * 2u,
+                     queryStream()
+                  ),
+                  "silo_gpu_mutations_grouped"
+               );
+            }
+         }
+         fetch = HostFetch(device_table.get(), table_words * sizeof(uint32_t), queryStream());
+         const auto* host = static_cast<const uint32_t*>(fetch.wait());
+         table.assign(host, host + table_words);
+      } catch (...) {
+         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+         (void)silo_gpu_stream_synchronize(queryStream());
+         throw;
+      }
+   }
+
+   std::vector<QueryResultEntry> result_rows;
+   result_rows.reserve(resolved.size() * n_ranges);
+   for (size_t m = 0; m < resolved.size(); ++m) {
+      const char from = SymbolType::symbolToChar(resolved[m].store->reference_sequence.at(resolved[m].position));
+      const std::string name = from + std::to_string(resolved[m].position + 1) + SymbolType::symbolToChar(mutations[m].symbol);
+      for (uint32_t r = 0; r < n_ranges; ++r) {
+         const size_t cell = (static_cast<size_t>(row_of[m]) * n_ranges + r) * 2u;
+         const uint32_t count = table.empty() ? 0u : table[cell];
+         const uint32_t coverage = table.empty() ? 0u : table[cell + 1u];
+         const auto dateText = [](const std::optional<common::Date>& date) -> JsonValue {
+            if (!date.has_value()) {
+               return std::nullopt;
+            }
+            return common::dateToString(*date).value_or("");
+         };
+         QueryResultEntry& entry = result_rows.emplace_back();
+         entry.fields.emplace("count", static_cast<int32_t>(count));
+         entry.fields.emplace("coverage", static_cast<int32_t>(coverage));
+         entry.fields.emplace("dateFrom", dateText(date_ranges[r].from));
+         entry.fields.emplace("dateTo", dateText(date_ranges[r].to));
+         entry.fields.emplace("mutation", name);
+         entry.fields.emplace("sequenceName", resolved[m].sequence_name);
+      }
+   }
+   return QueryResult{std::move(result_rows)};
+}
+
+template class MutationsOverTime<Nucleotide>;
+template class MutationsOverTime<AminoAcid>;
+
 // ---- JSON -> Action -----------------------------------------------------------------------------------
 namespace {
 
@@ -756,6 +917,97 @@ std::vector<std::string> parseRequiredSequenceNames(const json::Value& json, con
    });
 }
 
+/// One entry of the mutations field of MutationsOverTime: [<sequenceName>:][<reference symbol>]<1-based position><symbol>.
+template <typename SymbolType>
+typename MutationsOverTime<SymbolType>::Mutation parseOverTimeMutation(const std::string& text, const std::string& action_name) {
+   const std::string invalid = "The mutation '" + text + "' of " + action_name + " is not of the form [<sequenceName>:][<reference symbol>]<position><symbol>";
+   typename MutationsOverTime<SymbolType>::Mutation mutation{};
+   std::string rest = text;
+   if (const size_t colon = text.rfind(':'); colon != std::string::npos) {
+      mutation.sequence_name = text.substr(0, colon);
+      rest = text.substr(colon + 1);
+   }
+   CHECK_SILO_QUERY(
+      (std::is_same_v<SymbolType, Nucleotide>) || mutation.sequence_name.has_value(),
+      "The mutation '" + text + "' of " + action_name + " must name its gene: <sequenceName>:[<reference symbol>]<position><symbol>"
+   )
+   size_t first_digit = 0;
+   if (!rest.empty() && (rest[0] < '0' || rest[0] > '9')) {
+      mutation.reference_symbol = rest[0];
+      first_digit = 1;
+   }
+   size_t end = first_digit;
+   while (end < rest.size() && rest[end] >= '0' && rest[end] <= '9') {
+      ++end;
+   }
+   CHECK_SILO_QUERY(end > first_digit && end - first_digit <= 9 && end + 1 == rest.size(), invalid)
+   mutation.position = static_cast<uint32_t>(std::stoul(rest.substr(first_digit, end - first_digit)));
+   const auto symbol = SymbolType::charToSymbol(rest[end]);
+   const bool valid = symbol.has_value() &&
+                      std::find(SymbolType::VALID_MUTATION_SYMBOLS.begin(), SymbolType::VALID_MUTATION_SYMBOLS.end(), *symbol) != SymbolType::VALID_MUTATION_SYMBOLS.end();
+   CHECK_SILO_QUERY(valid, "The symbol '" + std::string(1, rest[end]) + "' of the mutation '" + text + "' of " + action_name + " is not a valid mutation symbol")
+   mutation.symbol = *symbol;
+   return mutation;
+}
+
+template <typename SymbolType>
+std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json) {
+   using OverTime = MutationsOverTime<SymbolType>;
+   const std::string action_name = std::is_same_v<SymbolType, Nucleotide> ? "MutationsOverTime" : "AminoAcidMutationsOverTime";
+   CHECK_SILO_QUERY(
+      json.contains("mutations") && json["mutations"].is_array(), action_name + " action must contain the field mutations of type array of strings"
+   )
+   std::vector<typename OverTime::Mutation> mutations;
+   for (const auto& element : json["mutations"].items()) {
+      CHECK_SILO_QUERY(element.is_string(), action_name + " action must contain the field mutations of type array of strings, found " + element.dump())
+      CHECK_SILO_QUERY(
+         mutations.size() < OverTime::MAX_MUTATIONS, action_name + " action takes at most " + std::to_string(OverTime::MAX_MUTATIONS) + " mutations"
+      )
+      mutations.push_back(parseOverTimeMutation<SymbolType>(element.as_string(), action_name));
+   }
+   CHECK_SILO_QUERY(
+      json.contains("dateField") && json["dateField"].is_string(), action_name + " action must contain the field dateField of type string"
+   )
+   CHECK_SILO_QUERY(
+      json.contains("dateRanges") && json["dateRanges"].is_array(),
+      action_name + " action must contain the field dateRanges: an array of objects {\"dateFrom\": string or null, \"dateTo\": string or null}"
+   )
+   std::vector<typename OverTime::DateRange> ranges;
+   for (const auto& element : json["dateRanges"].items()) {
+      CHECK_SILO_QUERY(
+         element.is_object(), action_name + " action: every entry of dateRanges must be an object {\"dateFrom\": string or null, \"dateTo\": string or null}"
+      )
+      CHECK_SILO_QUERY(
+         ranges.size() < OverTime::MAX_RANGES, action_name + " action takes at most " + std::to_string(OverTime::MAX_RANGES) + " date ranges"
+      )
+      typename OverTime::DateRange range;
+      for (const char* field : {"dateFrom", "dateTo"}) {
+         if (!element.contains(field) || element[field].is_null()) {
+            continue;
+         }
+         CHECK_SILO_QUERY(element[field].is_string(), action_name + " action: the field " + field + " of a date range must be a string or null")
+         const common::Date date = common::stringToDate(element[field].as_string());
+         CHECK_SILO_QUERY(date != common::NULL_DATE, action_name + " action: the " + field + " '" + element[field].as_string() + "' is not a valid date (YYYY-MM-DD)")
+         (std::string_view(field) == "dateFrom" ? range.from : range.to) = date;
+      }
+      CHECK_SILO_QUERY(
+         !range.from.has_value() || !range.to.has_value() || *range.from <= *range.to,
+         action_name + " action: a date range has dateFrom after dateTo: " + element.dump()
+      )
+      ranges.push_back(range);
+   }
+   // pairwise disjoint (both ends inclusive): in order of their start, each must begin after the one before ends
+   std::vector<std::pair<common::Date, common::Date>> spans;
+   for (const auto& range : ranges) {
+      spans.emplace_back(range.from.value_or(common::Date{0}), range.to.value_or(common::Date{UINT32_MAX}));
+   }
+   std::sort(spans.begin(), spans.end());
+   for (size_t k = 1; k < spans.size(); ++k) {
+      CHECK_SILO_QUERY(spans[k].first > spans[k - 1].second, action_name + " action: the date ranges overlap; each row may fall in at most one")
+   }
+   return std::make_unique<OverTime>(std::move(mutations), json["dateField"].as_string(), std::move(ranges));
+}
+
 }  // namespace
 
 namespace {
@@ -781,6 +1033,8 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"Fasta", [](const json::Value& json) -> std::unique_ptr<Action> { return std::make_unique<Fasta>(parseRequiredSequenceNames(json, "Fasta")); }},
    {"Insertions", parseInsertions<Nucleotide>},
    {"AminoAcidInsertions", parseInsertions<AminoAcid>},
+   {"MutationsOverTime", parseMutationsOverTime<Nucleotide>},
+   {"AminoAcidMutationsOverTime", parseMutationsOverTime<AminoAcid>},
 };
 
 }  // namespace

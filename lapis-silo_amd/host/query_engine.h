@@ -745,6 +745,39 @@ class Mutations : public Action {
        : sequence_names(std::move(sequence_names)), min_proportion(min_proportion) {}
 };
 
+/// MutationsOverTime / AminoAcidMutationsOverTime: for listed mutations and date ranges, per (mutation, range) the rows of the
+/// filter within the range that carry the symbol (count) and that have any valid mutation symbol at the position (coverage) —
+/// the cell and the total of a Mutations table under And(filter, date in range).  Dense: every (mutation, range) is a row.
+/// Both ends of a range are inclusive on every date column; NULL dates fall in no range.  One grouped count (K7) per
+/// (partition, sequence store), one table fetched per query.
+template <typename SymbolType>
+class MutationsOverTime : public Action {
+  public:
+   struct Mutation {
+      std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+      std::optional<char> reference_symbol;
+      uint32_t position;  // 1-based
+      typename SymbolType::Symbol symbol;
+   };
+   struct DateRange {
+      std::optional<common::Date> from;
+      std::optional<common::Date> to;
+   };
+   static constexpr uint32_t MAX_RANGES = SILO_GPU_MAX_DATE_RANGES;
+   static constexpr uint32_t MAX_MUTATIONS = SILO_GPU_MAX_GROUPED_MUTATIONS;
+
+   MutationsOverTime(std::vector<Mutation> mutations, std::string date_field, std::vector<DateRange> date_ranges)
+       : mutations(std::move(mutations)), date_field(std::move(date_field)), date_ranges(std::move(date_ranges)) {}
+
+  private:
+   std::vector<Mutation> mutations;
+   std::string date_field;
+   std::vector<DateRange> date_ranges;
+
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+};
+
 }  // namespace actions
 
 class Query {
