@@ -488,6 +488,10 @@ enum { SILO_GPU_TUNE_SCAN_ROWS_PER_BLOCK = 0, SILO_GPU_TUNE_SCAN_VARIANT = 1, SI
        SILO_GPU_TUNE_LAUNCH_COST = 9 /* finalize: what a further kind of plane-scan launch costs in the choice of layouts, in KiB of plane bytes; 0 = default (192 MiB), < 0 = nothing (small test stores that are to mix layouts) */,
        SILO_GPU_TUNE_SCAN_TIMING = 7 /* 1: bracket every plane-scan launch with HIP events (silo_gpu_scan_timings) */,
        SILO_GPU_TUNE_SIDE_STREAM = 5 /* the escape-key pass of a scan: 0 (default) on a side stream of the lowest priority, 1 of default priority, 2 on the caller's stream, 3 = as 0 over the position-major keys (k_scan_escapes) */,
+       SILO_GPU_TUNE_GAP_EVENTS = 10 /* a scan over a store with derived symbols: 0 (default) counts the rows without a valid symbol from the store's gap
+                                        events in the escape-key pass (k_scan_escapes_sliced); < 0 takes the runs of the missing symbol and the sparse
+                                        keys by themselves (k_scan_missing_runs, k_sum_run_parts, k_count_sparse_keys on a side stream), as SILO_GPU_TUNE_SIDE_STREAM = 3
+                                        and stores of more than 67 M rows always do */,
        SILO_GPU_TUNE_SCAN_SPARSE_DIVISOR = 3 /* a filter with a set bit in <= row_words / divisor of its 64-byte sectors takes the gather scan (K1s); 0 = default 16, < 0 = off */ };
 int silo_gpu_tune(int knob, int value);
 

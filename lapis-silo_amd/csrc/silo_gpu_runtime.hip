@@ -26,6 +26,7 @@ std::atomic<int> g_tune_missing_runs{0};
 std::atomic<int> g_tune_key_cost{0};
 std::atomic<int> g_tune_launch_cost{0};
 std::atomic<int> g_tune_sparse_divisor{0};
+std::atomic<int> g_tune_gap_events{0};
 
 namespace {
 thread_local std::string g_last_error;
@@ -74,6 +75,9 @@ int silo_gpu_tune(int knob, int value) {
    }
    if (knob == SILO_GPU_TUNE_LAUNCH_COST) {
       return g_tune_launch_cost.exchange(value);
+   }
+   if (knob == SILO_GPU_TUNE_GAP_EVENTS) {
+      return g_tune_gap_events.exchange(value);
    }
    return -1;
 }

@@ -605,22 +605,28 @@ __global__ __launch_bounds__(256) void k_scan_escapes(
    }
 }
 
-/// One launch for up to ESCAPE_MAX_RANGES position ranges (the 12 genes of an AminoAcidMutations query): grid =
-/// (blocks per slice, slice x range, filters / FILTERS); where a slice's keys of the scanned positions begin and end is read
-/// from the store's slice index on the device.
+/// One launch for up to ESCAPE_MAX_RANGES position ranges (the 12 genes of an AminoAcidMutations query), each over the
+/// escape keys or the gap events of its store: grid = (the blocks of every range — blocks_per_slice per slice, slice by slice
+/// —, 1, filters / FILTERS); where a slice's keys of the scanned positions begin and end is read from the store's slice index
+/// on the device.
 struct EscapeSliceArgs {
    const uint64_t* filters[SILO_GPU_MAX_SCAN_BATCH];
    uint32_t row_words;
    uint32_t n_slices;
-   uint32_t out_symbols;
+   uint32_t n_ranges;
    uint32_t block_keys;  // keys of a block's share: whole granules, at most ESCAPE_GRANULES_PER_BLOCK
    struct Range {
-      const uint32_t* keys;          // the packed slice-major keys of the store (SeqStoreHost::Layout::d_escapes_sliced)
+      const uint32_t* keys;          // the packed slice-major keys of the store (SeqStoreHost::Layout::d_escapes_sliced or d_gaps_sliced)
       const uint32_t* granule_base;  // counter of every granule's first key
       const uint32_t* slice_first;   // [n_slices][positions + 1], in the packed numbering
       uint32_t positions;
       uint32_t pos_begin;
       uint32_t pos_end;
+      uint32_t out_symbols;       // counters per position: the store's scan symbols (keys), 2 (gap events: starts, ends)
+      uint32_t key_from;          // the position whose keys a slice's are read from: pos_begin, or 0 for gap events, whose
+                                  // events before pos_begin count on pos_begin's counters (a gap open there counts as begun)
+      uint32_t first_block;       // the blocks of the ranges before
+      uint32_t blocks_per_slice;
       uint32_t* counts[SILO_GPU_MAX_SCAN_BATCH];  // of the range's first position
    } ranges[ESCAPE_MAX_RANGES];
 };
@@ -670,18 +676,25 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
    uint32_t* s_base = s_count + FILTERS * WINDOW;  // [ESCAPE_GRANULES_PER_BLOCK + 1] the counter of every granule's first key, then one past the share's last key's
    uint32_t* s_nowhere = s_base + ESCAPE_GRANULES_PER_BLOCK + 4u;  // [64] a word per lane: where an add of nothing goes
    const uint32_t first_filter = blockIdx.z * FILTERS;
-   const uint32_t slice = blockIdx.y % args.n_slices;
-   const EscapeSliceArgs::Range& range = args.ranges[blockIdx.y / args.n_slices];
+   uint32_t r = 0;
+   while (r + 1u < args.n_ranges && blockIdx.x >= args.ranges[r + 1u].first_block) {  // (uniform)
+      ++r;
+   }
+   const EscapeSliceArgs::Range& range = args.ranges[r];
+   const uint32_t slice = (blockIdx.x - range.first_block) / range.blocks_per_slice;
+   const uint32_t share = (blockIdx.x - range.first_block) % range.blocks_per_slice;
+   const uint32_t out_symbols = range.out_symbols;
    const uint32_t* first = range.slice_first + static_cast<size_t>(slice) * (range.positions + 1u);
-   const uint32_t key_begin = first[range.pos_begin];
+   const uint32_t key_begin = first[range.key_from];
    const uint32_t key_end = first[range.pos_end];
    // the block's share: args.block_keys keys (whole granules)
-   const uint32_t share_begin = key_begin / ESCAPE_GRANULE_KEYS * ESCAPE_GRANULE_KEYS + blockIdx.x * args.block_keys;
+   const uint32_t share_begin = key_begin / ESCAPE_GRANULE_KEYS * ESCAPE_GRANULE_KEYS + share * args.block_keys;
    if (share_begin >= key_end) {
       return;  // (uniform) no keys for this block
    }
    const uint32_t share_end = min(share_begin + args.block_keys, key_end);
-   const uint32_t range_first = range.pos_begin * args.out_symbols;
+   const uint32_t range_first = range.pos_begin * out_symbols;
+   const bool clamp = range.key_from < range.pos_begin;  // (uniform) gap events before the range's first position
    // Everything the block reads first is asked for at once, behind the one dependent load of the slice index: the filter
    // slices, the first keys, the granules' base counters, the share's last key — every memory latency put in a row would
    // show; the keys of the granule after the next are asked for while a granule is counted, across the chunks.
@@ -762,14 +775,14 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
       // the window begins at the chunk's first key's position (the range's first position where the granule begins before it)
       // and takes the granules that end within WINDOW counters of that, one at least
       const uint32_t first_counter = max(s_base[g], range_first);
-      window_first = first_counter / args.out_symbols * args.out_symbols - range_first;
+      window_first = first_counter / out_symbols * out_symbols - range_first;
       uint32_t h = g + 1u;
-      while (h < n_granules && s_base[h + 1u] - range_first - window_first < WINDOW) {  // (a granule's last key may sit on the next one's first counter)
+      while (h < n_granules && max(s_base[h + 1u], range_first) - range_first - window_first < WINDOW) {  // (a granule's last key may sit on the next one's first counter)
          ++h;
       }
       chunk_granules = h;
       chunk_end = min(share_begin + h * ESCAPE_GRANULE_KEYS, share_end);
-      window_used = min(WINDOW, (s_base[h] / args.out_symbols + 1u) * args.out_symbols - range_first - window_first);
+      window_used = min(WINDOW, (max(s_base[h], range_first) / out_symbols + 1u) * out_symbols - range_first - window_first);
    };
    // the chunk's window goes to the table — contiguous atomics, 64 consecutive counters per wave instruction — and is zero
    // again for the next chunk
@@ -821,6 +834,13 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
 #pragma unroll
          for (uint32_t c = 0; c < 4; ++c) {
             in_window[c] = granule_counter + (keys4[c] >> ESCAPE_SLICE_SHIFT);
+         }
+         if (clamp && s_base[g] < range_first) {  // (uniform) a gap event before the range's first position counts on its counters:
+            // the window begins there (window_first = 0) and an event below it keeps its kind (range_first is even)
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+               in_window[c] = static_cast<int32_t>(in_window[c]) < 0 ? in_window[c] & 1u : in_window[c];
+            }
          }
          // A lane's four keys are consecutive keys of the sorted list.  Those on the counter of its first key are summed in the
          // lane (n0 <= 4); across the lanes these first counters ascend, lanes on the same one form a stretch, and a stretch adds
@@ -977,6 +997,8 @@ __global__ __launch_bounds__(256) void k_scan_escapes_overflow(
 //      (k_scan_missing_runs: +1 where a selected row's run starts, -1 where it ends, summed along the positions afterwards)
 //      and those with an ambiguity code (k_count_sparse_keys),
 //   3. k_finish_scan: derived count = |filter| - (2.) - sum of (1.) at the position; private tables -> the caller's.
+// Where the store has its gap events (SeqStoreHost::Layout::d_gaps_sliced), 2. is part of the escape pass instead: the events
+// are one more range of k_scan_escapes_sliced, counted into gaps[n][2], and k_finish_scan<true> sums starts less ends.
 // The filter's cardinality comes from the prepare step (k_compact_filter, counter [2]).
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t DERIVED_MAX_RANGES = 16;
@@ -1235,6 +1257,9 @@ __global__ __launch_bounds__(256) void k_count_sparse_keys(const DerivedArgs arg
 /// before the block's positions summed by the block itself, then a scan over the block), plus those with an ambiguity code,
 /// are the rows without a valid symbol; what is left of the filter after them and after the other symbols' counts is the
 /// derived symbol's count.  The private table is added to the caller's.
+/// EVENTS: the private table holds gaps[n][2] (the selected rows' gap events that start and end at a position) behind the
+/// counts instead of diff and ambiguous; the rows without a valid symbol at p are the starts up to p less the ends up to p.
+template <bool EVENTS>
 __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedArgs args) {
    __shared__ uint32_t s_before[DERIVED_THREADS / 64];
    __shared__ uint32_t s_own[DERIVED_THREADS / 64];
@@ -1253,13 +1278,20 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
    const uint32_t* __restrict__ counts = range.scratch + static_cast<size_t>(q) * range.stride;
    const uint32_t* __restrict__ diff = counts + static_cast<size_t>(n) * n_scan;
    const uint32_t* __restrict__ ambiguous = diff + n + 1u;
+   const auto diffAt = [&](uint32_t j) {  // rows entering less rows leaving the gaps at j
+      if constexpr (EVENTS) {
+         return diff[2u * j] - diff[2u * j + 1u];
+      } else {
+         return diff[j];
+      }
+   };
    uint32_t without_symbol = 0;  // rows of the filter that have no valid symbol at p
    if (range.code_map != nullptr) {  // (uniform)
       uint32_t before = 0;
       for (uint32_t j = threadIdx.x; j < first_position; j += DERIVED_THREADS) {
-         before += diff[j];
+         before += diffAt(j);
       }
-      const uint32_t scanned = waveSumToLane63(p < n ? diff[p] : 0u);  // inclusive over the wave
+      const uint32_t scanned = waveSumToLane63(p < n ? diffAt(p) : 0u);  // inclusive over the wave
       before = waveSumToLane63(before);
       if (lane == 63u) {
          s_before[wave] = before;
@@ -1270,7 +1302,7 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
       for (uint32_t k = 0; k < DERIVED_THREADS / 64; ++k) {
          without_symbol += s_before[k] + (k < wave ? s_own[k] : 0u);
       }
-      if (p < n) {
+      if (!EVENTS && p < n) {
          without_symbol += ambiguous[p];
       }
    }
@@ -1793,12 +1825,14 @@ int scanPiecesDense(
 
 /// The rows the code planes do not carry: one pass over the escape keys of every range, for all filters (dense and
 /// sparse alike: the gather reads the same planes).
-int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream) {
+/// The escape keys of `ranges`; with `gaps` (one entry per range: its store and positions, counts = the range's gap tables,
+/// null where it has none) also the gap events of their stores, in the same launches.
+int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream, const std::vector<ScanRange>* gaps = nullptr) {
    // the ranges whose stores have slice-major keys go ESCAPE_MAX_RANGES at a time into one launch of k_scan_escapes_sliced
    EscapeSliceArgs sliced{};
    uint32_t n_sliced = 0;
-   uint32_t most_keys = 0;  // of one (range, slice)
-   uint64_t total_keys = 0, total_positions = 0;  // of the ranges of the launch
+   std::array<uint32_t, ESCAPE_MAX_RANGES> most_keys{};  // of one (range, slice)
+   uint64_t total_keys = 0;  // of the ranges of the launch
    const auto launchSliced = [&]() -> int {
       if (n_sliced == 0) {
          return SILO_GPU_OK;
@@ -1818,13 +1852,20 @@ int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* fil
       const uint32_t block_granules = static_cast<uint32_t>(std::min<uint64_t>(ESCAPE_GRANULES_PER_BLOCK, std::max<uint64_t>(1, granules / 1280)));  // (flat between 640 and 2 560: profiles/r03_notes.md)
       const uint32_t block_keys = block_granules * ESCAPE_GRANULE_KEYS;
       sliced.block_keys = block_keys;
-      const dim3 grid((most_keys + block_keys - 1) / block_keys, sliced.n_slices * n_sliced, passes);
+      sliced.n_ranges = n_sliced;
+      uint32_t blocks = 0;  // every range as many per slice as its slice with the most keys needs
+      for (uint32_t k = 0; k < n_sliced; ++k) {
+         sliced.ranges[k].first_block = blocks;
+         sliced.ranges[k].blocks_per_slice = std::max<uint32_t>(1, (most_keys[k] + block_keys - 1) / block_keys);
+         blocks += sliced.ranges[k].blocks_per_slice * sliced.n_slices;
+      }
+      const dim3 grid(blocks, 1, passes);
       char name[64];
       std::snprintf(name, sizeof(name), "k_scan_escapes_sliced<%u>", per_block);
-      // bytes: the keys (4 each) once per pass of `per_block` filters, plus a 16 KiB filter slice per block and filter
+      // bytes: the keys and gap events (4 each) once per pass of `per_block` filters, plus a 16 KiB filter slice per block and filter
       ScanLaunchTiming* timing = startLaunchTiming(
-         name, 0, total_keys * sizeof(uint32_t) * grid.z + static_cast<uint64_t>(grid.x) * grid.y * q_count * ESCAPE_SLICE_WORDS32 * sizeof(uint32_t), q_count,
-         grid.x * grid.y * grid.z, hip_stream
+         name, 0, total_keys * sizeof(uint32_t) * grid.z + static_cast<uint64_t>(grid.x) * q_count * ESCAPE_SLICE_WORDS32 * sizeof(uint32_t), q_count,
+         grid.x * grid.z, hip_stream
       );
       switch (per_block) {
          case 1: k_scan_escapes_sliced<1><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<1>(), hip_stream>>>(sliced, q_count); break;
@@ -1835,34 +1876,62 @@ int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* fil
       HIP_TRY(hipGetLastError());
       finishLaunchTiming(timing, hip_stream);
       n_sliced = 0;
-      most_keys = 0;
+      most_keys.fill(0);
       total_keys = 0;
-      total_positions = 0;
       return SILO_GPU_OK;
    };
-   for (const ScanRange& range : ranges) {
-      const SeqStoreHost::Layout& layout = range.seqstore->layout;
-      if (!layout.built || layout.d_escapes == nullptr) {
-         continue;
+   // one entry of a launch: the packed keys (or gap events) of a store over [key_from, pos_end) of its positions
+   const auto addSliced = [&](const ScanRange& range, uint32_t n_slices, const uint32_t* keys, const uint32_t* granule_base, const uint32_t* slice_first,
+                              const std::vector<uint32_t>& host_slice_first, uint32_t out_symbols, uint32_t key_from) -> int {
+      if (n_sliced == ESCAPE_MAX_RANGES || (n_sliced != 0 && sliced.n_slices != n_slices)) {
+         if (const int rc = launchSliced(); rc != SILO_GPU_OK) {
+            return rc;
+         }
       }
-      const uint32_t begin = layout.escape_first[range.pos_begin];
-      const uint32_t count = layout.escape_first[range.pos_end] - begin;
+      sliced.row_words = range.seqstore->dev.row_words;
+      sliced.n_slices = n_slices;
+      EscapeSliceArgs::Range& entry = sliced.ranges[n_sliced];
+      entry.keys = keys;
+      entry.granule_base = granule_base;
+      entry.slice_first = slice_first;
+      entry.positions = range.seqstore->dev.positions;
+      entry.pos_begin = range.pos_begin;
+      entry.pos_end = range.pos_end;
+      entry.out_symbols = out_symbols;
+      entry.key_from = key_from;
+      for (uint32_t q = 0; q < q_count; ++q) {
+         sliced.filters[q] = filters[q];
+         entry.counts[q] = range.counts[q];
+      }
+      const size_t stride = static_cast<size_t>(entry.positions) + 1;
+      for (uint32_t slice = 0; slice < n_slices; ++slice) {
+         const uint32_t n = host_slice_first[slice * stride + range.pos_end] - host_slice_first[slice * stride + key_from];
+         total_keys += n;
+         most_keys[n_sliced] = std::max(most_keys[n_sliced], n + ESCAPE_GRANULE_KEYS - 1u);  // (blocks start at a granule boundary)
+      }
+      ++n_sliced;
+      return SILO_GPU_OK;
+   };
+   // the gap events of a range's store, behind its keys: from its first position on where the range begins later (see EscapeSliceArgs)
+   const auto addGaps = [&](size_t r) -> int {
+      const SeqStoreHost::Layout& layout = ranges[r].seqstore->layout;
+      if (gaps == nullptr || (*gaps)[r].seqstore == nullptr || layout.d_gaps_sliced == nullptr) {
+         return SILO_GPU_OK;
+      }
+      return addSliced((*gaps)[r], layout.gap_slices, layout.d_gaps_sliced, layout.d_gap_granule_base, layout.d_gap_slice_first, layout.gap_slice_first, 2, 0);
+   };
+   for (size_t r = 0; r < ranges.size(); ++r) {
+      const ScanRange& range = ranges[r];
+      const SeqStoreHost::Layout& layout = range.seqstore->layout;
+      const uint32_t begin = layout.built && layout.d_escapes != nullptr ? layout.escape_first[range.pos_begin] : 0;
+      const uint32_t count = layout.built && layout.d_escapes != nullptr ? layout.escape_first[range.pos_end] - begin : 0;
       if (count == 0) {
+         if (const int rc = addGaps(r); rc != SILO_GPU_OK) {
+            return rc;
+         }
          continue;
       }
       if (layout.d_escapes_sliced != nullptr && g_tune_side_stream.load() != 3) {  // the slice-major keys, a slice of the filter in LDS
-         if (n_sliced == ESCAPE_MAX_RANGES || (n_sliced != 0 && sliced.n_slices != layout.n_slices)) {
-            if (const int rc = launchSliced(); rc != SILO_GPU_OK) {
-               return rc;
-            }
-         }
-         sliced.row_words = range.seqstore->dev.row_words;
-         sliced.n_slices = layout.n_slices;
-         sliced.out_symbols = range.seqstore->dev.n_scan;
-         EscapeSliceArgs::Range& entry = sliced.ranges[n_sliced++];
-         entry.keys = layout.d_escapes_sliced;
-         entry.granule_base = layout.d_granule_base;
-         entry.slice_first = layout.d_slice_first;
          if (layout.n_overflow != 0) {  // the few keys that do not fit the packed form: a small launch of their own
             ScanBatchArgs overflow{};
             overflow.out_symbols = range.seqstore->dev.n_scan;
@@ -1875,21 +1944,17 @@ int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* fil
             );
             HIP_TRY(hipGetLastError());
          }
-         entry.positions = range.seqstore->dev.positions;
-         entry.pos_begin = range.pos_begin;
-         entry.pos_end = range.pos_end;
-         for (uint32_t q = 0; q < q_count; ++q) {
-            sliced.filters[q] = filters[q];
-            entry.counts[q] = range.counts[q];
+         if (const int rc = addSliced(range, layout.n_slices, layout.d_escapes_sliced, layout.d_granule_base, layout.d_slice_first, layout.slice_first, range.seqstore->dev.n_scan, range.pos_begin);
+             rc != SILO_GPU_OK) {
+            return rc;
          }
-         total_keys += count;
-         total_positions += range.pos_end - range.pos_begin;
-         const size_t stride = static_cast<size_t>(entry.positions) + 1;
-         for (uint32_t slice = 0; slice < layout.n_slices; ++slice) {
-            const uint32_t keys = layout.slice_first[slice * stride + range.pos_end] - layout.slice_first[slice * stride + range.pos_begin];
-            most_keys = std::max(most_keys, keys + ESCAPE_GRANULE_KEYS - 1u);  // (blocks start at a granule boundary)
+         if (const int rc = addGaps(r); rc != SILO_GPU_OK) {
+            return rc;
          }
          continue;
+      }
+      if (const int rc = addGaps(r); rc != SILO_GPU_OK) {
+         return rc;
       }
       ScanBatchArgs escapes{};
       escapes.out_symbols = range.seqstore->dev.n_scan;
@@ -1910,6 +1975,10 @@ int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* fil
 struct DerivedPlan {
    std::vector<DerivedArgs> launches;     // ranges [16 k, 16 k + 16) of the scan
    std::vector<ScanRange> private_ranges;  // the ranges with their count tables replaced by the private ones
+   // every store with derived symbols has its gap events: the escape pass counts them into the gap tables (gap_ranges, one per
+   // range, seqstore null where it has none) and none of the passes of the runs and the sparse keys runs
+   bool events = false;
+   std::vector<ScanRange> gap_ranges;
    std::vector<std::array<uint64_t, DERIVED_MAX_RANGES>> run_counts;  // [launch][range] runs of the missing symbol of the range's store (for the timing log)
    size_t table_words = 0;       // zeroed by the prepare step: the tables, then the flags of the run parts
    size_t part_words = 0;        // behind them, not zeroed: the run parts (k_scan_missing_runs -> k_sum_run_parts)
@@ -1927,6 +1996,11 @@ void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& rang
    plan.private_ranges = ranges;
    plan.launches.assign((ranges.size() + DERIVED_MAX_RANGES - 1) / DERIVED_MAX_RANGES, DerivedArgs{});
    plan.run_counts.assign(plan.launches.size(), {});
+   plan.events = g_tune_gap_events.load() >= 0 && g_tune_side_stream.load() != 3;
+   for (const ScanRange& range : ranges) {
+      plan.events = plan.events && (!range.seqstore->layout.has_implicit || range.seqstore->layout.gap_stream);
+   }
+   plan.gap_ranges.assign(plan.events ? ranges.size() : 0, ScanRange{});
    size_t offset = 0;
    for (size_t r = 0; r < ranges.size(); ++r) {
       const ScanRange& range = ranges[r];
@@ -1937,7 +2011,9 @@ void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& rang
       entry.n_positions = n;
       entry.n_scan = seqstore.dev.n_scan;
       entry.pos_begin = range.pos_begin;
-      entry.stride = static_cast<uint32_t>((static_cast<size_t>(n) * seqstore.dev.n_scan + n + 1 + n + 3) / 4 * 4);
+      // counts[n][n_scan], then gaps[n][2] (the events: starts, ends) or diff[n + 1] and ambiguous[n]
+      const size_t rows_without = plan.events ? 2u * static_cast<size_t>(n) : static_cast<size_t>(n) + 1 + n;
+      entry.stride = static_cast<uint32_t>((static_cast<size_t>(n) * seqstore.dev.n_scan + rows_without + 3) / 4 * 4);
       entry.scratch = reinterpret_cast<uint32_t*>(offset * sizeof(uint32_t));  // + the scratch block's tables (bindDerived)
       offset += static_cast<size_t>(entry.stride) * q_count;
       if (seqstore.layout.has_implicit) {
@@ -1960,6 +2036,10 @@ void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& rang
       }
       launch.row_words = store->row_words;
    }
+   if (plan.events) {  // no run parts
+      plan.table_words = offset;
+      return;
+   }
    // the parts of the blocks of k_scan_missing_runs: flags in the zeroed area, the parts behind it (offsets until bindDerived)
    const uint32_t part_stride = (plan.most_positions + 4) / 4 * 4;
    size_t part_offset = 0;
@@ -1981,13 +2061,22 @@ void bindDerived(DerivedPlan& plan, const SparseScratch& scratch, uint32_t q_cou
    size_t r = 0;
    for (DerivedArgs& launch : plan.launches) {
       launch.counters = scratch.counters[scratch.set];
-      launch.run_flags = scratch.tables + reinterpret_cast<size_t>(launch.run_flags) / sizeof(uint32_t);
-      launch.run_parts = scratch.tables + plan.table_words + reinterpret_cast<size_t>(launch.run_parts) / sizeof(uint32_t);
+      if (!plan.events) {
+         launch.run_flags = scratch.tables + reinterpret_cast<size_t>(launch.run_flags) / sizeof(uint32_t);
+         launch.run_parts = scratch.tables + plan.table_words + reinterpret_cast<size_t>(launch.run_parts) / sizeof(uint32_t);
+      }
       for (uint32_t k = 0; k < launch.n_ranges; ++k, ++r) {
          DerivedRange& entry = launch.ranges[k];
          entry.scratch = scratch.tables + reinterpret_cast<size_t>(entry.scratch) / sizeof(uint32_t);
          for (uint32_t q = 0; q < q_count; ++q) {
             plan.private_ranges[r].counts[q] = entry.scratch + static_cast<size_t>(q) * entry.stride;
+         }
+         if (plan.events && entry.code_map != nullptr) {
+            ScanRange& gap = plan.gap_ranges[r];
+            gap = plan.private_ranges[r];
+            for (uint32_t q = 0; q < q_count; ++q) {
+               gap.counts[q] = entry.scratch + static_cast<size_t>(q) * entry.stride + static_cast<size_t>(entry.n_positions) * entry.n_scan;
+            }
          }
       }
    }
@@ -2050,7 +2139,11 @@ int finishDerived(DerivedPlan& plan, uint32_t q_count, hipStream_t hip_stream) {
          launch.first_unit[k + 1] = launch.first_unit[k] + (launch.ranges[k].n_positions + DERIVED_THREADS - 1) / DERIVED_THREADS;
       }
       if (launch.first_unit[launch.n_ranges] != 0) {
-         k_finish_scan<<<dim3(launch.first_unit[launch.n_ranges], q_count), DERIVED_THREADS, 0, hip_stream>>>(launch);
+         if (plan.events) {
+            k_finish_scan<true><<<dim3(launch.first_unit[launch.n_ranges], q_count), DERIVED_THREADS, 0, hip_stream>>>(launch);
+         } else {
+            k_finish_scan<false><<<dim3(launch.first_unit[launch.n_ranges], q_count), DERIVED_THREADS, 0, hip_stream>>>(launch);
+         }
          HIP_TRY(hipGetLastError());
       }
    }
@@ -2072,6 +2165,9 @@ int forkSidePasses(const std::vector<ScanRange>& ranges, const uint64_t* const* 
    }
    if (!any_escapes && derived == nullptr) {
       return SILO_GPU_OK;
+   }
+   if (derived != nullptr && derived->events) {  // one pass over the keys and the gap events, on the caller's stream
+      return scanEscapes(ranges, filters, q_count, hip_stream, &derived->gap_ranges);
    }
    const int mode = g_tune_side_stream.load();
    SideStreams* side = mode == 2 ? nullptr : sideStreams();

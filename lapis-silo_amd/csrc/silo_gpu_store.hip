@@ -793,6 +793,9 @@ void silo_gpu_store_destroy(silo_gpu_store* store) {
       (void)hipFree(seqstore.layout.d_escapes_overflow);
       (void)hipFree(seqstore.layout.d_slice_first);
       (void)hipFree(seqstore.layout.d_run_slice_first);
+      (void)hipFree(seqstore.layout.d_gaps_sliced);
+      (void)hipFree(seqstore.layout.d_gap_granule_base);
+      (void)hipFree(seqstore.layout.d_gap_slice_first);
       (void)hipFree(seqstore.layout.d_escape_first);
    }
    (void)hipFree(store->d_ones);
@@ -1223,6 +1226,189 @@ int buildRunSliceIndex(silo_gpu_store* store, SeqStoreHost& seqstore) {
    return SILO_GPU_OK;
 }
 
+/// The slice-major packed form of a list of 8-byte keys position << 37 | symbol << 32 | sequence (what k_scan_escapes_sliced
+/// streams; SeqStoreHost::Layout::d_escapes_sliced describes it).
+struct SliceMajorKeys {
+   uint32_t* d_keys = nullptr;
+   uint32_t* d_granule_base = nullptr;
+   uint64_t* d_overflow = nullptr;  // counter << 32 | sequence
+   uint32_t n_overflow = 0;
+   uint64_t packed_keys = 0;        // slots of d_keys (keys + padding)
+   uint32_t* d_slice_first = nullptr;
+   std::vector<uint32_t> slice_first;
+   void discard() {
+      (void)hipFree(d_keys);
+      (void)hipFree(d_granule_base);
+      (void)hipFree(d_overflow);
+      (void)hipFree(d_slice_first);
+      *this = SliceMajorKeys{};
+   }
+};
+
+/// `d_sorted` — n_keys keys in ascending order, the caller's scratch — is sorted slice-major (stably: (position, symbol,
+/// sequence) order within a slice), indexed [slice][position] and packed into `out`; counter = position * n_scan + symbol.
+/// max_span = 0: every slice's keys are cut into whole granules, and a key whose counter lies more than ESCAPE_MAX_RELATIVE past
+/// its granule's first goes to the overflow list.  max_span > 0: a granule also ends early where its next key's position lies
+/// more than max_span positions past its first key's (the rest is padding), so that no key overflows.  Keys at or past
+/// `positions` are left out.
+int packSliceMajor(uint64_t* d_sorted, uint64_t n_keys, uint32_t n_scan, uint32_t positions, uint32_t n_slices, uint32_t max_span, SliceMajorKeys& out) {
+   const size_t n_entries = static_cast<size_t>(n_slices) * (positions + 1);
+   uint32_t* d_unpacked = nullptr;
+   uint32_t* d_overflow_count = nullptr;
+   const auto discard = [&]() {
+      (void)hipFree(d_unpacked);
+      (void)hipFree(d_overflow_count);
+      out.discard();
+   };
+   const auto failed = [&](hipError_t status) {
+      discard();
+      (void)hipGetLastError();
+      return fail(status == hipErrorOutOfMemory ? SILO_GPU_ERR_OUT_OF_MEMORY : SILO_GPU_ERR_HIP, std::string("slice-major keys: ") + hipGetErrorString(status));
+   };
+   if (const int rc = silo_gpu_internal_sort_keys_by_bits(d_sorted, n_keys, ESCAPE_SLICE_SHIFT, ESCAPE_SLICE_SHIFT + ESCAPE_SLICE_BITS); rc != SILO_GPU_OK) {
+      discard();
+      return rc;
+   }
+   hipError_t status = hipMalloc(&out.d_slice_first, n_entries * sizeof(uint32_t));
+   if (status != hipSuccess) {
+      return failed(status);
+   }
+   k_slice_index<<<static_cast<uint32_t>((n_entries + 255) / 256), 256>>>(d_sorted, static_cast<uint32_t>(n_keys), ESCAPE_SLICE_SHIFT, n_slices, positions, out.d_slice_first);
+   out.slice_first.resize(n_entries);
+   status = hipGetLastError();
+   status = status != hipSuccess ? status : hipMemcpy(out.slice_first.data(), out.d_slice_first, n_entries * sizeof(uint32_t), hipMemcpyDeviceToHost);
+   if (status != hipSuccess) {
+      return failed(status);
+   }
+   // every slice's keys cut into granules (padded to whole ones); the index [slice][position] moves to the packed numbering
+   std::vector<uint32_t> unpacked_first, unpacked_end;
+   for (uint32_t slice = 0; slice < n_slices; ++slice) {
+      uint32_t* first = out.slice_first.data() + static_cast<size_t>(slice) * (positions + 1);
+      const uint32_t slice_begin = first[0];
+      const uint32_t slice_end = first[positions];
+      const size_t slice_granule = unpacked_first.size();
+      for (uint32_t at = slice_begin; at < slice_end;) {
+         uint32_t end = std::min(slice_end, at + ESCAPE_GRANULE_KEYS);
+         if (max_span != 0) {  // the position of the key `at`, and the keys within max_span positions of it
+            const uint32_t position = static_cast<uint32_t>(std::upper_bound(first, first + positions + 1, at) - first) - 1u;
+            end = std::min(end, first[std::min<uint64_t>(positions, static_cast<uint64_t>(position) + max_span + 1u)]);
+         }
+         unpacked_first.push_back(at);
+         unpacked_end.push_back(end);
+         at = end;
+      }
+      size_t g = slice_granule;
+      for (uint32_t p = 0; p <= positions; ++p) {
+         const uint32_t at = first[p];
+         while (g + 1 < unpacked_first.size() && unpacked_first[g + 1] <= at) {
+            ++g;
+         }
+         first[p] = g < unpacked_first.size() ? static_cast<uint32_t>(g * ESCAPE_GRANULE_KEYS + (at - unpacked_first[g])) : static_cast<uint32_t>(g * ESCAPE_GRANULE_KEYS);
+      }
+   }
+   const size_t n_granules = unpacked_first.size();
+   out.packed_keys = static_cast<uint64_t>(n_granules) * ESCAPE_GRANULE_KEYS;
+   const uint32_t overflow_capacity = max_span != 0 ? 0u : static_cast<uint32_t>(std::min<uint64_t>(n_keys, uint64_t{1} << 26));
+   if (out.packed_keys >= (uint64_t{1} << 32)) {
+      discard();
+      return fail(SILO_GPU_ERR_UNSUPPORTED, "more than 2^32 packed escape keys in one sequence store");
+   }
+   status = hipMalloc(&out.d_keys, out.packed_keys * sizeof(uint32_t) + 16);  // (16-byte loads: a quad of slack)
+   status = status != hipSuccess ? status : hipMalloc(&out.d_granule_base, std::max<size_t>(n_granules, 1) * sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMalloc(&d_unpacked, std::max<size_t>(n_granules, 1) * 2 * sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMalloc(&d_overflow_count, sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMalloc(&out.d_overflow, std::max<size_t>(overflow_capacity, 1) * sizeof(uint64_t));
+   status = status != hipSuccess ? status : hipMemset(d_overflow_count, 0, sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMemcpy(d_unpacked, unpacked_first.data(), n_granules * sizeof(uint32_t), hipMemcpyHostToDevice);
+   status = status != hipSuccess ? status : hipMemcpy(d_unpacked + n_granules, unpacked_end.data(), n_granules * sizeof(uint32_t), hipMemcpyHostToDevice);
+   status = status != hipSuccess ? status : hipMemcpy(out.d_slice_first, out.slice_first.data(), n_entries * sizeof(uint32_t), hipMemcpyHostToDevice);
+   if (status == hipSuccess && n_granules > 0) {
+      k_pack_sliced_keys<<<static_cast<uint32_t>(n_granules), 256>>>(
+         d_sorted, d_unpacked, d_unpacked + n_granules, n_scan, out.d_keys, out.d_granule_base, out.d_overflow, d_overflow_count, overflow_capacity
+      );
+      status = hipGetLastError();
+   }
+   status = status != hipSuccess ? status : hipMemcpy(&out.n_overflow, d_overflow_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
+   if (status != hipSuccess) {
+      return failed(status);
+   }
+   if (out.n_overflow > overflow_capacity) {
+      discard();
+      return fail(SILO_GPU_ERR_UNSUPPORTED, "too many escape keys outside their granule's counter range");
+   }
+   (void)hipFree(d_unpacked);
+   (void)hipFree(d_overflow_count);
+   if (out.n_overflow == 0) {
+      (void)hipFree(out.d_overflow);
+      out.d_overflow = nullptr;
+   }
+   return SILO_GPU_OK;
+}
+
+/// The gap events of a store with derived symbols (SeqStoreHost::Layout::d_gaps_sliced): two per run of the missing symbol,
+/// two per sparse key.  An empty run gives two events past the last position (left out by the slice index).
+__global__ void k_gap_events(
+   const uint64_t* __restrict__ run_keys, const uint32_t* __restrict__ run_ends, uint32_t n_runs, const uint64_t* __restrict__ sparse, uint32_t n_sparse,
+   uint32_t positions, uint64_t* __restrict__ events
+) {
+   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+   uint64_t sequence = 0, start = 0, end = 0;
+   if (i < n_runs) {
+      sequence = run_keys[i] >> 32;
+      start = static_cast<uint32_t>(run_keys[i]);
+      end = run_ends[i];
+   } else if (i < n_runs + n_sparse) {
+      sequence = static_cast<uint32_t>(sparse[i - n_runs]);
+      start = sparse[i - n_runs] >> 37;
+      end = start + 1u;
+   } else {
+      return;
+   }
+   if (start >= end) {
+      start = end = positions;
+   }
+   events[2u * static_cast<size_t>(i)] = (start << 37) | sequence;
+   events[2u * static_cast<size_t>(i) + 1u] = (end << 37) | (uint64_t{1} << 32) | sequence;
+}
+
+/// The gap events of a store with derived symbols, slice-major and packed: the scan's escape pass counts them with the keys.
+int buildGapEvents(silo_gpu_store* store, SeqStoreHost& seqstore) {
+   SeqStoreHost::Layout& layout = seqstore.layout;
+   const SeqStoreDev& dev = seqstore.dev;
+   const uint32_t n_slices = (store->sequence_count + (1u << ESCAPE_SLICE_SHIFT) - 1) >> ESCAPE_SLICE_SHIFT;
+   const uint64_t n_sparse = seqstore.sparse_sorted.size();
+   const uint64_t n_events = 2u * (static_cast<uint64_t>(dev.n_missing_runs) + n_sparse);
+   if (!layout.has_implicit || layout.gap_stream || n_slices > ESCAPE_MAX_SLICES || n_events >= (uint64_t{1} << 31)) {
+      return SILO_GPU_OK;  // (too many events: the scan takes the runs and the sparse keys by themselves)
+   }
+   layout.gap_stream = true;
+   if (n_events == 0) {
+      return SILO_GPU_OK;
+   }
+   uint64_t* d_events = nullptr;
+   HIP_TRY(hipMalloc(&d_events, n_events * sizeof(uint64_t)));
+   const uint32_t n_intervals = static_cast<uint32_t>(n_events / 2u);
+   k_gap_events<<<(n_intervals + 255) / 256, 256>>>(dev.missing_run_keys, dev.missing_run_ends, dev.n_missing_runs, seqstore.d_sparse, static_cast<uint32_t>(n_sparse), dev.positions, d_events);
+   int rc = hipGetLastError() == hipSuccess ? SILO_GPU_OK : fail(SILO_GPU_ERR_HIP, "gap events: the launch failed");
+   rc = rc != SILO_GPU_OK ? rc : silo_gpu_internal_sort_keys(d_events, n_events);  // ascending: (position, kind, sequence)
+   SliceMajorKeys gaps;
+   rc = rc != SILO_GPU_OK ? rc : packSliceMajor(d_events, n_events, 2, dev.positions, n_slices, GAP_MAX_SPAN, gaps);
+   (void)hipFree(d_events);
+   if (rc != SILO_GPU_OK) {
+      layout.gap_stream = false;
+      return rc;
+   }
+   layout.d_gaps_sliced = gaps.d_keys;
+   layout.d_gap_granule_base = gaps.d_granule_base;
+   layout.d_gap_slice_first = gaps.d_slice_first;
+   layout.gap_slices = n_slices;
+   layout.gap_slice_first = std::move(gaps.slice_first);
+   layout.gap_packed = gaps.packed_keys;
+   // (not charged to device_bytes: the stream is a scan-side copy of the runs and sparse keys, as d_run_slice_first is, and
+   // its padding depends on how the runs of a row were cut by the build)
+   return SILO_GPU_OK;
+}
+
 int finalizeSeqStore(silo_gpu_store* store, SeqStoreHost& seqstore) {
    if (seqstore.layout.built) {
       return SILO_GPU_OK;
@@ -1255,7 +1441,10 @@ int finalizeSeqStore(silo_gpu_store* store, SeqStoreHost& seqstore) {
    if (const int rc = buildLayout(store, seqstore); rc != SILO_GPU_OK) {
       return rc;
    }
-   return buildRunSliceIndex(store, seqstore);
+   if (const int rc = buildRunSliceIndex(store, seqstore); rc != SILO_GPU_OK) {
+      return rc;
+   }
+   return buildGapEvents(store, seqstore);
 }
 }  // namespace
 
@@ -1526,101 +1715,21 @@ int finishLayout(silo_gpu_store* store, SeqStoreHost& seqstore, SeqStoreHost::La
    }
    // the slice-major copy of the keys for the scan's escape pass — packed to 4 bytes per key — and where each position's keys
    // begin in every slice
-   uint32_t* d_escapes_sliced = nullptr;
-   uint32_t* d_granule_base = nullptr;
-   uint64_t* d_escapes_overflow = nullptr;
-   uint32_t n_overflow = 0;
-   uint64_t packed_keys = 0;
-   uint32_t* d_slice_first = nullptr;
-   std::vector<uint32_t> slice_first;
+   SliceMajorKeys sliced;
    const uint32_t n_slices = (store->sequence_count + (1u << ESCAPE_SLICE_SHIFT) - 1) >> ESCAPE_SLICE_SHIFT;
    if (work.total_escapes > 0 && n_slices <= ESCAPE_MAX_SLICES) {
-      const size_t n_entries = static_cast<size_t>(n_slices) * (positions + 1);
       uint64_t* d_sorted = nullptr;  // the keys slice-major, 8 bytes wide: what the packed list is made from
-      uint32_t* d_unpacked = nullptr;
-      uint32_t* d_overflow_count = nullptr;
-      const auto discardSliced = [&]() {
-         (void)hipFree(d_sorted);
-         (void)hipFree(d_unpacked);
-         (void)hipFree(d_overflow_count);
-         (void)hipFree(d_escapes_sliced);
-         (void)hipFree(d_granule_base);
-         (void)hipFree(d_escapes_overflow);
-         (void)hipFree(d_slice_first);
-      };
       hipError_t status = hipMalloc(&d_sorted, work.escape_bytes);
-      status = status != hipSuccess ? status : hipMalloc(&d_slice_first, n_entries * sizeof(uint32_t));
       status = status != hipSuccess ? status : hipMemcpy(d_sorted, work.d_escapes, work.total_escapes * sizeof(uint64_t), hipMemcpyDeviceToDevice);
       if (status != hipSuccess) {
-         discardSliced();
+         (void)hipFree(d_sorted);
          SILO_LAYOUT_TRY(status);
       }
-      if (const int rc = silo_gpu_internal_sort_keys_by_bits(d_sorted, work.total_escapes, ESCAPE_SLICE_SHIFT, ESCAPE_SLICE_SHIFT + ESCAPE_SLICE_BITS); rc != SILO_GPU_OK) {
-         discardSliced();
+      const int rc = packSliceMajor(d_sorted, work.total_escapes, dev.n_scan, positions, n_slices, 0, sliced);
+      (void)hipFree(d_sorted);
+      if (rc != SILO_GPU_OK) {
          work.discard();
          return rc;
-      }
-      k_slice_index<<<static_cast<uint32_t>((n_entries + 255) / 256), 256>>>(
-         d_sorted, static_cast<uint32_t>(work.total_escapes), ESCAPE_SLICE_SHIFT, n_slices, positions, d_slice_first
-      );
-      slice_first.resize(n_entries);
-      status = hipGetLastError();
-      status = status != hipSuccess ? status : hipMemcpy(slice_first.data(), d_slice_first, n_entries * sizeof(uint32_t), hipMemcpyDeviceToHost);
-      if (status != hipSuccess) {
-         discardSliced();
-         SILO_LAYOUT_TRY(status);
-      }
-      // every slice's keys padded to whole granules; the index [slice][position] moves to the packed numbering
-      std::vector<uint32_t> unpacked_first, unpacked_end;
-      for (uint32_t slice = 0; slice < n_slices; ++slice) {
-         uint32_t* first = slice_first.data() + static_cast<size_t>(slice) * (positions + 1);
-         const uint32_t slice_begin = first[0];
-         const uint32_t slice_end = first[positions];
-         const auto packed_begin = static_cast<uint32_t>(unpacked_first.size()) * ESCAPE_GRANULE_KEYS;
-         for (uint32_t at = slice_begin; at < slice_end; at += ESCAPE_GRANULE_KEYS) {
-            unpacked_first.push_back(at);
-            unpacked_end.push_back(std::min(slice_end, at + ESCAPE_GRANULE_KEYS));
-         }
-         for (uint32_t p = 0; p <= positions; ++p) {
-            first[p] = packed_begin + (first[p] - slice_begin);
-         }
-      }
-      const size_t n_granules = unpacked_first.size();
-      packed_keys = static_cast<uint64_t>(n_granules) * ESCAPE_GRANULE_KEYS;
-      const uint32_t overflow_capacity = static_cast<uint32_t>(std::min<uint64_t>(work.total_escapes, uint64_t{1} << 26));
-      if (packed_keys >= (uint64_t{1} << 32)) {
-         discardSliced();
-         work.discard();
-         return fail(SILO_GPU_ERR_UNSUPPORTED, "more than 2^32 packed escape keys in one sequence store");
-      }
-      status = hipMalloc(&d_escapes_sliced, packed_keys * sizeof(uint32_t) + 16);  // (16-byte loads: a quad of slack)
-      status = status != hipSuccess ? status : hipMalloc(&d_granule_base, std::max<size_t>(n_granules, 1) * sizeof(uint32_t));
-      status = status != hipSuccess ? status : hipMalloc(&d_unpacked, std::max<size_t>(n_granules, 1) * 2 * sizeof(uint32_t));
-      status = status != hipSuccess ? status : hipMalloc(&d_overflow_count, sizeof(uint32_t));
-      status = status != hipSuccess ? status : hipMalloc(&d_escapes_overflow, std::max<size_t>(overflow_capacity, 1) * sizeof(uint64_t));
-      status = status != hipSuccess ? status : hipMemset(d_overflow_count, 0, sizeof(uint32_t));
-      status = status != hipSuccess ? status : hipMemcpy(d_unpacked, unpacked_first.data(), n_granules * sizeof(uint32_t), hipMemcpyHostToDevice);
-      status = status != hipSuccess ? status : hipMemcpy(d_unpacked + n_granules, unpacked_end.data(), n_granules * sizeof(uint32_t), hipMemcpyHostToDevice);
-      status = status != hipSuccess ? status : hipMemcpy(d_slice_first, slice_first.data(), n_entries * sizeof(uint32_t), hipMemcpyHostToDevice);
-      if (status == hipSuccess && n_granules > 0) {
-         k_pack_sliced_keys<<<static_cast<uint32_t>(n_granules), 256>>>(
-            d_sorted, d_unpacked, d_unpacked + n_granules, dev.n_scan, d_escapes_sliced, d_granule_base, d_escapes_overflow, d_overflow_count, overflow_capacity
-         );
-         status = hipGetLastError();
-      }
-      status = status != hipSuccess ? status : hipMemcpy(&n_overflow, d_overflow_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
-      if (status != hipSuccess || n_overflow > overflow_capacity) {
-         discardSliced();
-         SILO_LAYOUT_TRY(status);
-         work.discard();
-         return fail(SILO_GPU_ERR_UNSUPPORTED, "too many escape keys outside their granule's counter range");
-      }
-      (void)hipFree(d_sorted);
-      (void)hipFree(d_unpacked);
-      (void)hipFree(d_overflow_count);
-      if (n_overflow == 0) {
-         (void)hipFree(d_escapes_overflow);
-         d_escapes_overflow = nullptr;
       }
    }
    (void)hipFree(work.d_first);
@@ -1638,15 +1747,15 @@ int finishLayout(silo_gpu_store* store, SeqStoreHost& seqstore, SeqStoreHost::La
    layout.d_row_target = work.d_row_target;
    layout.d_code_map = work.d_code_map;
    layout.d_escapes = work.d_escapes;
-   layout.d_escapes_sliced = d_escapes_sliced;
-   layout.d_granule_base = d_granule_base;
-   layout.d_escapes_overflow = d_escapes_overflow;
-   layout.n_overflow = n_overflow;
-   layout.packed_keys = packed_keys;
-   layout.d_slice_first = d_slice_first;
+   layout.d_escapes_sliced = sliced.d_keys;
+   layout.d_granule_base = sliced.d_granule_base;
+   layout.d_escapes_overflow = sliced.d_overflow;
+   layout.n_overflow = sliced.n_overflow;
+   layout.packed_keys = sliced.packed_keys;
+   layout.d_slice_first = sliced.d_slice_first;
    layout.slice_shift = ESCAPE_SLICE_SHIFT;
-   layout.n_slices = d_escapes_sliced != nullptr ? n_slices : 0;
-   layout.slice_first = std::move(slice_first);
+   layout.n_slices = sliced.d_keys != nullptr ? n_slices : 0;
+   layout.slice_first = std::move(sliced.slice_first);
    layout.d_escape_first = work.d_escape_first;
    layout.row_of = std::move(work.row_of);
    layout.code_map = std::move(work.code_map);
@@ -1654,7 +1763,7 @@ int finishLayout(silo_gpu_store* store, SeqStoreHost& seqstore, SeqStoreHost::La
    layout.escape_first_symbol = std::move(work.escape_first_symbol);
    layout.runs = std::move(work.runs);
    layout.has_implicit = work.has_implicit;
-   layout.device_bytes = work.plane_bytes + work.escape_bytes + packed_keys * sizeof(uint32_t) + static_cast<size_t>(n_overflow) * sizeof(uint64_t) +
+   layout.device_bytes = work.plane_bytes + work.escape_bytes + sliced.packed_keys * sizeof(uint32_t) + static_cast<size_t>(sliced.n_overflow) * sizeof(uint64_t) +
                          static_cast<size_t>(positions) * (CODE_MAP_STRIDE + 8) +
                          work.total_rows * sizeof(uint32_t);
    store->device_bytes += layout.device_bytes;

@@ -27,6 +27,7 @@ extern std::atomic<int> g_tune_rows_per_block;
 extern std::atomic<int> g_tune_scan_variant;
 extern std::atomic<int> g_tune_eval_leaf_batch;
 extern std::atomic<int> g_tune_compact_index;   // < 0: finalize keeps the build-time identity planes; 2 / 3: see SILO_GPU_TUNE_COMPACT_INDEX
+extern std::atomic<int> g_tune_gap_events;      // < 0: scans of derived symbols take the runs and the sparse keys by themselves (planDerived)
 extern std::atomic<int> g_tune_side_stream;     // the side passes of a scan: see forkSidePasses (silo_gpu_scan.hip)
 extern std::atomic<int> g_tune_scan_timing;     // 1: HIP events around every launch of a scan (silo_gpu_scan_timings)
 extern std::atomic<int> g_tune_missing_runs;    // < 0: finalize keeps the plane of the missing symbol instead of turning it into runs
@@ -296,6 +297,19 @@ struct SeqStoreHost {
       bool has_implicit = false;
       uint32_t* d_run_slice_first = nullptr;  // [n_run_slices + 1] first run of a slice of sequences
       uint32_t n_run_slices = 0;
+      // the same rows without a valid symbol as GAP EVENTS, slice-major and packed like d_escapes_sliced: every run of the
+      // missing symbol [start, end) and every sparse key (ambiguity code) at p as [p, p + 1) gives the keys
+      // start << 37 | 0 << 32 | sequence and end << 37 | 1 << 32 | sequence (counter = position * 2 + kind; an end at P is left
+      // out).  Granules end early where the next event lies more than GAP_MAX_SPAN positions past their first: no overflow.
+      // nullptr where the store has no derived symbol or more than ESCAPE_MAX_SLICES slices (the scan then takes the runs and
+      // the sparse keys by themselves: k_scan_missing_runs, k_count_sparse_keys).
+      bool gap_stream = false;  // built (empty where the store has neither runs nor sparse keys)
+      uint32_t* d_gaps_sliced = nullptr;
+      uint32_t* d_gap_granule_base = nullptr;
+      uint32_t* d_gap_slice_first = nullptr;  // [gap_slices][P + 1]
+      uint32_t gap_slices = 0;
+      std::vector<uint32_t> gap_slice_first;  // host copy
+            uint64_t gap_packed = 0;                // slots of d_gaps_sliced
    } layout;
 };
 
@@ -433,6 +447,7 @@ constexpr uint32_t ESCAPE_KEY_INVALID = 0xFFFFFFFFu;           // padding / a ke
 // window of LDS counters of k_scan_escapes_sliced<1> and <2> (6 144 counters less a position's worth), so that those count without
 // a path for keys past the window; the few keys further behind their granule's first go to the overflow list
 constexpr uint32_t ESCAPE_MAX_RELATIVE = 6000u;
+constexpr uint32_t GAP_MAX_SPAN = (ESCAPE_MAX_RELATIVE + 1u - 2u) / 2u;  // positions a granule of gap events spans at most (2 counters each)
 
 /// A position range of one sequence store with the count tables of every filter of the launch.
 struct ScanRange {
