@@ -171,6 +171,18 @@ def load_library():
     lib.silo_gpu_group_count.argtypes = [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, vp, vp]
     lib.silo_gpu_mutations_select.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_upload_bytes.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
+    lib.silo_gpu_count_slot_create.argtypes = [ctypes.POINTER(vp)]
+    lib.silo_gpu_count_slot_destroy.argtypes = [vp]
+    lib.silo_gpu_count_slot_destroy.restype = None
+    lib.silo_gpu_filter_eval_count.argtypes = [vp, ctypes.POINTER(BitProg), vp, vp, vp]
+    lib.silo_gpu_count_slot_wait.argtypes = [vp, c_u64p, vp]
+    lib.silo_gpu_row_slot_create.argtypes = [ctypes.c_uint32, ctypes.POINTER(vp)]
+    lib.silo_gpu_row_slot_destroy.argtypes = [vp]
+    lib.silo_gpu_row_slot_destroy.restype = None
+    lib.silo_gpu_mutations_select_to_slot.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, vp, vp]
+    lib.silo_gpu_row_slot_wait.argtypes = [vp, ctypes.POINTER(vp), c_u32p, vp]
+    lib.silo_gpu_bitset_from_pairs.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp]
+    lib.silo_gpu_count_pairs.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_group_count_hashed.argtypes = [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_uint32), vp]
     lib.silo_gpu_reconstruct_sequences.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp]
@@ -276,6 +288,67 @@ class GpuEvent:
     def __del__(self):
         if getattr(self, "handle", None):
             self.lib.silo_gpu_event_destroy(self.handle)
+            self.handle = None
+
+
+class GpuStream:
+    """A non-blocking HIP stream (silo_gpu_stream_create); pass `.handle` wherever a stream is taken."""
+
+    def __init__(self):
+        self.lib = load_library()
+        self.handle = ctypes.c_void_p()
+        _check(self.lib.silo_gpu_stream_create(ctypes.byref(self.handle)))
+
+    def synchronize(self):
+        _check(self.lib.silo_gpu_stream_synchronize(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.silo_gpu_stream_destroy(self.handle)
+            self.handle = None
+
+
+class CountSlot:
+    """silo_gpu_count_slot: where the blocks of GpuStore.filter_eval_count deliver their parts of the cardinality (page-locked
+    host memory); one slot serves one launch at a time."""
+
+    def __init__(self):
+        self.lib = load_library()
+        self.handle = ctypes.c_void_p()
+        _check(self.lib.silo_gpu_count_slot_create(ctypes.byref(self.handle)))
+
+    def wait(self, stream=None):
+        """The cardinality of the slot's last launch (`stream`: the one it was launched on)."""
+        count = ctypes.c_uint64()
+        _check(self.lib.silo_gpu_count_slot_wait(self.handle, ctypes.byref(count), stream))
+        return int(count.value)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.silo_gpu_count_slot_destroy(self.handle)
+            self.handle = None
+
+
+class RowSlot:
+    """silo_gpu_row_slot: a page-locked host buffer of `capacity` rows that GpuStore.mutations_select_to_slot writes into."""
+
+    def __init__(self, capacity):
+        self.lib = load_library()
+        self.capacity = int(capacity)
+        self.handle = ctypes.c_void_p()
+        _check(self.lib.silo_gpu_row_slot_create(self.capacity, ctypes.byref(self.handle)))
+
+    def wait(self, stream=None):
+        """(n_selected, a copy of rows[min(n, capacity)] as (position, symbol, count, total)) of the slot's last launch."""
+        rows, n = ctypes.c_void_p(), ctypes.c_uint32()
+        _check(self.lib.silo_gpu_row_slot_wait(self.handle, ctypes.byref(rows), ctypes.byref(n), stream))
+        delivered = min(n.value, self.capacity)
+        table = np.frombuffer(ctypes.string_at(rows.value, 16 * delivered), dtype=np.uint32).reshape(-1, 4)
+        return int(n.value), table
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.silo_gpu_row_slot_destroy(self.handle)
             self.handle = None
 
 
@@ -524,6 +597,16 @@ class GpuStore:
         """programs: list of (code, leaves, n_slots); returns the cardinalities (one launch for all of them)."""
         return filter_eval_batch(self.handle, programs, out_bitsets, stream)
 
+    def filter_eval_count(self, code, leaves, n_slots, slot, out_bitset=None, stream=None):
+        """silo_gpu_filter_eval_count: as filter_eval, the cardinality delivered into `slot` (a CountSlot; read it with
+        slot.wait(stream)).  Only launches."""
+        code = np.ascontiguousarray(code, dtype=np.uint32)
+        leaf_array = (ctypes.c_void_p * max(1, len(leaves)))(*[
+            (l.value if isinstance(l, ctypes.c_void_p) else l) for l in leaves
+        ])
+        prog = BitProg(len(code) // 2, code.ctypes.data_as(c_u32p), len(leaves), leaf_array, n_slots)
+        _check(self.lib.silo_gpu_filter_eval_count(self.handle, ctypes.byref(prog), out_bitset, None if slot is None else slot.handle, stream))
+
     def count_buffer(self, stream=None):
         """Zeroed accumulator for cardinalities: COUNT_SHARDS uint64 (their sum is the count)."""
         counter = self.malloc(8 * COUNT_SHARDS)
@@ -693,6 +776,42 @@ class GpuStore:
             self.free(pointer)
         n = int(words[0])
         return n, words[4:4 + 4 * min(n, capacity)].reshape(-1, 4)
+
+    def mutations_select_to_slot(self, counts, reference_index, min_proportion, slot, stream=None):
+        """K4 delivered into a RowSlot: (n_selected, rows[min(n, slot.capacity)]) as mutations_select returns them."""
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        positions, n_symbols = counts.shape
+        # (an empty table still gets a device address, so that it is the entry point that refuses it)
+        counts_dev = self.upload_column(counts.reshape(-1) if counts.size else np.zeros(1, dtype=np.uint32))
+        ref = np.ascontiguousarray(reference_index if len(reference_index) else [0], dtype=np.uint8)
+        ref_dev = ctypes.c_void_p()
+        try:
+            _check(self.lib.silo_gpu_upload_bytes(ref.ctypes.data_as(ctypes.c_void_p), ref.nbytes, ctypes.byref(ref_dev)))
+            _check(self.lib.silo_gpu_mutations_select_to_slot(counts_dev, ref_dev, positions, n_symbols, ctypes.c_double(min_proportion),
+                                                              None if slot is None else slot.handle, stream))
+            return slot.wait(stream)
+        finally:
+            for pointer in (counts_dev, ref_dev):
+                if pointer:
+                    self.lib.silo_gpu_free(pointer)
+
+    def bitset_from_value_ids(self, ptr, value_ids_ptr, membership, n_values=None, stream=None):
+        """bit i of the bitset at ptr = membership[value_ids[i]] (ids >= n_values select nothing); value_ids_ptr: a device
+        column of uint32 ids (upload_column).  n_values defaults to len(membership)."""
+        if membership is not None:
+            membership = np.ascontiguousarray(membership, dtype=np.uint8)
+            if n_values is None:
+                n_values = len(membership)
+        _check(self.lib.silo_gpu_bitset_from_value_ids(self.handle, ptr, value_ids_ptr, None if membership is None else _ptr(membership), n_values or 0, stream))
+
+    def bitset_from_pairs(self, ptr, rows_ptr, ids_ptr, n_pairs, membership, stream=None):
+        """The bitset at ptr = the rows of the (row, id) pairs with membership[id] != 0; rows_ptr / ids_ptr: device columns of uint32."""
+        membership = np.ascontiguousarray(membership, dtype=np.uint8)
+        _check(self.lib.silo_gpu_bitset_from_pairs(self.handle, ptr, rows_ptr, ids_ptr, n_pairs, _ptr(membership), len(membership), stream))
+
+    def count_pairs(self, filter_ptr, rows_ptr, ids_ptr, n_pairs, counts_ptr, stream=None):
+        """counts[id] += pairs of that id whose row is in the filter (None = all rows); counts_ptr: device uint32 table, accumulated into."""
+        _check(self.lib.silo_gpu_count_pairs(self.handle, filter_ptr, rows_ptr, ids_ptr, n_pairs, counts_ptr, stream))
 
     def last_scan_kernel(self):
         return self.lib.silo_gpu_last_scan_kernel().decode()

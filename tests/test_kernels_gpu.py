@@ -101,10 +101,54 @@ def _eval(store, code, leaves, n_slots):
     return words, count
 
 
-@pytest.mark.parametrize("n", [100, 777, 100000])
-def test_filter_eval_ops(built, n):
+def filter_eval_programs(masks):
+    """The bit-programs of test_filter_eval_ops over five leaves with the given row masks: (code, n_slots, expected mask) each."""
     from silo_amd import binding as b
 
+    assert len(masks) == 5
+    full = np.ones(len(masks[0]), bool)
+    programs = []
+
+    def add(code, n_slots, want):
+        programs.append((code, n_slots, want))
+
+    # (m0 & m1) | ~m2, minus m3
+    code = (b.encode(b.OP_LOAD, 0, imm=0) + b.encode(b.OP_LOAD, 1, imm=1) + b.encode(b.OP_AND, 0, 0, 1)
+            + b.encode(b.OP_LOAD, 1, imm=2) + b.encode(b.OP_NOT, 1, 1) + b.encode(b.OP_OR, 0, 0, 1)
+            + b.encode(b.OP_LOAD, 1, imm=3) + b.encode(b.OP_ANDNOT, 0, 0, 1))
+    add(code, 2, ((masks[0] & masks[1]) | ~masks[2]) & ~masks[3])
+    # leaf operands: (leaf0 & leaf1) | ~leaf2, minus leaf3 without a single LOAD
+    L = b.LEAF_OPERAND
+    code = (b.encode(b.OP_AND, 0, L + 0, L + 1) + b.encode(b.OP_NOT, 1, L + 2) + b.encode(b.OP_OR, 0, 0, 1)
+            + b.encode(b.OP_ANDNOT, 0, 0, L + 3))
+    add(code, 2, ((masks[0] & masks[1]) | ~masks[2]) & ~masks[3])
+    add(b.encode(b.OP_MOV, 0, L + 4), 1, masks[4])
+    # n-ary runs: Or / And over leaves 0..4 and 1..3, 2-of-5 and "exactly 1 of the complements"
+    add(b.encode(b.OP_OR_N, 0, imm=0 | (5 << 16)), 1, np.logical_or.reduce(masks))
+    add(b.encode(b.OP_AND_N, 0, imm=1 | (3 << 16)), 1, masks[1] & masks[2] & masks[3])
+    zero3 = b.encode(b.OP_ZERO, 1) + b.encode(b.OP_ZERO, 2) + b.encode(b.OP_ZERO, 3)
+    total5 = sum(m.astype(int) for m in masks)
+    add(zero3 + b.encode(b.OP_CNT_ADD_N, 1, 0, 3, imm=0 | (5 << 16)) + b.encode(b.OP_CNT_GE, 0, 1, 3, imm=2), 4, total5 >= 2)
+    add(zero3 + b.encode(b.OP_CNT_ADD_NOT_N, 1, 0, 3, imm=0 | (5 << 16)) + b.encode(b.OP_CNT_EQ, 0, 1, 3, imm=1), 4, (5 - total5) == 1)
+    add(b.encode(b.OP_ONES, 0), 1, full)
+    add(b.encode(b.OP_ZERO, 0), 1, ~full)
+    add(b.encode(b.OP_ZERO, 0) + b.encode(b.OP_NOT, 0, 0), 1, full)
+    # n-of-5 thresholds with a 3-bit counter in slots 1..3
+    total = sum(m.astype(int) for m in masks)
+    for k in range(0, 7):
+        code = b.encode(b.OP_ZERO, 1) + b.encode(b.OP_ZERO, 2) + b.encode(b.OP_ZERO, 3)
+        for leaf in range(5):
+            if leaf % 2 == 0:
+                code += b.encode(b.OP_LOAD, 0, imm=leaf) + b.encode(b.OP_CNT_ADD, 1, 0, 3)
+            else:
+                code += b.encode(b.OP_CNT_ADD, 1, b.LEAF_OPERAND + leaf, 3)
+        add(code + b.encode(b.OP_CNT_GE, 0, 1, 3, imm=k), 4, total >= k)
+        add(code + b.encode(b.OP_CNT_EQ, 0, 1, 3, imm=k), 4, total == k)
+    return programs
+
+
+@pytest.mark.parametrize("n", [100, 777, 100000])
+def test_filter_eval_ops(built, n):
     rng = np.random.default_rng(n)
     masks = [rng.random(n) < p for p in (0.5, 0.2, 0.7, 0.05, 0.9)]
     ref = np.ones(4, dtype=np.uint8)
@@ -114,46 +158,13 @@ def test_filter_eval_ops(built, n):
             ptr = store.bitset_alloc()
             store.bitset_upload(ptr, dense.pack_bits(m))
             leaves.append(ptr)
-        full = np.ones(n, bool)
-
-        def check(code, n_slots, want):
+        programs = filter_eval_programs(masks)
+        assert len(programs) == 24
+        for code, n_slots, want in programs:
             words, count = _eval(store, code, leaves, n_slots)
             assert np.array_equal(dense.unpack_bits(words, n), want)
             assert not dense.unpack_bits(words, store.row_words * 64)[n:].any()
             assert count == int(want.sum())
-
-        # (m0 & m1) | ~m2, minus m3
-        code = (b.encode(b.OP_LOAD, 0, imm=0) + b.encode(b.OP_LOAD, 1, imm=1) + b.encode(b.OP_AND, 0, 0, 1)
-                + b.encode(b.OP_LOAD, 1, imm=2) + b.encode(b.OP_NOT, 1, 1) + b.encode(b.OP_OR, 0, 0, 1)
-                + b.encode(b.OP_LOAD, 1, imm=3) + b.encode(b.OP_ANDNOT, 0, 0, 1))
-        check(code, 2, ((masks[0] & masks[1]) | ~masks[2]) & ~masks[3])
-        # leaf operands: (leaf0 & leaf1) | ~leaf2, minus leaf3 without a single LOAD
-        L = b.LEAF_OPERAND
-        code = (b.encode(b.OP_AND, 0, L + 0, L + 1) + b.encode(b.OP_NOT, 1, L + 2) + b.encode(b.OP_OR, 0, 0, 1)
-                + b.encode(b.OP_ANDNOT, 0, 0, L + 3))
-        check(code, 2, ((masks[0] & masks[1]) | ~masks[2]) & ~masks[3])
-        check(b.encode(b.OP_MOV, 0, L + 4), 1, masks[4])
-        # n-ary runs: Or / And over leaves 0..4 and 1..3, 2-of-5 and "exactly 1 of the complements"
-        check(b.encode(b.OP_OR_N, 0, imm=0 | (5 << 16)), 1, np.logical_or.reduce(masks))
-        check(b.encode(b.OP_AND_N, 0, imm=1 | (3 << 16)), 1, masks[1] & masks[2] & masks[3])
-        zero3 = b.encode(b.OP_ZERO, 1) + b.encode(b.OP_ZERO, 2) + b.encode(b.OP_ZERO, 3)
-        total5 = sum(m.astype(int) for m in masks)
-        check(zero3 + b.encode(b.OP_CNT_ADD_N, 1, 0, 3, imm=0 | (5 << 16)) + b.encode(b.OP_CNT_GE, 0, 1, 3, imm=2), 4, total5 >= 2)
-        check(zero3 + b.encode(b.OP_CNT_ADD_NOT_N, 1, 0, 3, imm=0 | (5 << 16)) + b.encode(b.OP_CNT_EQ, 0, 1, 3, imm=1), 4, (5 - total5) == 1)
-        check(b.encode(b.OP_ONES, 0), 1, full)
-        check(b.encode(b.OP_ZERO, 0), 1, ~full)
-        check(b.encode(b.OP_ZERO, 0) + b.encode(b.OP_NOT, 0, 0), 1, full)
-        # n-of-5 thresholds with a 3-bit counter in slots 1..3
-        total = sum(m.astype(int) for m in masks)
-        for k in range(0, 7):
-            code = b.encode(b.OP_ZERO, 1) + b.encode(b.OP_ZERO, 2) + b.encode(b.OP_ZERO, 3)
-            for leaf in range(5):
-                if leaf % 2 == 0:
-                    code += b.encode(b.OP_LOAD, 0, imm=leaf) + b.encode(b.OP_CNT_ADD, 1, 0, 3)
-                else:
-                    code += b.encode(b.OP_CNT_ADD, 1, b.LEAF_OPERAND + leaf, 3)
-            check(code + b.encode(b.OP_CNT_GE, 0, 1, 3, imm=k), 4, total >= k)
-            check(code + b.encode(b.OP_CNT_EQ, 0, 1, 3, imm=k), 4, total == k)
 
 
 def test_synthetic_store_matches_cpu_twin(built):
@@ -604,12 +615,13 @@ def test_group_count_hashed_reports_an_understated_row_bound(built):
         store.free(pointer)
 
 
-@pytest.mark.parametrize("n_symbols", [5, 22])
-def test_mutations_select_threshold_arithmetic_matches_host_doubles(built, n_symbols):
-    """K4: ceil((double)total * minProportion) - 1 on the device is the host's IEEE arithmetic bit for bit, for totals up
-    to tens of millions and proportions that sit on rounding edges (mutations.cpp:197-211)."""
-    rng = np.random.default_rng(n_symbols)
-    positions = 20000
+MUTATIONS_SELECT_PROPORTIONS = (0.0, 0.05, 1.0 / 3.0, 0.1, 0.3, 1e-9, 0.9999999, 1.0, 0.07, 2.0 / 7.0)
+
+
+def mutations_select_table(n_symbols, positions=20000, seed=None):
+    """(counts [positions][n_symbols], reference index per position, totals) of the K4 tests: totals from 0 to tens of millions,
+    positions nobody covers, reference symbols that are not valid mutation symbols (0xFF)."""
+    rng = np.random.default_rng(n_symbols if seed is None else seed)
     counts = np.zeros((positions, n_symbols), dtype=np.uint32)
     scale = rng.choice([1, 10, 1000, 100000, 10_000_000], size=positions)
     for s in range(n_symbols):
@@ -618,17 +630,30 @@ def test_mutations_select_threshold_arithmetic_matches_host_doubles(built, n_sym
     reference = rng.integers(0, n_symbols, size=positions).astype(np.uint8)
     reference[rng.random(positions) < 0.02] = 0xFF                 # reference symbol not among the valid ones
     totals = counts.sum(axis=1, dtype=np.uint64)
+    return counts, reference, totals
+
+
+def mutations_select_expected(counts, reference, totals, proportion):
+    """The (position, symbol, count, total) cells mutations.cpp:184-232 selects, in host doubles."""
+    positions, n_symbols = counts.shape
+    if proportion == 0:
+        threshold = np.zeros(positions, dtype=np.uint64)
+    else:
+        threshold = (np.ceil(totals.astype(np.float64) * proportion) - 1).astype(np.int64).astype(np.uint64) & 0xFFFFFFFF
+    selected = (totals[:, None] > 0) & (np.arange(n_symbols)[None, :] != reference[:, None]) & (counts.astype(np.uint64) > threshold[:, None])
+    position, symbol = np.nonzero(selected)
+    return set(zip(position.tolist(), symbol.tolist(), counts[position, symbol].tolist(), totals[position].tolist()))
+
+
+@pytest.mark.parametrize("n_symbols", [5, 22])
+def test_mutations_select_threshold_arithmetic_matches_host_doubles(built, n_symbols):
+    """K4: ceil((double)total * minProportion) - 1 on the device is the host's IEEE arithmetic bit for bit, for totals up
+    to tens of millions and proportions that sit on rounding edges (mutations.cpp:197-211)."""
+    positions = 20000
+    counts, reference, totals = mutations_select_table(n_symbols, positions)
     with make_store(64, [dict(name="s", alphabet="nuc", reference=np.ones(4, dtype=np.uint8))]) as store:
-        for proportion in (0.0, 0.05, 1.0 / 3.0, 0.1, 0.3, 1e-9, 0.9999999, 1.0, 0.07, 2.0 / 7.0):
-            if proportion == 0:
-                threshold = np.zeros(positions, dtype=np.uint64)
-            else:
-                threshold = (np.ceil(totals.astype(np.float64) * proportion) - 1).astype(np.int64).astype(np.uint64) & 0xFFFFFFFF
-            want = set()
-            for position in np.nonzero(totals)[0]:
-                for s in range(n_symbols):
-                    if s != reference[position] and counts[position, s] > threshold[position]:
-                        want.add((int(position), s, int(counts[position, s]), int(totals[position])))
+        for proportion in MUTATIONS_SELECT_PROPORTIONS:
+            want = mutations_select_expected(counts, reference, totals, proportion)
             n, rows = store.mutations_select(counts, reference, proportion, positions * n_symbols)
             assert n == len(want), proportion
             assert {tuple(int(v) for v in row) for row in rows} == want, proportion
