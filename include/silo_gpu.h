@@ -442,6 +442,26 @@ int silo_gpu_mutations_scan_ranges(
    uint32_t* const* counts_out_dev, void* stream
 );
 
+/* The same scan for a caller that only wants the Mutations rows of a minimal proportion: min_proportion[q] (NULL = as
+ * silo_gpu_mutations_scan_ranges) is the minProportion that filter q's table will be selected with.  For every range and filter
+ * the row sums over the symbols, sum_s counts[p][s], are exact at every position, and so is every cell that
+ * silo_gpu_mutations_select — with the store's reference symbols and that filter's proportion — emits from this table ALONE (a
+ * table that other scans are accumulated into as well, the partitions of a database, needs the exact entry).  Other cells may
+ * not be: at a position whose most numerous symbol is derived (SILO_GPU_TUNE_COMPACT_INDEX) and is the reference symbol, the
+ * scan leaves out escape keys of (position, symbol) groups too small in the whole store to reach the proportion under the
+ * filter, whole granules of the key stream at a time, and their rows are counted on the derived symbol instead — which is never
+ * reported.  A proportion of 0 (or outside (0, 1]), a store without gap events, SILO_GPU_TUNE_GAP_EVENTS < 0 or
+ * SILO_GPU_TUNE_PRUNE_KEYS < 0: exactly silo_gpu_mutations_scan_ranges. */
+int silo_gpu_mutations_scan_ranges_min_proportion(
+   const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
+   const double* min_proportion /* [n_filters] or NULL */, uint32_t* const* counts_out_dev, void* stream
+);
+/* How many granules (4 096 keys) of the store's slice-major escape keys the scan above skips for ONE filter of `cardinality`
+ * rows at `min_proportion`, and how many there are: the kernel's rule applied to the host copies of the store's bounds. */
+int silo_gpu_store_scan_prunable_granules(
+   const silo_gpu_store* store, uint32_t seqstore_id, uint32_t cardinality, double min_proportion, uint64_t* out_skippable, uint64_t* out_total
+);
+
 /* ---- K7: grouped mutation counts (MutationsOverTime) -------------------------------------------------
  * For each of n_mutations listed cells (positions[m] 0-based in the store, symbols[m] a VALID mutation symbol id of the
  * store's alphabet) and each of n_ranges date ranges (range_bounds[2r], range_bounds[2r + 1] = from, to, encoded dates
@@ -492,6 +512,8 @@ enum { SILO_GPU_TUNE_SCAN_ROWS_PER_BLOCK = 0, SILO_GPU_TUNE_SCAN_VARIANT = 1, SI
                                         events in the escape-key pass (k_scan_escapes_sliced); < 0 takes the runs of the missing symbol and the sparse
                                         keys by themselves (k_scan_missing_runs, k_sum_run_parts, k_count_sparse_keys on a side stream), as SILO_GPU_TUNE_SIDE_STREAM = 3
                                         and stores of more than 67 M rows always do */,
+       SILO_GPU_TUNE_PRUNE_KEYS = 11 /* silo_gpu_mutations_scan_ranges_min_proportion: 0 (default) skips the granules of escape keys that cannot
+                                        reach a filter's proportion; < 0 never skips one (the exact scan, for A/B runs) */,
        SILO_GPU_TUNE_SCAN_SPARSE_DIVISOR = 3 /* a filter with a set bit in <= row_words / divisor of its 64-byte sectors takes the gather scan (K1s); 0 = default 16, < 0 = off */ };
 int silo_gpu_tune(int knob, int value);
 
@@ -534,7 +556,8 @@ const char* silo_gpu_last_scan_kernel(void);
  * events of that thread's LAST scan and returns one entry per launch (at most `capacity`; *n_out = launches).  plane_rows =
  * plane rows the launch streams (each once, row_words * 8 bytes), filters = filter rows it holds in registers. */
 typedef struct silo_gpu_scan_timing {
-   char kernel[64];       /* e.g. "k_scan_sliced<2, 2, 8, 1, 2>", as rocprofv3 names it */
+   char kernel[64];       /* e.g. "k_scan_sliced<2, 2, 8, 1, 2>", as rocprofv3 names it; ", pruning" behind k_scan_escapes_sliced<N> where the
+                             launch may skip granules of keys (silo_gpu_mutations_scan_ranges_min_proportion) */
    uint64_t plane_rows;   /* plane rows a k_scan_sliced launch streams (0 for the other kernels) */
    uint64_t bytes;        /* what the launch has to read, each byte once: plane rows + filter rows; 8 bytes per escape key (+ a filter
                              slice per block); 12 bytes per run of the missing symbol; 8 per sparse key */

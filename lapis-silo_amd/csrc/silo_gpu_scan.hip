@@ -615,10 +615,17 @@ struct EscapeSliceArgs {
    uint32_t n_slices;
    uint32_t n_ranges;
    uint32_t block_keys;  // keys of a block's share: whole granules, at most ESCAPE_GRANULES_PER_BLOCK
+   // a scan that may leave out keys no Mutations row can come from (silo_gpu_mutations_scan_ranges_min_proportion): the counters of
+   // the prepare step ([q * SPARSE_COUNTER_STRIDE + 2] = the cardinality of filter q) and every filter's proportion; a range
+   // with bounds per granule (heaviest, without) skips the granules that granulePrunable() names for EVERY filter of the pass
+   const uint32_t* counters;
+   double min_proportion[SILO_GPU_MAX_SCAN_BATCH];
    struct Range {
       const uint32_t* keys;          // the packed slice-major keys of the store (SeqStoreHost::Layout::d_escapes_sliced or d_gaps_sliced)
       const uint32_t* granule_base;  // counter of every granule's first key
       const uint32_t* slice_first;   // [n_slices][positions + 1], in the packed numbering
+      const uint32_t* heaviest;      // per granule (SeqStoreHost::Layout::d_granule_heaviest), or nullptr: every granule is counted
+      const uint32_t* without;       // per granule (d_granule_without)
       uint32_t positions;
       uint32_t pos_begin;
       uint32_t pos_end;
@@ -630,6 +637,8 @@ struct EscapeSliceArgs {
       uint32_t* counts[SILO_GPU_MAX_SCAN_BATCH];  // of the range's first position
    } ranges[ESCAPE_MAX_RANGES];
 };
+
+static_assert(sizeof(EscapeSliceArgs) + sizeof(uint32_t) <= 4096, "k_scan_escapes_sliced takes its arguments by value: the kernel-argument segment holds 4 KiB");
 
 /// Workgroup barrier for data exchanged through LDS only: waits for the wave's LDS operations, NOT for its outstanding global
 /// loads — __syncthreads() is also a fence and drains vmcnt(0), which would stall a block on the loads it has prefetched for
@@ -664,7 +673,7 @@ constexpr uint32_t escapeWindow() {  // LDS counters per filter: 48 KiB of them 
 }
 template <int FILTERS>
 constexpr uint32_t escapeLdsBytes() {
-   return (FILTERS * (ESCAPE_SLICE_WORDS32 + escapeWindow<FILTERS>()) + ESCAPE_GRANULES_PER_BLOCK + 4u + 64u) * static_cast<uint32_t>(sizeof(uint32_t));
+   return (FILTERS * (ESCAPE_SLICE_WORDS32 + escapeWindow<FILTERS>()) + 3u * ESCAPE_GRANULES_PER_BLOCK + 4u + 64u) * static_cast<uint32_t>(sizeof(uint32_t));
 }
 
 template <int FILTERS>
@@ -673,8 +682,13 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
    static_assert(ESCAPE_GRANULE_KEYS == ESCAPE_SLICE_THREADS * 4u, "a granule is one 16-byte load per thread of the block");
    extern __shared__ uint32_t s_filter[];  // [FILTERS][ESCAPE_SLICE_WORDS32], then the counters [FILTERS][WINDOW], the granules' bases, the chunks' last keys
    uint32_t* s_count = s_filter + FILTERS * ESCAPE_SLICE_WORDS32;
-   uint32_t* s_base = s_count + FILTERS * WINDOW;  // [ESCAPE_GRANULES_PER_BLOCK + 1] the counter of every granule's first key, then one past the share's last key's
-   uint32_t* s_nowhere = s_base + ESCAPE_GRANULES_PER_BLOCK + 4u;  // [64] a word per lane: where an add of nothing goes
+   // the LIVE granules of the share — all of them, or those a pruning scan does not skip —, in order: the counter of each one's
+   // first key, one past the counter of its last key (the next granule's first; for the share's last granule one past its last
+   // key's), its number within the share; s_live[ESCAPE_GRANULES_PER_BLOCK] = how many there are
+   uint32_t* s_base = s_count + FILTERS * WINDOW;           // [ESCAPE_GRANULES_PER_BLOCK]
+   uint32_t* s_end = s_base + ESCAPE_GRANULES_PER_BLOCK;    // [ESCAPE_GRANULES_PER_BLOCK]
+   uint32_t* s_live = s_end + ESCAPE_GRANULES_PER_BLOCK;    // [ESCAPE_GRANULES_PER_BLOCK + 1]
+   uint32_t* s_nowhere = s_live + ESCAPE_GRANULES_PER_BLOCK + 4u;  // [64] a word per lane: where an add of nothing goes
    const uint32_t first_filter = blockIdx.z * FILTERS;
    uint32_t r = 0;
    while (r + 1u < args.n_ranges && blockIdx.x >= args.ranges[r + 1u].first_block) {  // (uniform)
@@ -703,10 +717,58 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
    // (unconditional: a load under a condition, or a loaded register handed on by a move, makes the compiler wait for ALL loads
    // in flight where the first is used — vmcnt(0) in the loop took a memory latency per granule: 86 us for 73 M keys.  A granule
    // past the share's last reads that one again; the whole granule exists, padded, past the slice's last key.)
-   const auto loadKeys = [&](uint32_t granule) {
-      const uint32_t g = min(granule, n_granules - 1u);
-      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(range.keys + share_begin + g * ESCAPE_GRANULE_KEYS + threadIdx.x * 4u));
+   const auto loadGranule = [&](uint32_t granule) {  // (its number within the share)
+      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(range.keys + share_begin + granule * ESCAPE_GRANULE_KEYS + threadIdx.x * 4u));
       return make_uint4(v.x, v.y, v.z, v.w);
+   };
+   // The list of live granules, by the block's first wave (a share has at most 64 granules: one per lane).  A pruning scan
+   // skips a granule where NO filter of the pass can report a row from its keys (granulePrunable: the select kernel's own
+   // arithmetic on a lower bound of the rows covered); the counts of such keys end up on the position's derived symbol.
+   const bool prune = range.heaviest != nullptr;  // (uniform)
+   const auto listGranules = [&]() {
+      if (threadIdx.x >= 64u) {
+         return;
+      }
+      const bool in_share = threadIdx.x < n_granules;
+      bool live = in_share;
+      if (prune && in_share) {
+         const uint32_t heaviest = range.heaviest[first_granule + threadIdx.x];
+         const uint32_t without = range.without[first_granule + threadIdx.x];
+         bool skip = true;
+#pragma unroll
+         for (int f = 0; f < FILTERS; ++f) {
+            if (first_filter + f < n_filters) {
+               skip = skip && granulePrunable(args.counters[(first_filter + f) * SPARSE_COUNTER_STRIDE + 2u], without, heaviest, args.min_proportion[first_filter + f]);
+            }
+         }
+         live = !skip;
+      }
+      const uint64_t live_lanes = __ballot(live);
+      if (live) {
+         const uint32_t k = static_cast<uint32_t>(__popcll(live_lanes & ((uint64_t{1} << threadIdx.x) - 1u)));
+         s_live[k] = threadIdx.x;
+         s_base[k] = range.granule_base[first_granule + threadIdx.x];
+         // (a key that went to the overflow list reads as the largest relative counter: a wider window, nothing else)
+         s_end[k] = threadIdx.x + 1u < n_granules ? range.granule_base[first_granule + threadIdx.x + 1u]
+                                                  : range.granule_base[first_granule + threadIdx.x] + (range.keys[share_end - 1u] >> ESCAPE_SLICE_SHIFT) + 1u;
+      }
+      if (threadIdx.x == 0) {
+         s_live[ESCAPE_GRANULES_PER_BLOCK] = static_cast<uint32_t>(__popcll(live_lanes));
+      }
+   };
+   // (the list's entries are the same for every lane: kept in scalar registers, not one vector register each)
+   const auto liveGranule = [&](uint32_t k) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(s_live[k]))); };
+   uint32_t n_live = n_granules;
+   if (prune) {  // (uniform) the list first: a block whose granules all skip leaves before it asks for its filter slices and keys
+      listGranules();
+      __syncthreads();
+      n_live = liveGranule(ESCAPE_GRANULES_PER_BLOCK);
+      if (n_live == 0) {
+         return;
+      }
+   }
+   const auto loadKeys = [&](uint32_t k) {  // the k-th live granule; past the last: that one again
+      return loadGranule(liveGranule(min(k, n_live - 1u)));
    };
    uint64_t any_bit = 0;
    ulonglong2 filter_part[FILTERS][ESCAPE_SLICE_WORDS32 / 4u / ESCAPE_SLICE_THREADS];
@@ -721,12 +783,12 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
          filter_part[f][j] = present && word < args.row_words ? *reinterpret_cast<const ulonglong2*>(filter + word) : make_ulonglong2(0, 0);
       }
    }
-   uint4 quad0 = loadKeys(0), quad1 = loadKeys(1), quad2 = loadKeys(2);  // three granules in flight per wave, in registers of their own
-   if (threadIdx.x < n_granules) {
-      s_base[threadIdx.x] = range.granule_base[first_granule + threadIdx.x];
-   }
-   if (threadIdx.x == 64u) {  // (a key that went to the overflow list reads as the largest relative counter: a wider window, nothing else)
-      s_base[n_granules] = range.granule_base[first_granule + n_granules - 1u] + (range.keys[share_end - 1u] >> ESCAPE_SLICE_SHIFT) + 1u;
+   // three granules in flight per wave, in registers of their own (without pruning the list is not written yet: granule k is live granule k)
+   uint4 quad0 = prune ? loadKeys(0) : loadGranule(0);
+   uint4 quad1 = prune ? loadKeys(1) : loadGranule(min(1u, n_granules - 1u));
+   uint4 quad2 = prune ? loadKeys(2) : loadGranule(min(2u, n_granules - 1u));
+   if (!prune) {
+      listGranules();
    }
    // Eight filters: their slices are kept as ONE BYTE PER ROW — bit f = filter f has the row — so that a key's lookup is one
    // LDS read for all eight (a read per filter and key made the eight-filter pass LDS-bound: 32 of its ~70 LDS instructions
@@ -777,12 +839,12 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
       const uint32_t first_counter = max(s_base[g], range_first);
       window_first = first_counter / out_symbols * out_symbols - range_first;
       uint32_t h = g + 1u;
-      while (h < n_granules && max(s_base[h + 1u], range_first) - range_first - window_first < WINDOW) {  // (a granule's last key may sit on the next one's first counter)
+      while (h < n_live && max(s_end[h], range_first) - range_first - window_first < WINDOW) {  // (a granule's last key may sit on the next one's first counter)
          ++h;
       }
       chunk_granules = h;
-      chunk_end = min(share_begin + h * ESCAPE_GRANULE_KEYS, share_end);
-      window_used = min(WINDOW, (max(s_base[h], range_first) / out_symbols + 1u) * out_symbols - range_first - window_first);
+      chunk_end = min(share_begin + (liveGranule(h - 1u) + 1u) * ESCAPE_GRANULE_KEYS, share_end);
+      window_used = min(WINDOW, (max(s_end[h - 1u], range_first) / out_symbols + 1u) * out_symbols - range_first - window_first);
    };
    // the chunk's window goes to the table — contiguous atomics, 64 consecutive counters per wave instruction — and is zero
    // again for the next chunk
@@ -801,8 +863,8 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
       }
       ldsBarrier();
    };
-   const auto countGranule = [&](uint4& in_flight, uint32_t g) {  // (g is uniform)
-      if (g >= n_granules) {
+   const auto countGranule = [&](uint4& in_flight, uint32_t g) {  // (g is uniform: the g-th live granule)
+      if (g >= n_live) {
          return;
       }
       if (g == chunk_granules) {
@@ -811,7 +873,7 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
       }
       const uint4 quad = in_flight;
       in_flight = loadKeys(g + 3u);
-      const uint32_t granule_first = share_begin + g * ESCAPE_GRANULE_KEYS;
+      const uint32_t granule_first = share_begin + liveGranule(g) * ESCAPE_GRANULE_KEYS;
       {
          const uint32_t granule_counter = s_base[g] - range_first - window_first;  // (wraps below the window: such keys are masked)
          const uint32_t i = granule_first + threadIdx.x * 4u;
@@ -961,7 +1023,7 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
       }
    };
    beginChunk(0);
-   for (uint32_t g = 0; g < n_granules; g += 3u) {  // (uniform)
+   for (uint32_t g = 0; g < n_live; g += 3u) {  // (uniform)
       countGranule(quad0, g);
       countGranule(quad1, g + 1u);
       countGranule(quad2, g + 2u);
@@ -1827,9 +1889,25 @@ int scanPiecesDense(
 /// sparse alike: the gather reads the same planes).
 /// The escape keys of `ranges`; with `gaps` (one entry per range: its store and positions, counts = the range's gap tables,
 /// null where it has none) also the gap events of their stores, in the same launches.
-int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream, const std::vector<ScanRange>* gaps = nullptr) {
+/// With `min_proportion` (one per filter; `counters` = the prepare step's, with the filters' cardinalities) the pass may skip the
+/// granules of keys that no Mutations row of that proportion can come from, where the store has the bounds for it
+/// (EscapeSliceArgs::counters); the gap events and the overflow keys are always counted.
+int scanEscapes(
+   const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream, const std::vector<ScanRange>* gaps = nullptr,
+   const uint32_t* counters = nullptr, const double* min_proportion = nullptr
+) {
    // the ranges whose stores have slice-major keys go ESCAPE_MAX_RANGES at a time into one launch of k_scan_escapes_sliced
    EscapeSliceArgs sliced{};
+   bool prune = gaps != nullptr && counters != nullptr && min_proportion != nullptr && g_tune_prune_keys.load() >= 0;
+   if (prune) {
+      bool any = false;
+      for (uint32_t q = 0; q < q_count; ++q) {
+         sliced.min_proportion[q] = min_proportion[q];
+         any = any || (min_proportion[q] > 0 && min_proportion[q] <= 1);
+      }
+      prune = any;  // (no filter with a proportion: nothing could be skipped)
+      sliced.counters = counters;
+   }
    uint32_t n_sliced = 0;
    std::array<uint32_t, ESCAPE_MAX_RANGES> most_keys{};  // of one (range, slice)
    uint64_t total_keys = 0;  // of the ranges of the launch
@@ -1861,7 +1939,11 @@ int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* fil
       }
       const dim3 grid(blocks, 1, passes);
       char name[64];
-      std::snprintf(name, sizeof(name), "k_scan_escapes_sliced<%u>", per_block);
+      bool bounds = false;  // a launch that may skip granules says so in the timing log (", pruning" behind the kernel's name)
+      for (uint32_t k = 0; k < n_sliced; ++k) {
+         bounds = bounds || sliced.ranges[k].heaviest != nullptr;
+      }
+      std::snprintf(name, sizeof(name), "k_scan_escapes_sliced<%u>%s", per_block, bounds ? ", pruning" : "");
       // bytes: the keys and gap events (4 each) once per pass of `per_block` filters, plus a 16 KiB filter slice per block and filter
       ScanLaunchTiming* timing = startLaunchTiming(
          name, 0, total_keys * sizeof(uint32_t) * grid.z + static_cast<uint64_t>(grid.x) * q_count * ESCAPE_SLICE_WORDS32 * sizeof(uint32_t), q_count,
@@ -1882,7 +1964,8 @@ int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* fil
    };
    // one entry of a launch: the packed keys (or gap events) of a store over [key_from, pos_end) of its positions
    const auto addSliced = [&](const ScanRange& range, uint32_t n_slices, const uint32_t* keys, const uint32_t* granule_base, const uint32_t* slice_first,
-                              const std::vector<uint32_t>& host_slice_first, uint32_t out_symbols, uint32_t key_from) -> int {
+                              const std::vector<uint32_t>& host_slice_first, uint32_t out_symbols, uint32_t key_from, const uint32_t* heaviest = nullptr,
+                              const uint32_t* without = nullptr) -> int {
       if (n_sliced == ESCAPE_MAX_RANGES || (n_sliced != 0 && sliced.n_slices != n_slices)) {
          if (const int rc = launchSliced(); rc != SILO_GPU_OK) {
             return rc;
@@ -1894,6 +1977,8 @@ int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* fil
       entry.keys = keys;
       entry.granule_base = granule_base;
       entry.slice_first = slice_first;
+      entry.heaviest = heaviest;
+      entry.without = without;
       entry.positions = range.seqstore->dev.positions;
       entry.pos_begin = range.pos_begin;
       entry.pos_end = range.pos_end;
@@ -1944,7 +2029,11 @@ int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* fil
             );
             HIP_TRY(hipGetLastError());
          }
-         if (const int rc = addSliced(range, layout.n_slices, layout.d_escapes_sliced, layout.d_granule_base, layout.d_slice_first, layout.slice_first, range.seqstore->dev.n_scan, range.pos_begin);
+         const bool bounds = prune && layout.d_granule_heaviest != nullptr && layout.d_granule_without != nullptr;
+         if (const int rc = addSliced(
+                range, layout.n_slices, layout.d_escapes_sliced, layout.d_granule_base, layout.d_slice_first, layout.slice_first, range.seqstore->dev.n_scan,
+                range.pos_begin, bounds ? layout.d_granule_heaviest : nullptr, bounds ? layout.d_granule_without : nullptr
+             );
              rc != SILO_GPU_OK) {
             return rc;
          }
@@ -2157,7 +2246,10 @@ int finishDerived(DerivedPlan& plan, uint32_t q_count, hipStream_t hip_stream) {
 /// that are bound by latency and LDS, not by bandwidth: the runs of the missing symbol and the sparse keys.  Forked behind
 /// everything already queued on `hip_stream` (the filters are complete, the tables zeroed), joined by joinSides before
 /// anything reads the tables.  SILO_GPU_TUNE_SIDE_STREAM: 0 as described, 1 side stream of default priority, 2 everything on the caller's stream.
-int forkSidePasses(const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, DerivedPlan* derived, hipStream_t hip_stream) {
+int forkSidePasses(
+   const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, DerivedPlan* derived, hipStream_t hip_stream,
+   const uint32_t* counters = nullptr, const double* min_proportion = nullptr
+) {
    bool any_escapes = false;
    for (const ScanRange& range : ranges) {
       const SeqStoreHost::Layout& layout = range.seqstore->layout;
@@ -2167,7 +2259,7 @@ int forkSidePasses(const std::vector<ScanRange>& ranges, const uint64_t* const* 
       return SILO_GPU_OK;
    }
    if (derived != nullptr && derived->events) {  // one pass over the keys and the gap events, on the caller's stream
-      return scanEscapes(ranges, filters, q_count, hip_stream, &derived->gap_ranges);
+      return scanEscapes(ranges, filters, q_count, hip_stream, &derived->gap_ranges, counters, min_proportion);
    }
    const int mode = g_tune_side_stream.load();
    SideStreams* side = mode == 2 ? nullptr : sideStreams();
@@ -2192,8 +2284,10 @@ int forkSidePasses(const std::vector<ScanRange>& ranges, const uint64_t* const* 
 /// sparse-filter routing (K1s) around the dense kernels: every filter is compacted ONCE for all ranges, the dense
 /// kernels skip the sparse ones, the gather kernel serves them.  All decisions are taken on the device.  Where a store
 /// derives the most numerous symbol of its positions the kernels count into private tables and k_finish_scan completes them.
+/// `min_proportion` (nullptr, or one per filter): see silo_gpu_mutations_scan_ranges_min_proportion.
 int scanRangesImpl(
-   const silo_gpu_store* store, const std::vector<ScanRange>& caller_ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream
+   const silo_gpu_store* store, const std::vector<ScanRange>& caller_ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream,
+   const double* min_proportion
 ) {
    const SeqStoreDev& any_store = caller_ranges.front().seqstore->dev;
    const bool nucleotide = any_store.n_bits == 3 && any_store.n_scan == 5;
@@ -2275,7 +2369,7 @@ int scanRangesImpl(
       }
       // the side passes are forked behind the prepare step: the plane scans wait for its counters, and beside a launch that
       // fills the device it takes ten times as long (62 instead of 6 us)
-      rc = forkSidePasses(ranges, filters, q_count, any_derived ? &plan : nullptr, hip_stream);
+      rc = forkSidePasses(ranges, filters, q_count, any_derived ? &plan : nullptr, hip_stream, counters, min_proportion);
       if (rc == SILO_GPU_OK) {
          rc = scanPiecesDense(pieces, any_store, filters, q_count, routing ? counters : nullptr, capacity, hip_stream);
       }
@@ -2313,10 +2407,18 @@ int scanRangesImpl(
 }  // namespace
 
 namespace silo_gpu_detail {
-int scanRanges(const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream) {
-   return scanRangesImpl(store, ranges, filters, q_count, hip_stream);
+int scanRanges(
+   const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream,
+   const double* min_proportion
+) {
+   return scanRangesImpl(store, ranges, filters, q_count, hip_stream, min_proportion);
 }
 }  // namespace silo_gpu_detail
+
+static int scanRangesEntry(
+   const char* entry, const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
+   const double* min_proportion, uint32_t* const* counts_out_dev, void* stream
+);
 
 extern "C" {
 
@@ -2328,18 +2430,35 @@ int silo_gpu_mutations_scan_ranges(
    const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
    uint32_t* const* counts_out_dev, void* stream
 ) {
+   return scanRangesEntry("silo_gpu_mutations_scan_ranges", store, ranges, n_ranges, filters_dev, n_filters, nullptr, counts_out_dev, stream);
+}
+
+int silo_gpu_mutations_scan_ranges_min_proportion(
+   const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
+   const double* min_proportion, uint32_t* const* counts_out_dev, void* stream
+) {
+   return scanRangesEntry("silo_gpu_mutations_scan_ranges_min_proportion", store, ranges, n_ranges, filters_dev, n_filters, min_proportion, counts_out_dev, stream);
+}
+
+}  // extern "C"
+
+/// The two entries above (`entry`: the one called, for its error messages).
+static int scanRangesEntry(
+   const char* entry, const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
+   const double* min_proportion, uint32_t* const* counts_out_dev, void* stream
+) {
    if (store == nullptr || (n_ranges != 0 && ranges == nullptr) || (n_filters != 0 && filters_dev == nullptr) ||
        (n_ranges != 0 && n_filters != 0 && counts_out_dev == nullptr)) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_mutations_scan_ranges: bad arguments");
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": bad arguments");
    }
    for (uint32_t q = 0; q < n_filters; ++q) {
       if (filters_dev[q] == nullptr) {
-         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_mutations_scan_ranges: null filter");
+         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": null filter");
       }
    }
    for (uint32_t r = 0; r < n_ranges; ++r) {
       if (ranges[r].seqstore_id >= store->seqstores.size()) {
-         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_mutations_scan_ranges: no such sequence store");
+         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": no such sequence store");
       }
       const SeqStoreDev& dev = store->seqstores[ranges[r].seqstore_id].dev;
       if (ranges[r].pos_begin > ranges[r].pos_end || ranges[r].pos_end > dev.positions) {
@@ -2347,7 +2466,7 @@ int silo_gpu_mutations_scan_ranges(
       }
       for (uint32_t q = 0; q < n_filters; ++q) {
          if (counts_out_dev[static_cast<size_t>(r) * n_filters + q] == nullptr) {
-            return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_mutations_scan_ranges: null counts buffer");
+            return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": null counts buffer");
          }
       }
    }
@@ -2368,7 +2487,7 @@ int silo_gpu_mutations_scan_ranges(
             }
             const SeqStoreHost& seqstore = store->seqstores[ranges[r].seqstore_id];
             if (dev.planes == nullptr) {
-               return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_mutations_scan_ranges: the sequence store holds no sequences yet");
+               return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": the sequence store holds no sequences yet");
             }
             ScanRange range{&seqstore, ranges[r].pos_begin, ranges[r].pos_end, {}};
             for (uint32_t q = 0; q < q_count; ++q) {
@@ -2377,7 +2496,7 @@ int silo_gpu_mutations_scan_ranges(
             group.push_back(range);
          }
          if (!group.empty()) {
-            const int rc = scanRanges(store, group, filters_dev + first, q_count, hip_stream);
+            const int rc = scanRanges(store, group, filters_dev + first, q_count, hip_stream, min_proportion != nullptr ? min_proportion + first : nullptr);
             if (rc != SILO_GPU_OK) {
                return rc;
             }
@@ -2386,6 +2505,8 @@ int silo_gpu_mutations_scan_ranges(
    }
    return SILO_GPU_OK;
 }
+
+extern "C" {
 
 int silo_gpu_scan_timings(silo_gpu_scan_timing* out, uint32_t capacity, uint32_t* n_out) {
    if (n_out == nullptr || (capacity != 0 && out == nullptr)) {
@@ -2463,6 +2584,21 @@ uint64_t silo_gpu_store_scan_sparse_keys(const silo_gpu_store* store, uint32_t s
       return 0;
    }
    return store->seqstores[seqstore_id].sparse_sorted.size();
+}
+
+int silo_gpu_store_scan_prunable_granules(
+   const silo_gpu_store* store, uint32_t seqstore_id, uint32_t cardinality, double min_proportion, uint64_t* out_skippable, uint64_t* out_total
+) {
+   if (store == nullptr || seqstore_id >= store->seqstores.size() || out_skippable == nullptr || out_total == nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_store_scan_prunable_granules: bad arguments");
+   }
+   const SeqStoreHost::Layout& layout = store->seqstores[seqstore_id].layout;
+   *out_total = layout.packed_keys / ESCAPE_GRANULE_KEYS;
+   *out_skippable = 0;
+   for (size_t g = 0; g < layout.granule_heaviest.size(); ++g) {  // (empty where the store has no bounds)
+      *out_skippable += granulePrunable(cardinality, layout.granule_without[g], layout.granule_heaviest[g], min_proportion) ? 1 : 0;
+   }
+   return SILO_GPU_OK;
 }
 
 uint64_t silo_gpu_store_scan_escapes(const silo_gpu_store* store, uint32_t seqstore_id) {

@@ -796,6 +796,8 @@ void silo_gpu_store_destroy(silo_gpu_store* store) {
       (void)hipFree(seqstore.layout.d_gaps_sliced);
       (void)hipFree(seqstore.layout.d_gap_granule_base);
       (void)hipFree(seqstore.layout.d_gap_slice_first);
+      (void)hipFree(seqstore.layout.d_granule_heaviest);
+      (void)hipFree(seqstore.layout.d_granule_without);
       (void)hipFree(seqstore.layout.d_escape_first);
    }
    (void)hipFree(store->d_ones);
@@ -1409,6 +1411,149 @@ int buildGapEvents(silo_gpu_store* store, SeqStoreHost& seqstore) {
    return SILO_GPU_OK;
 }
 
+/// +1 where a run of the missing symbol starts, -1 where it ends: summed along the positions, the rows with the missing symbol.
+__global__ void k_runs_diff_all(const uint64_t* __restrict__ run_keys, const uint32_t* __restrict__ run_ends, uint32_t n_runs, uint32_t* __restrict__ diff) {
+   const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x;
+   if (run < n_runs) {
+      atomicAdd(&diff[static_cast<uint32_t>(run_keys[run])], 1u);
+      atomicAdd(&diff[run_ends[run]], 0xFFFFFFFFu);
+   }
+}
+
+/// without[p] = the rows of the store without a valid symbol at position p: those inside a run of the missing symbol plus the
+/// sparsely stored symbols (ambiguity codes) there — what the gap events of the store count under the full filter.
+int rowsWithoutSymbol(const SeqStoreHost& seqstore, std::vector<uint32_t>& without) {
+   const SeqStoreDev& dev = seqstore.dev;
+   const uint32_t positions = dev.positions;
+   std::vector<uint32_t> diff(positions + 1, 0);
+   if (dev.n_missing_runs != 0) {
+      uint32_t* d_diff = nullptr;
+      HIP_TRY(hipMalloc(&d_diff, diff.size() * sizeof(uint32_t)));
+      hipError_t status = hipMemset(d_diff, 0, diff.size() * sizeof(uint32_t));
+      if (status == hipSuccess) {
+         k_runs_diff_all<<<(dev.n_missing_runs + 255) / 256, 256>>>(dev.missing_run_keys, dev.missing_run_ends, dev.n_missing_runs, d_diff);
+         status = hipGetLastError();
+      }
+      status = status != hipSuccess ? status : hipMemcpy(diff.data(), d_diff, diff.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+      (void)hipFree(d_diff);
+      HIP_TRY(status);
+   }
+   without.assign(positions, 0);
+   uint32_t missing = 0;
+   for (uint32_t p = 0; p < positions; ++p) {
+      missing += diff[p];
+      without[p] = missing;
+   }
+   for (const uint64_t key : seqstore.sparse_sorted) {
+      const uint64_t position = key >> 37;
+      if (position < positions) {
+         without[position] += 1;
+      }
+   }
+   return SILO_GPU_OK;
+}
+
+/// The two bounds of a granule of slice-major escape keys (SeqStoreHost::Layout::d_granule_heaviest, d_granule_without): the
+/// largest weight[counter] and the largest without[position] over its keys; one block per granule.  A key that went to the
+/// overflow list is no part of the stream and of its bounds.
+__global__ __launch_bounds__(256) void k_granule_bounds(
+   const uint32_t* __restrict__ packed, const uint32_t* __restrict__ granule_base, const uint32_t* __restrict__ weight, const uint32_t* __restrict__ without,
+   uint32_t n_scan, uint32_t n_counters, uint32_t* __restrict__ heaviest_out, uint32_t* __restrict__ without_out
+) {
+   __shared__ uint32_t s_bounds[2];
+   if (threadIdx.x < 2) {
+      s_bounds[threadIdx.x] = 0;
+   }
+   __syncthreads();
+   const uint32_t granule = blockIdx.x;
+   const uint32_t base = granule_base[granule];
+   uint32_t heaviest = 0, rows_without = 0;
+   for (uint32_t k = threadIdx.x; k < ESCAPE_GRANULE_KEYS; k += blockDim.x) {
+      const uint32_t key = packed[static_cast<size_t>(granule) * ESCAPE_GRANULE_KEYS + k];
+      if (key != ESCAPE_KEY_INVALID) {
+         const uint32_t counter = base + (key >> ESCAPE_SLICE_SHIFT);
+         heaviest = max(heaviest, counter < n_counters ? weight[counter] : 0xFFFFFFFFu);
+         rows_without = max(rows_without, counter < n_counters ? without[counter / n_scan] : 0xFFFFFFFFu);
+      }
+   }
+   atomicMax(&s_bounds[0], heaviest);
+   atomicMax(&s_bounds[1], rows_without);
+   __syncthreads();
+   if (threadIdx.x == 0) {
+      heaviest_out[granule] = s_bounds[0];
+      without_out[granule] = s_bounds[1];
+   }
+}
+
+/// The bounds per granule of escape keys that let a Mutations scan leave out keys no reported row can come from
+/// (silo_gpu_mutations_scan_ranges_min_proportion).  At a position whose derived symbol is the reference's, the keys of a
+/// (position, symbol) group that is small against the filter only move their count onto a symbol that is never reported; what
+/// "small" means needs the group's size in the whole store and the rows of the store without a valid symbol at the position.
+/// Built only where the store has its gap events (the scan prunes on that path alone).
+int buildPruneBounds(silo_gpu_store* store, SeqStoreHost& seqstore) {
+   SeqStoreHost::Layout& layout = seqstore.layout;
+   const SeqStoreDev& dev = seqstore.dev;
+   if (!layout.built || !layout.has_implicit || !layout.gap_stream || layout.d_escapes_sliced == nullptr || layout.d_granule_heaviest != nullptr) {
+      return SILO_GPU_OK;
+   }
+   const uint32_t positions = dev.positions;
+   const size_t n_counters = static_cast<size_t>(positions) * dev.n_scan;
+   const size_t n_granules = layout.packed_keys / ESCAPE_GRANULE_KEYS;
+   if (n_granules == 0 || n_counters >= (uint64_t{1} << 32)) {
+      return SILO_GPU_OK;
+   }
+   std::vector<uint32_t> without;
+   if (const int rc = rowsWithoutSymbol(seqstore, without); rc != SILO_GPU_OK) {
+      return rc;
+   }
+   // the keys of a (position, symbol) in the whole store; UINT32_MAX — never left out — where the position derives no symbol or
+   // another one than the reference's (that symbol is reported, so its count has to be exact)
+   std::vector<uint32_t> weight(n_counters);
+   for (uint32_t p = 0; p < positions; ++p) {
+      const uint8_t* map = layout.code_map.data() + static_cast<size_t>(p) * CODE_MAP_STRIDE;
+      const uint8_t reference = seqstore.reference[p];
+      const bool prunable = (map[0] & LAYOUT_IMPLICIT) != 0 && reference < dev.n_symbols && dev.kind[reference] == PLANE_SCAN && dev.index[reference] == map[IMPLICIT_SLOT];
+      for (uint32_t symbol = 0; symbol < dev.n_scan; ++symbol) {
+         const size_t counter = static_cast<size_t>(p) * dev.n_scan + symbol;
+         weight[counter] = prunable ? layout.escape_first_symbol[counter + 1] - layout.escape_first_symbol[counter] : 0xFFFFFFFFu;
+      }
+   }
+   uint32_t* d_weight = nullptr;
+   uint32_t* d_without = nullptr;
+   layout.granule_heaviest.assign(n_granules, 0xFFFFFFFFu);
+   layout.granule_without.assign(n_granules, 0xFFFFFFFFu);
+   hipError_t status = hipMalloc(&d_weight, n_counters * sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMalloc(&d_without, static_cast<size_t>(positions) * sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMalloc(&layout.d_granule_heaviest, n_granules * sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMalloc(&layout.d_granule_without, n_granules * sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMemcpy(d_weight, weight.data(), n_counters * sizeof(uint32_t), hipMemcpyHostToDevice);
+   status = status != hipSuccess ? status : hipMemcpy(d_without, without.data(), static_cast<size_t>(positions) * sizeof(uint32_t), hipMemcpyHostToDevice);
+   if (status == hipSuccess) {
+      k_granule_bounds<<<static_cast<uint32_t>(n_granules), 256>>>(
+         layout.d_escapes_sliced, layout.d_granule_base, d_weight, d_without, dev.n_scan, static_cast<uint32_t>(n_counters), layout.d_granule_heaviest,
+         layout.d_granule_without
+      );
+      status = hipGetLastError();
+   }
+   status = status != hipSuccess ? status : hipMemcpy(layout.granule_heaviest.data(), layout.d_granule_heaviest, n_granules * sizeof(uint32_t), hipMemcpyDeviceToHost);
+   status = status != hipSuccess ? status : hipMemcpy(layout.granule_without.data(), layout.d_granule_without, n_granules * sizeof(uint32_t), hipMemcpyDeviceToHost);
+   (void)hipFree(d_weight);
+   (void)hipFree(d_without);
+   if (status != hipSuccess) {
+      (void)hipFree(layout.d_granule_heaviest);
+      (void)hipFree(layout.d_granule_without);
+      layout.d_granule_heaviest = nullptr;
+      layout.d_granule_without = nullptr;
+      layout.granule_heaviest.clear();
+      layout.granule_without.clear();
+      HIP_TRY(status);
+   }
+   const uint64_t bytes = 2u * n_granules * sizeof(uint32_t);
+   layout.device_bytes += bytes;
+   store->device_bytes += bytes;
+   return SILO_GPU_OK;
+}
+
 int finalizeSeqStore(silo_gpu_store* store, SeqStoreHost& seqstore) {
    if (seqstore.layout.built) {
       return SILO_GPU_OK;
@@ -1444,7 +1589,10 @@ int finalizeSeqStore(silo_gpu_store* store, SeqStoreHost& seqstore) {
    if (const int rc = buildRunSliceIndex(store, seqstore); rc != SILO_GPU_OK) {
       return rc;
    }
-   return buildGapEvents(store, seqstore);
+   if (const int rc = buildGapEvents(store, seqstore); rc != SILO_GPU_OK) {
+      return rc;
+   }
+   return buildPruneBounds(store, seqstore);
 }
 }  // namespace
 
@@ -1777,15 +1925,6 @@ int finishLayout(silo_gpu_store* store, SeqStoreHost& seqstore, SeqStoreHost::La
    return SILO_GPU_OK;
 }
 
-/// +1 where a run of the missing symbol starts, -1 where it ends: summed along the positions, the rows with the missing symbol.
-__global__ void k_runs_diff_all(const uint64_t* __restrict__ run_keys, const uint32_t* __restrict__ run_ends, uint32_t n_runs, uint32_t* __restrict__ diff) {
-   const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x;
-   if (run < n_runs) {
-      atomicAdd(&diff[static_cast<uint32_t>(run_keys[run])], 1u);
-      atomicAdd(&diff[run_ends[run]], 0xFFFFFFFFu);
-   }
-}
-
 /// Does every row of the store have a symbol at every position — a valid one (the totals), the missing one (its runs) or a
 /// sparsely stored one (the sorted keys)?  Rows that never received a sequence, or an import whose bitmaps leave rows out,
 /// do not; such a store derives nothing (the derived symbol would take them in).
@@ -1798,30 +1937,12 @@ int everyRowHasASymbol(const silo_gpu_store* store, const SeqStoreHost& seqstore
    }
    std::vector<uint32_t> totals(static_cast<size_t>(positions) * dev.n_scan);
    HIP_TRY(hipMemcpy(totals.data(), seqstore.d_totals, totals.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-   std::vector<uint32_t> diff(positions + 1, 0);
-   if (dev.n_missing_runs != 0) {
-      uint32_t* d_diff = nullptr;
-      HIP_TRY(hipMalloc(&d_diff, diff.size() * sizeof(uint32_t)));
-      hipError_t status = hipMemset(d_diff, 0, diff.size() * sizeof(uint32_t));
-      if (status == hipSuccess) {
-         k_runs_diff_all<<<(dev.n_missing_runs + 255) / 256, 256>>>(dev.missing_run_keys, dev.missing_run_ends, dev.n_missing_runs, d_diff);
-         status = hipGetLastError();
-      }
-      status = status != hipSuccess ? status : hipMemcpy(diff.data(), d_diff, diff.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-      (void)hipFree(d_diff);
-      HIP_TRY(status);
+   std::vector<uint32_t> without;
+   if (const int rc = rowsWithoutSymbol(seqstore, without); rc != SILO_GPU_OK) {
+      return rc;
    }
-   std::vector<uint32_t> sparse(positions, 0);
-   for (const uint64_t key : seqstore.sparse_sorted) {
-      const uint64_t position = key >> 37;
-      if (position < positions) {
-         sparse[position] += 1;
-      }
-   }
-   uint32_t missing = 0;
    for (uint32_t p = 0; p < positions; ++p) {
-      missing += diff[p];
-      uint64_t covered = static_cast<uint64_t>(missing) + sparse[p];
+      uint64_t covered = without[p];
       for (uint32_t symbol = 0; symbol < dev.n_scan; ++symbol) {
          covered += totals[static_cast<size_t>(p) * dev.n_scan + symbol];
       }

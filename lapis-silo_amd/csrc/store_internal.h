@@ -28,6 +28,7 @@ extern std::atomic<int> g_tune_scan_variant;
 extern std::atomic<int> g_tune_eval_leaf_batch;
 extern std::atomic<int> g_tune_compact_index;   // < 0: finalize keeps the build-time identity planes; 2 / 3: see SILO_GPU_TUNE_COMPACT_INDEX
 extern std::atomic<int> g_tune_gap_events;      // < 0: scans of derived symbols take the runs and the sparse keys by themselves (planDerived)
+extern std::atomic<int> g_tune_prune_keys;      // < 0: silo_gpu_mutations_scan_ranges_min_proportion skips no granule of escape keys (scanEscapes)
 extern std::atomic<int> g_tune_side_stream;     // the side passes of a scan: see forkSidePasses (silo_gpu_scan.hip)
 extern std::atomic<int> g_tune_scan_timing;     // 1: HIP events around every launch of a scan (silo_gpu_scan_timings)
 extern std::atomic<int> g_tune_missing_runs;    // < 0: finalize keeps the plane of the missing symbol instead of turning it into runs
@@ -309,7 +310,16 @@ struct SeqStoreHost {
       uint32_t* d_gap_slice_first = nullptr;  // [gap_slices][P + 1]
       uint32_t gap_slices = 0;
       std::vector<uint32_t> gap_slice_first;  // host copy
-            uint64_t gap_packed = 0;                // slots of d_gaps_sliced
+      uint64_t gap_packed = 0;                // slots of d_gaps_sliced
+      // two bounds per granule of d_escapes_sliced, for a scan that may leave out the keys no Mutations row can come from
+      // (silo_gpu_mutations_scan_ranges_min_proportion; buildPruneBounds).  heaviest: the most keys the whole store has of a
+      // (position, symbol) with a key in the granule — UINT32_MAX where one of its keys lies at a position that derives no
+      // symbol or derives another one than the reference's.  without: the most rows without a valid symbol (inside a run of
+      // the missing symbol, ambiguity codes) at a position of the granule.  Built only beside the gap events.
+      uint32_t* d_granule_heaviest = nullptr;
+      uint32_t* d_granule_without = nullptr;
+      std::vector<uint32_t> granule_heaviest;  // host copies
+      std::vector<uint32_t> granule_without;
    } layout;
 };
 
@@ -449,6 +459,19 @@ constexpr uint32_t ESCAPE_KEY_INVALID = 0xFFFFFFFFu;           // padding / a ke
 constexpr uint32_t ESCAPE_MAX_RELATIVE = 6000u;
 constexpr uint32_t GAP_MAX_SPAN = (ESCAPE_MAX_RELATIVE + 1u - 2u) / 2u;  // positions a granule of gap events spans at most (2 counters each)
 
+/// May a scan for Mutations rows of at least `min_proportion` skip a granule of escape keys with these bounds, under a filter of
+/// `cardinality` rows?  The rows of the filter with a valid symbol at a position of the granule are at least cov_min =
+/// cardinality - without, k_mutations_select reports a cell only above ceil(covered * min_proportion) - 1, and that threshold is
+/// monotone in covered: a (position, symbol) whose keys in the WHOLE store are no more than the threshold at cov_min cannot be
+/// reported, whatever the filter selects.  The arithmetic is the select kernel's (IEEE double).
+__host__ __device__ inline bool granulePrunable(uint32_t cardinality, uint32_t without, uint32_t heaviest, double min_proportion) {
+   if (!(min_proportion > 0) || min_proportion > 1 || cardinality <= without) {
+      return false;
+   }
+   const uint32_t must_exceed = static_cast<uint32_t>(ceil(static_cast<double>(cardinality - without) * min_proportion) - 1);
+   return heaviest <= must_exceed;
+}
+
 /// A position range of one sequence store with the count tables of every filter of the launch.
 struct ScanRange {
    const SeqStoreHost* seqstore;
@@ -459,7 +482,11 @@ struct ScanRange {
 
 /// The Mutations scan of `q_count` filters over position ranges of sequence stores of one alphabet (silo_gpu_scan.hip); finalize
 /// uses it for the unfiltered totals that decide the layout.
-int scanRanges(const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream);
+/// min_proportion: nullptr, or one proportion per filter (silo_gpu_mutations_scan_ranges_min_proportion).
+int scanRanges(
+   const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream,
+   const double* min_proportion = nullptr
+);
 
 // host helpers of the store (silo_gpu_store.hip)
 int ensureDevice(int device);

@@ -160,6 +160,7 @@ void ScanBatcher::flush() {
    struct FilterScans {
       silo_gpu_store* store;
       const uint64_t* filter;
+      double min_proportion;  // of every range of the entry (Request::min_proportion)
       std::vector<silo_gpu_scan_range> ranges;
       std::vector<uint32_t*> counts;
    };
@@ -178,14 +179,14 @@ void ScanBatcher::flush() {
       const silo_gpu_scan_range range{request.seqstore_id, request.pos_begin, request.pos_end};
       FilterScans* entry = nullptr;
       for (FilterScans& candidate : by_filter) {
-         if (candidate.store == request.store && candidate.filter == request.filter &&
+         if (candidate.store == request.store && candidate.filter == request.filter && candidate.min_proportion == request.min_proportion &&
              std::none_of(candidate.ranges.begin(), candidate.ranges.end(), [&](const auto& other) { return same_range(other, range); })) {
             entry = &candidate;
             break;
          }
       }
       if (entry == nullptr) {
-         by_filter.push_back({request.store, request.filter, {}, {}});
+         by_filter.push_back({request.store, request.filter, request.min_proportion, {}, {}});
          entry = &by_filter.back();
       }
       entry->ranges.push_back(range);
@@ -207,8 +208,10 @@ void ScanBatcher::flush() {
          }
       }
       std::vector<const uint64_t*> filters;
+      std::vector<double> proportions;  // per filter: what its table will be selected with (0: every cell exact)
       for (const size_t k : group) {
          filters.push_back(by_filter[k].filter);
+         proportions.push_back(by_filter[k].min_proportion);
       }
       std::vector<uint32_t*> counts;  // [range][filter]
       for (size_t r = 0; r < first.ranges.size(); ++r) {
@@ -217,11 +220,11 @@ void ScanBatcher::flush() {
          }
       }
       checkGpu(
-         silo_gpu_mutations_scan_ranges(
+         silo_gpu_mutations_scan_ranges_min_proportion(
             first.store, first.ranges.data(), static_cast<uint32_t>(first.ranges.size()), filters.data(), static_cast<uint32_t>(filters.size()),
-            counts.data(), queryStream()
+            proportions.data(), counts.data(), queryStream()
          ),
-         "silo_gpu_mutations_scan_ranges"
+         "silo_gpu_mutations_scan_ranges_min_proportion"
       );
    }
    requests.clear();
@@ -300,7 +303,8 @@ std::map<std::string, typename Mutations<SymbolType>::PrefilteredBitmaps> Mutati
 
 template <typename SymbolType>
 void Mutations<SymbolType>::calculateMutationsPerPosition(
-   const Database& database, const SequenceStore<SymbolType>& sequence_store, const PrefilteredBitmaps& bitmap_filter, uint32_t* device_counts
+   const Database& database, const SequenceStore<SymbolType>& sequence_store, const PrefilteredBitmaps& bitmap_filter, uint32_t* device_counts,
+   double min_proportion
 ) {
    // mutations.cpp:139-164 runs and_cardinality(filter, column) per position x symbol under
    // tbb::parallel_for; here each (partition, sequence store) is ONE scan kernel (K1) that accumulates
@@ -313,9 +317,13 @@ void Mutations<SymbolType>::calculateMutationsPerPosition(
    // the device store of a rank holds exactly its window: local positions [0, pos_end - pos_begin)
    const uint32_t local_positions = pos_end - pos_begin;
    ScanBatcher* batcher = ScanBatcher::active();  // inside a batch of queries the scans are only recorded
+   // A scan may leave out keys below the proportion only where it is the ONLY scan into this slice of the table (a group of keys
+   // left out in one partition and counted in another would give a wrong sum) and the table is not summed across ranks.
+   const bool single_scan = bitmap_filter.bitmaps.size() + bitmap_filter.full_bitmaps.size() == 1 && database.all_reduce == nullptr;
+   const double prunable = single_scan && min_proportion > 0 ? min_proportion : 0;
    const auto scan = [&](const SequenceStorePartition<SymbolType>& store, const uint64_t* filter) {
       if (batcher != nullptr) {
-         batcher->add({store.store, store.seqstore_id, filter, 0, local_positions, window});
+         batcher->add({store.store, store.seqstore_id, filter, 0, local_positions, window, filter != nullptr ? prunable : 0});
       } else {
          checkGpu(
             silo_gpu_mutations_scan(store.store, store.seqstore_id, filter, 0, local_positions, window, queryStream()), "silo_gpu_mutations_scan"
@@ -442,7 +450,7 @@ std::unique_ptr<Action::Pending> Mutations<SymbolType>::begin(const Database& da
       const auto found = bitmaps_to_evaluate.find(sequence_name);
       calculateMutationsPerPosition(
          database, sequence_store, found != bitmaps_to_evaluate.end() ? found->second : no_bitmaps,
-         device_counts + static_cast<size_t>(layout.position_offset.at(sequence_name)) * n_symbols
+         device_counts + static_cast<size_t>(layout.position_offset.at(sequence_name)) * n_symbols, min_proportion
       );
    }
    Trace::mark("scan_launched");

@@ -534,6 +534,10 @@ class ScanBatcher {
       const uint64_t* filter;  // nullptr = full filter
       uint32_t pos_begin, pos_end;
       uint32_t* counts;
+      /// > 0: the table is read by the row selection of a Mutations action with this minProportion and by nothing else, and no
+      /// other scan adds into this store's part of it — the scan may then leave out escape keys that cannot reach the proportion
+      /// (silo_gpu_mutations_scan_ranges_min_proportion).  0: every cell exact.
+      double min_proportion = 0;
    };
    ScanBatcher();
    ~ScanBatcher();
@@ -690,9 +694,11 @@ class Mutations : public Action {
 
    /// Launches the K1 scans of one sequence store into its slice counts[position][valid symbol] of the query's
    /// count table (accumulating over partitions); returns with the scans in flight on this thread's stream.
+   /// min_proportion > 0: the table is read by this action's row selection alone; where ONE scan fills the store's slice, that
+   /// scan may leave out escape keys that cannot reach the proportion (ScanBatcher::Request::min_proportion).
    static void calculateMutationsPerPosition(
       const Database& database, const SequenceStore<SymbolType>& sequence_store, const PrefilteredBitmaps& bitmap_filter,
-      uint32_t* device_counts
+      uint32_t* device_counts, double min_proportion = 0
    );
 
    /// `counts` = the slice counts[position][valid symbol] of one store, on the host.

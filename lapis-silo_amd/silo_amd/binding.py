@@ -108,6 +108,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_event_destroy", "silo_gpu_event_synchronize", "silo_gpu_host_alloc", "silo_gpu_host_free", "silo_gpu_memcpy_d2h_async", "silo_gpu_mutations_select", "silo_gpu_upload_bytes", "silo_gpu_upload_column", "silo_gpu_bitset_from_compare", "silo_gpu_group_count", "silo_gpu_group_count_hashed", "silo_gpu_reconstruct_sequences", "silo_gpu_bitset_from_pairs", "silo_gpu_count_pairs", "silo_gpu_count_slot_create", "silo_gpu_count_slot_destroy", "silo_gpu_filter_eval_count", "silo_gpu_count_slot_wait", "silo_gpu_tune", "silo_gpu_last_scan_kernel", "silo_gpu_scan_timings", "silo_gpu_stream_read_probe", "silo_gpu_last_error",
     "silo_gpu_comm_unique_id", "silo_gpu_comm_create", "silo_gpu_comm_destroy", "silo_gpu_comm_rank", "silo_gpu_comm_world",
     "silo_gpu_allreduce_counts", "silo_gpu_broadcast_bytes",
+    "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules",
 ]
 
 _lib = None
@@ -164,6 +165,10 @@ def load_library():
     lib.silo_gpu_store_scan_escapes.argtypes = [vp, ctypes.c_uint32]
     lib.silo_gpu_store_scan_escapes.restype = ctypes.c_uint64
     lib.silo_gpu_mutations_scan_ranges.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32, ctypes.POINTER(vp), vp]
+    lib.silo_gpu_mutations_scan_ranges_min_proportion.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32,
+                                                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(vp), vp]
+    lib.silo_gpu_store_scan_prunable_granules.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64),
+                                                          ctypes.POINTER(ctypes.c_uint64)]
     lib.silo_gpu_mutations_grouped.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
@@ -676,9 +681,16 @@ class GpuStore:
     def scan_escapes(self, seqstore_id):
         return self.lib.silo_gpu_store_scan_escapes(self.handle, seqstore_id)
 
-    def mutations_scan_ranges(self, ranges, filter_ptrs, stream=None):
+    def scan_prunable_granules(self, seqstore_id, cardinality, min_proportion):
+        """(skippable, total) granules of the store's slice-major escape keys for one filter of `cardinality` rows."""
+        skippable, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(self.lib.silo_gpu_store_scan_prunable_granules(self.handle, seqstore_id, int(cardinality), ctypes.c_double(min_proportion),
+                                                              ctypes.byref(skippable), ctypes.byref(total)))
+        return skippable.value, total.value
+
+    def mutations_scan_ranges(self, ranges, filter_ptrs, stream=None, min_proportions=None):
         """Every filter over every (seqstore_id, pos_begin, pos_end) range in as few launches as the layouts allow;
-        returns tables[range][filter]."""
+        returns tables[range][filter].  min_proportions (one per filter): silo_gpu_mutations_scan_ranges_min_proportion."""
         flat = (ctypes.c_uint32 * (3 * len(ranges)))(*[int(v) for r in ranges for v in r])  # silo_gpu_scan_range[]
         outs = []
         for seqstore_id, pos_begin, pos_end in ranges:
@@ -689,7 +701,11 @@ class GpuStore:
                 outs.append(buf)
         filters = (ctypes.c_void_p * len(filter_ptrs))(*[(f.value if isinstance(f, ctypes.c_void_p) else f) for f in filter_ptrs])
         counts = (ctypes.c_void_p * max(1, len(outs)))(*[o.value for o in outs])
-        _check(self.lib.silo_gpu_mutations_scan_ranges(self.handle, flat, len(ranges), filters, len(filter_ptrs), counts, stream))
+        if min_proportions is None:
+            _check(self.lib.silo_gpu_mutations_scan_ranges(self.handle, flat, len(ranges), filters, len(filter_ptrs), counts, stream))
+        else:
+            proportions = (ctypes.c_double * max(1, len(filter_ptrs)))(*[float(p) for p in min_proportions])
+            _check(self.lib.silo_gpu_mutations_scan_ranges_min_proportion(self.handle, flat, len(ranges), filters, len(filter_ptrs), proportions, counts, stream))
         tables = []
         for r, (seqstore_id, pos_begin, pos_end) in enumerate(ranges):
             n_scan = len(self.scan_symbols[seqstore_id])
