@@ -415,6 +415,16 @@ def filter_eval_batch(store_handle, programs, out_bitsets=None, stream=None):
     return PreparedPrograms(programs, out_bitsets).launch(store_handle, stream)
 
 
+MAX_DATE_RANGES = 1024         # SILO_GPU_MAX_DATE_RANGES
+MAX_GROUPED_MUTATIONS = 4096   # SILO_GPU_MAX_GROUPED_MUTATIONS
+_OWN_SCRATCH = object()
+
+
+def grouped_scratch_bytes(row_words, n_ranges, n_mutations):
+    """SILO_GPU_GROUPED_SCRATCH_BYTES: the scratch silo_gpu_mutations_grouped needs."""
+    return row_words * 128 + n_mutations * 32 + n_ranges * 16 + n_ranges * 4 * (1 + 3 * n_mutations) + 1024
+
+
 class GpuStore:
     """One device shard: the dense restatement of a DatabasePartition's sequence stores."""
 
@@ -714,6 +724,45 @@ class GpuStore:
         for o in outs:
             self.free(o)
         return tables
+
+    def mutations_grouped(self, seqstore_id, filter_ptr, dates_ptr, ranges, positions, symbols, out_ptr=None, stream=None, return_groups=False,
+                          scratch_ptr=_OWN_SCRATCH):
+        """silo_gpu_mutations_grouped (K7).  ranges: (from, to) uint32 pairs in request order; positions / symbols: the listed
+        cells; dates_ptr: a device column of uint32 dates (upload_column).  Without out_ptr: a zeroed table for the call, returned
+        as uint32 [M][G][2] (count, coverage).  With out_ptr: accumulates into the caller's device table and returns nothing.
+        return_groups: also (or only, with out_ptr) the per-row range ids the call leaves at the start of its scratch, uint16
+        [row_words * 64] (0xFFFF = none).  scratch_ptr: the caller's scratch instead of one allocated for the call."""
+        bounds = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint32).reshape(-1, 2))
+        positions = np.ascontiguousarray(positions, dtype=np.uint32)
+        symbols = np.ascontiguousarray(symbols, dtype=np.uint32)
+        if len(positions) != len(symbols):
+            raise ValueError("one symbol per position")
+        n_ranges, n_mutations = len(bounds), len(positions)
+        cells = n_mutations * n_ranges * 2
+        own_scratch = scratch_ptr is _OWN_SCRATCH
+        scratch = self.malloc(grouped_scratch_bytes(self.row_words, n_ranges, n_mutations)) if own_scratch else scratch_ptr
+        table = out_ptr
+        try:
+            if out_ptr is None:
+                table = self.malloc(max(8, 4 * cells))
+                self.memset(table, 0, max(8, 4 * cells), stream)
+            if own_scratch and return_groups:
+                self.memset(scratch, 0xFF, self.row_words * 128, stream)  # a call that launches nothing assigns no row
+            _check(self.lib.silo_gpu_mutations_grouped(self.handle, seqstore_id, filter_ptr, dates_ptr, _ptr(bounds), n_ranges, _ptr(positions), _ptr(symbols),
+                                                       n_mutations, scratch, table, stream))
+            self.synchronize(stream)
+            result = None
+            if out_ptr is None:
+                result = (self.read(table, np.uint32, cells, stream) if cells else np.zeros(0, dtype=np.uint32)).reshape(n_mutations, n_ranges, 2)
+            if return_groups:
+                groups = self.read(scratch, np.uint16, self.row_words * 64, stream)
+                return groups if out_ptr is not None else (result, groups)
+            return result
+        finally:
+            if own_scratch:
+                self.free(scratch)
+            if out_ptr is None and table is not None:
+                self.free(table)
 
     # ---- metadata columns (K5 / K6) and FastaAligned ---------------------------------------------
     VALUE_TYPES = {np.dtype(np.int32): 0, np.dtype(np.uint32): 1, np.dtype(np.float64): 2}
