@@ -448,10 +448,10 @@ int silo_gpu_mutations_scan_ranges(
  * silo_gpu_mutations_select — with the store's reference symbols and that filter's proportion — emits from this table ALONE (a
  * table that other scans are accumulated into as well, the partitions of a database, needs the exact entry).  Other cells may
  * not be: at a position whose most numerous symbol is derived (SILO_GPU_TUNE_COMPACT_INDEX) and is the reference symbol, the
- * scan leaves out escape keys of (position, symbol) groups too small in the whole store to reach the proportion under the
- * filter, whole granules of the key stream at a time, and their rows are counted on the derived symbol instead — which is never
- * reported.  A proportion of 0 (or outside (0, 1]), a store without gap events, SILO_GPU_TUNE_GAP_EVENTS < 0 or
- * SILO_GPU_TUNE_PRUNE_KEYS < 0: exactly silo_gpu_mutations_scan_ranges. */
+ * scan leaves out (position, symbol) groups too small in the whole store to reach the proportion under the filter — their
+ * escape keys, whole granules of the key stream at a time, and their one-hot plane rows, a row at a time, where the derived symbol holds the majority of the position's valid rows — and their rows are
+ * counted on the derived symbol instead, which is never reported.  A proportion of 0 (or outside (0, 1]), a store without gap
+ * events, SILO_GPU_TUNE_GAP_EVENTS < 0 or SILO_GPU_TUNE_PRUNE_KEYS < 0: exactly silo_gpu_mutations_scan_ranges. */
 int silo_gpu_mutations_scan_ranges_min_proportion(
    const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
    const double* min_proportion /* [n_filters] or NULL */, uint32_t* const* counts_out_dev, void* stream
@@ -459,6 +459,11 @@ int silo_gpu_mutations_scan_ranges_min_proportion(
 /* How many granules (4 096 keys) of the store's slice-major escape keys the scan above skips for ONE filter of `cardinality`
  * rows at `min_proportion`, and how many there are: the kernel's rule applied to the host copies of the store's bounds. */
 int silo_gpu_store_scan_prunable_granules(
+   const silo_gpu_store* store, uint32_t seqstore_id, uint32_t cardinality, double min_proportion, uint64_t* out_skippable, uint64_t* out_total
+);
+/* Its twin for the one-hot plane rows: how many of them that scan skips for ONE filter of `cardinality` rows at `min_proportion`,
+ * and how many the store has (a store without bounds per row: 0 of them). */
+int silo_gpu_store_scan_prunable_rows(
    const silo_gpu_store* store, uint32_t seqstore_id, uint32_t cardinality, double min_proportion, uint64_t* out_skippable, uint64_t* out_total
 );
 
@@ -512,8 +517,8 @@ enum { SILO_GPU_TUNE_SCAN_ROWS_PER_BLOCK = 0, SILO_GPU_TUNE_SCAN_VARIANT = 1, SI
                                         events in the escape-key pass (k_scan_escapes_sliced); < 0 takes the runs of the missing symbol and the sparse
                                         keys by themselves (k_scan_missing_runs, k_sum_run_parts, k_count_sparse_keys on a side stream), as SILO_GPU_TUNE_SIDE_STREAM = 3
                                         and stores of more than 67 M rows always do */,
-       SILO_GPU_TUNE_PRUNE_KEYS = 11 /* silo_gpu_mutations_scan_ranges_min_proportion: 0 (default) skips the granules of escape keys that cannot
-                                        reach a filter's proportion; < 0 never skips one (the exact scan, for A/B runs) */,
+       SILO_GPU_TUNE_PRUNE_KEYS = 11 /* silo_gpu_mutations_scan_ranges_min_proportion: 0 (default) skips the granules of escape keys and the one-hot
+                                        plane rows that cannot reach a filter's proportion; 1 skips keys only; < 0 skips nothing (the exact scan) — for A/B runs */,
        SILO_GPU_TUNE_SCAN_SPARSE_DIVISOR = 3 /* a filter with a set bit in <= row_words / divisor of its 64-byte sectors takes the gather scan (K1s); 0 = default 16, < 0 = off */ };
 int silo_gpu_tune(int knob, int value);
 
@@ -557,7 +562,8 @@ const char* silo_gpu_last_scan_kernel(void);
  * plane rows the launch streams (each once, row_words * 8 bytes), filters = filter rows it holds in registers. */
 typedef struct silo_gpu_scan_timing {
    char kernel[64];       /* e.g. "k_scan_sliced<2, 2, 8, 1, 2>", as rocprofv3 names it; ", pruning" behind k_scan_escapes_sliced<N> where the
-                             launch may skip granules of keys (silo_gpu_mutations_scan_ranges_min_proportion) */
+                             launch may skip granules of keys and behind k_scan_sliced<2, 2, ..., 2> where it may skip one-hot rows
+                             (silo_gpu_mutations_scan_ranges_min_proportion); plane_rows and bytes stay those of ALL its rows */
    uint64_t plane_rows;   /* plane rows a k_scan_sliced launch streams (0 for the other kernels) */
    uint64_t bytes;        /* what the launch has to read, each byte once: plane rows + filter rows; 8 bytes per escape key (+ a filter
                              slice per block); 12 bytes per run of the missing symbol; 8 per sparse key */

@@ -23,6 +23,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "store_internal.h"
@@ -95,6 +96,21 @@ struct ScanBatchArgs {
 // what a run of plane rows holds
 enum : int { KIND_IDENTITY = 0, KIND_MAPPED = 1, KIND_ROWS = 2 };
 
+/// What a launch over one-hot rows (KIND_ROWS) needs to leave out the rows no Mutations row can come from
+/// (silo_gpu_mutations_scan_ranges_min_proportion), as the escape pass leaves out granules of keys (EscapeSliceArgs): the counters
+/// of the prepare step ([q * SPARSE_COUNTER_STRIDE + 2] = the cardinality of filter q of the launch), every filter's proportion,
+/// and per range the two bounds of its rows (SeqStoreHost::Layout::d_row_heaviest, d_row_without, from the range's first row on).
+/// A range with null bounds — every range of an exact scan, and of the other kinds of launch — walks all its rows.
+struct RowPruneArgs {
+   const uint32_t* counters;
+   double min_proportion[SILO_GPU_MAX_SCAN_BATCH];
+   const uint32_t* heaviest[SCAN_MAX_RANGES];
+   const uint32_t* without[SCAN_MAX_RANGES];
+};
+static_assert(sizeof(ScanBatchArgs) + sizeof(RowPruneArgs) + 3 * sizeof(uint32_t) <= 4096, "k_scan_sliced takes its arguments by value: the kernel-argument segment holds 4 KiB");
+// rows of a range whose live rows a block can list in LDS (4 KiB); a range of more rows is scanned in full
+constexpr uint32_t ROW_LIST_MAX = 1024;
+
 // positions whose partial counts sit in LDS between two flushes: ~16 KiB of LDS whatever NSYM * Q is
 template <int NSYM, int Q>
 constexpr int scanPositionsBatch() {
@@ -114,12 +130,14 @@ constexpr int scanMinBlocks() {
 
 template <int BITS, int NSYM, int WPT, int Q, int KIND>
 __global__ __launch_bounds__(SCAN_THREADS, (scanMinBlocks<BITS, NSYM, WPT, Q>())) void k_scan_sliced(
-   const ScanBatchArgs batch, uint32_t row_words, uint32_t positions_per_block, uint32_t n_tiles
+   const ScanBatchArgs batch, const RowPruneArgs rows, uint32_t row_words, uint32_t positions_per_block, uint32_t n_tiles
 ) {
    constexpr int CHUNKS = WPT / 2;  // 16-byte chunks per thread and plane
    constexpr uint32_t TILE_WORDS = SCAN_THREADS * WPT;
    constexpr int POS_BATCH = scanPositionsBatch<NSYM, Q>();
    __shared__ uint32_t s_partial[2][SCAN_WAVES][POS_BATCH][NSYM * Q];
+   // one-hot rows of a pruning scan: the LIVE rows of the range, ascending, and behind them how many there are
+   [[maybe_unused]] __shared__ uint32_t s_live_rows[KIND == KIND_ROWS ? ROW_LIST_MAX + 1u : 1u];
 
    const uint32_t tid = threadIdx.x;
    const uint32_t wave = tid >> 6;
@@ -136,9 +154,8 @@ __global__ __launch_bounds__(SCAN_THREADS, (scanMinBlocks<BITS, NSYM, WPT, Q>())
    const uint32_t n_positions = KIND == KIND_ROWS ? (n_rows + 1u) / 2u : n_rows;
    const uint32_t tile = block_in_range % n_tiles;
    const uint32_t position_group = block_in_range / n_tiles;
-   const uint32_t pos_begin = position_group * positions_per_block;
-   const uint32_t pos_end = min(n_positions, pos_begin + positions_per_block);
-   const uint32_t last_pos = pos_end - 1;
+   uint32_t pos_begin = position_group * positions_per_block;
+   uint32_t pos_end = min(n_positions, pos_begin + positions_per_block);
 
    // filters routed to the gather kernel count as empty here; a block with nothing left to do leaves at once
    bool dense[Q];
@@ -182,20 +199,99 @@ __global__ __launch_bounds__(SCAN_THREADS, (scanMinBlocks<BITS, NSYM, WPT, Q>())
             any_bit |= f[q][j].x | f[q][j].y;
          }
       }
+      // One-hot rows of a pruning scan: the block's first wave lists the rows of the range that stay — a row is left out where
+      // EVERY filter this launch counts allows it (granulePrunable, the escape pass's rule; a filter routed to the gather kernel is
+      // counted exactly there and has no say) — while the filter tile is on its way; the barrier below publishes the list.
+      // Lane l looks at rows l, l + 64, ...: a row's place in the list is the live rows of the ballots before plus those of
+      // the lanes below in its own.
+      if constexpr (KIND == KIND_ROWS) {
+         if (rows.heaviest[range] != nullptr && n_rows <= ROW_LIST_MAX && tid < 64u) {  // (uniform per wave)
+            constexpr uint32_t PER_LANE = ROW_LIST_MAX / 64u;
+            uint32_t heaviest[PER_LANE];
+            uint32_t without[PER_LANE];
+#pragma unroll
+            for (uint32_t k = 0; k < PER_LANE; ++k) {  // (unconditional, clamped: all in flight at once)
+               const uint32_t row = min(k * 64u + tid, n_rows - 1u);
+               heaviest[k] = rows.heaviest[range][row];
+               without[k] = rows.without[range][row];
+            }
+            uint32_t cardinality[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+               cardinality[q] = rows.counters[q * SPARSE_COUNTER_STRIDE + 2u];
+            }
+            uint32_t n_live = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < PER_LANE; ++k) {
+               const uint32_t row = k * 64u + tid;
+               bool skip = true;
+#pragma unroll
+               for (int q = 0; q < Q; ++q) {
+                  if (dense[q]) {
+                     skip = skip && granulePrunable(cardinality[q], without[k], heaviest[k], rows.min_proportion[q]);
+                  }
+               }
+               const bool live = row < n_rows && !skip;
+               const uint64_t live_lanes = __ballot(live);
+               if (live) {
+                  s_live_rows[n_live + static_cast<uint32_t>(__popcll(live_lanes & ((uint64_t{1} << tid) - 1u)))] = row;
+               }
+               n_live += static_cast<uint32_t>(__popcll(live_lanes));
+            }
+            if (tid == 0) {
+               s_live_rows[ROW_LIST_MAX] = n_live;
+            }
+         }
+      }
       if (__syncthreads_or(any_bit != 0 ? 1 : 0) == 0) {
          return;
       }
    }
+   // (the list's entries are the same for every lane: kept in scalar registers, as the escape pass keeps its granules)
+   [[maybe_unused]] const auto liveRow = [&](uint32_t k) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(s_live_rows[k]))); };
+   [[maybe_unused]] uint32_t n_live = n_rows;
+   bool listed = false;  // (uniform) the block walks the list of live rows, not rows 0 .. n_rows
+   if constexpr (KIND == KIND_ROWS) {
+      listed = rows.heaviest[range] != nullptr && n_rows <= ROW_LIST_MAX;
+      if (listed) {
+         // The position groups of the range take even shares of the LIVE pairs, not of all pairs: the rows left out cluster (the
+         // flanks of an alignment's ragged ends), all blocks of a launch are resident together, and the launch ends with its
+         // slowest group.  A group without a share leaves before its first plane load.
+         n_live = liveRow(ROW_LIST_MAX);
+         const uint32_t n_groups = (batch.first_unit[range + 1] - batch.first_unit[range]) / n_tiles;
+         const uint32_t live_pairs = (n_live + 1u) / 2u;
+         pos_begin = static_cast<uint32_t>(static_cast<uint64_t>(position_group) * live_pairs / n_groups);
+         pos_end = static_cast<uint32_t>(static_cast<uint64_t>(position_group + 1u) * live_pairs / n_groups);
+         if (pos_begin >= pos_end) {
+            return;
+         }
+      }
+   }
+   const uint32_t last_pos = pos_end - 1;
 
-   auto load_position = [&](uint32_t position, ulonglong2 (&dst)[BITS][CHUNKS]) {
-      const uint64_t* base = planes + static_cast<size_t>(position) * BITS * row_words;
+   // LISTED (a std::bool_constant): the pair of rows of a "position" is taken from the list of live rows
+   auto load_position = [&](auto LISTED, uint32_t position, ulonglong2 (&dst)[BITS][CHUNKS]) {
+      if constexpr (decltype(LISTED)::value) {
+         // the second row of the last pair of an odd list is the first one again (not stored)
+         const uint32_t pair[2] = {liveRow(position * 2u), liveRow(min(position * 2u + 1u, n_live - 1u))};
 #pragma unroll
-      for (int bit = 0; bit < BITS; ++bit) {
-         // the second row of the last pair of an odd run is the first one again (in bounds, not stored)
-         const size_t row = KIND == KIND_ROWS ? static_cast<size_t>(min(static_cast<uint32_t>(bit), n_rows - 1u - position * 2u)) : static_cast<size_t>(bit);
+         for (int bit = 0; bit < BITS; ++bit) {
+            const uint64_t* base = planes + static_cast<size_t>(pair[bit & 1]) * row_words;
 #pragma unroll
-         for (int j = 0; j < CHUNKS; ++j) {
-            dst[bit][j] = loadPlane16<true>(base + row * row_words + word[j]);
+            for (int j = 0; j < CHUNKS; ++j) {
+               dst[bit][j] = loadPlane16<true>(base + word[j]);
+            }
+         }
+      } else {
+         const uint64_t* base = planes + static_cast<size_t>(position) * BITS * row_words;
+#pragma unroll
+         for (int bit = 0; bit < BITS; ++bit) {
+            // the second row of the last pair of an odd run is the first one again (in bounds, not stored)
+            const size_t row = KIND == KIND_ROWS ? static_cast<size_t>(min(static_cast<uint32_t>(bit), n_rows - 1u - position * 2u)) : static_cast<size_t>(bit);
+#pragma unroll
+            for (int j = 0; j < CHUNKS; ++j) {
+               dst[bit][j] = loadPlane16<true>(base + row * row_words + word[j]);
+            }
          }
       }
    };
@@ -288,7 +384,7 @@ __global__ __launch_bounds__(SCAN_THREADS, (scanMinBlocks<BITS, NSYM, WPT, Q>())
          }
       }
    };
-   auto flush = [&](uint32_t batch_first_position, uint32_t n_batch, uint32_t buffer) {
+   auto flush = [&](auto LISTED, uint32_t batch_first_position, uint32_t n_batch, uint32_t buffer) {
       __syncthreads();
       for (uint32_t item = tid; item < n_batch * (NSYM * Q); item += SCAN_THREADS) {
          const uint32_t position = item / (NSYM * Q);
@@ -300,7 +396,10 @@ __global__ __launch_bounds__(SCAN_THREADS, (scanMinBlocks<BITS, NSYM, WPT, Q>())
          }
          if (total != 0) {
             if constexpr (KIND == KIND_ROWS) {  // row -> its (position, symbol) counter
-               const uint32_t row = (batch_first_position + position) * 2u + rest % NSYM;
+               uint32_t row = (batch_first_position + position) * 2u + rest % NSYM;
+               if constexpr (decltype(LISTED)::value) {
+                  row = row < n_live ? s_live_rows[row] : n_rows;
+               }
                if (row < n_rows) {
                   const uint32_t target = reinterpret_cast<const uint32_t*>(batch.code_map[range])[row] - batch.target_base[range];
                   atomicAdd(&batch.counts[range][rest / NSYM][target], total);
@@ -317,23 +416,32 @@ __global__ __launch_bounds__(SCAN_THREADS, (scanMinBlocks<BITS, NSYM, WPT, Q>())
       }
    };
 
-   ulonglong2 buf_a[BITS][CHUNKS];
-   ulonglong2 buf_b[BITS][CHUNKS];
-   load_position(pos_begin, buf_a);
-   uint32_t buffer = 0;
-   uint32_t batch_first_position = pos_begin;
-   for (uint32_t position = pos_begin; position < pos_end; position += 2) {
-      load_position(min(position + 1, last_pos), buf_b);
-      reduce_position(buf_a, buffer, position - batch_first_position, true);
-      load_position(min(position + 2, last_pos), buf_a);
-      reduce_position(buf_b, buffer, position + 1 - batch_first_position, position + 1 < pos_end);
-      const uint32_t done = min(position + 2, pos_end) - batch_first_position;
-      if (done >= static_cast<uint32_t>(POS_BATCH) || position + 2 >= pos_end) {  // POS_BATCH is even
-         flush(batch_first_position, done, buffer);
-         batch_first_position += done;
-         buffer ^= 1u;
+   auto scan_positions = [&](auto LISTED) {
+      ulonglong2 buf_a[BITS][CHUNKS];
+      ulonglong2 buf_b[BITS][CHUNKS];
+      load_position(LISTED, pos_begin, buf_a);
+      uint32_t buffer = 0;
+      uint32_t batch_first_position = pos_begin;
+      for (uint32_t position = pos_begin; position < pos_end; position += 2) {
+         load_position(LISTED, min(position + 1, last_pos), buf_b);
+         reduce_position(buf_a, buffer, position - batch_first_position, true);
+         load_position(LISTED, min(position + 2, last_pos), buf_a);
+         reduce_position(buf_b, buffer, position + 1 - batch_first_position, position + 1 < pos_end);
+         const uint32_t done = min(position + 2, pos_end) - batch_first_position;
+         if (done >= static_cast<uint32_t>(POS_BATCH) || position + 2 >= pos_end) {  // POS_BATCH is even
+            flush(LISTED, batch_first_position, done, buffer);
+            batch_first_position += done;
+            buffer ^= 1u;
+         }
+      }
+   };
+   if constexpr (KIND == KIND_ROWS) {
+      if (listed) {
+         scan_positions(std::true_type{});
+         return;
       }
    }
+   scan_positions(std::false_type{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1501,6 +1609,8 @@ struct ScanPiece {
    const uint8_t* code_map;   // of the piece's first position (mapped layouts); the row targets of its first row (one-hot rows); else nullptr
    uint32_t n_positions;      // one-hot rows: plane rows
    uint32_t target_base;      // one-hot rows: first position of the piece * n_scan
+   const uint32_t* row_heaviest;  // one-hot rows: the bounds of the piece's rows from its first row on (RowPruneArgs), or nullptr
+   const uint32_t* row_without;
    uint32_t* counts[SILO_GPU_MAX_SCAN_BATCH];  // tables at the piece's first position
 };
 
@@ -1537,6 +1647,10 @@ void cutIntoPieces(const std::vector<ScanRange>& ranges, uint32_t q_count, std::
             piece.code_map = reinterpret_cast<const uint8_t*>(seqstore.layout.d_row_target + first_row);
             piece.n_positions = seqstore.layout.row_of[end] - seqstore.layout.row_of[begin];
             piece.target_base = begin * dev.n_scan;
+            if (seqstore.layout.d_row_heaviest != nullptr && seqstore.layout.d_row_without != nullptr) {
+               piece.row_heaviest = seqstore.layout.d_row_heaviest + first_row;
+               piece.row_without = seqstore.layout.d_row_without + first_row;
+            }
             if (piece.n_positions == 0) {
                return;  // positions whose only stored symbol is derived: no rows
             }
@@ -1609,8 +1723,10 @@ void finishLaunchTiming(ScanLaunchTiming* timing, hipStream_t stream) {
 }
 
 /// Launches k_scan_sliced for the `q_count` filters and the pieces already entered in `batch` (planes, n_positions, counts).
+/// `rows`: what a launch over one-hot rows may leave rows out by (all null otherwise).  Such a launch is named "..., pruning" in the
+/// timing log, as the key pass is; its plane_rows and bytes stay those of ALL its rows, whatever it skips.
 template <int BITS, int NSYM, int KIND>
-int launchSlicedScan(ScanBatchArgs& batch, uint32_t row_words, uint32_t q_count, hipStream_t hip_stream) {
+int launchSlicedScan(ScanBatchArgs& batch, const RowPruneArgs& rows, uint32_t row_words, uint32_t q_count, hipStream_t hip_stream) {
    // words per thread: 8 for one filter over a layout of at most 5 counted symbols (2 or 3 planes x 4 chunks per position and
    // buffer), 4 otherwise (7 or 22 symbols; batches: Q filter tiles in registers).  SILO_GPU_TUNE_SCAN_VARIANT 10 / 12 force 4 / 8.
    const int variant = g_tune_scan_variant.load();
@@ -1655,12 +1771,16 @@ int launchSlicedScan(ScanBatchArgs& batch, uint32_t row_words, uint32_t q_count,
       for (uint32_t r = 0; r < batch.n_ranges; ++r) {
          plane_rows += KIND == KIND_ROWS ? batch.n_positions[r] : static_cast<uint64_t>(batch.n_positions[r]) * BITS;
       }
+      bool bounds = false;
+      for (uint32_t r = 0; r < batch.n_ranges; ++r) {
+         bounds = bounds || (KIND == KIND_ROWS && rows.heaviest[r] != nullptr);
+      }
       char name[64];
-      std::snprintf(name, sizeof(name), "k_scan_sliced<%d, %d, %d, %u, %d>", BITS, NSYM, wide ? 8 : 4, wide ? 1u : std::min(q_count, 8u), KIND);
+      std::snprintf(name, sizeof(name), "k_scan_sliced<%d, %d, %d, %u, %d>%s", BITS, NSYM, wide ? 8 : 4, wide ? 1u : std::min(q_count, 8u), KIND, bounds ? ", pruning" : "");
       timing = startLaunchTiming(name, plane_rows, (plane_rows + q_count) * row_words * sizeof(uint64_t), q_count, grid.x, hip_stream);
    }
 #define SILO_LAUNCH_SLICED(WPT, Q) \
-   k_scan_sliced<BITS, NSYM, WPT, Q, KIND><<<grid, SCAN_THREADS, 0, hip_stream>>>(batch, row_words, positions_per_block, n_tiles)
+   k_scan_sliced<BITS, NSYM, WPT, Q, KIND><<<grid, SCAN_THREADS, 0, hip_stream>>>(batch, rows, row_words, positions_per_block, n_tiles)
    if (wide) {
       if constexpr (CAN_BE_WIDE) {
          SILO_LAUNCH_SLICED(8, 1);
@@ -1847,10 +1967,21 @@ void enterPieces(ScanBatchArgs& batch, const std::vector<ScanPiece>& pieces, siz
 
 /// The dense kernels for `q_count` filters over the pieces of every layout: at most SCAN_MAX_RANGES pieces and 8 (layouts
 /// of 3 or 5 counted symbols) or 4 (7 or 22) filters per launch.  sparse_sectors carries the routing counters (or nullptr).
+/// With `min_proportion` (one per filter; `counters` = the prepare step's, with the filters' cardinalities) the launches over
+/// one-hot rows may leave out the rows that no Mutations row of that proportion can come from, where the store has the bounds
+/// for it — where and as scanEscapes leaves out granules of keys (SILO_GPU_TUNE_PRUNE_KEYS 0).
 int scanPiecesDense(
    const std::vector<ScanPiece> (&pieces)[N_SCAN_LAYOUTS], const SeqStoreDev& any_store, const uint64_t* const* filters, uint32_t q_count,
-   const uint32_t* sparse_sectors, uint32_t sparse_capacity, hipStream_t hip_stream
+   const uint32_t* sparse_sectors, uint32_t sparse_capacity, hipStream_t hip_stream, const uint32_t* counters = nullptr, const double* min_proportion = nullptr
 ) {
+   bool prune = counters != nullptr && min_proportion != nullptr && g_tune_prune_keys.load() == 0;
+   if (prune) {
+      bool any = false;
+      for (uint32_t q = 0; q < q_count; ++q) {
+         any = any || (min_proportion[q] > 0 && min_proportion[q] <= 1);
+      }
+      prune = any;  // (no filter with a proportion: nothing could be skipped)
+   }
    // (running the plane scans of a query's smaller layouts on side streams beside the largest one was tried: no gain, the
    // launches are bandwidth-bound together — profiles/r02_amino_acid.md)
    for (int layout = 0; layout < N_SCAN_LAYOUTS; ++layout) {
@@ -1868,13 +1999,24 @@ int scanPiecesDense(
                batch.filters[q] = filters[first + q];
             }
             enterPieces(batch, list, first_piece, n_pieces, first, n);
+            RowPruneArgs rows{};
+            if (prune && layout == SCAN_ONE_HOT_ROWS) {
+               rows.counters = counters + first * SPARSE_COUNTER_STRIDE;
+               for (uint32_t q = 0; q < n; ++q) {
+                  rows.min_proportion[q] = min_proportion[first + q];
+               }
+               for (uint32_t r = 0; r < n_pieces; ++r) {
+                  rows.heaviest[r] = list[first_piece + r].row_heaviest;
+                  rows.without[r] = list[first_piece + r].row_without;
+               }
+            }
             int rc = SILO_GPU_OK;
             switch (layout) {
-               case SCAN_2_PLANES: rc = launchSlicedScan<2, 3, KIND_MAPPED>(batch, any_store.row_words, n, hip_stream); break;
-               case SCAN_3_PLANES_MAPPED: rc = launchSlicedScan<3, 7, KIND_MAPPED>(batch, any_store.row_words, n, hip_stream); break;
-               case SCAN_FULL_NUCLEOTIDE: rc = launchSlicedScan<3, 5, KIND_IDENTITY>(batch, any_store.row_words, n, hip_stream); break;
-               case SCAN_ONE_HOT_ROWS: rc = launchSlicedScan<2, 2, KIND_ROWS>(batch, any_store.row_words, n, hip_stream); break;
-               default: rc = launchSlicedScan<5, 22, KIND_IDENTITY>(batch, any_store.row_words, n, hip_stream); break;
+               case SCAN_2_PLANES: rc = launchSlicedScan<2, 3, KIND_MAPPED>(batch, rows, any_store.row_words, n, hip_stream); break;
+               case SCAN_3_PLANES_MAPPED: rc = launchSlicedScan<3, 7, KIND_MAPPED>(batch, rows, any_store.row_words, n, hip_stream); break;
+               case SCAN_FULL_NUCLEOTIDE: rc = launchSlicedScan<3, 5, KIND_IDENTITY>(batch, rows, any_store.row_words, n, hip_stream); break;
+               case SCAN_ONE_HOT_ROWS: rc = launchSlicedScan<2, 2, KIND_ROWS>(batch, rows, any_store.row_words, n, hip_stream); break;
+               default: rc = launchSlicedScan<5, 22, KIND_IDENTITY>(batch, rows, any_store.row_words, n, hip_stream); break;
             }
             if (rc != SILO_GPU_OK) {
                return rc;
@@ -2371,7 +2513,9 @@ int scanRangesImpl(
       // fills the device it takes ten times as long (62 instead of 6 us)
       rc = forkSidePasses(ranges, filters, q_count, any_derived ? &plan : nullptr, hip_stream, counters, min_proportion);
       if (rc == SILO_GPU_OK) {
-         rc = scanPiecesDense(pieces, any_store, filters, q_count, routing ? counters : nullptr, capacity, hip_stream);
+         // (the rows are left out where the keys are: one pass over keys and gap events, the tables completed by k_finish_scan)
+         const bool events = any_derived && plan.events;
+         rc = scanPiecesDense(pieces, any_store, filters, q_count, routing ? counters : nullptr, capacity, hip_stream, events ? counters : nullptr, min_proportion);
       }
    }
    // the gather over the sectors of the sparse filters, over the same pieces of the same planes
@@ -2597,6 +2741,26 @@ int silo_gpu_store_scan_prunable_granules(
    *out_skippable = 0;
    for (size_t g = 0; g < layout.granule_heaviest.size(); ++g) {  // (empty where the store has no bounds)
       *out_skippable += granulePrunable(cardinality, layout.granule_without[g], layout.granule_heaviest[g], min_proportion) ? 1 : 0;
+   }
+   return SILO_GPU_OK;
+}
+
+int silo_gpu_store_scan_prunable_rows(
+   const silo_gpu_store* store, uint32_t seqstore_id, uint32_t cardinality, double min_proportion, uint64_t* out_skippable, uint64_t* out_total
+) {
+   if (store == nullptr || seqstore_id >= store->seqstores.size() || out_skippable == nullptr || out_total == nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_store_scan_prunable_rows: bad arguments");
+   }
+   const SeqStoreHost::Layout& layout = store->seqstores[seqstore_id].layout;
+   *out_total = 0;
+   *out_skippable = 0;
+   for (const SeqStoreHost::Run& run : layout.runs) {
+      for (uint32_t row = run.one_hot ? layout.row_of[run.begin] : 0; run.one_hot && row < layout.row_of[run.end]; ++row) {
+         *out_total += 1;
+         if (row < layout.row_heaviest.size()) {  // (empty where the store has no bounds)
+            *out_skippable += granulePrunable(cardinality, layout.row_without[row], layout.row_heaviest[row], min_proportion) ? 1 : 0;
+         }
+      }
    }
    return SILO_GPU_OK;
 }

@@ -798,6 +798,8 @@ void silo_gpu_store_destroy(silo_gpu_store* store) {
       (void)hipFree(seqstore.layout.d_gap_slice_first);
       (void)hipFree(seqstore.layout.d_granule_heaviest);
       (void)hipFree(seqstore.layout.d_granule_without);
+      (void)hipFree(seqstore.layout.d_row_heaviest);
+      (void)hipFree(seqstore.layout.d_row_without);
       (void)hipFree(seqstore.layout.d_escape_first);
    }
    (void)hipFree(store->d_ones);
@@ -1554,6 +1556,78 @@ int buildPruneBounds(silo_gpu_store* store, SeqStoreHost& seqstore) {
    return SILO_GPU_OK;
 }
 
+/// The same two bounds per one-hot plane row (SeqStoreHost::Layout::d_row_heaviest, d_row_without), so that the scan may leave
+/// out whole rows by the rule it leaves out granules of keys by.  A row holds every row of the store with its symbol at its
+/// position: its weight is the store's total of that (position, symbol), and the rows without a valid symbol are those of its
+/// own position.  Built where the store has its gap events and its totals; a store without either keeps null pointers.
+int buildRowBounds(silo_gpu_store* store, SeqStoreHost& seqstore) {
+   SeqStoreHost::Layout& layout = seqstore.layout;
+   const SeqStoreDev& dev = seqstore.dev;
+   if (!layout.built || !layout.has_implicit || !layout.gap_stream || layout.d_row_target == nullptr || layout.d_row_heaviest != nullptr ||
+       seqstore.d_totals == nullptr || !seqstore.totals_ready || layout.row_of.size() != static_cast<size_t>(dev.positions) + 1) {
+      return SILO_GPU_OK;
+   }
+   const uint32_t positions = dev.positions;
+   const size_t n_rows = layout.row_of[positions];
+   bool any_one_hot = false;
+   for (const SeqStoreHost::Run& run : layout.runs) {
+      any_one_hot = any_one_hot || (run.one_hot && layout.row_of[run.end] != layout.row_of[run.begin]);
+   }
+   if (!any_one_hot) {
+      return SILO_GPU_OK;
+   }
+   std::vector<uint32_t> without;
+   if (const int rc = rowsWithoutSymbol(seqstore, without); rc != SILO_GPU_OK) {
+      return rc;
+   }
+   std::vector<uint32_t> totals(static_cast<size_t>(positions) * dev.n_scan);
+   HIP_TRY(hipMemcpy(totals.data(), seqstore.d_totals, totals.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   layout.row_heaviest.assign(n_rows, 0xFFFFFFFFu);
+   layout.row_without.assign(n_rows, 0xFFFFFFFFu);
+   for (uint32_t p = 0; p < positions; ++p) {
+      const uint8_t* map = layout.code_map.data() + static_cast<size_t>(p) * CODE_MAP_STRIDE;
+      const uint8_t reference = seqstore.reference[p];
+      // (the condition of buildPruneBounds: the derived symbol is the reference's, so what falls onto it is never reported)
+      bool prunable = (map[0] & LAYOUT_ONE_HOT) != 0 && (map[0] & LAYOUT_IMPLICIT) != 0 && reference < dev.n_symbols && dev.kind[reference] == PLANE_SCAN &&
+                      dev.index[reference] == map[IMPLICIT_SLOT];
+      if (prunable) {
+         // ... and holds the majority of the position's valid rows.  The rows this is for are those of a settled position (a
+         // lineage's substitution, the flank of a ragged end: a few percent beside one symbol); a position that several symbols
+         // share keeps every cell exact, as a block of code planes does — the key pass keeps such cells as well, its granules
+         // reaching across their neighbours.
+         uint64_t valid = 0;
+         for (uint32_t symbol = 0; symbol < dev.n_scan; ++symbol) {
+            valid += totals[static_cast<size_t>(p) * dev.n_scan + symbol];
+         }
+         prunable = 2u * static_cast<uint64_t>(totals[static_cast<size_t>(p) * dev.n_scan + map[IMPLICIT_SLOT]]) > valid;
+      }
+      for (uint32_t row = layout.row_of[p]; prunable && row < layout.row_of[p + 1]; ++row) {
+         const uint8_t symbol = map[1 + (row - layout.row_of[p])];
+         if (symbol < dev.n_scan) {  // (a row without a symbol is empty and stays as it is)
+            layout.row_heaviest[row] = totals[static_cast<size_t>(p) * dev.n_scan + symbol];
+            layout.row_without[row] = without[p];
+         }
+      }
+   }
+   hipError_t status = hipMalloc(&layout.d_row_heaviest, n_rows * sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMalloc(&layout.d_row_without, n_rows * sizeof(uint32_t));
+   status = status != hipSuccess ? status : hipMemcpy(layout.d_row_heaviest, layout.row_heaviest.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice);
+   status = status != hipSuccess ? status : hipMemcpy(layout.d_row_without, layout.row_without.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice);
+   if (status != hipSuccess) {
+      (void)hipFree(layout.d_row_heaviest);
+      (void)hipFree(layout.d_row_without);
+      layout.d_row_heaviest = nullptr;
+      layout.d_row_without = nullptr;
+      layout.row_heaviest.clear();
+      layout.row_without.clear();
+      HIP_TRY(status);
+   }
+   const uint64_t bytes = 2u * n_rows * sizeof(uint32_t);
+   layout.device_bytes += bytes;
+   store->device_bytes += bytes;
+   return SILO_GPU_OK;
+}
+
 int finalizeSeqStore(silo_gpu_store* store, SeqStoreHost& seqstore) {
    if (seqstore.layout.built) {
       return SILO_GPU_OK;
@@ -1592,7 +1666,10 @@ int finalizeSeqStore(silo_gpu_store* store, SeqStoreHost& seqstore) {
    if (const int rc = buildGapEvents(store, seqstore); rc != SILO_GPU_OK) {
       return rc;
    }
-   return buildPruneBounds(store, seqstore);
+   if (const int rc = buildPruneBounds(store, seqstore); rc != SILO_GPU_OK) {
+      return rc;
+   }
+   return buildRowBounds(store, seqstore);
 }
 }  // namespace
 

@@ -28,7 +28,7 @@ extern std::atomic<int> g_tune_scan_variant;
 extern std::atomic<int> g_tune_eval_leaf_batch;
 extern std::atomic<int> g_tune_compact_index;   // < 0: finalize keeps the build-time identity planes; 2 / 3: see SILO_GPU_TUNE_COMPACT_INDEX
 extern std::atomic<int> g_tune_gap_events;      // < 0: scans of derived symbols take the runs and the sparse keys by themselves (planDerived)
-extern std::atomic<int> g_tune_prune_keys;      // < 0: silo_gpu_mutations_scan_ranges_min_proportion skips no granule of escape keys (scanEscapes)
+extern std::atomic<int> g_tune_prune_keys;      // silo_gpu_mutations_scan_ranges_min_proportion: < 0 skips nothing, 0 granules of escape keys (scanEscapes) and one-hot rows (k_scan_sliced), 1 keys only
 extern std::atomic<int> g_tune_side_stream;     // the side passes of a scan: see forkSidePasses (silo_gpu_scan.hip)
 extern std::atomic<int> g_tune_scan_timing;     // 1: HIP events around every launch of a scan (silo_gpu_scan_timings)
 extern std::atomic<int> g_tune_missing_runs;    // < 0: finalize keeps the plane of the missing symbol instead of turning it into runs
@@ -320,6 +320,15 @@ struct SeqStoreHost {
       uint32_t* d_granule_without = nullptr;
       std::vector<uint32_t> granule_heaviest;  // host copies
       std::vector<uint32_t> granule_without;
+      // the same two bounds per plane row, in the order of d_row_target, for the rows of one-hot positions (buildRowBounds): a
+      // row holds ALL rows of the store with its symbol at its position, so its heaviest is the store's total of that
+      // (position, symbol) — UINT32_MAX for a row of a position that derives no symbol or another one than the reference's or
+      // whose derived symbol does not hold the majority of its valid rows, for a row without a symbol and for the rows of code planes — and its without the rows of the store without a valid symbol
+      // at that very position.  Built beside the gap events; nullptr where the store has none (the scan stays exact).
+      uint32_t* d_row_heaviest = nullptr;
+      uint32_t* d_row_without = nullptr;
+      std::vector<uint32_t> row_heaviest;  // host copies
+      std::vector<uint32_t> row_without;
    } layout;
 };
 

@@ -108,7 +108,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_event_destroy", "silo_gpu_event_synchronize", "silo_gpu_host_alloc", "silo_gpu_host_free", "silo_gpu_memcpy_d2h_async", "silo_gpu_mutations_select", "silo_gpu_upload_bytes", "silo_gpu_upload_column", "silo_gpu_bitset_from_compare", "silo_gpu_group_count", "silo_gpu_group_count_hashed", "silo_gpu_reconstruct_sequences", "silo_gpu_bitset_from_pairs", "silo_gpu_count_pairs", "silo_gpu_count_slot_create", "silo_gpu_count_slot_destroy", "silo_gpu_filter_eval_count", "silo_gpu_count_slot_wait", "silo_gpu_tune", "silo_gpu_last_scan_kernel", "silo_gpu_scan_timings", "silo_gpu_stream_read_probe", "silo_gpu_last_error",
     "silo_gpu_comm_unique_id", "silo_gpu_comm_create", "silo_gpu_comm_destroy", "silo_gpu_comm_rank", "silo_gpu_comm_world",
     "silo_gpu_allreduce_counts", "silo_gpu_broadcast_bytes",
-    "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules",
+    "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules", "silo_gpu_store_scan_prunable_rows",
 ]
 
 _lib = None
@@ -169,6 +169,7 @@ def load_library():
                                                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(vp), vp]
     lib.silo_gpu_store_scan_prunable_granules.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64),
                                                           ctypes.POINTER(ctypes.c_uint64)]
+    lib.silo_gpu_store_scan_prunable_rows.argtypes = lib.silo_gpu_store_scan_prunable_granules.argtypes
     lib.silo_gpu_mutations_grouped.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
@@ -696,6 +697,13 @@ class GpuStore:
         skippable, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
         _check(self.lib.silo_gpu_store_scan_prunable_granules(self.handle, seqstore_id, int(cardinality), ctypes.c_double(min_proportion),
                                                               ctypes.byref(skippable), ctypes.byref(total)))
+        return skippable.value, total.value
+
+    def scan_prunable_rows(self, seqstore_id, cardinality, min_proportion):
+        """(skippable, total) one-hot plane rows of the store for one filter of `cardinality` rows."""
+        skippable, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(self.lib.silo_gpu_store_scan_prunable_rows(self.handle, seqstore_id, int(cardinality), ctypes.c_double(min_proportion),
+                                                          ctypes.byref(skippable), ctypes.byref(total)))
         return skippable.value, total.value
 
     def mutations_scan_ranges(self, ranges, filter_ptrs, stream=None, min_proportions=None):
