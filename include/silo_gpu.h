@@ -493,6 +493,26 @@ int silo_gpu_mutations_grouped(
    void* stream
 );
 
+/* ---- K8: grouped filter counts (QueriesOverTime) ----------------------------------------------------
+ * For each of n_filters row bitsets (filters_dev: a HOST array of device pointers, row_words words each; a NULL entry = all
+ * rows) and each of n_ranges date ranges (range_bounds, date_column_dev and the rules for ranges exactly as for K7: both ends
+ * inclusive, pairwise disjoint, NULL dates in no range), over the rows selected by base_filter_dev (NULL = all rows):
+ *     out_dev[f * n_ranges + r] += |{row < sequence_count : base(row) and filter_f(row) and from_r <= date(row) <= to_r}|
+ * ACCUMULATED into, like K1 and K7.  Bits of a filter or of the base at or past sequence_count never count.
+ * scratch_dev: device memory of SILO_GPU_FILTERS_GROUPED_SCRATCH_BYTES(row_words, n_ranges, n_filters) bytes, 16-byte aligned;
+ * its first row_words * 64 uint16 hold each row's range under the base filter (0xFFFF = none) after the call.  Uploads its
+ * small host tables and waits for them (one stream synchronisation), then makes two launches on `stream` without waiting.
+ * No ranges or no filters: success, nothing launched.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT for more than
+ * SILO_GPU_MAX_DATE_RANGES ranges or SILO_GPU_MAX_GROUPED_FILTERS filters, from > to, overlapping ranges, a NULL date column,
+ * scratch, table or filter array, or a store without rows. */
+#define SILO_GPU_MAX_GROUPED_FILTERS 2048
+#define SILO_GPU_FILTERS_GROUPED_SCRATCH_BYTES(row_words, n_ranges, n_filters)                                              \
+   ((size_t)(row_words) * 128u + (size_t)(n_filters) * 8u + (size_t)(n_ranges) * 16u + 1024u)
+int silo_gpu_filters_grouped(
+   const silo_gpu_store* store, const uint64_t* base_filter_dev, const uint32_t* date_column_dev, const uint32_t* range_bounds, uint32_t n_ranges,
+   const uint64_t* const* filters_dev, uint32_t n_filters, void* scratch_dev, uint32_t* out_dev, void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

@@ -9,6 +9,9 @@
 //   k_grouped_missing_runs, k_grouped_sparse_keys   rows without a valid symbol at the listed derived positions: runs of the
 //                               missing symbol (one pass over all runs for all positions), sparse ambiguity keys
 //   k_finish_grouped            count / coverage per (mutation, group), added to the caller's table
+// And the grouped count behind QueriesOverTime (K8, silo_gpu_filters_grouped): many filter bitsets against the same group ids.
+//   k_assign_groups             as above, over the base filter
+//   k_grouped_filter_counts     per filter and group: the rows of the filter in the group, added to the caller's table
 #include <algorithm>
 #include <cstring>
 #include <numeric>
@@ -24,6 +27,7 @@ constexpr uint32_t GROUP_THREADS = 256;
 constexpr uint32_t POSITION_THREADS = 256;   // one row word per thread: a block covers 256 words = 16 384 rows
 constexpr uint32_t MUTATIONS_PER_BLOCK = 16;  // mutations a block of k_grouped_position_counts counts, the groups of its rows decoded once
 constexpr uint32_t WORD_SEGMENTS = 4;          // distinct groups of a word kept as (group, mask) pairs; beyond: per row
+constexpr uint32_t FILTERS_PER_BLOCK = 8;      // filters a block of k_grouped_filter_counts counts: an LDS histogram of 32 KiB at 1 024 groups
 constexpr uint32_t MAX_EXTRA = 16;
 constexpr uint32_t NO_POSITION = 0xFFFFFFFFu;
 
@@ -97,21 +101,12 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_assign_groups(const GroupedAr
    }
 }
 
-/// grid = (row_words / POSITION_THREADS rounded up, mutation batches of MUTATIONS_PER_BLOCK).  A thread owns one row word: it
-/// reads the 64 group ids once and keeps up to WORD_SEGMENTS (group, row mask) pairs (rows are in (lineage, date) order: a word
-/// rarely spans more groups); a word with more goes row by row.  Per mutation the word's symbol / stored / no-symbol masks are
-/// split by those pairs into LDS histograms, which are flushed with one global add per non-zero entry.
-__global__ __launch_bounds__(POSITION_THREADS) void k_grouped_position_counts(const GroupedArgs args) {
-   __shared__ uint32_t s_hist[3 * SILO_GPU_MAX_DATE_RANGES];  // [group][sym, stored, no symbol]
-   const uint32_t n_groups = args.n_groups;
-   const uint32_t row_words = args.dev.row_words;
-   const uint32_t word = blockIdx.x * POSITION_THREADS + threadIdx.x;
-   const bool has_word = word < row_words;
-   for (uint32_t i = threadIdx.x; i < 3u * n_groups; i += POSITION_THREADS) {
-      s_hist[i] = 0;
-   }
-   uint32_t seg_group[WORD_SEGMENTS];
-   uint64_t seg_mask[WORD_SEGMENTS];
+/// The 64 group ids of row word `word` as up to WORD_SEGMENTS (group, row mask) pairs, in the order the groups first occur
+/// (unused pairs: NO_GROUP, 0; rows without a group are in no mask).  true: the word has more groups than that — the masks are
+/// incomplete and the word has to be taken row by row.  Without a word: no pair.
+__device__ __forceinline__ bool decodeWordGroups(
+   const uint16_t* groups, uint32_t word, bool has_word, uint32_t (&seg_group)[WORD_SEGMENTS], uint64_t (&seg_mask)[WORD_SEGMENTS]
+) {
 #pragma unroll
    for (uint32_t s = 0; s < WORD_SEGMENTS; ++s) {
       seg_group[s] = NO_GROUP;
@@ -119,7 +114,7 @@ __global__ __launch_bounds__(POSITION_THREADS) void k_grouped_position_counts(co
    }
    bool row_by_row = false;
    if (has_word) {
-      const uint4* ids = reinterpret_cast<const uint4*>(args.groups + static_cast<size_t>(word) * 64u);
+      const uint4* ids = reinterpret_cast<const uint4*>(groups + static_cast<size_t>(word) * 64u);
 #pragma unroll
       for (uint32_t chunk = 0; chunk < 8; ++chunk) {
          const uint4 v = ids[chunk];
@@ -144,6 +139,25 @@ __global__ __launch_bounds__(POSITION_THREADS) void k_grouped_position_counts(co
          }
       }
    }
+   return row_by_row;
+}
+
+/// grid = (row_words / POSITION_THREADS rounded up, mutation batches of MUTATIONS_PER_BLOCK).  A thread owns one row word: it
+/// reads the 64 group ids once and keeps up to WORD_SEGMENTS (group, row mask) pairs (rows are in (lineage, date) order: a word
+/// rarely spans more groups); a word with more goes row by row.  Per mutation the word's symbol / stored / no-symbol masks are
+/// split by those pairs into LDS histograms, which are flushed with one global add per non-zero entry.
+__global__ __launch_bounds__(POSITION_THREADS) void k_grouped_position_counts(const GroupedArgs args) {
+   __shared__ uint32_t s_hist[3 * SILO_GPU_MAX_DATE_RANGES];  // [group][sym, stored, no symbol]
+   const uint32_t n_groups = args.n_groups;
+   const uint32_t row_words = args.dev.row_words;
+   const uint32_t word = blockIdx.x * POSITION_THREADS + threadIdx.x;
+   const bool has_word = word < row_words;
+   for (uint32_t i = threadIdx.x; i < 3u * n_groups; i += POSITION_THREADS) {
+      s_hist[i] = 0;
+   }
+   uint32_t seg_group[WORD_SEGMENTS];
+   uint64_t seg_mask[WORD_SEGMENTS];
+   const bool row_by_row = decodeWordGroups(args.groups, word, has_word, seg_group, seg_mask);
    __syncthreads();
    const uint32_t m_end = min(args.n_mutations, (blockIdx.y + 1u) * MUTATIONS_PER_BLOCK);
    for (uint32_t m = blockIdx.y * MUTATIONS_PER_BLOCK; m < m_end; ++m) {
@@ -320,8 +334,88 @@ __global__ __launch_bounds__(256) void k_finish_grouped(const GroupedArgs args, 
    out[2u * i + 1u] += coverage;
 }
 
+/// The filters of a K8 launch: filters[f] = a row bitset of row_words words, nullptr = all rows.
+struct FilterCountArgs {
+   const uint16_t* groups;          // [row_words * 64], as k_assign_groups left them
+   const uint64_t* const* filters;  // [n_filters] (device array)
+   uint32_t* out;                   // [n_filters][n_groups], accumulated into
+   uint32_t row_words;
+   uint32_t n_filters;
+   uint32_t n_groups;
+};
+
+/// grid = (row_words / POSITION_THREADS rounded up, filter batches of FILTERS_PER_BLOCK); dynamic LDS: a histogram
+/// [FILTERS_PER_BLOCK][n_groups].  A thread owns one row word: it decodes the 64 group ids once (decodeWordGroups), then per
+/// filter of the batch splits the filter word by the (group, mask) pairs — row by row where the word has more groups than pairs.
+/// A word without a row in any group reads no filter.  Rows past sequence_count have no group, so a filter's padding bits never
+/// count.  One global add per non-zero entry at the end.
+__global__ __launch_bounds__(POSITION_THREADS) void k_grouped_filter_counts(const FilterCountArgs args) {
+   extern __shared__ uint32_t s_filter_hist[];  // [FILTERS_PER_BLOCK][n_groups]
+   const uint32_t n_groups = args.n_groups;
+   const uint32_t word = blockIdx.x * POSITION_THREADS + threadIdx.x;
+   const bool has_word = word < args.row_words;
+   const uint32_t f_begin = blockIdx.y * FILTERS_PER_BLOCK;
+   const uint32_t batch = min(args.n_filters - f_begin, FILTERS_PER_BLOCK);  // (the grid has no block without a filter)
+   for (uint32_t i = threadIdx.x; i < batch * n_groups; i += POSITION_THREADS) {
+      s_filter_hist[i] = 0;
+   }
+   uint32_t seg_group[WORD_SEGMENTS];
+   uint64_t seg_mask[WORD_SEGMENTS];
+   const bool row_by_row = decodeWordGroups(args.groups, word, has_word, seg_group, seg_mask);
+   __syncthreads();
+   if (row_by_row || seg_mask[0] != 0) {  // (the first group met takes the first pair: none there = no row of the word in a group)
+      for (uint32_t f = 0; f < batch; ++f) {
+         const uint64_t* filter = args.filters[f_begin + f];  // (uniform)
+         const uint64_t bits = filter != nullptr ? filter[word] : ~0ull;
+         uint32_t* hist = s_filter_hist + f * n_groups;
+         if (!row_by_row) {
+#pragma unroll
+            for (uint32_t s = 0; s < WORD_SEGMENTS; ++s) {
+               const uint32_t count = static_cast<uint32_t>(__popcll(bits & seg_mask[s]));
+               if (count != 0) {
+                  atomicAdd(hist + seg_group[s], count);
+               }
+            }
+         } else {
+            for (uint64_t rest = bits; rest != 0; rest &= rest - 1) {
+               const uint32_t g = args.groups[static_cast<size_t>(word) * 64u + static_cast<uint32_t>(__builtin_ctzll(rest))];
+               if (g != NO_GROUP) {
+                  atomicAdd(hist + g, 1u);
+               }
+            }
+         }
+      }
+   }
+   __syncthreads();
+   uint32_t* out = args.out + static_cast<size_t>(f_begin) * n_groups;
+   for (uint32_t i = threadIdx.x; i < batch * n_groups; i += POSITION_THREADS) {
+      const uint32_t count = s_filter_hist[i];
+      if (count != 0) {
+         atomicAdd(out + i, count);
+      }
+   }
+}
+
 size_t align256(size_t bytes) {
    return (bytes + 255u) / 256u * 256u;
+}
+
+/// The ranges in order of their start (`order`: request indices; a range's group is its request index); they must be disjoint
+/// with both ends inclusive.  Returns what is wrong with them, nullptr if nothing.
+const char* orderRanges(const uint32_t* range_bounds, uint32_t n_ranges, std::vector<uint32_t>& order) {
+   order.resize(n_ranges);
+   std::iota(order.begin(), order.end(), 0u);
+   std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return range_bounds[2u * a] < range_bounds[2u * b]; });
+   for (uint32_t k = 0; k < n_ranges; ++k) {
+      const uint32_t from = range_bounds[2u * order[k]], to = range_bounds[2u * order[k] + 1u];
+      if (from > to) {
+         return "a date range ends before it starts";
+      }
+      if (k > 0 && from <= range_bounds[2u * order[k - 1] + 1u]) {
+         return "date ranges overlap";
+      }
+   }
+   return nullptr;
 }
 
 }  // namespace
@@ -345,18 +439,9 @@ int silo_gpu_mutations_grouped(
    if (dev.planes == nullptr) {
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_mutations_grouped: the sequence store holds no sequences yet");
    }
-   // the ranges in order of their start, each one's group = its request index; disjoint, inclusive, NULL (0) in none
-   std::vector<uint32_t> order(n_ranges);
-   std::iota(order.begin(), order.end(), 0u);
-   std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return range_bounds[2u * a] < range_bounds[2u * b]; });
-   for (uint32_t k = 0; k < n_ranges; ++k) {
-      const uint32_t from = range_bounds[2u * order[k]], to = range_bounds[2u * order[k] + 1u];
-      if (from > to) {
-         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_mutations_grouped: a date range ends before it starts");
-      }
-      if (k > 0 && from <= range_bounds[2u * order[k - 1] + 1u]) {
-         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_mutations_grouped: date ranges overlap");
-      }
+   std::vector<uint32_t> order;
+   if (const char* complaint = orderRanges(range_bounds, n_ranges, order); complaint != nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_mutations_grouped: ") + complaint);
    }
    std::vector<uint32_t> scan_index(n_mutations);
    for (uint32_t m = 0; m < n_mutations; ++m) {
@@ -487,6 +572,82 @@ int silo_gpu_mutations_grouped(
    }
    const size_t cells = static_cast<size_t>(M) * G;
    k_finish_grouped<<<static_cast<uint32_t>((cells + 255u) / 256u), 256, 0, hip_stream>>>(args, out_dev);
+   HIP_TRY(hipGetLastError());
+   return SILO_GPU_OK;
+}
+
+int silo_gpu_filters_grouped(
+   const silo_gpu_store* store, const uint64_t* base_filter_dev, const uint32_t* date_column_dev, const uint32_t* range_bounds, uint32_t n_ranges,
+   const uint64_t* const* filters_dev, uint32_t n_filters, void* scratch_dev, uint32_t* out_dev, void* stream
+) {
+   if (store == nullptr || date_column_dev == nullptr || scratch_dev == nullptr || out_dev == nullptr || filters_dev == nullptr ||
+       (n_ranges != 0 && range_bounds == nullptr)) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_filters_grouped: bad arguments");
+   }
+   if (n_ranges > SILO_GPU_MAX_DATE_RANGES || n_filters > SILO_GPU_MAX_GROUPED_FILTERS) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_filters_grouped: too many date ranges or filters");
+   }
+   if (store->sequence_count == 0 || store->row_words == 0) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_filters_grouped: the store has no rows");
+   }
+   std::vector<uint32_t> order;
+   if (const char* complaint = orderRanges(range_bounds, n_ranges, order); complaint != nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_filters_grouped: ") + complaint);
+   }
+   if (n_ranges == 0 || n_filters == 0) {
+      return SILO_GPU_OK;
+   }
+   HIP_TRY(hipSetDevice(store->device));
+   auto hip_stream = static_cast<hipStream_t>(stream);
+
+   // scratch: group ids, then the host tables (filter pointers, sorted bounds), then |base ∩ range| per group (zeroed)
+   const uint32_t F = n_filters, G = n_ranges;
+   std::vector<uint64_t> tables(static_cast<size_t>(F) + (3u * static_cast<size_t>(G) + 1u) / 2u, 0u);
+   for (uint32_t f = 0; f < F; ++f) {
+      tables[f] = reinterpret_cast<uint64_t>(filters_dev[f]);
+   }
+   auto* t_from = reinterpret_cast<uint32_t*>(tables.data() + F);
+   uint32_t* t_to = t_from + G;
+   uint32_t* t_group = t_to + G;
+   for (uint32_t k = 0; k < G; ++k) {
+      t_from[k] = std::max<uint32_t>(range_bounds[2u * order[k]], 1u);
+      t_to[k] = range_bounds[2u * order[k] + 1u];
+      t_group[k] = order[k];
+   }
+   auto* base = static_cast<uint8_t*>(scratch_dev);
+   const size_t group_bytes = static_cast<size_t>(store->row_words) * 64u * sizeof(uint16_t);
+   const size_t table_bytes = align256(tables.size() * sizeof(uint64_t));
+   auto* d_tables = reinterpret_cast<uint64_t*>(base + group_bytes);
+   auto* d_cardinality = reinterpret_cast<uint32_t*>(base + group_bytes + table_bytes);
+   if (group_bytes + table_bytes + G * sizeof(uint32_t) > SILO_GPU_FILTERS_GROUPED_SCRATCH_BYTES(store->row_words, n_ranges, n_filters)) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_filters_grouped: scratch layout exceeds its documented size");  // (cannot happen)
+   }
+   HIP_TRY(hipMemcpyAsync(d_tables, tables.data(), tables.size() * sizeof(uint64_t), hipMemcpyHostToDevice, hip_stream));
+   HIP_TRY(hipMemsetAsync(d_cardinality, 0, G * sizeof(uint32_t), hip_stream));
+   HIP_TRY(hipStreamSynchronize(hip_stream));  // `tables` is pageable host memory that leaves with this call
+
+   GroupedArgs args{};  // what k_assign_groups reads
+   args.groups = reinterpret_cast<uint16_t*>(base);
+   args.bound_from = reinterpret_cast<const uint32_t*>(d_tables + F);
+   args.bound_to = args.bound_from + G;
+   args.bound_group = args.bound_to + G;
+   args.cardinality = d_cardinality;
+   args.n_groups = G;
+   args.sequence_count = store->sequence_count;
+   const uint32_t rows = store->row_words * 64u;  // a multiple of GROUP_THREADS (rows are whole 256-byte lines)
+   k_assign_groups<<<rows / GROUP_THREADS, GROUP_THREADS, 0, hip_stream>>>(args, base_filter_dev, date_column_dev);
+   HIP_TRY(hipGetLastError());
+
+   FilterCountArgs count_args{};
+   count_args.groups = args.groups;
+   count_args.filters = reinterpret_cast<const uint64_t* const*>(d_tables);
+   count_args.out = out_dev;
+   count_args.row_words = store->row_words;
+   count_args.n_filters = F;
+   count_args.n_groups = G;
+   const dim3 grid((store->row_words + POSITION_THREADS - 1) / POSITION_THREADS, (F + FILTERS_PER_BLOCK - 1) / FILTERS_PER_BLOCK);
+   const size_t lds_bytes = static_cast<size_t>(std::min(F, FILTERS_PER_BLOCK)) * G * sizeof(uint32_t);  // <= 32 KiB
+   k_grouped_filter_counts<<<grid, POSITION_THREADS, lds_bytes, hip_stream>>>(count_args);
    HIP_TRY(hipGetLastError());
    return SILO_GPU_OK;
 }

@@ -1,4 +1,5 @@
-// actions.cpp — Action base (ordering / limit / offset), Aggregated (count), Mutations<SymbolType> and MutationsOverTime<SymbolType>.
+// actions.cpp — Action base (ordering / limit / offset), Aggregated (count), Mutations<SymbolType>, MutationsOverTime<SymbolType> and
+// QueriesOverTime.
 // Reference: src/silo/query_engine/actions/{action,aggregated,mutations}.cpp.
 #include <algorithm>
 #include <charconv>
@@ -839,6 +840,140 @@ QueryResult MutationsOverTime<SymbolType>::execute(const Database& database, std
 template class MutationsOverTime<Nucleotide>;
 template class MutationsOverTime<AminoAcid>;
 
+// ---- QueriesOverTime -----------------------------------------------------------------------------------
+namespace {
+const std::string QUERIES_OVER_TIME_FIELDS[] = {"displayLabel", "dateFrom", "dateTo", "count", "coverage"};
+}
+
+void QueriesOverTime::validateOrderByFields(const Database& /*database*/) const {
+   for (const OrderByField& field : order_by_fields) {
+      const bool known =
+         std::find(std::begin(QUERIES_OVER_TIME_FIELDS), std::end(QUERIES_OVER_TIME_FIELDS), field.name) != std::end(QUERIES_OVER_TIME_FIELDS);
+      CHECK_SILO_QUERY(known, "OrderByField " + field.name + " is not contained in the result of this operation.")
+   }
+}
+
+QueryResult QueriesOverTime::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   CHECK_SILO_QUERY(
+      database.shard_world <= 1, "QueriesOverTime is not supported on a sharded database yet: its counts are not all-reduced across ranks"
+   )
+   const std::optional<storage::ColumnMetadata> column = database.database_config.getMetadata(date_field);
+   CHECK_SILO_QUERY(
+      column.has_value() && column->type == config::ColumnType::DATE, "The field dateField of QueriesOverTime ('" + date_field + "') is not a date column"
+   )
+   const auto n_ranges = static_cast<uint32_t>(date_ranges.size());
+   const auto n_filters = static_cast<uint32_t>(filters.size());
+   std::vector<uint32_t> bounds(2u * n_ranges);
+   for (uint32_t r = 0; r < n_ranges; ++r) {
+      bounds[2u * r] = date_ranges[r].from.value_or(common::Date{1});
+      bounds[2u * r + 1u] = date_ranges[r].to.value_or(common::Date{UINT32_MAX});
+   }
+
+   // one table [distinct sub-expression][range], accumulated over the partitions
+   std::vector<uint32_t> table;
+   const size_t table_words = static_cast<size_t>(n_filters) * n_ranges;
+   if (table_words != 0 && !database.partitions.empty()) {
+      DeviceBuffer device_table = database.partitions.front().pool.acquire(table_words * sizeof(uint32_t));
+      checkGpu(silo_gpu_memset_async(device_table.get(), 0, table_words * sizeof(uint32_t), queryStream()), "silo_gpu_memset_async");
+      // what the launches of one batch read: the bitsets of its sub-expressions and its scratch
+      std::vector<OperatorResult> live_filters;
+      DeviceBuffer live_scratch;
+      HostFetch fetch;
+      try {
+         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+            const DatabasePartition& partition = database.partitions[partition_id];
+            const OperatorResult& filter = bitmap_filter[partition_id];
+            const uint32_t selected = partition.sequence_count == 0 ? 0 : filter.cardinality();
+            if (selected == 0) {
+               continue;
+            }
+            // a filter that selects every row is passed as NULL (no all-ones bitset is made for it)
+            const uint64_t* base_bits = selected == partition.sequence_count ? nullptr : filter.bitset();
+            const auto* dates = partition.columns.find(date_field, config::ColumnType::DATE);
+            CHECK_SILO_QUERY(dates != nullptr, "The field dateField of QueriesOverTime ('" + date_field + "') is not a date column")
+            for (uint32_t batch_begin = 0; batch_begin < n_filters; batch_begin += MAX_LIVE_FILTERS) {
+               const uint32_t batch_end = std::min(n_filters, batch_begin + MAX_LIVE_FILTERS);
+               if (live_scratch) {
+                  // the launches of the batch before may still read its bitsets: wait before those return to the pool
+                  checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+                  live_filters.clear();
+               }
+               live_scratch = partition.pool.acquire(SILO_GPU_FILTERS_GROUPED_SCRATCH_BYTES(partition.rowWords(), n_ranges, batch_end - batch_begin));
+               // K8 counts filters that stand side by side in the table: a sub-expression that selects no row here ends a run
+               uint32_t run_begin = batch_begin;
+               std::vector<const uint64_t*> run;
+               const auto launchRun = [&]() {
+                  if (!run.empty()) {
+                     checkGpu(
+                        silo_gpu_filters_grouped(
+                           partition.store, base_bits, static_cast<const uint32_t*>(dates->deviceValues()), bounds.data(), n_ranges, run.data(),
+                           static_cast<uint32_t>(run.size()), live_scratch.get(), device_table.as<uint32_t>() + static_cast<size_t>(run_begin) * n_ranges,
+                           queryStream()
+                        ),
+                        "silo_gpu_filters_grouped"
+                     );
+                     run.clear();
+                  }
+               };
+               for (uint32_t f = batch_begin; f < batch_end; ++f) {
+                  // compiled and evaluated as the top-level filter is (compileFilter, query_engine.cpp)
+                  std::unique_ptr<operators::Operator> root = filters[f]->compile(database, partition, filter_expressions::Expression::AmbiguityMode::NONE);
+                  const operators::Type type = root->type();
+                  uint32_t cardinality = type == operators::FULL ? partition.sequence_count : 0;
+                  OperatorResult result;
+                  if (type != operators::EMPTY && type != operators::FULL) {
+                     result = operators::Operator::evaluate(std::move(root));
+                     result.materialize();  // one launch yields both the bitset and its cardinality
+                     cardinality = result.cardinality();
+                  }
+                  if (cardinality == 0) {  // its cells stay 0
+                     launchRun();
+                     run_begin = f + 1;
+                     continue;
+                  }
+                  if (cardinality == partition.sequence_count) {
+                     run.push_back(nullptr);  // all rows: no bitset is read
+                  } else {
+                     run.push_back(result.bitset());
+                     live_filters.push_back(std::move(result));
+                  }
+               }
+               launchRun();
+            }
+         }
+         fetch = HostFetch(device_table.get(), table_words * sizeof(uint32_t), queryStream());
+         const auto* host = static_cast<const uint32_t*>(fetch.wait());
+         table.assign(host, host + table_words);
+      } catch (...) {
+         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+         (void)silo_gpu_stream_synchronize(queryStream());
+         throw;
+      }
+   }
+
+   const auto dateText = [](const std::optional<common::Date>& date) -> std::optional<std::variant<std::string, int32_t, double>> {
+      if (!date.has_value()) {
+         return std::nullopt;
+      }
+      return common::dateToString(*date).value_or("");
+   };
+   std::vector<QueryResultEntry> result_rows;
+   result_rows.reserve(queries.size() * n_ranges);
+   for (const LabelledQuery& query : queries) {
+      for (uint32_t r = 0; r < n_ranges; ++r) {
+         const uint32_t count = table.empty() ? 0u : table[static_cast<size_t>(query.count_filter) * n_ranges + r];
+         const uint32_t coverage = table.empty() ? 0u : table[static_cast<size_t>(query.coverage_filter) * n_ranges + r];
+         QueryResultEntry& entry = result_rows.emplace_back();
+         entry.fields.emplace("count", static_cast<int32_t>(count));
+         entry.fields.emplace("coverage", static_cast<int32_t>(coverage));
+         entry.fields.emplace("dateFrom", dateText(date_ranges[r].from));
+         entry.fields.emplace("dateTo", dateText(date_ranges[r].to));
+         entry.fields.emplace("displayLabel", query.display_label);
+      }
+   }
+   return QueryResult{std::move(result_rows)};
+}
+
 // ---- JSON -> Action -----------------------------------------------------------------------------------
 namespace {
 
@@ -958,21 +1093,9 @@ typename MutationsOverTime<SymbolType>::Mutation parseOverTimeMutation(const std
    return mutation;
 }
 
-template <typename SymbolType>
-std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json) {
-   using OverTime = MutationsOverTime<SymbolType>;
-   const std::string action_name = std::is_same_v<SymbolType, Nucleotide> ? "MutationsOverTime" : "AminoAcidMutationsOverTime";
-   CHECK_SILO_QUERY(
-      json.contains("mutations") && json["mutations"].is_array(), action_name + " action must contain the field mutations of type array of strings"
-   )
-   std::vector<typename OverTime::Mutation> mutations;
-   for (const auto& element : json["mutations"].items()) {
-      CHECK_SILO_QUERY(element.is_string(), action_name + " action must contain the field mutations of type array of strings, found " + element.dump())
-      CHECK_SILO_QUERY(
-         mutations.size() < OverTime::MAX_MUTATIONS, action_name + " action takes at most " + std::to_string(OverTime::MAX_MUTATIONS) + " mutations"
-      )
-      mutations.push_back(parseOverTimeMutation<SymbolType>(element.as_string(), action_name));
-   }
+/// The dateField and dateRanges fields of the over-time actions: the column's name and the ranges in request order (validated:
+/// at most SILO_GPU_MAX_DATE_RANGES, valid dates, dateFrom <= dateTo, pairwise disjoint with both ends inclusive).
+std::pair<std::string, std::vector<OverTimeDateRange>> parseDateFieldAndRanges(const json::Value& json, const std::string& action_name) {
    CHECK_SILO_QUERY(
       json.contains("dateField") && json["dateField"].is_string(), action_name + " action must contain the field dateField of type string"
    )
@@ -980,15 +1103,15 @@ std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json) {
       json.contains("dateRanges") && json["dateRanges"].is_array(),
       action_name + " action must contain the field dateRanges: an array of objects {\"dateFrom\": string or null, \"dateTo\": string or null}"
    )
-   std::vector<typename OverTime::DateRange> ranges;
+   std::vector<OverTimeDateRange> ranges;
    for (const auto& element : json["dateRanges"].items()) {
       CHECK_SILO_QUERY(
          element.is_object(), action_name + " action: every entry of dateRanges must be an object {\"dateFrom\": string or null, \"dateTo\": string or null}"
       )
       CHECK_SILO_QUERY(
-         ranges.size() < OverTime::MAX_RANGES, action_name + " action takes at most " + std::to_string(OverTime::MAX_RANGES) + " date ranges"
+         ranges.size() < SILO_GPU_MAX_DATE_RANGES, action_name + " action takes at most " + std::to_string(SILO_GPU_MAX_DATE_RANGES) + " date ranges"
       )
-      typename OverTime::DateRange range;
+      OverTimeDateRange range;
       for (const char* field : {"dateFrom", "dateTo"}) {
          if (!element.contains(field) || element[field].is_null()) {
             continue;
@@ -1013,7 +1136,70 @@ std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json) {
    for (size_t k = 1; k < spans.size(); ++k) {
       CHECK_SILO_QUERY(spans[k].first > spans[k - 1].second, action_name + " action: the date ranges overlap; each row may fall in at most one")
    }
-   return std::make_unique<OverTime>(std::move(mutations), json["dateField"].as_string(), std::move(ranges));
+   return {json["dateField"].as_string(), std::move(ranges)};
+}
+
+template <typename SymbolType>
+std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json) {
+   using OverTime = MutationsOverTime<SymbolType>;
+   const std::string action_name = std::is_same_v<SymbolType, Nucleotide> ? "MutationsOverTime" : "AminoAcidMutationsOverTime";
+   CHECK_SILO_QUERY(
+      json.contains("mutations") && json["mutations"].is_array(), action_name + " action must contain the field mutations of type array of strings"
+   )
+   std::vector<typename OverTime::Mutation> mutations;
+   for (const auto& element : json["mutations"].items()) {
+      CHECK_SILO_QUERY(element.is_string(), action_name + " action must contain the field mutations of type array of strings, found " + element.dump())
+      CHECK_SILO_QUERY(
+         mutations.size() < OverTime::MAX_MUTATIONS, action_name + " action takes at most " + std::to_string(OverTime::MAX_MUTATIONS) + " mutations"
+      )
+      mutations.push_back(parseOverTimeMutation<SymbolType>(element.as_string(), action_name));
+   }
+   auto [date_field, ranges] = parseDateFieldAndRanges(json, action_name);
+   return std::make_unique<OverTime>(std::move(mutations), std::move(date_field), std::move(ranges));
+}
+
+std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json) {
+   const std::string action_name = "QueriesOverTime";
+   const std::string entry_form = "{\"displayLabel\": string, \"countQuery\": filter expression, \"coverageQuery\": filter expression}";
+   CHECK_SILO_QUERY(
+      json.contains("queries") && json["queries"].is_array(), action_name + " action must contain the field queries: an array of objects " + entry_form
+   )
+   std::vector<QueriesOverTime::LabelledQuery> queries;
+   filter_expressions::ExpressionVector filters;
+   std::map<std::string, uint32_t> filter_of_text;  // sub-expressions with the same JSON text share a row of the table
+   std::map<std::string, bool> labels;
+   for (const auto& element : json["queries"].items()) {
+      CHECK_SILO_QUERY(element.is_object(), action_name + " action: every entry of queries must be an object " + entry_form)
+      CHECK_SILO_QUERY(
+         queries.size() < QueriesOverTime::MAX_QUERIES, action_name + " action takes at most " + std::to_string(QueriesOverTime::MAX_QUERIES) + " queries"
+      )
+      CHECK_SILO_QUERY(
+         element.contains("displayLabel") && element["displayLabel"].is_string(),
+         action_name + " action: every entry of queries must contain the field displayLabel of type string"
+      )
+      const std::string label = element["displayLabel"].as_string();
+      CHECK_SILO_QUERY(labels.emplace(label, true).second, action_name + " action: the displayLabel '" + label + "' occurs more than once in queries")
+      const auto subFilter = [&](const char* field) {
+         CHECK_SILO_QUERY(
+            element.contains(field) && element[field].is_object(),
+            action_name + " action: the query '" + label + "' must contain the field " + field + " of type object (a filter expression)"
+         )
+         const auto [found, is_new] = filter_of_text.emplace(element[field].dump(), static_cast<uint32_t>(filters.size()));
+         if (is_new) {
+            try {
+               filters.push_back(filter_expressions::parseExpression(element[field]));
+            } catch (const QueryParseException& ex) {
+               throw QueryParseException(action_name + " action: the field " + field + " of the query '" + label + "' is not a valid filter expression: " + ex.what());
+            }
+         }
+         return found->second;
+      };
+      const uint32_t count_filter = subFilter("countQuery");
+      const uint32_t coverage_filter = subFilter("coverageQuery");
+      queries.push_back({label, count_filter, coverage_filter});
+   }
+   auto [date_field, ranges] = parseDateFieldAndRanges(json, action_name);
+   return std::make_unique<QueriesOverTime>(std::move(queries), std::move(filters), std::move(date_field), std::move(ranges));
 }
 
 }  // namespace
@@ -1043,6 +1229,7 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"AminoAcidInsertions", parseInsertions<AminoAcid>},
    {"MutationsOverTime", parseMutationsOverTime<Nucleotide>},
    {"AminoAcidMutationsOverTime", parseMutationsOverTime<AminoAcid>},
+   {"QueriesOverTime", parseQueriesOverTime},
 };
 
 }  // namespace

@@ -751,6 +751,12 @@ class Mutations : public Action {
        : sequence_names(std::move(sequence_names)), min_proportion(min_proportion) {}
 };
 
+/// A date range of the over-time actions: both ends inclusive, none = unbounded on that side.
+struct OverTimeDateRange {
+   std::optional<common::Date> from;
+   std::optional<common::Date> to;
+};
+
 /// MutationsOverTime / AminoAcidMutationsOverTime: for listed mutations and date ranges, per (mutation, range) the rows of the
 /// filter within the range that carry the symbol (count) and that have any valid mutation symbol at the position (coverage) —
 /// the cell and the total of a Mutations table under And(filter, date in range).  Dense: every (mutation, range) is a row.
@@ -765,10 +771,7 @@ class MutationsOverTime : public Action {
       uint32_t position;  // 1-based
       typename SymbolType::Symbol symbol;
    };
-   struct DateRange {
-      std::optional<common::Date> from;
-      std::optional<common::Date> to;
-   };
+   using DateRange = OverTimeDateRange;
    static constexpr uint32_t MAX_RANGES = SILO_GPU_MAX_DATE_RANGES;
    static constexpr uint32_t MAX_MUTATIONS = SILO_GPU_MAX_GROUPED_MUTATIONS;
 
@@ -779,6 +782,39 @@ class MutationsOverTime : public Action {
    std::vector<Mutation> mutations;
    std::string date_field;
    std::vector<DateRange> date_ranges;
+
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+};
+
+/// QueriesOverTime: for labelled queries and date ranges, per (query, range) the rows of the filter within the range that match
+/// the query's countQuery (count) and its coverageQuery (coverage) — what Aggregated counts under And(filter, query, date in
+/// range), with both ends of a range inclusive on every date column and NULL dates in no range.  Dense: every (query, range) is a
+/// row, queries outermost, in request order.  Sub-expressions with the same JSON text are evaluated and counted once per partition;
+/// per partition one grouped filter count (K8) per MAX_LIVE_FILTERS bitsets, one table fetched per query.
+class QueriesOverTime : public Action {
+  public:
+   struct LabelledQuery {
+      std::string display_label;
+      uint32_t count_filter;     // indices into the distinct sub-expressions
+      uint32_t coverage_filter;
+   };
+   static constexpr uint32_t MAX_RANGES = SILO_GPU_MAX_DATE_RANGES;
+   static constexpr uint32_t MAX_QUERIES = 1024;
+   /// Bitsets of sub-expressions alive at a time: bounds the pool memory of a partition at 64 x row_words x 8 bytes.
+   static constexpr uint32_t MAX_LIVE_FILTERS = 64;
+   static_assert(2 * MAX_QUERIES <= SILO_GPU_MAX_GROUPED_FILTERS && MAX_LIVE_FILTERS <= SILO_GPU_MAX_GROUPED_FILTERS);
+
+   QueriesOverTime(
+      std::vector<LabelledQuery> queries, filter_expressions::ExpressionVector filters, std::string date_field, std::vector<OverTimeDateRange> date_ranges
+   )
+       : queries(std::move(queries)), filters(std::move(filters)), date_field(std::move(date_field)), date_ranges(std::move(date_ranges)) {}
+
+  private:
+   std::vector<LabelledQuery> queries;
+   filter_expressions::ExpressionVector filters;  // the distinct countQuery / coverageQuery expressions
+   std::string date_field;
+   std::vector<OverTimeDateRange> date_ranges;
 
    void validateOrderByFields(const Database& database) const override;
    [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;

@@ -109,6 +109,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_comm_unique_id", "silo_gpu_comm_create", "silo_gpu_comm_destroy", "silo_gpu_comm_rank", "silo_gpu_comm_world",
     "silo_gpu_allreduce_counts", "silo_gpu_broadcast_bytes",
     "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules", "silo_gpu_store_scan_prunable_rows",
+    "silo_gpu_filters_grouped",
 ]
 
 _lib = None
@@ -171,6 +172,7 @@ def load_library():
                                                           ctypes.POINTER(ctypes.c_uint64)]
     lib.silo_gpu_store_scan_prunable_rows.argtypes = lib.silo_gpu_store_scan_prunable_granules.argtypes
     lib.silo_gpu_mutations_grouped.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_filters_grouped.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -418,12 +420,18 @@ def filter_eval_batch(store_handle, programs, out_bitsets=None, stream=None):
 
 MAX_DATE_RANGES = 1024         # SILO_GPU_MAX_DATE_RANGES
 MAX_GROUPED_MUTATIONS = 4096   # SILO_GPU_MAX_GROUPED_MUTATIONS
+MAX_GROUPED_FILTERS = 2048     # SILO_GPU_MAX_GROUPED_FILTERS
 _OWN_SCRATCH = object()
 
 
 def grouped_scratch_bytes(row_words, n_ranges, n_mutations):
     """SILO_GPU_GROUPED_SCRATCH_BYTES: the scratch silo_gpu_mutations_grouped needs."""
     return row_words * 128 + n_mutations * 32 + n_ranges * 16 + n_ranges * 4 * (1 + 3 * n_mutations) + 1024
+
+
+def filters_grouped_scratch_bytes(row_words, n_ranges, n_filters):
+    """SILO_GPU_FILTERS_GROUPED_SCRATCH_BYTES: the scratch silo_gpu_filters_grouped needs."""
+    return row_words * 128 + n_filters * 8 + n_ranges * 16 + 1024
 
 
 class GpuStore:
@@ -762,6 +770,44 @@ class GpuStore:
             result = None
             if out_ptr is None:
                 result = (self.read(table, np.uint32, cells, stream) if cells else np.zeros(0, dtype=np.uint32)).reshape(n_mutations, n_ranges, 2)
+            if return_groups:
+                groups = self.read(scratch, np.uint16, self.row_words * 64, stream)
+                return groups if out_ptr is not None else (result, groups)
+            return result
+        finally:
+            if own_scratch:
+                self.free(scratch)
+            if out_ptr is None and table is not None:
+                self.free(table)
+
+    def filters_grouped(self, base_ptr, dates_ptr, ranges, filter_ptrs, out_ptr=None, stream=None, return_groups=False, scratch_ptr=_OWN_SCRATCH):
+        """silo_gpu_filters_grouped (K8).  ranges: (from, to) uint32 pairs in request order; filter_ptrs: device row bitsets
+        (None = all rows), None for the whole list = a null array; base_ptr: the bitset every filter is intersected with (None = all
+        rows); dates_ptr: a device column of uint32 dates (upload_column).  Without out_ptr: a zeroed table for the call, returned
+        as uint32 [F][G].  With out_ptr: accumulates into the caller's device table and returns nothing.  return_groups: also (or
+        only, with out_ptr) the per-row range ids under the base filter that the call leaves at the start of its scratch, uint16
+        [row_words * 64] (0xFFFF = none).  scratch_ptr: the caller's scratch instead of one allocated for the call."""
+        bounds = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint32).reshape(-1, 2))
+        n_ranges = len(bounds)
+        n_filters = 0 if filter_ptrs is None else len(filter_ptrs)
+        filters = None
+        if filter_ptrs is not None:
+            filters = (ctypes.c_void_p * max(1, n_filters))(*[(f.value if isinstance(f, ctypes.c_void_p) else f) for f in filter_ptrs])
+        cells = n_filters * n_ranges
+        own_scratch = scratch_ptr is _OWN_SCRATCH
+        scratch = self.malloc(filters_grouped_scratch_bytes(self.row_words, n_ranges, n_filters)) if own_scratch else scratch_ptr
+        table = out_ptr
+        try:
+            if out_ptr is None:
+                table = self.malloc(max(8, 4 * cells))
+                self.memset(table, 0, max(8, 4 * cells), stream)
+            if own_scratch and return_groups:
+                self.memset(scratch, 0xFF, self.row_words * 128, stream)  # a call that launches nothing assigns no row
+            _check(self.lib.silo_gpu_filters_grouped(self.handle, base_ptr, dates_ptr, _ptr(bounds), n_ranges, filters, n_filters, scratch, table, stream))
+            self.synchronize(stream)
+            result = None
+            if out_ptr is None:
+                result = (self.read(table, np.uint32, cells, stream) if cells else np.zeros(0, dtype=np.uint32)).reshape(n_filters, n_ranges)
             if return_groups:
                 groups = self.read(scratch, np.uint16, self.row_words * 64, stream)
                 return groups if out_ptr is not None else (result, groups)
