@@ -1,0 +1,679 @@
+// silo_gpu_scan_keys.hip — the escape keys of K1, the Mutations scan ("The escape pass", "Keys that cannot reach
+// minProportion"): the rows the plane rows do not carry, one key per (position, symbol, sequence); and, in the same launches, the
+// gap events of a store with derived symbols.
+//
+// Kernels:
+//   k_scan_escapes_sliced<FILTERS>   the slice-major 4-byte keys against a slice of 1, 2, 4 or 8 filters in LDS
+//   k_scan_escapes_overflow          the few keys that do not fit the packed form
+//   k_scan_escapes                   the position-major 8-byte keys (stores of more than 512 slices; an independent check)
+// Exported (scan_internal.h): scanEscapes.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <array>
+#include <mutex>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "scan_internal.h"
+
+using namespace silo_gpu_detail;
+
+namespace {
+
+/// The rows the code planes do not carry: one key per (position, symbol, sequence); grid.y = filter.  A thread takes
+/// ESCAPE_KEYS_PER_THREAD keys a block-width apart (their loads and the filter lookups behind them are in flight together).
+constexpr uint32_t ESCAPE_KEYS_PER_THREAD = 4;
+__global__ __launch_bounds__(256) void k_scan_escapes(
+   const uint64_t* __restrict__ escapes, uint32_t n_escapes, const ScanBatchArgs batch, uint32_t pos_begin
+) {
+   const uint32_t q = blockIdx.y;  // every filter: dense scan and sparse-filter gather of a range both read the same planes
+   const uint32_t lane = threadIdx.x & 63u;
+   const uint32_t first = blockIdx.x * (256u * ESCAPE_KEYS_PER_THREAD) + threadIdx.x;
+   uint64_t key[ESCAPE_KEYS_PER_THREAD];
+   bool selected[ESCAPE_KEYS_PER_THREAD];
+#pragma unroll
+   for (uint32_t k = 0; k < ESCAPE_KEYS_PER_THREAD; ++k) {
+      const uint32_t i = first + k * 256u;
+      key[k] = i < n_escapes ? escapes[i] : 0;
+   }
+#pragma unroll
+   for (uint32_t k = 0; k < ESCAPE_KEYS_PER_THREAD; ++k) {
+      const uint32_t sequence = static_cast<uint32_t>(key[k]);
+      selected[k] = first + k * 256u < n_escapes && ((batch.filters[q][sequence >> 6] >> (sequence & 63u)) & 1ull) != 0;
+   }
+#pragma unroll
+   for (uint32_t k = 0; k < ESCAPE_KEYS_PER_THREAD; ++k) {
+      bool pending = selected[k];
+      // keys of one position sit together and share a few symbols: one atomic per distinct counter and wave, not per key
+      const uint32_t counter = (static_cast<uint32_t>(key[k] >> 37) - pos_begin) * batch.out_symbols + (static_cast<uint32_t>(key[k] >> 32) & 31u);
+      for (uint64_t open = __ballot(pending); open != 0; open = __ballot(pending)) {
+         const uint32_t leader = static_cast<uint32_t>(__builtin_ctzll(open));
+         const uint32_t leader_counter = __shfl(counter, leader);
+         const uint64_t same = __ballot(pending && counter == leader_counter);
+         if (lane == leader) {
+            atomicAdd(&batch.counts[0][q][leader_counter], static_cast<uint32_t>(__popcll(same)));
+         }
+         if (counter == leader_counter) {
+            pending = false;
+         }
+      }
+   }
+}
+
+/// One launch for up to ESCAPE_MAX_RANGES position ranges (the 12 genes of an AminoAcidMutations query), each over the
+/// escape keys or the gap events of its store: grid = (the blocks of every range — blocks_per_slice per slice, slice by slice
+/// —, 1, filters / FILTERS); where a slice's keys of the scanned positions begin and end is read from the store's slice index
+/// on the device.
+struct EscapeSliceArgs {
+   const uint64_t* filters[SILO_GPU_MAX_SCAN_BATCH];
+   uint32_t row_words;
+   uint32_t n_slices;
+   uint32_t n_ranges;
+   uint32_t block_keys;  // keys of a block's share: whole granules, at most ESCAPE_GRANULES_PER_BLOCK
+   // a scan that may leave out keys no Mutations row can come from (silo_gpu_mutations_scan_ranges_min_proportion): the counters of
+   // the prepare step ([q * SPARSE_COUNTER_STRIDE + 2] = the cardinality of filter q) and every filter's proportion; a range
+   // with bounds per granule (heaviest, without) skips the granules that granulePrunable() names for EVERY filter of the pass
+   const uint32_t* counters;
+   double min_proportion[SILO_GPU_MAX_SCAN_BATCH];
+   struct Range {
+      const uint32_t* keys;          // the packed slice-major keys of the store (SeqStoreHost::Layout::d_escapes_sliced or d_gaps_sliced)
+      const uint32_t* granule_base;  // counter of every granule's first key
+      const uint32_t* slice_first;   // [n_slices][positions + 1], in the packed numbering
+      const uint32_t* heaviest;      // per granule (SeqStoreHost::Layout::d_granule_heaviest), or nullptr: every granule is counted
+      const uint32_t* without;       // per granule (d_granule_without)
+      uint32_t positions;
+      uint32_t pos_begin;
+      uint32_t pos_end;
+      uint32_t out_symbols;       // counters per position: the store's scan symbols (keys), 2 (gap events: starts, ends)
+      uint32_t key_from;          // the position whose keys a slice's are read from: pos_begin, or 0 for gap events, whose
+                                  // events before pos_begin count on pos_begin's counters (a gap open there counts as begun)
+      uint32_t first_block;       // the blocks of the ranges before
+      uint32_t blocks_per_slice;
+      uint32_t* counts[SILO_GPU_MAX_SCAN_BATCH];  // of the range's first position
+   } ranges[ESCAPE_MAX_RANGES];
+};
+
+static_assert(sizeof(EscapeSliceArgs) + sizeof(uint32_t) <= 4096, "k_scan_escapes_sliced takes its arguments by value: the kernel-argument segment holds 4 KiB");
+
+/// Workgroup barrier for data exchanged through LDS only: waits for the wave's LDS operations, NOT for its outstanding global
+/// loads — __syncthreads() is also a fence and drains vmcnt(0), which would stall a block on the loads it has prefetched for
+/// its next step at every barrier.
+__device__ __forceinline__ void ldsBarrier() {
+   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+/// FILTERS = filters a block serves with ONE pass over its keys (1, 2, 4 or 8: a batch of 8 filters keeps 8 x 16 KiB of filter
+/// slices in LDS and reads every key once, not once per filter); blockIdx.z = first filter / FILTERS.
+///
+/// Keys.  4 bytes each: row within the slice | (counter - counter of the granule's first key) << 17; a granule is 4 096
+/// consecutive keys of a slice, so ONE 16-byte load per lane of the block fetches a granule, four consecutive keys per lane,
+/// and the granule's base counter is a scalar.
+///
+/// Counting.  The keys of a slice are sorted by (position, symbol), so the counters a run of keys adds to lie in a narrow
+/// window behind its first key: the block counts into a window of LDS counters per filter and then adds the window to the
+/// table with CONTIGUOUS atomics — 64 consecutive counters per wave instruction, the shape the memory side takes at full
+/// rate; a lane per scattered counter, as the first version did, is an order of magnitude slower per add (MI355X guide,
+/// "Global float atomics": access shape).  The block's share of keys is cut into chunks where the window is full: as many
+/// granules as end within WINDOW counters of the chunk's first (the granules' base counters tell) — thousands of keys per
+/// chunk where a position has many, one granule where private substitutions lie thirteen to a position; the window is
+/// flushed and reused chunk by chunk, the filter slices stay.  Lanes whose keys share a counter add through the stretch's last
+/// lane only (identical addresses do not combine for LDS atomics), and the loop body has no per-key branch (see there).  No
+/// barrier between a chunk's granules: the waves run on by themselves, one waits for its keys while another counts; two
+/// blocks per CU for one and two filters (<= 64 VGPRs, 64 KiB of LDS) cover each other's first and last steps.  Eight filters:
+/// the slices as one byte per row and the lanes' sums in packed fields (see there), one block per CU.
+constexpr uint32_t ESCAPE_GRANULES_PER_BLOCK = 64;  // of a block's share, at most
+template <int FILTERS>
+constexpr uint32_t escapeWindow() {  // LDS counters per filter: 48 KiB of them for 1-4 filters, 28 KiB for 8 (beside 128 KiB of filter slices)
+   return FILTERS >= 8 ? 896u : 12288u / FILTERS;
+}
+template <int FILTERS>
+constexpr uint32_t escapeLdsBytes() {
+   return (FILTERS * (ESCAPE_SLICE_WORDS32 + escapeWindow<FILTERS>()) + 3u * ESCAPE_GRANULES_PER_BLOCK + 4u + 64u) * static_cast<uint32_t>(sizeof(uint32_t));
+}
+
+template <int FILTERS>
+__global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_scan_escapes_sliced(const EscapeSliceArgs args, uint32_t n_filters) {
+   constexpr uint32_t WINDOW = escapeWindow<FILTERS>();
+   static_assert(ESCAPE_GRANULE_KEYS == ESCAPE_SLICE_THREADS * 4u, "a granule is one 16-byte load per thread of the block");
+   extern __shared__ uint32_t s_filter[];  // [FILTERS][ESCAPE_SLICE_WORDS32], then the counters [FILTERS][WINDOW], the granules' bases, the chunks' last keys
+   uint32_t* s_count = s_filter + FILTERS * ESCAPE_SLICE_WORDS32;
+   // the LIVE granules of the share — all of them, or those a pruning scan does not skip —, in order: the counter of each one's
+   // first key, one past the counter of its last key (the next granule's first; for the share's last granule one past its last
+   // key's), its number within the share; s_live[ESCAPE_GRANULES_PER_BLOCK] = how many there are
+   uint32_t* s_base = s_count + FILTERS * WINDOW;           // [ESCAPE_GRANULES_PER_BLOCK]
+   uint32_t* s_end = s_base + ESCAPE_GRANULES_PER_BLOCK;    // [ESCAPE_GRANULES_PER_BLOCK]
+   uint32_t* s_live = s_end + ESCAPE_GRANULES_PER_BLOCK;    // [ESCAPE_GRANULES_PER_BLOCK + 1]
+   uint32_t* s_nowhere = s_live + ESCAPE_GRANULES_PER_BLOCK + 4u;  // [64] a word per lane: where an add of nothing goes
+   const uint32_t first_filter = blockIdx.z * FILTERS;
+   uint32_t r = 0;
+   while (r + 1u < args.n_ranges && blockIdx.x >= args.ranges[r + 1u].first_block) {  // (uniform)
+      ++r;
+   }
+   const EscapeSliceArgs::Range& range = args.ranges[r];
+   const uint32_t slice = (blockIdx.x - range.first_block) / range.blocks_per_slice;
+   const uint32_t share = (blockIdx.x - range.first_block) % range.blocks_per_slice;
+   const uint32_t out_symbols = range.out_symbols;
+   const uint32_t* first = range.slice_first + static_cast<size_t>(slice) * (range.positions + 1u);
+   const uint32_t key_begin = first[range.key_from];
+   const uint32_t key_end = first[range.pos_end];
+   // the block's share: args.block_keys keys (whole granules)
+   const uint32_t share_begin = key_begin / ESCAPE_GRANULE_KEYS * ESCAPE_GRANULE_KEYS + share * args.block_keys;
+   if (share_begin >= key_end) {
+      return;  // (uniform) no keys for this block
+   }
+   const uint32_t share_end = min(share_begin + args.block_keys, key_end);
+   const uint32_t range_first = range.pos_begin * out_symbols;
+   const bool clamp = range.key_from < range.pos_begin;  // (uniform) gap events before the range's first position
+   // Everything the block reads first is asked for at once, behind the one dependent load of the slice index: the filter
+   // slices, the first keys, the granules' base counters, the share's last key — every memory latency put in a row would
+   // show; the keys of the granule after the next are asked for while a granule is counted, across the chunks.
+   const uint32_t first_granule = share_begin / ESCAPE_GRANULE_KEYS;
+   const uint32_t n_granules = (share_end - share_begin + ESCAPE_GRANULE_KEYS - 1u) / ESCAPE_GRANULE_KEYS;  // <= ESCAPE_GRANULES_PER_BLOCK
+   // (unconditional: a load under a condition, or a loaded register handed on by a move, makes the compiler wait for ALL loads
+   // in flight where the first is used — vmcnt(0) in the loop took a memory latency per granule: 86 us for 73 M keys.  A granule
+   // past the share's last reads that one again; the whole granule exists, padded, past the slice's last key.)
+   const auto loadGranule = [&](uint32_t granule) {  // (its number within the share)
+      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(range.keys + share_begin + granule * ESCAPE_GRANULE_KEYS + threadIdx.x * 4u));
+      return make_uint4(v.x, v.y, v.z, v.w);
+   };
+   // The list of live granules, by the block's first wave (a share has at most 64 granules: one per lane).  A pruning scan
+   // skips a granule where NO filter of the pass can report a row from its keys (granulePrunable: the select kernel's own
+   // arithmetic on a lower bound of the rows covered); the counts of such keys end up on the position's derived symbol.
+   const bool prune = range.heaviest != nullptr;  // (uniform)
+   const auto listGranules = [&]() {
+      if (threadIdx.x >= 64u) {
+         return;
+      }
+      const bool in_share = threadIdx.x < n_granules;
+      bool live = in_share;
+      if (prune && in_share) {
+         const uint32_t heaviest = range.heaviest[first_granule + threadIdx.x];
+         const uint32_t without = range.without[first_granule + threadIdx.x];
+         bool skip = true;
+#pragma unroll
+         for (int f = 0; f < FILTERS; ++f) {
+            if (first_filter + f < n_filters) {
+               skip = skip && granulePrunable(args.counters[(first_filter + f) * SPARSE_COUNTER_STRIDE + 2u], without, heaviest, args.min_proportion[first_filter + f]);
+            }
+         }
+         live = !skip;
+      }
+      const uint64_t live_lanes = __ballot(live);
+      if (live) {
+         const uint32_t k = static_cast<uint32_t>(__popcll(live_lanes & ((uint64_t{1} << threadIdx.x) - 1u)));
+         s_live[k] = threadIdx.x;
+         s_base[k] = range.granule_base[first_granule + threadIdx.x];
+         // (a key that went to the overflow list reads as the largest relative counter: a wider window, nothing else)
+         s_end[k] = threadIdx.x + 1u < n_granules ? range.granule_base[first_granule + threadIdx.x + 1u]
+                                                  : range.granule_base[first_granule + threadIdx.x] + (range.keys[share_end - 1u] >> ESCAPE_SLICE_SHIFT) + 1u;
+      }
+      if (threadIdx.x == 0) {
+         s_live[ESCAPE_GRANULES_PER_BLOCK] = static_cast<uint32_t>(__popcll(live_lanes));
+      }
+   };
+   // (the list's entries are the same for every lane: kept in scalar registers, not one vector register each)
+   const auto liveGranule = [&](uint32_t k) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(s_live[k]))); };
+   uint32_t n_live = n_granules;
+   if (prune) {  // (uniform) the list first: a block whose granules all skip leaves before it asks for its filter slices and keys
+      listGranules();
+      __syncthreads();
+      n_live = liveGranule(ESCAPE_GRANULES_PER_BLOCK);
+      if (n_live == 0) {
+         return;
+      }
+   }
+   const auto loadKeys = [&](uint32_t k) {  // the k-th live granule; past the last: that one again
+      return loadGranule(liveGranule(min(k, n_live - 1u)));
+   };
+   uint64_t any_bit = 0;
+   ulonglong2 filter_part[FILTERS][ESCAPE_SLICE_WORDS32 / 4u / ESCAPE_SLICE_THREADS];
+#pragma unroll
+   for (int f = 0; f < FILTERS; ++f) {  // this slice of every filter: 16 bytes per thread, zeros past the end of the row (and for a filter past the last)
+      const uint32_t first_word = slice * (ESCAPE_SLICE_WORDS32 / 2u);
+      const bool present = first_filter + f < n_filters;
+      const uint64_t* filter = args.filters[present ? first_filter + f : first_filter];
+#pragma unroll
+      for (uint32_t j = 0; j < ESCAPE_SLICE_WORDS32 / 4u / ESCAPE_SLICE_THREADS; ++j) {
+         const uint32_t word = first_word + (j * ESCAPE_SLICE_THREADS + threadIdx.x) * 2u;  // 16-byte chunk of the slice
+         filter_part[f][j] = present && word < args.row_words ? *reinterpret_cast<const ulonglong2*>(filter + word) : make_ulonglong2(0, 0);
+      }
+   }
+   // three granules in flight per wave, in registers of their own (without pruning the list is not written yet: granule k is live granule k)
+   uint4 quad0 = prune ? loadKeys(0) : loadGranule(0);
+   uint4 quad1 = prune ? loadKeys(1) : loadGranule(min(1u, n_granules - 1u));
+   uint4 quad2 = prune ? loadKeys(2) : loadGranule(min(2u, n_granules - 1u));
+   if (!prune) {
+      listGranules();
+   }
+   // Eight filters: their slices are kept as ONE BYTE PER ROW — bit f = filter f has the row — so that a key's lookup is one
+   // LDS read for all eight (a read per filter and key made the eight-filter pass LDS-bound: 32 of its ~70 LDS instructions
+   // per granule and wave).  A thread holds the 128 rows of its 16-byte part of every filter and writes their 128 bytes.
+   constexpr bool BYTE_PER_ROW = FILTERS == 8;
+   static_assert(ESCAPE_SLICE_WORDS32 / 4u / ESCAPE_SLICE_THREADS == 1u, "a thread holds one 16-byte part of a filter slice");
+#pragma unroll
+   for (int f = 0; f < FILTERS; ++f) {
+      for (uint32_t j = threadIdx.x * 4u; j < WINDOW; j += ESCAPE_SLICE_THREADS * 4u) {  // (16 bytes per store; WINDOW is a multiple of 4)
+         *reinterpret_cast<uint4*>(s_count + f * WINDOW + j) = make_uint4(0, 0, 0, 0);
+      }
+      if constexpr (!BYTE_PER_ROW) {
+         *reinterpret_cast<ulonglong2*>(s_filter + f * ESCAPE_SLICE_WORDS32 + threadIdx.x * 4u) = filter_part[f][0];
+      }
+      any_bit |= filter_part[f][0].x | filter_part[f][0].y;
+   }
+   if constexpr (BYTE_PER_ROW) {
+#pragma unroll
+      for (uint32_t quarter = 0; quarter < 4; ++quarter) {  // 32 rows of the thread's 128: 32 bytes
+         uint32_t bytes[8];
+#pragma unroll
+         for (uint32_t k = 0; k < 8; ++k) {
+            bytes[k] = 0;
+         }
+#pragma unroll
+         for (int f = 0; f < FILTERS; ++f) {
+            const uint64_t half = quarter < 2 ? filter_part[f][0].x : filter_part[f][0].y;
+            const uint32_t rows32 = static_cast<uint32_t>(half >> (32u * (quarter & 1u)));
+#pragma unroll
+            for (uint32_t k = 0; k < 8; ++k) {  // four rows -> the low bits of four bytes
+               bytes[k] |= ((((rows32 >> (4u * k)) & 0xFu) * 0x00204081u) & 0x01010101u) << f;
+            }
+         }
+         uint32_t* out = s_filter + threadIdx.x * 32u + quarter * 8u;  // (row r of the slice = byte r)
+         *reinterpret_cast<uint4*>(out) = make_uint4(bytes[0], bytes[1], bytes[2], bytes[3]);
+         *reinterpret_cast<uint4*>(out + 4) = make_uint4(bytes[4], bytes[5], bytes[6], bytes[7]);
+      }
+   }
+   if (__syncthreads_or(any_bit != 0 ? 1 : 0) == 0) {
+      return;  // no row of this slice is selected: none of its keys counts
+   }
+   const uint32_t lane = __lane_id();
+   // the chunk being counted: the granules up to chunk_granules, its window of counters
+   uint32_t window_first = 0, window_used = 0, chunk_granules = 0, chunk_end = 0;
+   const auto beginChunk = [&](uint32_t g) {
+      // the window begins at the chunk's first key's position (the range's first position where the granule begins before it)
+      // and takes the granules that end within WINDOW counters of that, one at least
+      const uint32_t first_counter = max(s_base[g], range_first);
+      window_first = first_counter / out_symbols * out_symbols - range_first;
+      uint32_t h = g + 1u;
+      while (h < n_live && max(s_end[h], range_first) - range_first - window_first < WINDOW) {  // (a granule's last key may sit on the next one's first counter)
+         ++h;
+      }
+      chunk_granules = h;
+      chunk_end = min(share_begin + (liveGranule(h - 1u) + 1u) * ESCAPE_GRANULE_KEYS, share_end);
+      window_used = min(WINDOW, (max(s_end[h - 1u], range_first) / out_symbols + 1u) * out_symbols - range_first - window_first);
+   };
+   // the chunk's window goes to the table — contiguous atomics, 64 consecutive counters per wave instruction — and is zero
+   // again for the next chunk
+   const auto flushChunk = [&]() {
+      ldsBarrier();
+#pragma unroll
+      for (int f = 0; f < FILTERS; ++f) {
+         uint32_t* __restrict__ counts = range.counts[first_filter + f < n_filters ? first_filter + f : first_filter] + window_first;
+         for (uint32_t j = threadIdx.x; j < window_used; j += ESCAPE_SLICE_THREADS) {
+            const uint32_t value = s_count[f * WINDOW + j];
+            if (value != 0) {
+               s_count[f * WINDOW + j] = 0;
+               atomicAdd(&counts[j], value);
+            }
+         }
+      }
+      ldsBarrier();
+   };
+   const auto countGranule = [&](uint4& in_flight, uint32_t g) {  // (g is uniform: the g-th live granule)
+      if (g >= n_live) {
+         return;
+      }
+      if (g == chunk_granules) {
+         flushChunk();
+         beginChunk(g);
+      }
+      const uint4 quad = in_flight;
+      in_flight = loadKeys(g + 3u);
+      const uint32_t granule_first = share_begin + liveGranule(g) * ESCAPE_GRANULE_KEYS;
+      {
+         const uint32_t granule_counter = s_base[g] - range_first - window_first;  // (wraps below the window: such keys are masked)
+         const uint32_t i = granule_first + threadIdx.x * 4u;
+         const uint32_t keys4[4] = {quad.x, quad.y, quad.z, quad.w};
+         uint32_t in_window[4];
+         bool valid[4];
+         // the keys before the scanned positions' first and behind their last, read along in the first and the last granule, are masked out
+         // (one unsigned comparison per key: index - first valid index < number of valid indices)
+         if (granule_first >= key_begin && granule_first + ESCAPE_GRANULE_KEYS <= chunk_end) {  // (uniform) the granule lies inside: nearly all do
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+               valid[c] = keys4[c] != ESCAPE_KEY_INVALID;
+            }
+         } else {
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+               valid[c] = static_cast<bool>(static_cast<uint32_t>(keys4[c] != ESCAPE_KEY_INVALID) & static_cast<uint32_t>(i + c - key_begin < chunk_end - key_begin));
+            }
+         }
+#pragma unroll
+         for (uint32_t c = 0; c < 4; ++c) {
+            in_window[c] = granule_counter + (keys4[c] >> ESCAPE_SLICE_SHIFT);
+         }
+         if (clamp && s_base[g] < range_first) {  // (uniform) a gap event before the range's first position counts on its counters:
+            // the window begins there (window_first = 0) and an event below it keeps its kind (range_first is even)
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+               in_window[c] = static_cast<int32_t>(in_window[c]) < 0 ? in_window[c] & 1u : in_window[c];
+            }
+         }
+         // A lane's four keys are consecutive keys of the sorted list.  Those on the counter of its first key are summed in the
+         // lane (n0 <= 4); across the lanes these first counters ascend, lanes on the same one form a stretch, and a stretch adds
+         // ONCE, through its last lane: the selected keys of the lanes up to and including it (population counts of the wave's
+         // ballots of the bits of n0) minus those before the stretch's first lane (fetched from that lane) — no 64 lanes on one
+         // LDS counter (identical addresses do not combine: ~12 cycles per lane), no add at all for a stretch without a selected
+         // key (the keys read along outside the chunk lie in such stretches), and ~80 instructions per four keys where a stretch
+         // mask per key column took 300.  A key on another counter than the lane's first (a lane on a boundary) adds by itself.
+         const uint32_t counter0 = in_window[0];
+         const uint32_t previous = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(counter0), 0x138 /* wave_shr:1 */, 0xF, 0xF, false));
+         const uint32_t following = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(counter0), 0x130 /* wave_shl:1 */, 0xF, 0xF, false));
+         const bool head = lane == 0 || counter0 != previous;
+         const bool tail = lane == 63 || counter0 != following;
+         const uint64_t heads_at_or_below = __ballot(head) & (~uint64_t{0} >> (63u - lane));  // (lane 0 is one: never empty)
+         const uint32_t first_of_stretch = 63u - static_cast<uint32_t>(__builtin_clzll(heads_at_or_below));
+         // The body has no per-key branch: an add that has nothing to add goes to a word of the lane's own (64 lanes adding zero
+         // to one counter would still serialise) — 4 LDS atomics per granule and filter whatever the keys.  Where a granule by
+         // itself always fits the window (FILTERS <= 2: ESCAPE_MAX_RELATIVE) every selected key of a chunk lies inside it and
+         // there is no second path either.  With per-key branches and a table path through a merged (flat) address the body
+         // took 250 instructions per granule and wave, half of them exec-mask traffic, and the kernel was bound by them
+         // (profiles/r03_notes.md): 151 now.
+         constexpr bool EVERY_KEY_IN_WINDOW = WINDOW >= ESCAPE_MAX_RELATIVE + 64u;
+         [[maybe_unused]] uint32_t filters_with[4] = {0, 0, 0, 0};  // (one byte per row: bit f = filter f has the key's row)
+         if constexpr (BYTE_PER_ROW) {
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+               filters_with[c] = reinterpret_cast<const uint8_t*>(s_filter)[keys4[c] & ESCAPE_ROW_MASK] & (valid[c] ? 0xFFu : 0u);  // (the read itself is always inside the slice)
+            }
+         }
+         if constexpr (BYTE_PER_ROW) {
+            // Eight filters at once.  The lane's sums per filter (<= 4) sit two to a register in 16-bit fields, so ONE inclusive
+            // scan over the lanes (6 DPP adds per register) gives every filter's prefix, and one ds_bpermute per register the
+            // prefixes at the stretch's first lane; only the final adds are per filter.  (Filter by filter — ballots, mbcnt,
+            // a bpermute each — the pass cost eight times the one-filter kernel per key: 2/3 of the configs[4] batch.)
+            const auto add8 = [&](uint32_t counter, uint32_t value, int f) {
+               const bool here = value != 0 && counter < WINDOW;
+               if (__ballot(here) != 0) {
+                  atomicAdd(here ? &s_count[f * WINDOW + counter] : &s_nowhere[lane], here ? value : 0u);
+               }
+               if (value != 0 && counter >= WINDOW) {  // a key past the window: straight to the table
+                  atomicAdd(&range.counts[first_filter + f < n_filters ? first_filter + f : first_filter][window_first + counter], value);
+               }
+            };
+            uint32_t on_first = filters_with[0];          // per key: the filters that have it, if it sits on the lane's first counter
+            uint32_t sums[4] = {0, 0, 0, 0};              // [k]: filters 2k (low field) and 2k + 1 (high field)
+            uint32_t elsewhere[4] = {0, 0, 0, 0};         // per key: the filters that have it, if it sits on another counter
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+               if (c != 0) {
+                  const bool same = in_window[c] == counter0;
+                  on_first = same ? filters_with[c] : 0u;
+                  elsewhere[c] = same ? 0u : filters_with[c];
+               }
+#pragma unroll
+               for (uint32_t k = 0; k < 4; ++k) {
+                  sums[k] += ((on_first >> (2u * k)) & 1u) | (((on_first >> (2u * k + 1u)) & 1u) << 16);
+               }
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+               const uint32_t through = waveSumToLane63(sums[k]);  // (inclusive scan over the lanes: <= 256 per field)
+               const uint32_t before = through - sums[k];
+               const uint32_t before_stretch = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>(first_of_stretch * 4u), static_cast<int>(before)));
+               const uint32_t stretch = through - before_stretch;  // (field by field: no borrow, a prefix never exceeds a later one)
+               add8(counter0, tail ? stretch & 0xFFFFu : 0u, static_cast<int>(2u * k));
+               add8(counter0, tail ? stretch >> 16 : 0u, static_cast<int>(2u * k + 1u));
+            }
+#pragma unroll
+            for (uint32_t c = 1; c < 4; ++c) {
+               if (__ballot(elsewhere[c] != 0) != 0) {  // (uniform) a lane on a boundary of counters
+#pragma unroll
+                  for (int f = 0; f < FILTERS; ++f) {
+                     add8(in_window[c], (elsewhere[c] >> f) & 1u, f);
+                  }
+               }
+            }
+            return;
+         }
+#pragma unroll
+         for (int f = 0; f < FILTERS; ++f) {
+            uint32_t* __restrict__ window = s_count + f * WINDOW;
+            // (an add of nothing goes to the lane's own word; where a key may lie past the window it goes to the table by itself)
+            [[maybe_unused]] uint32_t* __restrict__ table = range.counts[first_filter + f < n_filters ? first_filter + f : first_filter] + window_first;
+            const auto add = [&](uint32_t counter, uint32_t value) {
+               const bool here = EVERY_KEY_IN_WINDOW ? value != 0 : value != 0 && counter < WINDOW;
+               atomicAdd(here ? &window[counter] : &s_nowhere[lane], here ? value : 0u);
+               if constexpr (!EVERY_KEY_IN_WINDOW) {
+                  if (value != 0 && counter >= WINDOW) {
+                     atomicAdd(&table[counter], value);
+                  }
+               }
+            };
+            uint32_t n0 = 0;
+            uint32_t elsewhere[4] = {0, 0, 0, 0};  // a key of the lane on another counter than its first, selected
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+               const uint32_t row = keys4[c] & ESCAPE_ROW_MASK;
+               const uint32_t selected = (s_filter[f * ESCAPE_SLICE_WORDS32 + (row >> 5)] >> (row & 31u)) & (valid[c] ? 1u : 0u);  // (the read itself is always inside the slice)
+               if (c == 0) {
+                  n0 = selected;
+               } else {
+                  const bool same = in_window[c] == counter0;
+                  n0 += same ? selected : 0u;
+                  elsewhere[c] = same ? 0u : selected;
+               }
+            }
+            if (__ballot((elsewhere[1] | elsewhere[2] | elsewhere[3]) != 0) != 0) {  // (uniform: where the keys are many to a counter no lane has one)
+#pragma unroll
+               for (uint32_t c = 1; c < 4; ++c) {
+                  add(in_window[c], elsewhere[c]);
+               }
+            }
+            // the stretch's sum at its last lane: an inclusive scan of the lanes' sums (6 DPP adds) less the prefix at its first lane
+            const uint32_t through = waveSumToLane63(n0);
+            const uint32_t before_stretch = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>(first_of_stretch * 4u), static_cast<int>(through - n0)));
+            add(counter0, tail ? through - before_stretch : 0u);
+         }
+      }
+   };
+   beginChunk(0);
+   for (uint32_t g = 0; g < n_live; g += 3u) {  // (uniform)
+      countGranule(quad0, g);
+      countGranule(quad1, g + 1u);
+      countGranule(quad2, g + 2u);
+   }
+   flushChunk();
+}
+
+/// The few keys of a store that do not fit the packed form (SeqStoreHost::Layout::d_escapes_overflow: counter << 32 | sequence),
+/// for the positions [pos_begin, pos_end): one global filter lookup and one atomic each; grid.y = filter.
+__global__ __launch_bounds__(256) void k_scan_escapes_overflow(
+   const uint64_t* __restrict__ keys, uint32_t n_keys, const ScanBatchArgs batch, uint32_t pos_begin, uint32_t pos_end
+) {
+   const uint32_t q = blockIdx.y;
+   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+   if (i >= n_keys) {
+      return;
+   }
+   const uint64_t key = keys[i];
+   const uint32_t counter = static_cast<uint32_t>(key >> 32);
+   const uint32_t sequence = static_cast<uint32_t>(key);
+   if (counter >= pos_begin * batch.out_symbols && counter < pos_end * batch.out_symbols && ((batch.filters[q][sequence >> 6] >> (sequence & 63u)) & 1ull) != 0) {
+      atomicAdd(&batch.counts[0][q][counter - pos_begin * batch.out_symbols], 1u);
+   }
+}
+
+/// The launch descriptor of the position-major and the overflow keys of `range`: its filters and its count tables.
+ScanBatchArgs keyBatch(const ScanRange& range, const uint64_t* const* filters, uint32_t q_count) {
+   ScanBatchArgs batch{};
+   batch.out_symbols = range.seqstore->dev.n_scan;
+   copyFilters(batch.filters, filters, q_count);
+   std::copy_n(range.counts, q_count, batch.counts[0]);
+   return batch;
+}
+
+}  // namespace
+
+namespace silo_gpu_detail {
+
+/// The rows the code planes do not carry: one pass over the escape keys of every range, for all filters (dense and
+/// sparse alike: the gather reads the same planes); with `gaps` (one entry per range: its store and positions, counts = the range's gap tables,
+/// null where it has none) also the gap events of their stores, in the same launches.
+/// With `gaps` and pruning->keys the pass may skip the granules of keys that no Mutations row of the filters' proportions can come
+/// from, where the store has the bounds for it (EscapeSliceArgs::counters); the gap events and the overflow keys are always counted.
+int scanEscapes(
+   const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream, const std::vector<ScanRange>* gaps,
+   const ScanPruning* pruning
+) {
+   // the ranges whose stores have slice-major keys go ESCAPE_MAX_RANGES at a time into one launch of k_scan_escapes_sliced
+   EscapeSliceArgs sliced{};
+   copyFilters(sliced.filters, filters, q_count);
+   const bool prune = gaps != nullptr && pruning != nullptr && pruning->keys;
+   if (prune) {
+      std::copy_n(pruning->min_proportion, q_count, sliced.min_proportion);
+      sliced.counters = pruning->counters;
+   }
+   uint32_t n_sliced = 0;
+   std::array<uint32_t, ESCAPE_MAX_RANGES> most_keys{};  // of one (range, slice)
+   uint64_t total_keys = 0;  // of the ranges of the launch
+   const auto launchSliced = [&]() -> int {
+      if (n_sliced == 0) {
+         return SILO_GPU_OK;
+      }
+      static std::once_flag lds_once;
+      std::call_once(lds_once, [] {  // filter slices + counter windows: beyond what a kernel may ask for by default
+         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_escapes_sliced<1>), hipFuncAttributeMaxDynamicSharedMemorySize, escapeLdsBytes<1>());
+         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_escapes_sliced<2>), hipFuncAttributeMaxDynamicSharedMemorySize, escapeLdsBytes<2>());
+         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_escapes_sliced<4>), hipFuncAttributeMaxDynamicSharedMemorySize, escapeLdsBytes<4>());
+         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_escapes_sliced<8>), hipFuncAttributeMaxDynamicSharedMemorySize, escapeLdsBytes<8>());
+      });
+      const uint32_t per_block = q_count <= 1 ? 1 : (q_count <= 2 ? 2 : (q_count <= 4 ? 4 : 8));  // filters per pass over the keys
+      // a block's share of a slice's keys: whole granules, about five shares to each of the 512 places of the chip (the slices
+      // differ in their keys, and a share's time in how its keys lie), at most ESCAPE_GRANULES_PER_BLOCK
+      const uint32_t passes = (q_count + per_block - 1) / per_block;
+      const uint64_t granules = (total_keys + ESCAPE_GRANULE_KEYS - 1) / ESCAPE_GRANULE_KEYS * passes;
+      const uint32_t block_granules = static_cast<uint32_t>(std::min<uint64_t>(ESCAPE_GRANULES_PER_BLOCK, std::max<uint64_t>(1, granules / 1280)));  // (flat between 640 and 2 560: profiles/r03_notes.md)
+      const uint32_t block_keys = block_granules * ESCAPE_GRANULE_KEYS;
+      sliced.block_keys = block_keys;
+      sliced.n_ranges = n_sliced;
+      uint32_t blocks = 0;  // every range as many per slice as its slice with the most keys needs
+      for (uint32_t k = 0; k < n_sliced; ++k) {
+         sliced.ranges[k].first_block = blocks;
+         sliced.ranges[k].blocks_per_slice = std::max<uint32_t>(1, (most_keys[k] + block_keys - 1) / block_keys);
+         blocks += sliced.ranges[k].blocks_per_slice * sliced.n_slices;
+      }
+      const dim3 grid(blocks, 1, passes);
+      char name[64];
+      bool bounds = false;  // a launch that may skip granules says so in the timing log (", pruning" behind the kernel's name)
+      for (uint32_t k = 0; k < n_sliced; ++k) {
+         bounds = bounds || sliced.ranges[k].heaviest != nullptr;
+      }
+      std::snprintf(name, sizeof(name), "k_scan_escapes_sliced<%u>%s", per_block, bounds ? ", pruning" : "");
+      // bytes: the keys and gap events (4 each) once per pass of `per_block` filters, plus a 16 KiB filter slice per block and filter
+      ScanLaunchTiming* timing = startLaunchTiming(
+         name, 0, total_keys * sizeof(uint32_t) * grid.z + static_cast<uint64_t>(grid.x) * q_count * ESCAPE_SLICE_WORDS32 * sizeof(uint32_t), q_count,
+         grid.x * grid.z, hip_stream
+      );
+      switch (per_block) {
+         case 1: k_scan_escapes_sliced<1><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<1>(), hip_stream>>>(sliced, q_count); break;
+         case 2: k_scan_escapes_sliced<2><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<2>(), hip_stream>>>(sliced, q_count); break;
+         case 4: k_scan_escapes_sliced<4><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<4>(), hip_stream>>>(sliced, q_count); break;
+         default: k_scan_escapes_sliced<8><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<8>(), hip_stream>>>(sliced, q_count); break;
+      }
+      HIP_TRY(hipGetLastError());
+      finishLaunchTiming(timing, hip_stream);
+      n_sliced = 0;
+      most_keys.fill(0);
+      total_keys = 0;
+      return SILO_GPU_OK;
+   };
+   // one entry of a launch: the packed keys (or gap events) of a store over [key_from, pos_end) of its positions
+   const auto addSliced = [&](const ScanRange& range, uint32_t n_slices, const uint32_t* keys, const uint32_t* granule_base, const uint32_t* slice_first,
+                              const std::vector<uint32_t>& host_slice_first, uint32_t out_symbols, uint32_t key_from, const uint32_t* heaviest = nullptr,
+                              const uint32_t* without = nullptr) -> int {
+      if (n_sliced == ESCAPE_MAX_RANGES || (n_sliced != 0 && sliced.n_slices != n_slices)) {
+         if (const int rc = launchSliced(); rc != SILO_GPU_OK) {
+            return rc;
+         }
+      }
+      sliced.row_words = range.seqstore->dev.row_words;
+      sliced.n_slices = n_slices;
+      EscapeSliceArgs::Range& entry = sliced.ranges[n_sliced];
+      entry.keys = keys;
+      entry.granule_base = granule_base;
+      entry.slice_first = slice_first;
+      entry.heaviest = heaviest;
+      entry.without = without;
+      entry.positions = range.seqstore->dev.positions;
+      entry.pos_begin = range.pos_begin;
+      entry.pos_end = range.pos_end;
+      entry.out_symbols = out_symbols;
+      entry.key_from = key_from;
+      std::copy_n(range.counts, q_count, entry.counts);
+      const size_t stride = static_cast<size_t>(entry.positions) + 1;
+      for (uint32_t slice = 0; slice < n_slices; ++slice) {
+         const uint32_t n = host_slice_first[slice * stride + range.pos_end] - host_slice_first[slice * stride + key_from];
+         total_keys += n;
+         most_keys[n_sliced] = std::max(most_keys[n_sliced], n + ESCAPE_GRANULE_KEYS - 1u);  // (blocks start at a granule boundary)
+      }
+      ++n_sliced;
+      return SILO_GPU_OK;
+   };
+   // the gap events of a range's store, behind its keys: from its first position on where the range begins later (see EscapeSliceArgs)
+   const auto addGaps = [&](size_t r) -> int {
+      const SeqStoreHost::Layout& layout = ranges[r].seqstore->layout;
+      if (gaps == nullptr || (*gaps)[r].seqstore == nullptr || layout.d_gaps_sliced == nullptr) {
+         return SILO_GPU_OK;
+      }
+      return addSliced((*gaps)[r], layout.gap_slices, layout.d_gaps_sliced, layout.d_gap_granule_base, layout.d_gap_slice_first, layout.gap_slice_first, 2, 0);
+   };
+   for (size_t r = 0; r < ranges.size(); ++r) {
+      const ScanRange& range = ranges[r];
+      const SeqStoreHost::Layout& layout = range.seqstore->layout;
+      const uint32_t begin = layout.built && layout.d_escapes != nullptr ? layout.escape_first[range.pos_begin] : 0;
+      const uint32_t count = layout.built && layout.d_escapes != nullptr ? layout.escape_first[range.pos_end] - begin : 0;
+      if (count == 0) {
+         if (const int rc = addGaps(r); rc != SILO_GPU_OK) {
+            return rc;
+         }
+         continue;
+      }
+      if (layout.d_escapes_sliced != nullptr && g_tune_side_stream.load() != 3) {  // the slice-major keys, a slice of the filter in LDS
+         if (layout.n_overflow != 0) {  // the few keys that do not fit the packed form: a small launch of their own
+            k_scan_escapes_overflow<<<dim3((layout.n_overflow + 255) / 256, q_count), 256, 0, hip_stream>>>(
+               layout.d_escapes_overflow, layout.n_overflow, keyBatch(range, filters, q_count), range.pos_begin, range.pos_end
+            );
+            HIP_TRY(hipGetLastError());
+         }
+         const bool bounds = prune && layout.d_granule_heaviest != nullptr && layout.d_granule_without != nullptr;
+         if (const int rc = addSliced(
+                range, layout.n_slices, layout.d_escapes_sliced, layout.d_granule_base, layout.d_slice_first, layout.slice_first, range.seqstore->dev.n_scan,
+                range.pos_begin, bounds ? layout.d_granule_heaviest : nullptr, bounds ? layout.d_granule_without : nullptr
+             );
+             rc != SILO_GPU_OK) {
+            return rc;
+         }
+         if (const int rc = addGaps(r); rc != SILO_GPU_OK) {
+            return rc;
+         }
+         continue;
+      }
+      if (const int rc = addGaps(r); rc != SILO_GPU_OK) {
+         return rc;
+      }
+      const uint32_t keys_per_block = 256 * ESCAPE_KEYS_PER_THREAD;
+      k_scan_escapes<<<dim3((count + keys_per_block - 1) / keys_per_block, q_count), 256, 0, hip_stream>>>(
+         layout.d_escapes + begin, count, keyBatch(range, filters, q_count), range.pos_begin
+      );
+      HIP_TRY(hipGetLastError());
+   }
+   return launchSliced();
+}
+
+}  // namespace silo_gpu_detail

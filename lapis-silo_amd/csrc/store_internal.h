@@ -2,7 +2,9 @@
 // description of a sequence store, its host-side state, the store itself, the wave-level helpers and a few constants.
 //   silo_gpu_runtime.hip   errors, tuning knobs, memory / stream / event wrappers, the stream-read probe
 //   silo_gpu_store.hip     store lifetime, the build kernels (transpose, generator), finalize: runs of the missing symbol, layout
-//   silo_gpu_scan.hip      K1 the Mutations scan (plane rows, escape keys, derived symbols), K4 row selection, row slots
+//   silo_gpu_scan.hip      K1 the Mutations scan over ranges; its passes, one file each behind scan_internal.h:
+//                          silo_gpu_scan_planes.hip (plane rows), silo_gpu_scan_keys.hip (escape keys), silo_gpu_scan_derived.hip (derived symbols)
+//   silo_gpu_select.hip    K4 row selection, row slots
 //   silo_gpu_filter.hip    K2 / K3 / K3b filter evaluation, count slots, bitsets, planes of single symbols, FastaAligned
 //   silo_gpu_import.hip    import of the reference's roaring payloads
 //   silo_gpu_columns.hip, silo_gpu_comm.hip, silo_gpu_sort.hip   metadata columns, RCCL, rocPRIM sorts
@@ -10,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+#include <string.h>
 
 #include <atomic>
 #include <memory>
@@ -28,7 +31,7 @@ extern std::atomic<int> g_tune_scan_variant;
 extern std::atomic<int> g_tune_eval_leaf_batch;
 extern std::atomic<int> g_tune_compact_index;   // < 0: finalize keeps the build-time identity planes; 2 / 3: see SILO_GPU_TUNE_COMPACT_INDEX
 extern std::atomic<int> g_tune_gap_events;      // < 0: scans of derived symbols take the runs and the sparse keys by themselves (planDerived)
-extern std::atomic<int> g_tune_prune_keys;      // silo_gpu_mutations_scan_ranges_min_proportion: < 0 skips nothing, 0 granules of escape keys (scanEscapes) and one-hot rows (k_scan_sliced), 1 keys only
+extern std::atomic<int> g_tune_prune_keys;      // silo_gpu_mutations_scan_ranges_min_proportion: < 0 skips nothing, 0 granules of escape keys and one-hot rows, 1 keys only (ScanPruning, scan_internal.h)
 extern std::atomic<int> g_tune_side_stream;     // the side passes of a scan: see forkSidePasses (silo_gpu_scan.hip)
 extern std::atomic<int> g_tune_scan_timing;     // 1: HIP events around every launch of a scan (silo_gpu_scan_timings)
 extern std::atomic<int> g_tune_missing_runs;    // < 0: finalize keeps the plane of the missing symbol instead of turning it into runs
@@ -489,7 +492,7 @@ struct ScanRange {
    uint32_t* counts[SILO_GPU_MAX_SCAN_BATCH];
 };
 
-/// The Mutations scan of `q_count` filters over position ranges of sequence stores of one alphabet (silo_gpu_scan.hip); finalize
+/// The Mutations scan of `q_count` filters over position ranges of sequence stores of one alphabet (silo_gpu_scan.hip, its passes: scan_internal.h); finalize
 /// uses it for the unfiltered totals that decide the layout.
 /// min_proportion: nullptr, or one proportion per filter (silo_gpu_mutations_scan_ranges_min_proportion).
 int scanRanges(
