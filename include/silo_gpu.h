@@ -513,6 +513,33 @@ int silo_gpu_filters_grouped(
    const uint64_t* const* filters_dev, uint32_t n_filters, void* scratch_dev, uint32_t* out_dev, void* stream
 );
 
+/* ---- K9: pair counts of two filter lists (CrossTabulation) ------------------------------------------
+ * out_dev is a table [out_rows][out_cols] of uint32, ACCUMULATED into, like K1, K7 and K8.  For every i < n_rows and j < n_cols,
+ * with ri(i) = row_index[i] and cj(j) = col_index[j]:
+ *     out_dev[ri(i) * out_cols + cj(j)] += |{row < sequence_count : base(row) and rowfilter_i(row) and colfilter_j(row)}|
+ * row_filters_dev, col_filters_dev: HOST arrays of device pointers, row_words words each; a NULL entry = all rows.
+ * base_filter_dev: NULL = all rows.  row_index, col_index: HOST arrays that say where filter i / j lands in the table (NULL =
+ * identity); entries must be < out_rows / < out_cols and distinct within their array.  A caller leaves out a filter that selects
+ * no row (its cells stay untouched) or fills a large table in sub-blocks with them.  The same pointer may stand on both sides:
+ * cell (i, i) is then that filter's cardinality under the base.  Bits of the base, a row filter or a column filter at or past
+ * sequence_count never count: NULL x NULL under a NULL base is exactly sequence_count.
+ * scratch_dev: device memory of SILO_GPU_FILTERS_CROSS_SCRATCH_BYTES(n_rows, n_cols) bytes, 16-byte aligned.  Uploads its
+ * pointer and index tables there and waits for them (one stream synchronisation), then makes one launch on `stream` without
+ * waiting: a block counts SILO_GPU_CROSS_TILE x SILO_GPU_CROSS_TILE pairs over SILO_GPU_CROSS_CHUNK_WORDS row words, so every
+ * bitset is read once per SILO_GPU_CROSS_TILE filters of the other side.
+ * n_rows == 0 or n_cols == 0: success, nothing launched.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT for more than
+ * SILO_GPU_MAX_CROSS_FILTERS filters on a side, a NULL table, scratch or filter array, an index out of bounds or given twice, or
+ * a store without rows. */
+#define SILO_GPU_MAX_CROSS_FILTERS 1024 /* per side */
+#define SILO_GPU_CROSS_TILE 8
+#define SILO_GPU_CROSS_CHUNK_WORDS 1024
+#define SILO_GPU_FILTERS_CROSS_SCRATCH_BYTES(n_rows, n_cols) (((size_t)(n_rows) + (size_t)(n_cols)) * 16u + 1024u)
+int silo_gpu_filters_cross(
+   const silo_gpu_store* store, const uint64_t* base_filter_dev, const uint64_t* const* row_filters_dev, const uint32_t* row_index, uint32_t n_rows,
+   const uint64_t* const* col_filters_dev, const uint32_t* col_index, uint32_t n_cols, void* scratch_dev, uint32_t* out_dev, uint32_t out_rows,
+   uint32_t out_cols, void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

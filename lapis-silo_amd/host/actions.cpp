@@ -974,6 +974,153 @@ QueryResult QueriesOverTime::execute(const Database& database, std::vector<Opera
    return QueryResult{std::move(result_rows)};
 }
 
+// ---- CrossTabulation -----------------------------------------------------------------------------------
+namespace {
+const std::string CROSS_TABULATION_FIELDS[] = {"rowLabel", "columnLabel", "count", "rowCount", "columnCount", "total"};
+}
+
+void CrossTabulation::validateOrderByFields(const Database& /*database*/) const {
+   for (const OrderByField& field : order_by_fields) {
+      const bool known =
+         std::find(std::begin(CROSS_TABULATION_FIELDS), std::end(CROSS_TABULATION_FIELDS), field.name) != std::end(CROSS_TABULATION_FIELDS);
+      CHECK_SILO_QUERY(known, "OrderByField " + field.name + " is not contained in the result of this operation.")
+   }
+}
+
+QueryResult CrossTabulation::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   CHECK_SILO_QUERY(
+      database.shard_world <= 1, "CrossTabulation is not supported on a sharded database yet: its counts are not all-reduced across ranks"
+   )
+   // one table [distinct row sub-expression + 1][distinct column sub-expression + 1], accumulated over the partitions: the last
+   // row and the last column belong to an all-rows entry, so the marginals and the total come out of the same pass
+   const auto n_row_filters = static_cast<uint32_t>(row_filters.size());
+   const auto n_column_filters = static_cast<uint32_t>(column_filters.size());
+   const uint32_t table_rows = n_row_filters + 1u;
+   const uint32_t table_columns = n_column_filters + 1u;
+   std::vector<uint32_t> table;
+   const size_t table_words = static_cast<size_t>(table_rows) * table_columns;
+   if (!row_queries.empty() && !column_queries.empty() && !database.partitions.empty()) {
+      DeviceBuffer device_table = database.partitions.front().pool.acquire(table_words * sizeof(uint32_t));
+      checkGpu(silo_gpu_memset_async(device_table.get(), 0, table_words * sizeof(uint32_t), queryStream()), "silo_gpu_memset_async");
+      // what the launch of one batch reads: the bitsets of its sub-expressions on either side and its scratch
+      constexpr uint32_t SIDE_BATCH = MAX_LIVE_FILTERS / 2;
+      std::vector<OperatorResult> live_rows;
+      std::vector<OperatorResult> live_columns;
+      DeviceBuffer live_scratch;
+      bool in_flight = false;
+      // a launch may still read the bitsets and the scratch of its batch: wait before any of them returns to the pool
+      const auto waitForLaunches = [&]() {
+         if (in_flight) {
+            checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+            in_flight = false;
+         }
+      };
+      HostFetch fetch;
+      try {
+         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+            const DatabasePartition& partition = database.partitions[partition_id];
+            const OperatorResult& filter = bitmap_filter[partition_id];
+            const uint32_t selected = partition.sequence_count == 0 ? 0 : filter.cardinality();
+            if (selected == 0) {
+               continue;
+            }
+            // a filter that selects every row is passed as NULL (no all-ones bitset is made for it)
+            const uint64_t* base_bits = selected == partition.sequence_count ? nullptr : filter.bitset();
+            // entries [begin, end) of one side (the entry past the side's last sub-expression is all rows): the bitsets and where
+            // each lands in the table; a sub-expression that selects no row here is left out, one that selects every row is NULL
+            const auto evaluateSide = [&](const std::vector<uint32_t>& side, uint32_t begin, uint32_t end, std::vector<const uint64_t*>& bitsets,
+                                          std::vector<uint32_t>& index, std::vector<OperatorResult>& live) {
+               bitsets.clear();
+               index.clear();
+               for (uint32_t entry = begin; entry < end; ++entry) {
+                  if (entry == side.size()) {
+                     bitsets.push_back(nullptr);
+                     index.push_back(entry);
+                     continue;
+                  }
+                  // compiled and evaluated as the top-level filter is (compileFilter, query_engine.cpp)
+                  std::unique_ptr<operators::Operator> root =
+                     filters[side[entry]]->compile(database, partition, filter_expressions::Expression::AmbiguityMode::NONE);
+                  const operators::Type type = root->type();
+                  uint32_t cardinality = type == operators::FULL ? partition.sequence_count : 0;
+                  OperatorResult result;
+                  if (type != operators::EMPTY && type != operators::FULL) {
+                     result = operators::Operator::evaluate(std::move(root));
+                     result.materialize();  // one launch yields both the bitset and its cardinality
+                     cardinality = result.cardinality();
+                  }
+                  if (cardinality == 0) {  // its cells stay 0
+                     continue;
+                  }
+                  index.push_back(entry);
+                  if (cardinality == partition.sequence_count) {
+                     bitsets.push_back(nullptr);  // all rows: no bitset is read
+                  } else {
+                     bitsets.push_back(result.bitset());
+                     live.push_back(std::move(result));
+                  }
+               }
+            };
+            std::vector<const uint64_t*> row_bitsets, column_bitsets;
+            std::vector<uint32_t> row_index, column_index;
+            for (uint32_t row_begin = 0; row_begin < table_rows; row_begin += SIDE_BATCH) {
+               waitForLaunches();
+               live_rows.clear();
+               evaluateSide(row_filters, row_begin, std::min(table_rows, row_begin + SIDE_BATCH), row_bitsets, row_index, live_rows);
+               if (row_bitsets.empty()) {
+                  continue;
+               }
+               // the column side is streamed past every row batch: a column sub-expression is evaluated once per row batch
+               for (uint32_t column_begin = 0; column_begin < table_columns; column_begin += SIDE_BATCH) {
+                  waitForLaunches();
+                  live_columns.clear();
+                  evaluateSide(column_filters, column_begin, std::min(table_columns, column_begin + SIDE_BATCH), column_bitsets, column_index, live_columns);
+                  if (column_bitsets.empty()) {
+                     continue;
+                  }
+                  const auto n_rows = static_cast<uint32_t>(row_bitsets.size());
+                  const auto n_columns = static_cast<uint32_t>(column_bitsets.size());
+                  live_scratch = partition.pool.acquire(SILO_GPU_FILTERS_CROSS_SCRATCH_BYTES(n_rows, n_columns));
+                  checkGpu(
+                     silo_gpu_filters_cross(
+                        partition.store, base_bits, row_bitsets.data(), row_index.data(), n_rows, column_bitsets.data(), column_index.data(), n_columns,
+                        live_scratch.get(), device_table.as<uint32_t>(), table_rows, table_columns, queryStream()
+                     ),
+                     "silo_gpu_filters_cross"
+                  );
+                  in_flight = true;
+               }
+            }
+         }
+         fetch = HostFetch(device_table.get(), table_words * sizeof(uint32_t), queryStream());
+         const auto* host = static_cast<const uint32_t*>(fetch.wait());
+         table.assign(host, host + table_words);
+      } catch (...) {
+         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+         (void)silo_gpu_stream_synchronize(queryStream());
+         throw;
+      }
+   }
+
+   const auto cell = [&](uint32_t row, uint32_t column) {
+      return table.empty() ? int32_t{0} : static_cast<int32_t>(table[static_cast<size_t>(row) * table_columns + column]);
+   };
+   std::vector<QueryResultEntry> result_rows;
+   result_rows.reserve(row_queries.size() * column_queries.size());
+   for (const LabelledQuery& row : row_queries) {
+      for (const LabelledQuery& column : column_queries) {
+         QueryResultEntry& entry = result_rows.emplace_back();
+         entry.fields.emplace("rowLabel", row.display_label);
+         entry.fields.emplace("columnLabel", column.display_label);
+         entry.fields.emplace("count", cell(row.slot, column.slot));
+         entry.fields.emplace("rowCount", cell(row.slot, n_column_filters));
+         entry.fields.emplace("columnCount", cell(n_row_filters, column.slot));
+         entry.fields.emplace("total", cell(n_row_filters, n_column_filters));
+      }
+   }
+   return QueryResult{std::move(result_rows)};
+}
+
 // ---- JSON -> Action -----------------------------------------------------------------------------------
 namespace {
 
@@ -1202,6 +1349,74 @@ std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json) {
    return std::make_unique<QueriesOverTime>(std::move(queries), std::move(filters), std::move(date_field), std::move(ranges));
 }
 
+std::unique_ptr<Action> parseCrossTabulation(const json::Value& json) {
+   const std::string action_name = "CrossTabulation";
+   const std::string entry_form = "{\"displayLabel\": string, \"query\": filter expression}";
+   CHECK_SILO_QUERY(
+      json.contains("rowQueries") && json["rowQueries"].is_array(), action_name + " action must contain the field rowQueries: an array of objects " + entry_form
+   )
+   CHECK_SILO_QUERY(
+      !json.contains("columnQueries") || json["columnQueries"].is_array(),
+      action_name + " action: the field columnQueries, if present, must be an array of objects " + entry_form
+   )
+   filter_expressions::ExpressionVector filters;
+   std::map<std::string, uint32_t> filter_of_text;  // sub-expressions with the same JSON text, in either list, are parsed once
+   const auto parseList = [&](const char* list, std::vector<CrossTabulation::LabelledQuery>& queries, std::vector<uint32_t>& side) {
+      std::map<std::string, bool> labels;
+      std::map<uint32_t, uint32_t> slot_of_filter;
+      for (const auto& element : json[list].items()) {
+         CHECK_SILO_QUERY(element.is_object(), action_name + " action: every entry of " + list + " must be an object " + entry_form)
+         CHECK_SILO_QUERY(
+            queries.size() < CrossTabulation::MAX_QUERIES,
+            action_name + " action takes at most " + std::to_string(CrossTabulation::MAX_QUERIES) + " entries in " + list
+         )
+         CHECK_SILO_QUERY(
+            element.contains("displayLabel") && element["displayLabel"].is_string(),
+            action_name + " action: every entry of " + list + " must contain the field displayLabel of type string"
+         )
+         const std::string label = element["displayLabel"].as_string();
+         CHECK_SILO_QUERY(labels.emplace(label, true).second, action_name + " action: the displayLabel '" + label + "' occurs more than once in " + list)
+         CHECK_SILO_QUERY(
+            element.contains("query") && element["query"].is_object(),
+            action_name + " action: the entry '" + label + "' of " + list + " must contain the field query of type object (a filter expression)"
+         )
+         const auto [found, is_new] = filter_of_text.emplace(element["query"].dump(), static_cast<uint32_t>(filters.size()));
+         if (is_new) {
+            try {
+               filters.push_back(filter_expressions::parseExpression(element["query"]));
+            } catch (const QueryParseException& ex) {
+               throw QueryParseException(
+                  action_name + " action: the field query of the entry '" + label + "' of " + list + " is not a valid filter expression: " + ex.what()
+               );
+            }
+         }
+         const auto [slot, first_use] = slot_of_filter.emplace(found->second, static_cast<uint32_t>(side.size()));
+         if (first_use) {
+            side.push_back(found->second);
+         }
+         queries.push_back({label, slot->second});
+      }
+   };
+   std::vector<CrossTabulation::LabelledQuery> row_queries, column_queries;
+   std::vector<uint32_t> row_filters, column_filters;
+   parseList("rowQueries", row_queries, row_filters);
+   if (json.contains("columnQueries")) {
+      parseList("columnQueries", column_queries, column_filters);
+   } else {  // the co-occurrence matrix of the row queries
+      column_queries = row_queries;
+      column_filters = row_filters;
+   }
+   CHECK_SILO_QUERY(
+      row_queries.size() * column_queries.size() <= CrossTabulation::MAX_CELLS,
+      action_name + " action: " + std::to_string(row_queries.size()) + " rowQueries x " + std::to_string(column_queries.size()) +
+         (json.contains("columnQueries") ? " columnQueries" : " columnQueries (the rowQueries again)") + " are more than the " +
+         std::to_string(CrossTabulation::MAX_CELLS) + " cells a response may hold"
+   )
+   return std::make_unique<CrossTabulation>(
+      std::move(row_queries), std::move(column_queries), std::move(row_filters), std::move(column_filters), std::move(filters)
+   );
+}
+
 }  // namespace
 
 namespace {
@@ -1230,6 +1445,7 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"MutationsOverTime", parseMutationsOverTime<Nucleotide>},
    {"AminoAcidMutationsOverTime", parseMutationsOverTime<AminoAcid>},
    {"QueriesOverTime", parseQueriesOverTime},
+   {"CrossTabulation", parseCrossTabulation},
 };
 
 }  // namespace

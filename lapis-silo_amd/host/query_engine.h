@@ -820,6 +820,45 @@ class QueriesOverTime : public Action {
    [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
 };
 
+/// CrossTabulation: for two lists of labelled queries, per (row query, column query) the rows of the filter that match both —
+/// what Aggregated counts under And(filter, row, column) — with the marginals And(filter, row), And(filter, column) and the rows
+/// of the filter itself.  Dense: every pair is a row, row queries outermost, in request order.  No columnQueries: the row
+/// queries stand on both sides (the co-occurrence matrix).  Sub-expressions with the same JSON text are parsed once and take one
+/// row / column of the device table; per partition one pair count (K9) per batch of at most MAX_LIVE_FILTERS / 2 bitsets a side,
+/// one table fetched per query.
+class CrossTabulation : public Action {
+  public:
+   struct LabelledQuery {
+      std::string display_label;
+      uint32_t slot;  // index into its side's distinct sub-expressions: the row / column of the device table
+   };
+   static constexpr uint32_t MAX_QUERIES = SILO_GPU_MAX_CROSS_FILTERS;  // per list
+   static constexpr uint32_t MAX_CELLS = 65536;                         // the response has one JSON row per cell
+   /// Bitsets of sub-expressions alive at a time, half of them per side: bounds the pool memory of a partition as QueriesOverTime does.
+   static constexpr uint32_t MAX_LIVE_FILTERS = QueriesOverTime::MAX_LIVE_FILTERS;
+   static_assert(MAX_LIVE_FILTERS / 2 >= 2 && MAX_LIVE_FILTERS / 2 <= SILO_GPU_MAX_CROSS_FILTERS);
+
+   CrossTabulation(
+      std::vector<LabelledQuery> row_queries, std::vector<LabelledQuery> column_queries, std::vector<uint32_t> row_filters,
+      std::vector<uint32_t> column_filters, filter_expressions::ExpressionVector filters
+   )
+       : row_queries(std::move(row_queries)),
+         column_queries(std::move(column_queries)),
+         row_filters(std::move(row_filters)),
+         column_filters(std::move(column_filters)),
+         filters(std::move(filters)) {}
+
+  private:
+   std::vector<LabelledQuery> row_queries;
+   std::vector<LabelledQuery> column_queries;
+   std::vector<uint32_t> row_filters;     // the distinct sub-expressions of each side (indices into filters), in order of first use
+   std::vector<uint32_t> column_filters;
+   filter_expressions::ExpressionVector filters;  // the distinct sub-expressions of both lists
+
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+};
+
 }  // namespace actions
 
 class Query {

@@ -109,7 +109,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_comm_unique_id", "silo_gpu_comm_create", "silo_gpu_comm_destroy", "silo_gpu_comm_rank", "silo_gpu_comm_world",
     "silo_gpu_allreduce_counts", "silo_gpu_broadcast_bytes",
     "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules", "silo_gpu_store_scan_prunable_rows",
-    "silo_gpu_filters_grouped",
+    "silo_gpu_filters_grouped", "silo_gpu_filters_cross",
 ]
 
 _lib = None
@@ -173,6 +173,8 @@ def load_library():
     lib.silo_gpu_store_scan_prunable_rows.argtypes = lib.silo_gpu_store_scan_prunable_granules.argtypes
     lib.silo_gpu_mutations_grouped.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_filters_grouped.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_filters_cross.argtypes = [vp, vp, ctypes.POINTER(vp), vp, ctypes.c_uint32, ctypes.POINTER(vp), vp, ctypes.c_uint32, vp, vp,
+                                           ctypes.c_uint32, ctypes.c_uint32, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -421,6 +423,9 @@ def filter_eval_batch(store_handle, programs, out_bitsets=None, stream=None):
 MAX_DATE_RANGES = 1024         # SILO_GPU_MAX_DATE_RANGES
 MAX_GROUPED_MUTATIONS = 4096   # SILO_GPU_MAX_GROUPED_MUTATIONS
 MAX_GROUPED_FILTERS = 2048     # SILO_GPU_MAX_GROUPED_FILTERS
+MAX_CROSS_FILTERS = 1024      # SILO_GPU_MAX_CROSS_FILTERS, per side
+CROSS_TILE = 8                 # SILO_GPU_CROSS_TILE: filters per side that a block of K9 counts
+CROSS_CHUNK_WORDS = 1024       # SILO_GPU_CROSS_CHUNK_WORDS: row words that a block of K9 covers
 _OWN_SCRATCH = object()
 
 
@@ -432,6 +437,11 @@ def grouped_scratch_bytes(row_words, n_ranges, n_mutations):
 def filters_grouped_scratch_bytes(row_words, n_ranges, n_filters):
     """SILO_GPU_FILTERS_GROUPED_SCRATCH_BYTES: the scratch silo_gpu_filters_grouped needs."""
     return row_words * 128 + n_filters * 8 + n_ranges * 16 + 1024
+
+
+def filters_cross_scratch_bytes(n_rows, n_cols):
+    """SILO_GPU_FILTERS_CROSS_SCRATCH_BYTES: the scratch silo_gpu_filters_cross needs."""
+    return (n_rows + n_cols) * 16 + 1024
 
 
 class GpuStore:
@@ -812,6 +822,45 @@ class GpuStore:
                 groups = self.read(scratch, np.uint16, self.row_words * 64, stream)
                 return groups if out_ptr is not None else (result, groups)
             return result
+        finally:
+            if own_scratch:
+                self.free(scratch)
+            if out_ptr is None and table is not None:
+                self.free(table)
+
+    def filters_cross(self, base_ptr, row_ptrs, col_ptrs, row_index=None, col_index=None, out_shape=None, out_ptr=None, stream=None,
+                      scratch_ptr=_OWN_SCRATCH):
+        """silo_gpu_filters_cross (K9).  row_ptrs / col_ptrs: device row bitsets (None = all rows), None for a whole list = a null
+        array; base_ptr: the bitset every pair is intersected with (None = all rows); row_index / col_index: where filter i / j
+        lands in the table (None = identity); out_shape: (out_rows, out_cols), by default (len(row_ptrs), len(col_ptrs)).  Without
+        out_ptr: a zeroed table for the call, returned as uint32 [out_rows][out_cols].  With out_ptr: accumulates into the caller's
+        device table and returns nothing.  scratch_ptr: the caller's scratch instead of one allocated for the call."""
+        def pointer_array(pointers):
+            if pointers is None:
+                return None, 0
+            return (ctypes.c_void_p * max(1, len(pointers)))(*[(f.value if isinstance(f, ctypes.c_void_p) else f) for f in pointers]), len(pointers)
+
+        rows, n_rows = pointer_array(row_ptrs)
+        cols, n_cols = pointer_array(col_ptrs)
+        row_index = None if row_index is None else np.ascontiguousarray(row_index, dtype=np.uint32)
+        col_index = None if col_index is None else np.ascontiguousarray(col_index, dtype=np.uint32)
+        if (row_index is not None and len(row_index) != n_rows) or (col_index is not None and len(col_index) != n_cols):
+            raise ValueError("one index per filter")
+        out_rows, out_cols = (n_rows, n_cols) if out_shape is None else out_shape
+        cells = out_rows * out_cols
+        own_scratch = scratch_ptr is _OWN_SCRATCH
+        scratch = self.malloc(filters_cross_scratch_bytes(n_rows, n_cols)) if own_scratch else scratch_ptr
+        table = out_ptr
+        try:
+            if out_ptr is None:
+                table = self.malloc(max(8, 4 * cells))
+                self.memset(table, 0, max(8, 4 * cells), stream)
+            _check(self.lib.silo_gpu_filters_cross(self.handle, base_ptr, rows, None if row_index is None else _ptr(row_index), n_rows,
+                                                   cols, None if col_index is None else _ptr(col_index), n_cols, scratch, table, out_rows, out_cols, stream))
+            self.synchronize(stream)
+            if out_ptr is not None:
+                return None
+            return (self.read(table, np.uint32, cells, stream) if cells else np.zeros(0, dtype=np.uint32)).reshape(out_rows, out_cols)
         finally:
             if own_scratch:
                 self.free(scratch)
