@@ -390,12 +390,7 @@ QueryResult Fasta::execute(const Database& database, std::vector<OperatorResult>
 // ---- Insertions / AminoAcidInsertions (insertions.cpp) ---------------------------------------------------
 template <typename SymbolType>
 void InsertionAggregation<SymbolType>::validateOrderByFields(const Database& /*database*/) const {  // :41-59
-   for (const OrderByField& field : order_by_fields) {
-      CHECK_SILO_QUERY(
-         field.name == "position" || field.name == "insertions" || field.name == "sequenceName" || field.name == "count",
-         "OrderByField " + field.name + " is not contained in the result of this operation."
-      )
-   }
+   checkOrderByFields({"position", "insertions", "sequenceName", "count"});
 }
 
 template <typename SymbolType>

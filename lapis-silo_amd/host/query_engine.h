@@ -15,11 +15,13 @@
 
 #include <cstdint>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 #include <variant>
 #include <vector>
 
@@ -582,6 +584,8 @@ class Action {
    void applySort(QueryResult& result) const;
    void applyOffsetAndLimit(QueryResult& result) const;
    virtual void validateOrderByFields(const Database& database) const = 0;
+   /// For validateOrderByFields of an action whose rows have a fixed set of fields: every field ordered by is one of `fields`.
+   void checkOrderByFields(std::initializer_list<std::string_view> fields) const;
    [[nodiscard]] virtual QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const = 0;
 
   public:
@@ -614,6 +618,11 @@ class Action {
 
 /// action.cpp:144-187
 std::unique_ptr<Action> parseAction(const json::Value& json);
+/// The parsers of the count-table actions (table_actions.cpp), which parseAction's table of action types names.
+template <typename SymbolType>
+std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json);
+std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json);
+std::unique_ptr<Action> parseCrossTabulation(const json::Value& json);
 
 class Aggregated : public Action {
    std::vector<std::string> group_by_fields;
@@ -751,17 +760,27 @@ class Mutations : public Action {
        : sequence_names(std::move(sequence_names)), min_proportion(min_proportion) {}
 };
 
+// ---- the count-table actions (table_actions.cpp) --------------------------------------------------------------------------
+// MutationsOverTime, QueriesOverTime and CrossTabulation each fill one small uint32 table on the device, one kernel call (K7 / K8 /
+// K9) per partition and batch, and fetch it once.  What they share is written once in table_actions.cpp: requireUnsharded, the
+// date column (requireDateColumn, deviceDates, dateBounds, dateText), the table's life (countTable), evaluateSubFilter, and the
+// LiveSet that keeps bitsets and scratch out of the pool while a launch may read them.
+
 /// A date range of the over-time actions: both ends inclusive, none = unbounded on that side.
 struct OverTimeDateRange {
    std::optional<common::Date> from;
    std::optional<common::Date> to;
 };
 
+/// Bitsets of sub-expressions QueriesOverTime and CrossTabulation (half of them per side) keep alive at a time: bounds the pool
+/// memory of a partition at 64 x row_words x 8 bytes.
+constexpr uint32_t MAX_LIVE_FILTERS = 64;
+
 /// MutationsOverTime / AminoAcidMutationsOverTime: for listed mutations and date ranges, per (mutation, range) the rows of the
 /// filter within the range that carry the symbol (count) and that have any valid mutation symbol at the position (coverage) —
 /// the cell and the total of a Mutations table under And(filter, date in range).  Dense: every (mutation, range) is a row.
 /// Both ends of a range are inclusive on every date column; NULL dates fall in no range.  One grouped count (K7) per
-/// (partition, sequence store), one table fetched per query.
+/// (partition, sequence store), one table fetched per query (countTable).
 template <typename SymbolType>
 class MutationsOverTime : public Action {
   public:
@@ -791,7 +810,8 @@ class MutationsOverTime : public Action {
 /// the query's countQuery (count) and its coverageQuery (coverage) — what Aggregated counts under And(filter, query, date in
 /// range), with both ends of a range inclusive on every date column and NULL dates in no range.  Dense: every (query, range) is a
 /// row, queries outermost, in request order.  Sub-expressions with the same JSON text are evaluated and counted once per partition;
-/// per partition one grouped filter count (K8) per MAX_LIVE_FILTERS bitsets, one table fetched per query.
+/// per partition one grouped filter count (K8) per MAX_LIVE_FILTERS bitsets (evaluateSubFilter, LiveSet), one table fetched per
+/// query (countTable).
 class QueriesOverTime : public Action {
   public:
    struct LabelledQuery {
@@ -801,8 +821,6 @@ class QueriesOverTime : public Action {
    };
    static constexpr uint32_t MAX_RANGES = SILO_GPU_MAX_DATE_RANGES;
    static constexpr uint32_t MAX_QUERIES = 1024;
-   /// Bitsets of sub-expressions alive at a time: bounds the pool memory of a partition at 64 x row_words x 8 bytes.
-   static constexpr uint32_t MAX_LIVE_FILTERS = 64;
    static_assert(2 * MAX_QUERIES <= SILO_GPU_MAX_GROUPED_FILTERS && MAX_LIVE_FILTERS <= SILO_GPU_MAX_GROUPED_FILTERS);
 
    QueriesOverTime(
@@ -825,7 +843,7 @@ class QueriesOverTime : public Action {
 /// of the filter itself.  Dense: every pair is a row, row queries outermost, in request order.  No columnQueries: the row
 /// queries stand on both sides (the co-occurrence matrix).  Sub-expressions with the same JSON text are parsed once and take one
 /// row / column of the device table; per partition one pair count (K9) per batch of at most MAX_LIVE_FILTERS / 2 bitsets a side,
-/// one table fetched per query.
+/// one table fetched per query (the same helpers of table_actions.cpp as QueriesOverTime).
 class CrossTabulation : public Action {
   public:
    struct LabelledQuery {
@@ -834,8 +852,6 @@ class CrossTabulation : public Action {
    };
    static constexpr uint32_t MAX_QUERIES = SILO_GPU_MAX_CROSS_FILTERS;  // per list
    static constexpr uint32_t MAX_CELLS = 65536;                         // the response has one JSON row per cell
-   /// Bitsets of sub-expressions alive at a time, half of them per side: bounds the pool memory of a partition as QueriesOverTime does.
-   static constexpr uint32_t MAX_LIVE_FILTERS = QueriesOverTime::MAX_LIVE_FILTERS;
    static_assert(MAX_LIVE_FILTERS / 2 >= 2 && MAX_LIVE_FILTERS / 2 <= SILO_GPU_MAX_CROSS_FILTERS);
 
    CrossTabulation(

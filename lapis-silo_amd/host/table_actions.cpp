@@ -1,0 +1,653 @@
+// table_actions.cpp — the actions that answer from one small table of counts filled on the device: MutationsOverTime<SymbolType>
+// (K7), QueriesOverTime (K8) and CrossTabulation (K9), with their parsers.  Each differs in the kernel call of a partition and in
+// the rows it makes of the table; what stands around that — the refusals, the date column, the table's life on the device, the
+// evaluation of labelled sub-expressions and what has to stay alive while launches run — is here once.
+#include <algorithm>
+#include <functional>
+#include <set>
+#include <string_view>
+
+#include "query_engine.h"
+
+namespace silo::query_engine::actions {
+
+namespace {
+
+// ---- what the three actions share ----------------------------------------------------------------------
+void requireUnsharded(const Database& database, const std::string& action_name) {
+   CHECK_SILO_QUERY(
+      database.shard_world <= 1, action_name + " is not supported on a sharded database yet: its counts are not all-reduced across ranks"
+   )
+}
+
+std::string notADateColumn(const std::string& date_field, const std::string& action_name) {
+   return "The field dateField of " + action_name + " ('" + date_field + "') is not a date column";
+}
+
+/// The configuration knows `date_field` as a date column.
+void requireDateColumn(const Database& database, const std::string& date_field, const std::string& action_name) {
+   const std::optional<storage::ColumnMetadata> column = database.database_config.getMetadata(date_field);
+   CHECK_SILO_QUERY(column.has_value() && column->type == config::ColumnType::DATE, notADateColumn(date_field, action_name))
+}
+
+/// The dates of a partition's rows on the device, one uint32 per row.
+const uint32_t* deviceDates(const DatabasePartition& partition, const std::string& date_field, const std::string& action_name) {
+   const auto* dates = partition.columns.find(date_field, config::ColumnType::DATE);
+   CHECK_SILO_QUERY(dates != nullptr, notADateColumn(date_field, action_name))
+   return static_cast<const uint32_t*>(dates->deviceValues());
+}
+
+/// (from, to) per range as K7 / K8 take them: both inclusive, an open end as the least / greatest date (0 is the NULL date).
+std::vector<uint32_t> dateBounds(const std::vector<OverTimeDateRange>& date_ranges) {
+   std::vector<uint32_t> bounds;
+   bounds.reserve(2 * date_ranges.size());
+   for (const OverTimeDateRange& range : date_ranges) {
+      bounds.push_back(range.from.value_or(common::Date{1}));
+      bounds.push_back(range.to.value_or(common::Date{UINT32_MAX}));
+   }
+   return bounds;
+}
+
+/// An end of a range in a result row: null when open.
+JsonValue dateText(const std::optional<common::Date>& date) {
+   if (!date.has_value()) {
+      return std::nullopt;
+   }
+   return common::dateToString(*date).value_or("");
+}
+
+/// What launches on queryStream() read besides the table: the bitsets of sub-expressions (kept per side: CrossTabulation has
+/// two) and scratch.  Nothing in it returns to the pool while a launch that was given it may still run: bitsets leave only
+/// through waitAndRelease, a scratch only once the stream has been waited for after it was handed out.
+class LiveSet {
+   std::vector<OperatorResult> filters[2];
+   std::vector<DeviceBuffer> scratches;
+   bool in_flight = false;  // scratch was handed out since the last wait: launches may be running
+
+  public:
+   /// Scratch for the launches that follow.  Those handed out before stay unless the stream was waited for since.
+   void* scratch(const DatabasePartition& partition, size_t bytes) {
+      DeviceBuffer fresh = partition.pool.acquire(bytes);
+      if (!in_flight) {
+         scratches.clear();
+      }
+      scratches.push_back(std::move(fresh));
+      in_flight = true;
+      return scratches.back().get();
+   }
+   /// Keeps the bitset of a sub-expression for the launches that follow.
+   const uint64_t* keep(OperatorResult result, size_t side = 0) {
+      const uint64_t* bits = result.bitset();
+      filters[side].push_back(std::move(result));
+      return bits;
+   }
+   /// Launches since the last wait may still read the bitsets: wait for them, then those of `side` return to the pool.
+   void waitAndRelease(size_t side = 0) {
+      if (in_flight) {
+         checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+         in_flight = false;
+      }
+      filters[side].clear();
+   }
+};
+
+/// The launches of one partition into the table.  base_bits: the rows of the query's filter, nullptr when it selects every row.
+using PartitionLaunches = std::function<void(const DatabasePartition& partition, const uint64_t* base_bits, uint32_t* device_table, LiveSet& live)>;
+
+/// The life of a table of `words` uint32 counts: zeroed on the device (pool of the first partition), filled by `launches` for
+/// every partition whose filter selects a row, fetched once.  Empty for a database without partitions.  If anything throws,
+/// the stream is waited for before the table and the live set return to the pool.
+std::vector<uint32_t> countTable(
+   const Database& database, const std::vector<OperatorResult>& bitmap_filter, size_t words, const PartitionLaunches& launches
+) {
+   std::vector<uint32_t> table;
+   if (database.partitions.empty()) {
+      return table;
+   }
+   DeviceBuffer device_table = database.partitions.front().pool.acquire(words * sizeof(uint32_t));
+   checkGpu(silo_gpu_memset_async(device_table.get(), 0, words * sizeof(uint32_t), queryStream()), "silo_gpu_memset_async");
+   LiveSet live;  // kept until the table has landed: the launches read it
+   HostFetch fetch;
+   try {
+      for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+         const DatabasePartition& partition = database.partitions[partition_id];
+         const OperatorResult& filter = bitmap_filter[partition_id];
+         const uint32_t selected = partition.sequence_count == 0 ? 0 : filter.cardinality();
+         if (selected == 0) {
+            continue;
+         }
+         // a filter that selects every row is passed as NULL (no all-ones bitset is made for it)
+         launches(partition, selected == partition.sequence_count ? nullptr : filter.bitset(), device_table.as<uint32_t>(), live);
+      }
+      fetch = HostFetch(device_table.get(), words * sizeof(uint32_t), queryStream());
+      const auto* host = static_cast<const uint32_t*>(fetch.wait());
+      table.assign(host, host + words);
+   } catch (...) {
+      // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+      (void)silo_gpu_stream_synchronize(queryStream());
+      throw;
+   }
+   return table;
+}
+
+/// A labelled sub-expression on one partition: the rows it selects and, unless those are none or all, their bitset.
+struct SubFilter {
+   uint32_t cardinality;
+   OperatorResult result;
+};
+
+/// Compiled and evaluated as the top-level filter is (compileFilter, query_engine.cpp).
+SubFilter evaluateSubFilter(const Database& database, const DatabasePartition& partition, const filter_expressions::Expression& expression) {
+   std::unique_ptr<operators::Operator> root = expression.compile(database, partition, filter_expressions::Expression::AmbiguityMode::NONE);
+   const operators::Type type = root->type();
+   SubFilter sub{type == operators::FULL ? partition.sequence_count : 0, {}};
+   if (type != operators::EMPTY && type != operators::FULL) {
+      sub.result = operators::Operator::evaluate(std::move(root));
+      sub.result.materialize();  // one launch yields both the bitset and its cardinality
+      sub.cardinality = sub.result.cardinality();
+   }
+   return sub;
+}
+
+}  // namespace
+
+// ---- MutationsOverTime ---------------------------------------------------------------------------------
+template <typename SymbolType>
+void MutationsOverTime<SymbolType>::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"mutation", "sequenceName", "dateFrom", "dateTo", "count", "coverage"});
+}
+
+template <typename SymbolType>
+QueryResult MutationsOverTime<SymbolType>::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string action_name = std::is_same_v<SymbolType, Nucleotide> ? "MutationsOverTime" : "AminoAcidMutationsOverTime";
+   requireUnsharded(database, action_name);
+   requireDateColumn(database, date_field, action_name);
+
+   // resolve every mutation against its sequence store: the name, the 0-based position, the reference symbol
+   struct Resolved {
+      std::string sequence_name;
+      const SequenceStore<SymbolType>* store;
+      uint32_t position;  // 0-based
+   };
+   std::vector<Resolved> resolved;
+   resolved.reserve(mutations.size());
+   for (const Mutation& mutation : mutations) {
+      const std::string name = mutation.sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+      const auto found = database.getSequenceStores<SymbolType>().find(name);
+      CHECK_SILO_QUERY(
+         found != database.getSequenceStores<SymbolType>().end(),
+         "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + name + "'"
+      )
+      const auto& reference = found->second.reference_sequence;
+      CHECK_SILO_QUERY(
+         mutation.position >= 1 && mutation.position <= reference.size(),
+         "The position " + std::to_string(mutation.position) + " of a mutation of " + action_name + " is outside the sequence '" + name + "' (1 to " +
+            std::to_string(reference.size()) + ")"
+      )
+      const auto reference_symbol = reference[mutation.position - 1];
+      if (mutation.reference_symbol.has_value()) {
+         CHECK_SILO_QUERY(
+            SymbolType::charToSymbol(*mutation.reference_symbol) == reference_symbol,
+            std::string("The reference symbol '") + *mutation.reference_symbol + "' of a mutation of " + action_name + " does not match the reference genome ('" +
+               SymbolType::symbolToChar(reference_symbol) + "' at position " + std::to_string(mutation.position) + " of '" + name + "')"
+         )
+      }
+      resolved.push_back({name, &found->second, mutation.position - 1});
+   }
+
+   // the table: one block of rows per sequence store touched, the store's mutations in request order within it
+   const auto n_ranges = static_cast<uint32_t>(date_ranges.size());
+   std::vector<std::string> store_names;
+   std::vector<std::vector<uint32_t>> members;  // request indices per store
+   for (uint32_t m = 0; m < resolved.size(); ++m) {
+      const auto s = static_cast<size_t>(std::find(store_names.begin(), store_names.end(), resolved[m].sequence_name) - store_names.begin());
+      if (s == store_names.size()) {
+         store_names.push_back(resolved[m].sequence_name);
+         members.emplace_back();
+      }
+      members[s].push_back(m);
+   }
+   std::vector<uint32_t> row_of(resolved.size());  // request index -> row of the table
+   std::vector<uint32_t> first_row(store_names.size());
+   uint32_t rows = 0;
+   for (size_t s = 0; s < store_names.size(); ++s) {
+      first_row[s] = rows;
+      for (const uint32_t m : members[s]) {
+         row_of[m] = rows++;
+      }
+   }
+   const std::vector<uint32_t> bounds = dateBounds(date_ranges);
+
+   std::vector<uint32_t> table;
+   const size_t table_words = static_cast<size_t>(rows) * n_ranges * 2u;
+   if (table_words != 0) {
+      table = countTable(
+         database, bitmap_filter, table_words,
+         [&](const DatabasePartition& partition, const uint64_t* base_bits, uint32_t* device_table, LiveSet& live) {
+            const uint32_t* dates = deviceDates(partition, date_field, action_name);
+            for (size_t s = 0; s < store_names.size(); ++s) {  // one K7 call per store; every scratch stays until the table has landed
+               const SequenceStorePartition<SymbolType>& store = partition.getSequenceStores<SymbolType>().at(store_names[s]);
+               std::vector<uint32_t> positions, symbols;
+               for (const uint32_t m : members[s]) {
+                  positions.push_back(resolved[m].position);
+                  symbols.push_back(static_cast<uint32_t>(mutations[m].symbol));
+               }
+               const auto n = static_cast<uint32_t>(positions.size());
+               void* scratch = live.scratch(partition, SILO_GPU_GROUPED_SCRATCH_BYTES(partition.rowWords(), n_ranges, n));
+               checkGpu(
+                  silo_gpu_mutations_grouped(
+                     store.store, store.seqstore_id, base_bits, dates, bounds.data(), n_ranges, positions.data(), symbols.data(), n, scratch,
+                     device_table + static_cast<size_t>(first_row[s]) * n_ranges * 2u, queryStream()
+                  ),
+                  "silo_gpu_mutations_grouped"
+               );
+            }
+         }
+      );
+   }
+
+   std::vector<QueryResultEntry> result_rows;
+   result_rows.reserve(resolved.size() * n_ranges);
+   for (size_t m = 0; m < resolved.size(); ++m) {
+      const char from = SymbolType::symbolToChar(resolved[m].store->reference_sequence.at(resolved[m].position));
+      const std::string name = from + std::to_string(resolved[m].position + 1) + SymbolType::symbolToChar(mutations[m].symbol);
+      for (uint32_t r = 0; r < n_ranges; ++r) {
+         const size_t cell = (static_cast<size_t>(row_of[m]) * n_ranges + r) * 2u;
+         const uint32_t count = table.empty() ? 0u : table[cell];
+         const uint32_t coverage = table.empty() ? 0u : table[cell + 1u];
+         QueryResultEntry& entry = result_rows.emplace_back();
+         entry.fields.emplace("count", static_cast<int32_t>(count));
+         entry.fields.emplace("coverage", static_cast<int32_t>(coverage));
+         entry.fields.emplace("dateFrom", dateText(date_ranges[r].from));
+         entry.fields.emplace("dateTo", dateText(date_ranges[r].to));
+         entry.fields.emplace("mutation", name);
+         entry.fields.emplace("sequenceName", resolved[m].sequence_name);
+      }
+   }
+   return QueryResult{std::move(result_rows)};
+}
+
+template class MutationsOverTime<Nucleotide>;
+template class MutationsOverTime<AminoAcid>;
+
+// ---- QueriesOverTime -----------------------------------------------------------------------------------
+void QueriesOverTime::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"displayLabel", "dateFrom", "dateTo", "count", "coverage"});
+}
+
+QueryResult QueriesOverTime::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string action_name = "QueriesOverTime";
+   requireUnsharded(database, action_name);
+   requireDateColumn(database, date_field, action_name);
+   const auto n_ranges = static_cast<uint32_t>(date_ranges.size());
+   const auto n_filters = static_cast<uint32_t>(filters.size());
+   const std::vector<uint32_t> bounds = dateBounds(date_ranges);
+
+   // one table [distinct sub-expression][range], accumulated over the partitions
+   std::vector<uint32_t> table;
+   const size_t table_words = static_cast<size_t>(n_filters) * n_ranges;
+   if (table_words != 0) {
+      table = countTable(
+         database, bitmap_filter, table_words,
+         [&](const DatabasePartition& partition, const uint64_t* base_bits, uint32_t* device_table, LiveSet& live) {
+            const uint32_t* dates = deviceDates(partition, date_field, action_name);
+            for (uint32_t batch_begin = 0; batch_begin < n_filters; batch_begin += MAX_LIVE_FILTERS) {
+               const uint32_t batch_end = std::min(n_filters, batch_begin + MAX_LIVE_FILTERS);
+               live.waitAndRelease();  // the launches of the batch before may still read its bitsets
+               void* scratch = live.scratch(partition, SILO_GPU_FILTERS_GROUPED_SCRATCH_BYTES(partition.rowWords(), n_ranges, batch_end - batch_begin));
+               // K8 counts filters that stand side by side in the table: a sub-expression that selects no row here ends a run
+               uint32_t run_begin = batch_begin;
+               std::vector<const uint64_t*> run;
+               const auto launchRun = [&]() {
+                  if (!run.empty()) {
+                     checkGpu(
+                        silo_gpu_filters_grouped(
+                           partition.store, base_bits, dates, bounds.data(), n_ranges, run.data(), static_cast<uint32_t>(run.size()), scratch,
+                           device_table + static_cast<size_t>(run_begin) * n_ranges, queryStream()
+                        ),
+                        "silo_gpu_filters_grouped"
+                     );
+                     run.clear();
+                  }
+               };
+               for (uint32_t f = batch_begin; f < batch_end; ++f) {
+                  SubFilter sub = evaluateSubFilter(database, partition, *filters[f]);
+                  if (sub.cardinality == 0) {  // its cells stay 0
+                     launchRun();
+                     run_begin = f + 1;
+                     continue;
+                  }
+                  // all rows: no bitset is read
+                  run.push_back(sub.cardinality == partition.sequence_count ? nullptr : live.keep(std::move(sub.result)));
+               }
+               launchRun();
+            }
+         }
+      );
+   }
+
+   std::vector<QueryResultEntry> result_rows;
+   result_rows.reserve(queries.size() * n_ranges);
+   for (const LabelledQuery& query : queries) {
+      for (uint32_t r = 0; r < n_ranges; ++r) {
+         const uint32_t count = table.empty() ? 0u : table[static_cast<size_t>(query.count_filter) * n_ranges + r];
+         const uint32_t coverage = table.empty() ? 0u : table[static_cast<size_t>(query.coverage_filter) * n_ranges + r];
+         QueryResultEntry& entry = result_rows.emplace_back();
+         entry.fields.emplace("count", static_cast<int32_t>(count));
+         entry.fields.emplace("coverage", static_cast<int32_t>(coverage));
+         entry.fields.emplace("dateFrom", dateText(date_ranges[r].from));
+         entry.fields.emplace("dateTo", dateText(date_ranges[r].to));
+         entry.fields.emplace("displayLabel", query.display_label);
+      }
+   }
+   return QueryResult{std::move(result_rows)};
+}
+
+// ---- CrossTabulation -----------------------------------------------------------------------------------
+void CrossTabulation::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"rowLabel", "columnLabel", "count", "rowCount", "columnCount", "total"});
+}
+
+QueryResult CrossTabulation::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   requireUnsharded(database, "CrossTabulation");
+   // one table [distinct row sub-expression + 1][distinct column sub-expression + 1], accumulated over the partitions: the last
+   // row and the last column belong to an all-rows entry, so the marginals and the total come out of the same pass
+   const auto n_row_filters = static_cast<uint32_t>(row_filters.size());
+   const auto n_column_filters = static_cast<uint32_t>(column_filters.size());
+   const uint32_t table_rows = n_row_filters + 1u;
+   const uint32_t table_columns = n_column_filters + 1u;
+   std::vector<uint32_t> table;
+   if (!row_queries.empty() && !column_queries.empty()) {
+      constexpr uint32_t SIDE_BATCH = MAX_LIVE_FILTERS / 2;
+      enum Side : size_t { ROWS, COLUMNS };
+      table = countTable(
+         database, bitmap_filter, static_cast<size_t>(table_rows) * table_columns,
+         [&](const DatabasePartition& partition, const uint64_t* base_bits, uint32_t* device_table, LiveSet& live) {
+            // entries [begin, end) of one side (the entry past the side's last sub-expression is all rows): the bitsets and where
+            // each lands in the table; a sub-expression that selects no row here is left out, one that selects every row is NULL
+            const auto evaluateSide = [&](Side which, uint32_t begin, uint32_t end, std::vector<const uint64_t*>& bitsets, std::vector<uint32_t>& index) {
+               const std::vector<uint32_t>& side = which == ROWS ? row_filters : column_filters;
+               bitsets.clear();
+               index.clear();
+               for (uint32_t entry = begin; entry < end; ++entry) {
+                  if (entry == side.size()) {
+                     bitsets.push_back(nullptr);
+                     index.push_back(entry);
+                     continue;
+                  }
+                  SubFilter sub = evaluateSubFilter(database, partition, *filters[side[entry]]);
+                  if (sub.cardinality == 0) {  // its cells stay 0
+                     continue;
+                  }
+                  index.push_back(entry);
+                  // all rows: no bitset is read
+                  bitsets.push_back(sub.cardinality == partition.sequence_count ? nullptr : live.keep(std::move(sub.result), which));
+               }
+            };
+            std::vector<const uint64_t*> row_bitsets, column_bitsets;
+            std::vector<uint32_t> row_index, column_index;
+            for (uint32_t row_begin = 0; row_begin < table_rows; row_begin += SIDE_BATCH) {
+               live.waitAndRelease(ROWS);  // a launch may still read the bitsets of the batch before
+               evaluateSide(ROWS, row_begin, std::min(table_rows, row_begin + SIDE_BATCH), row_bitsets, row_index);
+               if (row_bitsets.empty()) {
+                  continue;
+               }
+               // the column side is streamed past every row batch: a column sub-expression is evaluated once per row batch
+               for (uint32_t column_begin = 0; column_begin < table_columns; column_begin += SIDE_BATCH) {
+                  live.waitAndRelease(COLUMNS);
+                  evaluateSide(COLUMNS, column_begin, std::min(table_columns, column_begin + SIDE_BATCH), column_bitsets, column_index);
+                  if (column_bitsets.empty()) {
+                     continue;
+                  }
+                  const auto n_rows = static_cast<uint32_t>(row_bitsets.size());
+                  const auto n_columns = static_cast<uint32_t>(column_bitsets.size());
+                  void* scratch = live.scratch(partition, SILO_GPU_FILTERS_CROSS_SCRATCH_BYTES(n_rows, n_columns));
+                  checkGpu(
+                     silo_gpu_filters_cross(
+                        partition.store, base_bits, row_bitsets.data(), row_index.data(), n_rows, column_bitsets.data(), column_index.data(), n_columns,
+                        scratch, device_table, table_rows, table_columns, queryStream()
+                     ),
+                     "silo_gpu_filters_cross"
+                  );
+               }
+            }
+         }
+      );
+   }
+
+   const auto cell = [&](uint32_t row, uint32_t column) {
+      return table.empty() ? int32_t{0} : static_cast<int32_t>(table[static_cast<size_t>(row) * table_columns + column]);
+   };
+   std::vector<QueryResultEntry> result_rows;
+   result_rows.reserve(row_queries.size() * column_queries.size());
+   for (const LabelledQuery& row : row_queries) {
+      for (const LabelledQuery& column : column_queries) {
+         QueryResultEntry& entry = result_rows.emplace_back();
+         entry.fields.emplace("rowLabel", row.display_label);
+         entry.fields.emplace("columnLabel", column.display_label);
+         entry.fields.emplace("count", cell(row.slot, column.slot));
+         entry.fields.emplace("rowCount", cell(row.slot, n_column_filters));
+         entry.fields.emplace("columnCount", cell(n_row_filters, column.slot));
+         entry.fields.emplace("total", cell(n_row_filters, n_column_filters));
+      }
+   }
+   return QueryResult{std::move(result_rows)};
+}
+
+// ---- JSON -> the three actions ---------------------------------------------------------------------------
+namespace {
+
+/// One entry of the mutations field of MutationsOverTime: [<sequenceName>:][<reference symbol>]<1-based position><symbol>.
+template <typename SymbolType>
+typename MutationsOverTime<SymbolType>::Mutation parseOverTimeMutation(const std::string& text, const std::string& action_name) {
+   const std::string invalid = "The mutation '" + text + "' of " + action_name + " is not of the form [<sequenceName>:][<reference symbol>]<position><symbol>";
+   typename MutationsOverTime<SymbolType>::Mutation mutation{};
+   std::string rest = text;
+   if (const size_t colon = text.rfind(':'); colon != std::string::npos) {
+      mutation.sequence_name = text.substr(0, colon);
+      rest = text.substr(colon + 1);
+   }
+   CHECK_SILO_QUERY(
+      (std::is_same_v<SymbolType, Nucleotide>) || mutation.sequence_name.has_value(),
+      "The mutation '" + text + "' of " + action_name + " must name its gene: <sequenceName>:[<reference symbol>]<position><symbol>"
+   )
+   size_t first_digit = 0;
+   if (!rest.empty() && (rest[0] < '0' || rest[0] > '9')) {
+      mutation.reference_symbol = rest[0];
+      first_digit = 1;
+   }
+   size_t end = first_digit;
+   while (end < rest.size() && rest[end] >= '0' && rest[end] <= '9') {
+      ++end;
+   }
+   CHECK_SILO_QUERY(end > first_digit && end - first_digit <= 9 && end + 1 == rest.size(), invalid)
+   mutation.position = static_cast<uint32_t>(std::stoul(rest.substr(first_digit, end - first_digit)));
+   const auto symbol = SymbolType::charToSymbol(rest[end]);
+   const bool valid = symbol.has_value() &&
+                      std::find(SymbolType::VALID_MUTATION_SYMBOLS.begin(), SymbolType::VALID_MUTATION_SYMBOLS.end(), *symbol) != SymbolType::VALID_MUTATION_SYMBOLS.end();
+   CHECK_SILO_QUERY(valid, "The symbol '" + std::string(1, rest[end]) + "' of the mutation '" + text + "' of " + action_name + " is not a valid mutation symbol")
+   mutation.symbol = *symbol;
+   return mutation;
+}
+
+/// The dateField and dateRanges fields of the over-time actions: the column's name and the ranges in request order (validated:
+/// at most SILO_GPU_MAX_DATE_RANGES, valid dates, dateFrom <= dateTo, pairwise disjoint with both ends inclusive).
+std::pair<std::string, std::vector<OverTimeDateRange>> parseDateFieldAndRanges(const json::Value& json, const std::string& action_name) {
+   CHECK_SILO_QUERY(
+      json.contains("dateField") && json["dateField"].is_string(), action_name + " action must contain the field dateField of type string"
+   )
+   CHECK_SILO_QUERY(
+      json.contains("dateRanges") && json["dateRanges"].is_array(),
+      action_name + " action must contain the field dateRanges: an array of objects {\"dateFrom\": string or null, \"dateTo\": string or null}"
+   )
+   std::vector<OverTimeDateRange> ranges;
+   for (const auto& element : json["dateRanges"].items()) {
+      CHECK_SILO_QUERY(
+         element.is_object(), action_name + " action: every entry of dateRanges must be an object {\"dateFrom\": string or null, \"dateTo\": string or null}"
+      )
+      CHECK_SILO_QUERY(
+         ranges.size() < SILO_GPU_MAX_DATE_RANGES, action_name + " action takes at most " + std::to_string(SILO_GPU_MAX_DATE_RANGES) + " date ranges"
+      )
+      OverTimeDateRange range;
+      for (const char* field : {"dateFrom", "dateTo"}) {
+         if (!element.contains(field) || element[field].is_null()) {
+            continue;
+         }
+         CHECK_SILO_QUERY(element[field].is_string(), action_name + " action: the field " + field + " of a date range must be a string or null")
+         const common::Date date = common::stringToDate(element[field].as_string());
+         CHECK_SILO_QUERY(date != common::NULL_DATE, action_name + " action: the " + field + " '" + element[field].as_string() + "' is not a valid date (YYYY-MM-DD)")
+         (std::string_view(field) == "dateFrom" ? range.from : range.to) = date;
+      }
+      CHECK_SILO_QUERY(
+         !range.from.has_value() || !range.to.has_value() || *range.from <= *range.to,
+         action_name + " action: a date range has dateFrom after dateTo: " + element.dump()
+      )
+      ranges.push_back(range);
+   }
+   // pairwise disjoint (both ends inclusive): in order of their start, each must begin after the one before ends
+   std::vector<std::pair<common::Date, common::Date>> spans;
+   for (const auto& range : ranges) {
+      spans.emplace_back(range.from.value_or(common::Date{0}), range.to.value_or(common::Date{UINT32_MAX}));
+   }
+   std::sort(spans.begin(), spans.end());
+   for (size_t k = 1; k < spans.size(); ++k) {
+      CHECK_SILO_QUERY(spans[k].first > spans[k - 1].second, action_name + " action: the date ranges overlap; each row may fall in at most one")
+   }
+   return {json["dateField"].as_string(), std::move(ranges)};
+}
+
+/// One entry of a list of labelled queries (`list`: the field that holds the list): an object, below the list's limit
+/// (`limit_message` otherwise), with a string displayLabel that no entry of the list had before.  Returns the label.
+std::string parseLabelledEntry(
+   const json::Value& element, const std::string& action_name, const std::string& list, const std::string& entry_form, bool below_limit,
+   const std::string& limit_message, std::set<std::string>& labels
+) {
+   CHECK_SILO_QUERY(element.is_object(), action_name + " action: every entry of " + list + " must be an object " + entry_form)
+   CHECK_SILO_QUERY(below_limit, limit_message)
+   CHECK_SILO_QUERY(
+      element.contains("displayLabel") && element["displayLabel"].is_string(),
+      action_name + " action: every entry of " + list + " must contain the field displayLabel of type string"
+   )
+   const std::string label = element["displayLabel"].as_string();
+   CHECK_SILO_QUERY(labels.insert(label).second, action_name + " action: the displayLabel '" + label + "' occurs more than once in " + list)
+   return label;
+}
+
+/// The sub-expressions of a request: those with the same JSON text are parsed once and share an index.
+struct DistinctFilters {
+   filter_expressions::ExpressionVector filters;
+   std::map<std::string, uint32_t> index_of_text;
+
+   /// The index of the filter expression in `field` of a labelled entry; `owner` is what messages call the entry.
+   uint32_t parse(const json::Value& element, const char* field, const std::string& action_name, const std::string& owner) {
+      CHECK_SILO_QUERY(
+         element.contains(field) && element[field].is_object(),
+         action_name + " action: " + owner + " must contain the field " + field + " of type object (a filter expression)"
+      )
+      const auto [found, is_new] = index_of_text.emplace(element[field].dump(), static_cast<uint32_t>(filters.size()));
+      if (is_new) {
+         try {
+            filters.push_back(filter_expressions::parseExpression(element[field]));
+         } catch (const QueryParseException& ex) {
+            throw QueryParseException(action_name + " action: the field " + field + " of " + owner + " is not a valid filter expression: " + ex.what());
+         }
+      }
+      return found->second;
+   }
+};
+
+}  // namespace
+
+template <typename SymbolType>
+std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json) {
+   using OverTime = MutationsOverTime<SymbolType>;
+   const std::string action_name = std::is_same_v<SymbolType, Nucleotide> ? "MutationsOverTime" : "AminoAcidMutationsOverTime";
+   CHECK_SILO_QUERY(
+      json.contains("mutations") && json["mutations"].is_array(), action_name + " action must contain the field mutations of type array of strings"
+   )
+   std::vector<typename OverTime::Mutation> mutations;
+   for (const auto& element : json["mutations"].items()) {
+      CHECK_SILO_QUERY(element.is_string(), action_name + " action must contain the field mutations of type array of strings, found " + element.dump())
+      CHECK_SILO_QUERY(
+         mutations.size() < OverTime::MAX_MUTATIONS, action_name + " action takes at most " + std::to_string(OverTime::MAX_MUTATIONS) + " mutations"
+      )
+      mutations.push_back(parseOverTimeMutation<SymbolType>(element.as_string(), action_name));
+   }
+   auto [date_field, ranges] = parseDateFieldAndRanges(json, action_name);
+   return std::make_unique<OverTime>(std::move(mutations), std::move(date_field), std::move(ranges));
+}
+
+template std::unique_ptr<Action> parseMutationsOverTime<Nucleotide>(const json::Value& json);
+template std::unique_ptr<Action> parseMutationsOverTime<AminoAcid>(const json::Value& json);
+
+std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json) {
+   const std::string action_name = "QueriesOverTime";
+   const std::string entry_form = "{\"displayLabel\": string, \"countQuery\": filter expression, \"coverageQuery\": filter expression}";
+   CHECK_SILO_QUERY(
+      json.contains("queries") && json["queries"].is_array(), action_name + " action must contain the field queries: an array of objects " + entry_form
+   )
+   std::vector<QueriesOverTime::LabelledQuery> queries;
+   DistinctFilters distinct;  // sub-expressions with the same JSON text share a row of the table
+   std::set<std::string> labels;
+   for (const auto& element : json["queries"].items()) {
+      const std::string label = parseLabelledEntry(
+         element, action_name, "queries", entry_form, queries.size() < QueriesOverTime::MAX_QUERIES,
+         action_name + " action takes at most " + std::to_string(QueriesOverTime::MAX_QUERIES) + " queries", labels
+      );
+      const std::string owner = "the query '" + label + "'";
+      const uint32_t count_filter = distinct.parse(element, "countQuery", action_name, owner);
+      const uint32_t coverage_filter = distinct.parse(element, "coverageQuery", action_name, owner);
+      queries.push_back({label, count_filter, coverage_filter});
+   }
+   auto [date_field, ranges] = parseDateFieldAndRanges(json, action_name);
+   return std::make_unique<QueriesOverTime>(std::move(queries), std::move(distinct.filters), std::move(date_field), std::move(ranges));
+}
+
+std::unique_ptr<Action> parseCrossTabulation(const json::Value& json) {
+   const std::string action_name = "CrossTabulation";
+   const std::string entry_form = "{\"displayLabel\": string, \"query\": filter expression}";
+   CHECK_SILO_QUERY(
+      json.contains("rowQueries") && json["rowQueries"].is_array(), action_name + " action must contain the field rowQueries: an array of objects " + entry_form
+   )
+   CHECK_SILO_QUERY(
+      !json.contains("columnQueries") || json["columnQueries"].is_array(),
+      action_name + " action: the field columnQueries, if present, must be an array of objects " + entry_form
+   )
+   DistinctFilters distinct;  // sub-expressions with the same JSON text, in either list, are parsed once
+   const auto parseList = [&](const std::string& list, std::vector<CrossTabulation::LabelledQuery>& queries, std::vector<uint32_t>& side) {
+      std::set<std::string> labels;
+      std::map<uint32_t, uint32_t> slot_of_filter;
+      for (const auto& element : json[list].items()) {
+         const std::string label = parseLabelledEntry(
+            element, action_name, list, entry_form, queries.size() < CrossTabulation::MAX_QUERIES,
+            action_name + " action takes at most " + std::to_string(CrossTabulation::MAX_QUERIES) + " entries in " + list, labels
+         );
+         const uint32_t filter = distinct.parse(element, "query", action_name, "the entry '" + label + "' of " + list);
+         const auto [slot, first_use] = slot_of_filter.emplace(filter, static_cast<uint32_t>(side.size()));
+         if (first_use) {
+            side.push_back(filter);
+         }
+         queries.push_back({label, slot->second});
+      }
+   };
+   std::vector<CrossTabulation::LabelledQuery> row_queries, column_queries;
+   std::vector<uint32_t> row_filters, column_filters;
+   parseList("rowQueries", row_queries, row_filters);
+   if (json.contains("columnQueries")) {
+      parseList("columnQueries", column_queries, column_filters);
+   } else {  // the co-occurrence matrix of the row queries
+      column_queries = row_queries;
+      column_filters = row_filters;
+   }
+   CHECK_SILO_QUERY(
+      row_queries.size() * column_queries.size() <= CrossTabulation::MAX_CELLS,
+      action_name + " action: " + std::to_string(row_queries.size()) + " rowQueries x " + std::to_string(column_queries.size()) +
+         (json.contains("columnQueries") ? " columnQueries" : " columnQueries (the rowQueries again)") + " are more than the " +
+         std::to_string(CrossTabulation::MAX_CELLS) + " cells a response may hold"
+   )
+   return std::make_unique<CrossTabulation>(
+      std::move(row_queries), std::move(column_queries), std::move(row_filters), std::move(column_filters), std::move(distinct.filters)
+   );
+}
+
+}  // namespace silo::query_engine::actions

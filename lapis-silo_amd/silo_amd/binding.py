@@ -751,6 +751,43 @@ class GpuStore:
             self.free(o)
         return tables
 
+    def _count_table_call(self, launch, shape, scratch_bytes, out_ptr, stream, scratch_ptr, return_groups=False):
+        """What the three count-table entries (K7, K8, K9) share around launch(scratch, table) -> status: the call's own scratch or
+        the caller's; the call's own zeroed uint32 table of `shape`, read back and returned, or the caller's out_ptr, which
+        returns nothing; return_groups: also (or only, with out_ptr) the uint16 [row_words * 64] range ids at the start of the
+        scratch.  Whatever the call allocated is freed, also when it raises."""
+        cells = int(np.prod(shape, dtype=np.int64))
+        own_scratch = scratch_ptr is _OWN_SCRATCH
+        scratch = self.malloc(scratch_bytes) if own_scratch else scratch_ptr
+        table = out_ptr
+        try:
+            if out_ptr is None:
+                table = self.malloc(max(8, 4 * cells))
+                self.memset(table, 0, max(8, 4 * cells), stream)
+            if own_scratch and return_groups:
+                self.memset(scratch, 0xFF, self.row_words * 128, stream)  # a call that launches nothing assigns no row
+            _check(launch(scratch, table))
+            self.synchronize(stream)
+            result = None
+            if out_ptr is None:
+                result = (self.read(table, np.uint32, cells, stream) if cells else np.zeros(0, dtype=np.uint32)).reshape(shape)
+            if return_groups:
+                groups = self.read(scratch, np.uint16, self.row_words * 64, stream)
+                return groups if out_ptr is not None else (result, groups)
+            return result
+        finally:
+            if own_scratch:
+                self.free(scratch)
+            if out_ptr is None and table is not None:
+                self.free(table)
+
+    @staticmethod
+    def _pointer_array(pointers):
+        """(array of device pointers, its length) for a list of row bitsets (None = all rows); (None, 0) for no list at all."""
+        if pointers is None:
+            return None, 0
+        return (ctypes.c_void_p * max(1, len(pointers)))(*[(f.value if isinstance(f, ctypes.c_void_p) else f) for f in pointers]), len(pointers)
+
     def mutations_grouped(self, seqstore_id, filter_ptr, dates_ptr, ranges, positions, symbols, out_ptr=None, stream=None, return_groups=False,
                           scratch_ptr=_OWN_SCRATCH):
         """silo_gpu_mutations_grouped (K7).  ranges: (from, to) uint32 pairs in request order; positions / symbols: the listed
@@ -764,31 +801,13 @@ class GpuStore:
         if len(positions) != len(symbols):
             raise ValueError("one symbol per position")
         n_ranges, n_mutations = len(bounds), len(positions)
-        cells = n_mutations * n_ranges * 2
-        own_scratch = scratch_ptr is _OWN_SCRATCH
-        scratch = self.malloc(grouped_scratch_bytes(self.row_words, n_ranges, n_mutations)) if own_scratch else scratch_ptr
-        table = out_ptr
-        try:
-            if out_ptr is None:
-                table = self.malloc(max(8, 4 * cells))
-                self.memset(table, 0, max(8, 4 * cells), stream)
-            if own_scratch and return_groups:
-                self.memset(scratch, 0xFF, self.row_words * 128, stream)  # a call that launches nothing assigns no row
-            _check(self.lib.silo_gpu_mutations_grouped(self.handle, seqstore_id, filter_ptr, dates_ptr, _ptr(bounds), n_ranges, _ptr(positions), _ptr(symbols),
-                                                       n_mutations, scratch, table, stream))
-            self.synchronize(stream)
-            result = None
-            if out_ptr is None:
-                result = (self.read(table, np.uint32, cells, stream) if cells else np.zeros(0, dtype=np.uint32)).reshape(n_mutations, n_ranges, 2)
-            if return_groups:
-                groups = self.read(scratch, np.uint16, self.row_words * 64, stream)
-                return groups if out_ptr is not None else (result, groups)
-            return result
-        finally:
-            if own_scratch:
-                self.free(scratch)
-            if out_ptr is None and table is not None:
-                self.free(table)
+
+        def launch(scratch, table):
+            return self.lib.silo_gpu_mutations_grouped(self.handle, seqstore_id, filter_ptr, dates_ptr, _ptr(bounds), n_ranges, _ptr(positions),
+                                                       _ptr(symbols), n_mutations, scratch, table, stream)
+
+        return self._count_table_call(launch, (n_mutations, n_ranges, 2), grouped_scratch_bytes(self.row_words, n_ranges, n_mutations),
+                                      out_ptr, stream, scratch_ptr, return_groups)
 
     def filters_grouped(self, base_ptr, dates_ptr, ranges, filter_ptrs, out_ptr=None, stream=None, return_groups=False, scratch_ptr=_OWN_SCRATCH):
         """silo_gpu_filters_grouped (K8).  ranges: (from, to) uint32 pairs in request order; filter_ptrs: device row bitsets
@@ -799,34 +818,13 @@ class GpuStore:
         [row_words * 64] (0xFFFF = none).  scratch_ptr: the caller's scratch instead of one allocated for the call."""
         bounds = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint32).reshape(-1, 2))
         n_ranges = len(bounds)
-        n_filters = 0 if filter_ptrs is None else len(filter_ptrs)
-        filters = None
-        if filter_ptrs is not None:
-            filters = (ctypes.c_void_p * max(1, n_filters))(*[(f.value if isinstance(f, ctypes.c_void_p) else f) for f in filter_ptrs])
-        cells = n_filters * n_ranges
-        own_scratch = scratch_ptr is _OWN_SCRATCH
-        scratch = self.malloc(filters_grouped_scratch_bytes(self.row_words, n_ranges, n_filters)) if own_scratch else scratch_ptr
-        table = out_ptr
-        try:
-            if out_ptr is None:
-                table = self.malloc(max(8, 4 * cells))
-                self.memset(table, 0, max(8, 4 * cells), stream)
-            if own_scratch and return_groups:
-                self.memset(scratch, 0xFF, self.row_words * 128, stream)  # a call that launches nothing assigns no row
-            _check(self.lib.silo_gpu_filters_grouped(self.handle, base_ptr, dates_ptr, _ptr(bounds), n_ranges, filters, n_filters, scratch, table, stream))
-            self.synchronize(stream)
-            result = None
-            if out_ptr is None:
-                result = (self.read(table, np.uint32, cells, stream) if cells else np.zeros(0, dtype=np.uint32)).reshape(n_filters, n_ranges)
-            if return_groups:
-                groups = self.read(scratch, np.uint16, self.row_words * 64, stream)
-                return groups if out_ptr is not None else (result, groups)
-            return result
-        finally:
-            if own_scratch:
-                self.free(scratch)
-            if out_ptr is None and table is not None:
-                self.free(table)
+        filters, n_filters = self._pointer_array(filter_ptrs)
+
+        def launch(scratch, table):
+            return self.lib.silo_gpu_filters_grouped(self.handle, base_ptr, dates_ptr, _ptr(bounds), n_ranges, filters, n_filters, scratch, table, stream)
+
+        return self._count_table_call(launch, (n_filters, n_ranges), filters_grouped_scratch_bytes(self.row_words, n_ranges, n_filters),
+                                      out_ptr, stream, scratch_ptr, return_groups)
 
     def filters_cross(self, base_ptr, row_ptrs, col_ptrs, row_index=None, col_index=None, out_shape=None, out_ptr=None, stream=None,
                       scratch_ptr=_OWN_SCRATCH):
@@ -835,37 +833,19 @@ class GpuStore:
         lands in the table (None = identity); out_shape: (out_rows, out_cols), by default (len(row_ptrs), len(col_ptrs)).  Without
         out_ptr: a zeroed table for the call, returned as uint32 [out_rows][out_cols].  With out_ptr: accumulates into the caller's
         device table and returns nothing.  scratch_ptr: the caller's scratch instead of one allocated for the call."""
-        def pointer_array(pointers):
-            if pointers is None:
-                return None, 0
-            return (ctypes.c_void_p * max(1, len(pointers)))(*[(f.value if isinstance(f, ctypes.c_void_p) else f) for f in pointers]), len(pointers)
-
-        rows, n_rows = pointer_array(row_ptrs)
-        cols, n_cols = pointer_array(col_ptrs)
+        rows, n_rows = self._pointer_array(row_ptrs)
+        cols, n_cols = self._pointer_array(col_ptrs)
         row_index = None if row_index is None else np.ascontiguousarray(row_index, dtype=np.uint32)
         col_index = None if col_index is None else np.ascontiguousarray(col_index, dtype=np.uint32)
         if (row_index is not None and len(row_index) != n_rows) or (col_index is not None and len(col_index) != n_cols):
             raise ValueError("one index per filter")
         out_rows, out_cols = (n_rows, n_cols) if out_shape is None else out_shape
-        cells = out_rows * out_cols
-        own_scratch = scratch_ptr is _OWN_SCRATCH
-        scratch = self.malloc(filters_cross_scratch_bytes(n_rows, n_cols)) if own_scratch else scratch_ptr
-        table = out_ptr
-        try:
-            if out_ptr is None:
-                table = self.malloc(max(8, 4 * cells))
-                self.memset(table, 0, max(8, 4 * cells), stream)
-            _check(self.lib.silo_gpu_filters_cross(self.handle, base_ptr, rows, None if row_index is None else _ptr(row_index), n_rows,
-                                                   cols, None if col_index is None else _ptr(col_index), n_cols, scratch, table, out_rows, out_cols, stream))
-            self.synchronize(stream)
-            if out_ptr is not None:
-                return None
-            return (self.read(table, np.uint32, cells, stream) if cells else np.zeros(0, dtype=np.uint32)).reshape(out_rows, out_cols)
-        finally:
-            if own_scratch:
-                self.free(scratch)
-            if out_ptr is None and table is not None:
-                self.free(table)
+
+        def launch(scratch, table):
+            return self.lib.silo_gpu_filters_cross(self.handle, base_ptr, rows, None if row_index is None else _ptr(row_index), n_rows,
+                                                   cols, None if col_index is None else _ptr(col_index), n_cols, scratch, table, out_rows, out_cols, stream)
+
+        return self._count_table_call(launch, (out_rows, out_cols), filters_cross_scratch_bytes(n_rows, n_cols), out_ptr, stream, scratch_ptr)
 
     # ---- metadata columns (K5 / K6) and FastaAligned ---------------------------------------------
     VALUE_TYPES = {np.dtype(np.int32): 0, np.dtype(np.uint32): 1, np.dtype(np.float64): 2}
