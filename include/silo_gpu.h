@@ -540,6 +540,34 @@ int silo_gpu_filters_cross(
    uint32_t out_cols, void* stream
 );
 
+/* ---- K10: pairwise distances of rows of characters (DistanceMatrix) ----------------------------------
+ * Neither entry takes a store (like silo_gpu_mutations_select): they start from the characters that
+ * silo_gpu_reconstruct_sequences writes for every store layout, chars_dev[r * positions + p].
+ * silo_gpu_distance_pack turns every row into SILO_GPU_DISTANCE_PLANES(alphabet) bit planes over POSITIONS of
+ * SILO_GPU_DISTANCE_WORDS(positions) words each, planes_dev[(r * PLANES + k) * WORDS + w], bit b of word w = position 64 w + b:
+ *     plane 0      the character is a valid mutation symbol of the alphabet (nucleotide "-ACGT", amino acid
+ *                  "-ACDEFGHIKLMNPQRSTVWY*": what Mutations counts);
+ *     plane 1 + k  bit k of that symbol's index in the string above, 0 where the position is not valid.
+ * Every other byte — N, X, the ambiguity codes, bytes that are no symbol at all — is not valid.  Every word of every row's slot
+ * is written, the bits at or past `positions` as zeros: the caller never clears the buffer.
+ * silo_gpu_distance_pairs WRITES (no accumulation, no atomics) for every pair i <= j < n_rows
+ *     out_dev[(i * n_rows + j) * 2]     = differing = sum_w popcount(valid_i & valid_j & OR_k (code_i,k ^ code_j,k))
+ *     out_dev[(i * n_rows + j) * 2 + 1] = compared  = sum_w popcount(valid_i & valid_j)
+ * so the diagonal holds (0, valid positions of row i); cells with i > j are never touched.  Only tiles of SILO_GPU_DISTANCE_TILE x
+ * SILO_GPU_DISTANCE_TILE pairs on or above the diagonal are launched; a block stages SILO_GPU_DISTANCE_CHUNK_WORDS words of every
+ * plane of its 2 x SILO_GPU_DISTANCE_TILE rows in LDS at a time, so a packed word is read from memory once per tile of the other
+ * side.  Each pair belongs to one thread of one block: the result does not depend on how the blocks are scheduled.
+ * Both make their launch on `stream` and return without waiting.  n_rows == 0 or positions == 0: success, nothing launched.
+ * Fail with SILO_GPU_ERR_INVALID_ARGUMENT for an alphabet other than the two, a NULL buffer or more than
+ * SILO_GPU_MAX_DISTANCE_ROWS rows. */
+#define SILO_GPU_MAX_DISTANCE_ROWS 2048
+#define SILO_GPU_DISTANCE_PLANES(alphabet) ((alphabet) == SILO_GPU_ALPHABET_AMINO_ACID ? 6u : 4u) /* 1 valid plane + 5 / 3 code bits */
+#define SILO_GPU_DISTANCE_WORDS(positions) (((positions) + 63u) / 64u)
+#define SILO_GPU_DISTANCE_TILE 16
+#define SILO_GPU_DISTANCE_CHUNK_WORDS 32
+int silo_gpu_distance_pack(int alphabet, const char* chars_dev, uint32_t n_rows, uint32_t positions, uint64_t* planes_dev, void* stream);
+int silo_gpu_distance_pairs(int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, uint32_t* out_dev, void* stream);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

@@ -1,0 +1,222 @@
+// silo_gpu_distance.hip — the pairwise distances behind DistanceMatrix (K10): for n rows of characters, per pair
+// the positions where both rows hold a valid mutation symbol (compared) and where those two symbols differ (differing).
+// Neither entry point takes a store: they start from the characters silo_gpu_reconstruct_sequences yields for every layout.
+//
+// Kernels:
+//   k_distance_pack    one row of characters -> bit planes over positions (silo_gpu_distance_pack): a wave maps 64 consecutive
+//                      characters through a 256-byte table, one ballot per plane is the plane's word
+//   k_distance_pairs   an AND / XOR-popcount "GEMM" over the planes (silo_gpu_distance_pairs): a block owns a tile of
+//                      DISTANCE_TILE x DISTANCE_TILE pairs on or above the diagonal, stages the words of its 2 x DISTANCE_TILE
+//                      rows in LDS chunk by chunk, and WRITES each pair's two counts once
+#include "store_internal.h"
+
+using namespace silo_gpu_detail;
+
+namespace {
+
+constexpr uint32_t DISTANCE_THREADS = 256;
+constexpr uint32_t DISTANCE_TILE = SILO_GPU_DISTANCE_TILE;                // rows per side of a block's tile: one pair per thread
+constexpr uint32_t DISTANCE_CHUNK_WORDS = SILO_GPU_DISTANCE_CHUNK_WORDS;  // words of every plane of a row that are staged at a time
+constexpr uint32_t DISTANCE_PACK_WAVES = DISTANCE_THREADS / 64;           // words of a row per block of k_distance_pack
+constexpr uint8_t NOT_VALID = 0xFF;
+static_assert(DISTANCE_TILE * DISTANCE_TILE == DISTANCE_THREADS);
+
+/// The valid mutation symbols of an alphabet as characters, in the order of Nucleotide / AminoAcid::VALID_MUTATION_SYMBOLS
+/// (host/symbols.h): the index of a character in here is the code the planes hold.
+struct DistanceSymbols {
+   char symbols[24];
+   uint32_t count;
+};
+
+constexpr DistanceSymbols NUCLEOTIDE_SYMBOLS{"-ACGT", 5};
+constexpr DistanceSymbols AMINO_ACID_SYMBOLS{"-ACDEFGHIKLMNPQRSTVWY*", 22};
+static_assert((1u << (SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_NUCLEOTIDE) - 1u)) >= NUCLEOTIDE_SYMBOLS.count);
+static_assert((1u << (SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_AMINO_ACID) - 1u)) >= AMINO_ACID_SYMBOLS.count);
+
+/// grid = (words of a row / DISTANCE_PACK_WAVES rounded up, n_rows).  The block first makes the table byte -> code (the index
+/// among the valid symbols, NOT_VALID for every other byte, one entry per thread); then wave v takes word blockIdx.x *
+/// DISTANCE_PACK_WAVES + v of row blockIdx.y: lane l reads the character at position 64 * word + l — a lane at or past
+/// `positions` reads nothing and counts as not valid, so the padding bits of the last word are zero — and the ballots over the
+/// wave are the word of plane 0 (valid) and of planes 1 .. PLANES - 1 (bit k - 1 of the code).  Lane 0 stores them.
+template <uint32_t PLANES>
+__global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_pack(
+   const DistanceSymbols valid, const uint8_t* __restrict__ chars, uint32_t positions, uint32_t words, uint64_t* __restrict__ planes
+) {
+   __shared__ uint8_t s_code[256];
+   {
+      uint8_t code = NOT_VALID;
+      for (uint32_t s = 0; s < valid.count; ++s) {
+         if (static_cast<uint8_t>(valid.symbols[s]) == threadIdx.x) {
+            code = static_cast<uint8_t>(s);
+         }
+      }
+      s_code[threadIdx.x] = code;
+   }
+   __syncthreads();
+   const uint32_t word = blockIdx.x * DISTANCE_PACK_WAVES + threadIdx.x / 64u;  // the same for the whole wave
+   if (word >= words) {
+      return;
+   }
+   const uint32_t row = blockIdx.y;
+   const uint32_t lane = threadIdx.x & 63u;
+   const uint64_t position = static_cast<uint64_t>(word) * 64u + lane;
+   uint8_t code = NOT_VALID;
+   if (position < positions) {
+      code = s_code[chars[static_cast<size_t>(row) * positions + position]];
+   }
+   const bool is_valid = code != NOT_VALID;
+   uint64_t bits[PLANES];
+   bits[0] = __ballot(is_valid);
+#pragma unroll
+   for (uint32_t k = 1; k < PLANES; ++k) {
+      bits[k] = __ballot(is_valid && ((code >> (k - 1u)) & 1u) != 0);
+   }
+   if (lane == 0) {
+      uint64_t* slot = planes + static_cast<size_t>(row) * PLANES * words + word;
+#pragma unroll
+      for (uint32_t k = 0; k < PLANES; ++k) {
+         slot[static_cast<size_t>(k) * words] = bits[k];
+      }
+   }
+}
+
+/// A row of the staged tile in LDS: DISTANCE_CHUNK_WORDS words of each plane, and one word of padding — the 16 rows that the
+/// lanes of a half wave read at the same (plane, word) then lie on 16 different bank pairs.
+template <uint32_t PLANES>
+constexpr uint32_t stagedRowWords() {
+   return PLANES * DISTANCE_CHUNK_WORDS + 1u;
+}
+
+/// grid = the tiles (ti, tj), ti <= tj, of the upper triangle, row-major: tiles_per_side * (tiles_per_side + 1) / 2 blocks.
+/// Thread t owns the pair (row ti * TILE + t / TILE, row tj * TILE + t % TILE).  Per chunk of DISTANCE_CHUNK_WORDS words the
+/// block copies the words of all planes of its 2 x TILE rows into LDS — consecutive threads take consecutive words of one plane
+/// of one row; a row at or past n_rows is staged as zeros, so nothing past the buffer is read — and every thread walks the
+/// chunk: the lanes that share a row of the first side read the same LDS address (broadcast).  Two register accumulators per
+/// thread; the pair's cell is written once at the end, and only where i <= j < n_rows.
+template <uint32_t PLANES>
+__global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_pairs(
+   const uint64_t* __restrict__ planes, uint32_t n_rows, uint32_t words, uint32_t tiles_per_side, uint32_t* __restrict__ out
+) {
+   constexpr uint32_t ROW_WORDS = stagedRowWords<PLANES>();
+   constexpr uint32_t STAGED = 2u * DISTANCE_TILE * PLANES * DISTANCE_CHUNK_WORDS;  // words copied per chunk
+   static_assert(STAGED % DISTANCE_THREADS == 0);
+   __shared__ uint64_t s_rows[2u * DISTANCE_TILE * ROW_WORDS];
+
+   // the tile of this block: row ti of the triangle has tiles_per_side - ti tiles (uniform, at most tiles_per_side steps)
+   uint32_t ti = 0;
+   uint32_t tj = blockIdx.x;
+   for (uint32_t row_tiles = tiles_per_side; tj >= row_tiles; --row_tiles) {
+      tj -= row_tiles;
+      ++ti;
+   }
+   tj += ti;
+   const uint32_t i = threadIdx.x / DISTANCE_TILE;
+   const uint32_t j = threadIdx.x % DISTANCE_TILE;
+   const uint64_t* mine = s_rows + i * ROW_WORDS;
+   const uint64_t* other = s_rows + (DISTANCE_TILE + j) * ROW_WORDS;
+   uint32_t compared = 0;
+   uint32_t differing = 0;
+   for (uint32_t chunk_begin = 0; chunk_begin < words; chunk_begin += DISTANCE_CHUNK_WORDS) {
+      const uint32_t chunk_words = min(words - chunk_begin, DISTANCE_CHUNK_WORDS);
+      uint64_t staged[STAGED / DISTANCE_THREADS];
+#pragma unroll
+      for (uint32_t k = 0; k < STAGED / DISTANCE_THREADS; ++k) {  // all loads in flight
+         const uint32_t element = k * DISTANCE_THREADS + threadIdx.x;
+         const uint32_t word = element % DISTANCE_CHUNK_WORDS;
+         const uint32_t row_plane = element / DISTANCE_CHUNK_WORDS;  // (side * TILE + row of the side) * PLANES + plane
+         const uint32_t local_row = row_plane / PLANES;
+         const uint32_t row = local_row < DISTANCE_TILE ? ti * DISTANCE_TILE + local_row : tj * DISTANCE_TILE + (local_row - DISTANCE_TILE);
+         staged[k] = 0;
+         if (row < n_rows && word < chunk_words) {
+            staged[k] = planes[(static_cast<size_t>(row) * PLANES + row_plane % PLANES) * words + chunk_begin + word];
+         }
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < STAGED / DISTANCE_THREADS; ++k) {
+         const uint32_t element = k * DISTANCE_THREADS + threadIdx.x;
+         const uint32_t row_plane = element / DISTANCE_CHUNK_WORDS;
+         s_rows[(row_plane / PLANES) * ROW_WORDS + (row_plane % PLANES) * DISTANCE_CHUNK_WORDS + element % DISTANCE_CHUNK_WORDS] = staged[k];
+      }
+      __syncthreads();
+      for (uint32_t word = 0; word < chunk_words; ++word) {
+         const uint64_t both = mine[word] & other[word];
+         uint64_t unequal = 0;
+#pragma unroll
+         for (uint32_t k = 1; k < PLANES; ++k) {
+            unequal |= mine[k * DISTANCE_CHUNK_WORDS + word] ^ other[k * DISTANCE_CHUNK_WORDS + word];
+         }
+         compared += static_cast<uint32_t>(__popcll(both));
+         differing += static_cast<uint32_t>(__popcll(both & unequal));
+      }
+      __syncthreads();  // the next chunk overwrites what was just read
+   }
+   const uint32_t row_i = ti * DISTANCE_TILE + i;
+   const uint32_t row_j = tj * DISTANCE_TILE + j;
+   if (row_i <= row_j && row_j < n_rows) {
+      *reinterpret_cast<uint2*>(out + (static_cast<size_t>(row_i) * n_rows + row_j) * 2u) = make_uint2(differing, compared);
+   }
+}
+
+/// What both entries refuse; nullptr if nothing.
+const char* distanceComplaint(int alphabet, const void* in_dev, const void* out_dev, uint32_t n_rows) {
+   if (alphabet != SILO_GPU_ALPHABET_NUCLEOTIDE && alphabet != SILO_GPU_ALPHABET_AMINO_ACID) {
+      return "the alphabet is neither SILO_GPU_ALPHABET_NUCLEOTIDE nor SILO_GPU_ALPHABET_AMINO_ACID";
+   }
+   if (in_dev == nullptr || out_dev == nullptr) {
+      return "a buffer is NULL";
+   }
+   if (n_rows > SILO_GPU_MAX_DISTANCE_ROWS) {
+      return "more rows than SILO_GPU_MAX_DISTANCE_ROWS";
+   }
+   return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int silo_gpu_distance_pack(int alphabet, const char* chars_dev, uint32_t n_rows, uint32_t positions, uint64_t* planes_dev, void* stream) {
+   if (const char* complaint = distanceComplaint(alphabet, chars_dev, planes_dev, n_rows); complaint != nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_distance_pack: ") + complaint);
+   }
+   if (n_rows == 0 || positions == 0) {
+      return SILO_GPU_OK;
+   }
+   const uint32_t words = SILO_GPU_DISTANCE_WORDS(positions);
+   const dim3 grid((words + DISTANCE_PACK_WAVES - 1) / DISTANCE_PACK_WAVES, n_rows);
+   auto hip_stream = static_cast<hipStream_t>(stream);
+   const auto* chars = reinterpret_cast<const uint8_t*>(chars_dev);
+   if (alphabet == SILO_GPU_ALPHABET_NUCLEOTIDE) {
+      k_distance_pack<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_NUCLEOTIDE)>
+         <<<grid, DISTANCE_THREADS, 0, hip_stream>>>(NUCLEOTIDE_SYMBOLS, chars, positions, words, planes_dev);
+   } else {
+      k_distance_pack<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_AMINO_ACID)>
+         <<<grid, DISTANCE_THREADS, 0, hip_stream>>>(AMINO_ACID_SYMBOLS, chars, positions, words, planes_dev);
+   }
+   HIP_TRY(hipGetLastError());
+   return SILO_GPU_OK;
+}
+
+int silo_gpu_distance_pairs(int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, uint32_t* out_dev, void* stream) {
+   if (const char* complaint = distanceComplaint(alphabet, planes_dev, out_dev, n_rows); complaint != nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_distance_pairs: ") + complaint);
+   }
+   if (n_rows == 0 || positions == 0) {
+      return SILO_GPU_OK;
+   }
+   const uint32_t words = SILO_GPU_DISTANCE_WORDS(positions);
+   const uint32_t tiles_per_side = (n_rows + DISTANCE_TILE - 1) / DISTANCE_TILE;
+   const uint32_t grid = tiles_per_side * (tiles_per_side + 1u) / 2u;
+   auto hip_stream = static_cast<hipStream_t>(stream);
+   if (alphabet == SILO_GPU_ALPHABET_NUCLEOTIDE) {
+      k_distance_pairs<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_NUCLEOTIDE)>
+         <<<grid, DISTANCE_THREADS, 0, hip_stream>>>(planes_dev, n_rows, words, tiles_per_side, out_dev);
+   } else {
+      k_distance_pairs<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_AMINO_ACID)>
+         <<<grid, DISTANCE_THREADS, 0, hip_stream>>>(planes_dev, n_rows, words, tiles_per_side, out_dev);
+   }
+   HIP_TRY(hipGetLastError());
+   return SILO_GPU_OK;
+}
+
+}  // extern "C"

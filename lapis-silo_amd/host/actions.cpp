@@ -798,6 +798,7 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"AminoAcidMutationsOverTime", parseMutationsOverTime<AminoAcid>},
    {"QueriesOverTime", parseQueriesOverTime},
    {"CrossTabulation", parseCrossTabulation},
+   {"DistanceMatrix", parseDistanceMatrix},
 };
 
 }  // namespace

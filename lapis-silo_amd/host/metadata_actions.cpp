@@ -2,6 +2,7 @@
 //   Aggregated with groupByFields   src/silo/query_engine/actions/aggregated.cpp:100-149
 //   Details                         src/silo/query_engine/actions/details.cpp
 //   FastaAligned                    src/silo/query_engine/actions/fasta_aligned.cpp
+//   DistanceMatrix                  (not in the reference) the rows FastaAligned would return, compared pairwise on the device (K10)
 #include <algorithm>
 #include <type_traits>
 #include <unordered_map>
@@ -570,6 +571,136 @@ QueryResult FastaAligned::execute(const Database& database, std::vector<Operator
       }
    }
    return results;
+}
+
+// ---- DistanceMatrix --------------------------------------------------------------------------------------
+// The pairwise distances of the selected sequences from the pair kernel (K10), with its parser.  No counterpart in the reference:
+// its clients fetch FastaAligned and compare the strings themselves.
+void DistanceMatrix::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"firstKey", "secondKey", "distance", "comparedPositions"});
+}
+
+QueryResult DistanceMatrix::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+   const bool is_amino_acid = database.nuc_sequences.count(name) == 0;
+   CHECK_SILO_QUERY(!is_amino_acid || database.aa_sequences.count(name) != 0, "Database does not contain a sequence with name: '" + name + "'")
+   size_t total_count = 0;
+   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+      total_count += database.partitions[partition_id].sequence_count == 0 ? 0 : bitmap_filter[partition_id].cardinality();
+   }
+   CHECK_SILO_QUERY(total_count <= SEQUENCE_LIMIT, "DistanceMatrix action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences")
+   requireUnsharded(database, "DistanceMatrix");
+   QueryResult results;
+   if (total_count < 2) {
+      return results;
+   }
+   const auto n = static_cast<uint32_t>(total_count);
+   const int alphabet = is_amino_acid ? SILO_GPU_ALPHABET_AMINO_ACID : SILO_GPU_ALPHABET_NUCLEOTIDE;
+   const auto positions =
+      static_cast<uint32_t>(is_amino_acid ? database.aa_sequences.at(name).reference_sequence.size() : database.nuc_sequences.at(name).reference_sequence.size());
+   const size_t row_plane_words = static_cast<size_t>(SILO_GPU_DISTANCE_PLANES(alphabet)) * SILO_GPU_DISTANCE_WORDS(positions);
+   const size_t table_words = static_cast<size_t>(n) * n * 2u;
+
+   const std::string& primary_key_column = database.database_config.primary_key;
+   std::vector<JsonValue> keys;  // of sequence 0 .. n - 1: partition order, then ascending row id
+   keys.reserve(n);
+   std::vector<uint32_t> table(positions == 0 ? table_words : 0u, 0u);  // (a sequence without positions: nothing to compare, nothing launched)
+   {
+      // nothing in here returns to the pool before the stream has been waited for: the launches read it
+      DevicePool& pool = database.partitions.front().pool;
+      DeviceBuffer device_planes = pool.acquire(std::max<size_t>(8, n * row_plane_words * sizeof(uint64_t)));
+      DeviceBuffer device_table = pool.acquire(table_words * sizeof(uint32_t));
+      std::vector<DeviceBuffer> live;  // per partition: its row ids and its characters
+      try {
+         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+            const DatabasePartition& partition = database.partitions[partition_id];
+            if (partition.sequence_count == 0) {
+               continue;
+            }
+            const std::vector<uint32_t> rows = selectedRows(partition, bitmap_filter[partition_id]);
+            if (rows.empty()) {
+               continue;
+            }
+            const size_t first_sequence = keys.size();
+            const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
+            for (const uint32_t row : rows) {
+               keys.push_back(primary_key.jsonOfRow(row));
+            }
+            if (keys.size() > n) {
+               throw std::runtime_error("DistanceMatrix: a filter selects more rows than its cardinality says");
+            }
+            if (positions == 0) {
+               continue;
+            }
+            const auto n_rows = static_cast<uint32_t>(rows.size());
+            const uint32_t seqstore_id = is_amino_acid ? partition.aa_sequences.at(name).seqstore_id : partition.nuc_sequences.at(name).seqstore_id;
+            auto* device_rows = live.emplace_back(partition.pool.acquire(rows.size() * sizeof(uint32_t))).as<uint32_t>();
+            checkGpu(silo_gpu_memcpy_h2d(device_rows, rows.data(), rows.size() * sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
+            auto* device_chars = live.emplace_back(partition.pool.acquire(rows.size() * static_cast<size_t>(positions))).as<char>();
+            checkGpu(
+               silo_gpu_reconstruct_sequences(partition.store, seqstore_id, device_rows, n_rows, device_chars, queryStream()),
+               "silo_gpu_reconstruct_sequences"
+            );
+            checkGpu(
+               silo_gpu_distance_pack(alphabet, device_chars, n_rows, positions, device_planes.as<uint64_t>() + first_sequence * row_plane_words, queryStream()),
+               "silo_gpu_distance_pack"
+            );
+         }
+         if (keys.size() != n) {
+            throw std::runtime_error("DistanceMatrix: a filter selects fewer rows than its cardinality says");
+         }
+         if (positions != 0) {
+            // rows of different partitions are compared with each other: one call over all of them, one table fetched
+            checkGpu(
+               silo_gpu_distance_pairs(alphabet, device_planes.as<uint64_t>(), n, positions, device_table.as<uint32_t>(), queryStream()),
+               "silo_gpu_distance_pairs"
+            );
+            HostFetch fetch(device_table.get(), table_words * sizeof(uint32_t), queryStream());
+            const auto* host = static_cast<const uint32_t*>(fetch.wait());
+            table.assign(host, host + table_words);
+         }
+         // the copy was the last thing enqueued, but say it: nothing of this query runs any more when its buffers go back
+         checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+      } catch (...) {
+         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+         (void)silo_gpu_stream_synchronize(queryStream());
+         throw;
+      }
+   }
+
+   // maxDistance is applied here, before a row is built
+   for (uint32_t i = 0; i < n; ++i) {
+      for (uint32_t j = i + 1; j < n; ++j) {
+         const size_t cell = (static_cast<size_t>(i) * n + j) * 2u;
+         const uint32_t distance = table[cell];
+         if (max_distance.has_value() && distance > *max_distance) {
+            continue;
+         }
+         QueryResultEntry& entry = results.query_result.emplace_back();
+         entry.fields.emplace("firstKey", keys[i]);
+         entry.fields.emplace("secondKey", keys[j]);
+         entry.fields.emplace("distance", static_cast<int32_t>(distance));
+         entry.fields.emplace("comparedPositions", static_cast<int32_t>(table[cell + 1u]));
+      }
+   }
+   return results;
+}
+
+std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json) {
+   std::optional<std::string> sequence_name;
+   if (json.contains("sequenceName")) {
+      CHECK_SILO_QUERY(json["sequenceName"].is_string(), "DistanceMatrix action: the field sequenceName, if present, must be of type string")
+      sequence_name = json["sequenceName"].as_string();
+   }
+   std::optional<uint32_t> max_distance;
+   if (json.contains("maxDistance")) {
+      CHECK_SILO_QUERY(
+         json["maxDistance"].is_number_unsigned() && json["maxDistance"].as_int64() <= INT32_MAX,
+         "DistanceMatrix action: the field maxDistance, if present, must be a non-negative integer"
+      )
+      max_distance = json["maxDistance"].as_uint32();
+   }
+   return std::make_unique<DistanceMatrix>(std::move(sequence_name), max_distance);
 }
 
 }  // namespace silo::query_engine::actions

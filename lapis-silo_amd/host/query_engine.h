@@ -623,6 +623,11 @@ template <typename SymbolType>
 std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json);
 std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json);
 std::unique_ptr<Action> parseCrossTabulation(const json::Value& json);
+/// The parser of DistanceMatrix (metadata_actions.cpp).
+std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json);
+
+/// Refuses a sharded database on behalf of an action whose counts are not all-reduced across ranks (table_actions.cpp).
+void requireUnsharded(const Database& database, const std::string& action_name);
 
 class Aggregated : public Action {
    std::vector<std::string> group_by_fields;
@@ -682,6 +687,25 @@ class FastaAligned : public Action {
 
   public:
    explicit FastaAligned(std::vector<std::string>&& sequence_names) : sequence_names(std::move(sequence_names)) {}
+};
+
+/// DistanceMatrix (metadata_actions.cpp): per unordered pair of the selected sequences the positions of one aligned sequence where
+/// both hold a valid mutation symbol (comparedPositions) and where those two differ (distance) — the SNP distance matrix a
+/// client would otherwise compute from a FastaAligned response.  The sequences are numbered in partition order, then by
+/// ascending row id; one row per pair i < j, row-major; with maxDistance only the pairs at most that far apart.  The rows
+/// of every partition are gathered (silo_gpu_reconstruct_sequences) and packed into bit planes over positions
+/// (silo_gpu_distance_pack) in ONE buffer, so that one pair kernel (K10, silo_gpu_distance_pairs) compares rows of different
+/// partitions too, and one table is fetched per query.
+class DistanceMatrix : public Action {
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   std::optional<uint32_t> max_distance;
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+
+  public:
+   static constexpr uint32_t SEQUENCE_LIMIT = SILO_GPU_MAX_DISTANCE_ROWS;
+   DistanceMatrix(std::optional<std::string> sequence_name, std::optional<uint32_t> max_distance)
+       : sequence_name(std::move(sequence_name)), max_distance(max_distance) {}
 };
 
 template <typename SymbolType>

@@ -11,14 +11,14 @@
 
 namespace silo::query_engine::actions {
 
-namespace {
-
-// ---- what the three actions share ----------------------------------------------------------------------
+// ---- what the three actions share (requireUnsharded: with DistanceMatrix too) ----------------------------
 void requireUnsharded(const Database& database, const std::string& action_name) {
    CHECK_SILO_QUERY(
       database.shard_world <= 1, action_name + " is not supported on a sharded database yet: its counts are not all-reduced across ranks"
    )
 }
+
+namespace {
 
 std::string notADateColumn(const std::string& date_field, const std::string& action_name) {
    return "The field dateField of " + action_name + " ('" + date_field + "') is not a date column";

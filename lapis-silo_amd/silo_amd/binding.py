@@ -110,6 +110,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_allreduce_counts", "silo_gpu_broadcast_bytes",
     "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules", "silo_gpu_store_scan_prunable_rows",
     "silo_gpu_filters_grouped", "silo_gpu_filters_cross",
+    "silo_gpu_distance_pack", "silo_gpu_distance_pairs",
 ]
 
 _lib = None
@@ -175,6 +176,8 @@ def load_library():
     lib.silo_gpu_filters_grouped.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_filters_cross.argtypes = [vp, vp, ctypes.POINTER(vp), vp, ctypes.c_uint32, ctypes.POINTER(vp), vp, ctypes.c_uint32, vp, vp,
                                            ctypes.c_uint32, ctypes.c_uint32, vp]
+    lib.silo_gpu_distance_pack.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_distance_pairs.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -442,6 +445,84 @@ def filters_grouped_scratch_bytes(row_words, n_ranges, n_filters):
 def filters_cross_scratch_bytes(n_rows, n_cols):
     """SILO_GPU_FILTERS_CROSS_SCRATCH_BYTES: the scratch silo_gpu_filters_cross needs."""
     return (n_rows + n_cols) * 16 + 1024
+
+
+MAX_DISTANCE_ROWS = 2048       # SILO_GPU_MAX_DISTANCE_ROWS
+DISTANCE_TILE = 16             # SILO_GPU_DISTANCE_TILE: rows per side of the pair tile that a block of K10 owns
+DISTANCE_CHUNK_WORDS = 32      # SILO_GPU_DISTANCE_CHUNK_WORDS: words of every plane of a row that a block of K10 stages at a time
+
+
+def _abi_alphabet(name_or_id):
+    return alphabet.ALPHABETS[name_or_id].abi_id if isinstance(name_or_id, str) else int(name_or_id)
+
+
+def distance_planes(alphabet_id):
+    """SILO_GPU_DISTANCE_PLANES: the valid plane and the code bits (nucleotide 1 + 3, amino acid 1 + 5)."""
+    return 6 if _abi_alphabet(alphabet_id) == 1 else 4
+
+
+def distance_words(positions):
+    """SILO_GPU_DISTANCE_WORDS: 64-bit words per plane of a row."""
+    return (positions + 63) // 64
+
+
+def device_malloc(nbytes, fill=None, stream=None):
+    """A device allocation that belongs to no store (free with device_free); fill: the byte every byte of it is set to."""
+    lib = load_library()
+    ptr = ctypes.c_void_p()
+    _check(lib.silo_gpu_malloc(max(1, nbytes), ctypes.byref(ptr)))
+    if fill is not None and nbytes:
+        _check(lib.silo_gpu_memset_async(ptr, fill, nbytes, stream))
+    return ptr
+
+
+def device_free(ptr):
+    load_library().silo_gpu_free(ptr)
+
+
+def device_read(ptr, dtype, count, stream=None):
+    out = np.empty(count, dtype=dtype)
+    if count:
+        _check(load_library().silo_gpu_memcpy_d2h(_ptr(out), ptr, out.nbytes, stream))
+    return out
+
+
+def distance_pack(alphabet_id, chars, fill=None, stream=None):
+    """silo_gpu_distance_pack (K10): chars uint8 [n][P] -> a device pointer to the planes uint64 [n][PLANES][WORDS] (free with
+    device_free, read with device_read).  alphabet_id: 'nuc' / 'aa' or the id of the C ABI.  fill: the byte the plane buffer is
+    filled with before the launch, so a test can see that every word is written."""
+    lib = load_library()
+    chars = np.ascontiguousarray(chars, dtype=np.uint8)
+    n_rows, positions = chars.shape
+    abi = _abi_alphabet(alphabet_id)
+    planes = device_malloc(n_rows * distance_planes(abi) * distance_words(positions) * 8, fill, stream)
+    chars_dev = device_malloc(chars.size)
+    try:
+        if chars.size:
+            _check(lib.silo_gpu_memcpy_h2d(chars_dev, _ptr(chars), chars.size, stream))
+        _check(lib.silo_gpu_distance_pack(abi, chars_dev, n_rows, positions, planes, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+    except Exception:
+        device_free(planes)
+        raise
+    finally:
+        device_free(chars_dev)
+    return planes
+
+
+def distance_pairs(alphabet_id, planes_ptr, n_rows, positions, fill=None, stream=None):
+    """silo_gpu_distance_pairs (K10) over planes as distance_pack leaves them: uint32 [n][n][2], cell (i, j) = (differing,
+    compared) for i <= j.  Cells with i > j are not written: they hold the byte `fill` repeated (the output is filled with it
+    before the launch), or whatever the allocation held."""
+    lib = load_library()
+    cells = n_rows * n_rows * 2
+    out = device_malloc(cells * 4, fill, stream)
+    try:
+        _check(lib.silo_gpu_distance_pairs(_abi_alphabet(alphabet_id), planes_ptr, n_rows, positions, out, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(out, np.uint32, cells, stream).reshape(n_rows, n_rows, 2)
+    finally:
+        device_free(out)
 
 
 class GpuStore:
