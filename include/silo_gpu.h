@@ -568,6 +568,41 @@ int silo_gpu_filters_cross(
 int silo_gpu_distance_pack(int alphabet, const char* chars_dev, uint32_t n_rows, uint32_t positions, uint64_t* planes_dev, void* stream);
 int silo_gpu_distance_pairs(int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, uint32_t* out_dev, void* stream);
 
+/* ---- K11: the rows of the whole store nearest to a query (NearestNeighbours) --------------------------
+ * silo_gpu_query_distances compares one query — query_chars, `positions` characters in HOST memory — with EVERY row of a sequence
+ * store, read off the store's own layout (identity / code planes with escape keys, one-hot rows with a derived symbol, runs of the
+ * missing symbol, sparse or extra ambiguity planes) instead of gathered characters.  It WRITES for every row r < row_words * 64
+ *     out_dev[r * 2]     = distance = positions where the query and row r both hold a valid mutation symbol and the two differ
+ *     out_dev[r * 2 + 1] = compared = positions where both hold a valid mutation symbol
+ * with "valid" as in K10 (nucleotide "-ACGT", amino acid "-ACDEFGHIKLMNPQRSTVWY*"; every other byte of the query never compares):
+ * exactly the two numbers silo_gpu_distance_pairs gives for the pair (query, r).  Rows at or past sequence_count get (0, 0); the
+ * caller never clears out_dev.  Integer adds only: the table does not depend on how the blocks are scheduled.
+ * scratch_dev: device memory of SILO_GPU_QUERY_DISTANCE_SCRATCH_BYTES(positions) bytes, 16-byte aligned.  Uploads its per-position
+ * tables there and waits for them (one stream synchronisation), then launches its passes on `stream` without waiting: the constants
+ * of the derived positions, the plane rows (a thread owns 64 rows and adds each position's masks into vertical counters of
+ * SILO_GPU_QUERY_DISTANCE_COUNTER_PLANES bit planes), the escape keys, the runs of the missing symbol, the sparse keys.
+ * silo_gpu_nearest_rows takes such a table (no store, like silo_gpu_mutations_select and K10) and WRITES the k smallest rows by
+ * (distance, row) among the rows r < sequence_count that filter_dev selects (NULL = all rows; bits at or past sequence_count never
+ * select a row), other than exclude_row (UINT32_MAX: none), with distance <= max_distance (UINT32_MAX: no bound):
+ *     out_dev[i * 3 + 0 .. 2] = row, distance, compared     for i < *out_count_dev <= k, ascending by (distance, row)
+ * Entries at or past *out_count_dev are not touched.  Rows tied at the k-th distance are taken by ascending row id; two calls with
+ * the same arguments give the same output.  scratch_dev: SILO_GPU_NEAREST_ROWS_SCRATCH_BYTES bytes, 16-byte aligned.  Launches on
+ * `stream` and returns without waiting.
+ * Both fail with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL store, query, table, output or scratch, a seqstore_id
+ * out of range, a store or table without rows, k == 0 or k > SILO_GPU_MAX_NEAREST_ROWS. */
+#define SILO_GPU_MAX_NEAREST_ROWS 1024
+#define SILO_GPU_QUERY_DISTANCE_COUNTER_PLANES 12 /* a vertical counter is unpacked after 2^12 - 1 adds */
+#define SILO_GPU_QUERY_DISTANCE_SCRATCH_BYTES(positions)                                                                    \
+   (((size_t)(positions) / 256u + 1u) * 256u + 2u * ((((size_t)(positions) + 1u) * 4u) / 256u + 1u) * 256u)
+#define SILO_GPU_NEAREST_ROWS_SCRATCH_BYTES 32768u
+int silo_gpu_query_distances(
+   const silo_gpu_store* store, uint32_t seqstore_id, const char* query_chars, uint32_t* out_dev, void* scratch_dev, void* stream
+);
+int silo_gpu_nearest_rows(
+   const uint32_t* table_dev, const uint64_t* filter_dev, uint32_t sequence_count, uint32_t exclude_row, uint32_t max_distance, uint32_t k,
+   uint32_t* out_dev, uint32_t* out_count_dev, void* scratch_dev, void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

@@ -3,7 +3,9 @@
 //   Details                         src/silo/query_engine/actions/details.cpp
 //   FastaAligned                    src/silo/query_engine/actions/fasta_aligned.cpp
 //   DistanceMatrix                  (not in the reference) the rows FastaAligned would return, compared pairwise on the device (K10)
+//   NearestNeighbours               (not in the reference) the rows of the whole database closest to one query sequence (K11)
 #include <algorithm>
+#include <tuple>
 #include <type_traits>
 #include <unordered_map>
 
@@ -701,6 +703,193 @@ std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json) {
       max_distance = json["maxDistance"].as_uint32();
    }
    return std::make_unique<DistanceMatrix>(std::move(sequence_name), max_distance);
+}
+
+// ---- NearestNeighbours -----------------------------------------------------------------------------------
+// The rows of the whole database nearest to one query, from the per-row pass over the store's layout and the selection on the
+// device (K11), with its parser.  No counterpart in the reference.
+namespace {
+
+/// The row of a partition whose primary key is `key`, read off the host copy of the column.
+std::optional<uint32_t> rowOfKey(const MetadataColumnPartition& column, const json::Value& key) {
+   if (column.isStringLike()) {
+      CHECK_SILO_QUERY(key.is_string(), "NearestNeighbours action: the primary key column holds strings, primaryKey is " + key.dump())
+      const std::optional<uint32_t> id = column.lookupId(key.as_string());
+      if (!id.has_value()) {
+         return std::nullopt;
+      }
+      const auto found = std::find(column.words.begin(), column.words.end(), *id);
+      return found == column.words.end() ? std::nullopt : std::optional<uint32_t>(static_cast<uint32_t>(found - column.words.begin()));
+   }
+   CHECK_SILO_QUERY(column.type == config::ColumnType::INT, "NearestNeighbours action: the primary key column is neither a string nor an int column")
+   CHECK_SILO_QUERY(
+      key.is_number_integer() && key.as_int64() > INT32_MIN && key.as_int64() <= INT32_MAX,
+      "NearestNeighbours action: the primary key column holds integers, primaryKey is " + key.dump()
+   )
+   const auto found = std::find(column.ints.begin(), column.ints.end(), static_cast<int32_t>(key.as_int64()));
+   return found == column.ints.end() ? std::nullopt : std::optional<uint32_t>(static_cast<uint32_t>(found - column.ints.begin()));
+}
+
+}  // namespace
+
+void NearestNeighbours::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"primaryKey", "distance", "comparedPositions"});
+}
+
+QueryResult NearestNeighbours::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+   const bool is_amino_acid = database.nuc_sequences.count(name) == 0;
+   CHECK_SILO_QUERY(!is_amino_acid || database.aa_sequences.count(name) != 0, "Database does not contain a sequence with name: '" + name + "'")
+   requireUnsharded(database, "NearestNeighbours");
+   const size_t positions = is_amino_acid ? database.aa_sequences.at(name).reference_sequence.size() : database.nuc_sequences.at(name).reference_sequence.size();
+   const auto seqstoreOf = [&](const DatabasePartition& partition) {
+      return is_amino_acid ? partition.aa_sequences.at(name).seqstore_id : partition.nuc_sequences.at(name).seqstore_id;
+   };
+   const std::string& primary_key_column = database.database_config.primary_key;
+
+   struct Hit {
+      uint32_t distance;
+      size_t partition;
+      uint32_t row;
+      uint32_t compared;
+   };
+   std::vector<Hit> hits;
+   {
+      // nothing in here returns to the pool before the stream has been waited for: the launches read it
+      std::vector<DeviceBuffer> live;
+      try {
+         // the query's characters: the literal string, or the row of that key gathered from its partition (and left out there)
+         std::string query;
+         size_t own_partition = SIZE_MAX;
+         uint32_t own_row = UINT32_MAX;
+         if (sequence.has_value()) {
+            CHECK_SILO_QUERY(
+               sequence->size() == positions, "NearestNeighbours action: the field sequence has " + std::to_string(sequence->size()) +
+                                                 " characters, the sequence '" + name + "' has " + std::to_string(positions)
+            )
+            query = *sequence;
+         } else {
+            for (size_t partition_id = 0; partition_id < database.partitions.size() && own_partition == SIZE_MAX; ++partition_id) {
+               const DatabasePartition& partition = database.partitions[partition_id];
+               if (partition.sequence_count == 0) {
+                  continue;
+               }
+               if (const std::optional<uint32_t> row = rowOfKey(columnOf(partition, primary_key_column), *primary_key); row.has_value()) {
+                  own_partition = partition_id;
+                  own_row = *row;
+               }
+            }
+            CHECK_SILO_QUERY(own_partition != SIZE_MAX, "NearestNeighbours action: no sequence has the primary key " + primary_key->dump())
+            query.resize(positions);
+            if (positions != 0) {
+               const DatabasePartition& partition = database.partitions[own_partition];
+               auto* device_row = live.emplace_back(partition.pool.acquire(sizeof(uint32_t))).as<uint32_t>();
+               checkGpu(silo_gpu_memcpy_h2d(device_row, &own_row, sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
+               auto* device_chars = live.emplace_back(partition.pool.acquire(positions)).as<char>();
+               checkGpu(
+                  silo_gpu_reconstruct_sequences(partition.store, seqstoreOf(partition), device_row, 1, device_chars, queryStream()),
+                  "silo_gpu_reconstruct_sequences"
+               );
+               checkGpu(silo_gpu_memcpy_d2h(query.data(), device_chars, positions, queryStream()), "silo_gpu_memcpy_d2h");
+            }
+         }
+
+         const size_t list_words = static_cast<size_t>(neighbours) * 3u + 1u;  // the list, then its length
+         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+            const DatabasePartition& partition = database.partitions[partition_id];
+            const OperatorResult& filter = bitmap_filter[partition_id];
+            const uint32_t selected = partition.sequence_count == 0 ? 0 : filter.cardinality();
+            if (selected == 0) {
+               continue;
+            }
+            // a filter that selects every row is passed as NULL (no all-ones bitset is made for it)
+            const uint64_t* filter_bits = selected == partition.sequence_count ? nullptr : filter.bitset();
+            auto* table = live.emplace_back(partition.pool.acquire(static_cast<size_t>(partition.rowWords()) * 64u * 2u * sizeof(uint32_t))).as<uint32_t>();
+            void* table_scratch = live.emplace_back(partition.pool.acquire(SILO_GPU_QUERY_DISTANCE_SCRATCH_BYTES(positions))).get();
+            void* select_scratch = live.emplace_back(partition.pool.acquire(SILO_GPU_NEAREST_ROWS_SCRATCH_BYTES)).get();
+            auto* list = live.emplace_back(partition.pool.acquire(list_words * sizeof(uint32_t))).as<uint32_t>();
+            checkGpu(
+               silo_gpu_query_distances(partition.store, seqstoreOf(partition), query.data(), table, table_scratch, queryStream()),
+               "silo_gpu_query_distances"
+            );
+            checkGpu(
+               silo_gpu_nearest_rows(
+                  table, filter_bits, partition.sequence_count, partition_id == own_partition ? own_row : UINT32_MAX, max_distance.value_or(UINT32_MAX),
+                  neighbours, list, list + list_words - 1u, select_scratch, queryStream()
+               ),
+               "silo_gpu_nearest_rows"
+            );
+            HostFetch fetch(list, list_words * sizeof(uint32_t), queryStream());
+            const auto* host = static_cast<const uint32_t*>(fetch.wait());
+            const uint32_t count = std::min(host[list_words - 1u], neighbours);
+            for (uint32_t i = 0; i < count; ++i) {
+               hits.push_back({host[3u * i + 1u], partition_id, host[3u * i], host[3u * i + 2u]});
+            }
+         }
+         // the copies were the last things enqueued, but say it: nothing of this query runs any more when its buffers go back
+         checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+      } catch (...) {
+         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+         (void)silo_gpu_stream_synchronize(queryStream());
+         throw;
+      }
+   }
+
+   // every partition's list is ascending by (distance, row): the merge order is (distance, partition, row)
+   std::sort(hits.begin(), hits.end(), [](const Hit& a, const Hit& b) {
+      return std::tie(a.distance, a.partition, a.row) < std::tie(b.distance, b.partition, b.row);
+   });
+   if (hits.size() > neighbours) {
+      hits.resize(neighbours);
+   }
+   QueryResult results;
+   results.query_result.reserve(hits.size());
+   for (const Hit& hit : hits) {
+      QueryResultEntry& entry = results.query_result.emplace_back();
+      entry.fields.emplace("primaryKey", columnOf(database.partitions[hit.partition], primary_key_column).jsonOfRow(hit.row));
+      entry.fields.emplace("distance", static_cast<int32_t>(hit.distance));
+      entry.fields.emplace("comparedPositions", static_cast<int32_t>(hit.compared));
+   }
+   return results;
+}
+
+std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json) {
+   std::optional<std::string> sequence_name;
+   if (json.contains("sequenceName")) {
+      CHECK_SILO_QUERY(json["sequenceName"].is_string(), "NearestNeighbours action: the field sequenceName, if present, must be of type string")
+      sequence_name = json["sequenceName"].as_string();
+   }
+   CHECK_SILO_QUERY(
+      json.contains("primaryKey") != json.contains("sequence"), "NearestNeighbours action: exactly one of the fields primaryKey and sequence must be given"
+   )
+   std::optional<json::Value> primary_key;
+   std::optional<std::string> sequence;
+   if (json.contains("primaryKey")) {
+      CHECK_SILO_QUERY(
+         json["primaryKey"].is_string() || json["primaryKey"].is_number_integer(), "NearestNeighbours action: the field primaryKey must be a string or an integer"
+      )
+      primary_key = json["primaryKey"];
+   } else {
+      CHECK_SILO_QUERY(json["sequence"].is_string(), "NearestNeighbours action: the field sequence must be of type string")
+      sequence = json["sequence"].as_string();
+   }
+   uint32_t neighbours = NearestNeighbours::DEFAULT_NEIGHBOURS;
+   if (json.contains("neighbours")) {
+      CHECK_SILO_QUERY(
+         json["neighbours"].is_number_unsigned() && json["neighbours"].as_int64() >= 1 && json["neighbours"].as_int64() <= NearestNeighbours::NEIGHBOUR_LIMIT,
+         "NearestNeighbours action: the field neighbours, if present, must be an integer from 1 to " + std::to_string(NearestNeighbours::NEIGHBOUR_LIMIT)
+      )
+      neighbours = json["neighbours"].as_uint32();
+   }
+   std::optional<uint32_t> max_distance;
+   if (json.contains("maxDistance")) {
+      CHECK_SILO_QUERY(
+         json["maxDistance"].is_number_unsigned() && json["maxDistance"].as_int64() <= INT32_MAX,
+         "NearestNeighbours action: the field maxDistance, if present, must be a non-negative integer"
+      )
+      max_distance = json["maxDistance"].as_uint32();
+   }
+   return std::make_unique<NearestNeighbours>(std::move(sequence_name), std::move(primary_key), std::move(sequence), neighbours, max_distance);
 }
 
 }  // namespace silo::query_engine::actions

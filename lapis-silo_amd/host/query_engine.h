@@ -625,6 +625,8 @@ std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json);
 std::unique_ptr<Action> parseCrossTabulation(const json::Value& json);
 /// The parser of DistanceMatrix (metadata_actions.cpp).
 std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json);
+/// The parser of NearestNeighbours (metadata_actions.cpp).
+std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json);
 
 /// Refuses a sharded database on behalf of an action whose counts are not all-reduced across ranks (table_actions.cpp).
 void requireUnsharded(const Database& database, const std::string& action_name);
@@ -706,6 +708,34 @@ class DistanceMatrix : public Action {
    static constexpr uint32_t SEQUENCE_LIMIT = SILO_GPU_MAX_DISTANCE_ROWS;
    DistanceMatrix(std::optional<std::string> sequence_name, std::optional<uint32_t> max_distance)
        : sequence_name(std::move(sequence_name)), max_distance(max_distance) {}
+};
+
+/// NearestNeighbours (metadata_actions.cpp): the `neighbours` rows of the WHOLE database closest to one query sequence — a row named
+/// by its primary key (then left out of its own list) or a literal aligned string — by DistanceMatrix's distance on one aligned
+/// sequence, among the rows the filter selects and, with maxDistance, at most that far away.  Per partition one
+/// silo_gpu_query_distances (every row's distance and compared positions read off the store's layout, K11) and one
+/// silo_gpu_nearest_rows (the k smallest on the device); the partitions' lists are merged by (distance, partition, row).
+class NearestNeighbours : public Action {
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   std::optional<json::Value> primary_key;    // exactly one of the two
+   std::optional<std::string> sequence;
+   uint32_t neighbours;
+   std::optional<uint32_t> max_distance;
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+
+  public:
+   static constexpr uint32_t NEIGHBOUR_LIMIT = SILO_GPU_MAX_NEAREST_ROWS;
+   static constexpr uint32_t DEFAULT_NEIGHBOURS = 10;
+   NearestNeighbours(
+      std::optional<std::string> sequence_name, std::optional<json::Value> primary_key, std::optional<std::string> sequence, uint32_t neighbours,
+      std::optional<uint32_t> max_distance
+   )
+       : sequence_name(std::move(sequence_name)),
+         primary_key(std::move(primary_key)),
+         sequence(std::move(sequence)),
+         neighbours(neighbours),
+         max_distance(max_distance) {}
 };
 
 template <typename SymbolType>

@@ -111,6 +111,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules", "silo_gpu_store_scan_prunable_rows",
     "silo_gpu_filters_grouped", "silo_gpu_filters_cross",
     "silo_gpu_distance_pack", "silo_gpu_distance_pairs",
+    "silo_gpu_query_distances", "silo_gpu_nearest_rows",
 ]
 
 _lib = None
@@ -178,6 +179,8 @@ def load_library():
                                            ctypes.c_uint32, ctypes.c_uint32, vp]
     lib.silo_gpu_distance_pack.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_distance_pairs.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_query_distances.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
+    lib.silo_gpu_nearest_rows.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -523,6 +526,52 @@ def distance_pairs(alphabet_id, planes_ptr, n_rows, positions, fill=None, stream
         return device_read(out, np.uint32, cells, stream).reshape(n_rows, n_rows, 2)
     finally:
         device_free(out)
+
+
+MAX_NEAREST_ROWS = 1024              # SILO_GPU_MAX_NEAREST_ROWS
+NEAREST_ROWS_SCRATCH_BYTES = 32768   # SILO_GPU_NEAREST_ROWS_SCRATCH_BYTES
+QUERY_DISTANCE_COUNTER_PLANES = 12   # SILO_GPU_QUERY_DISTANCE_COUNTER_PLANES: a vertical counter of K11 is unpacked after 2^12 - 1 adds
+NO_ROW = 0xFFFFFFFF                  # exclude_row / max_distance of silo_gpu_nearest_rows: none
+
+
+def query_distance_scratch_bytes(positions):
+    """SILO_GPU_QUERY_DISTANCE_SCRATCH_BYTES: the scratch silo_gpu_query_distances needs."""
+    return (positions // 256 + 1) * 256 + 2 * (((positions + 1) * 4) // 256 + 1) * 256
+
+
+def nearest_rows_call(table_ptr, filter_ptr, sequence_count, exclude_row, max_distance, k, out_ptr, count_ptr, scratch_ptr, stream=None):
+    """silo_gpu_nearest_rows (K11) on the caller's device buffers, waited for."""
+    lib = load_library()
+    _check(lib.silo_gpu_nearest_rows(table_ptr, filter_ptr, sequence_count, exclude_row, max_distance, k, out_ptr, count_ptr, scratch_ptr, stream))
+    _check(lib.silo_gpu_stream_synchronize(stream))
+
+
+def nearest_rows(table, filter_words, sequence_count, k, exclude_row=NO_ROW, max_distance=NO_ROW, fill=None, stream=None):
+    """silo_gpu_nearest_rows (K11) over a host table uint32 [rows][2] (distance, compared) as silo_gpu_query_distances leaves it.
+    filter_words: uint64 row bitset, None = all rows.  Returns (count, list): list uint32 [k][3] = row, distance, compared, of
+    which the first `count` entries were written; the others hold the byte `fill` repeated (the list is filled with it before the
+    launch), or whatever the allocation held."""
+    lib = load_library()
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    k_cells = max(int(k), 1) * 3
+    table_dev = device_malloc(table.nbytes)
+    filter_dev = None
+    out = device_malloc(k_cells * 4, fill, stream)
+    count = device_malloc(4, fill, stream)
+    scratch = device_malloc(NEAREST_ROWS_SCRATCH_BYTES, fill, stream)
+    try:
+        if table.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(table_dev, _ptr(table), table.nbytes, stream))
+        if filter_words is not None:
+            filter_words = np.ascontiguousarray(filter_words, dtype=np.uint64)
+            filter_dev = device_malloc(filter_words.nbytes)
+            _check(lib.silo_gpu_memcpy_h2d(filter_dev, _ptr(filter_words), filter_words.nbytes, stream))
+        nearest_rows_call(table_dev, filter_dev, sequence_count, exclude_row, max_distance, k, out, count, scratch, stream)
+        return int(device_read(count, np.uint32, 1, stream)[0]), device_read(out, np.uint32, k_cells, stream).reshape(-1, 3)
+    finally:
+        for ptr in (table_dev, filter_dev, out, count, scratch):
+            if ptr is not None:
+                device_free(ptr)
 
 
 class GpuStore:
@@ -927,6 +976,35 @@ class GpuStore:
                                                    cols, None if col_index is None else _ptr(col_index), n_cols, scratch, table, out_rows, out_cols, stream)
 
         return self._count_table_call(launch, (out_rows, out_cols), filters_cross_scratch_bytes(n_rows, n_cols), out_ptr, stream, scratch_ptr)
+
+    def query_distances(self, seqstore_id, query, fill=None, stream=None, out_ptr=None, scratch_ptr=_OWN_SCRATCH):
+        """silo_gpu_query_distances (K11).  query: the aligned query as bytes / uint8 [P] (None = a null pointer).  Without out_ptr:
+        a table for the call — filled with the byte `fill` before the launch, so a test can see that every cell is written —
+        returned as uint32 [row_words * 64][2] (distance, compared).  With out_ptr: writes the caller's device table and returns
+        nothing.  scratch_ptr: the caller's scratch instead of one allocated for the call."""
+        if query is not None:
+            query = np.ascontiguousarray(np.frombuffer(query, dtype=np.uint8) if isinstance(query, (bytes, bytearray)) else query, dtype=np.uint8)
+        known = seqstore_id < len(self.references)
+        positions = len(self.references[seqstore_id]) if known else 0
+        if known and query is not None and len(query) != positions:
+            raise ValueError("the query has to be as long as the sequence store's reference")
+        cells = self.row_words * 64 * 2
+        own_scratch = scratch_ptr is _OWN_SCRATCH
+        scratch = self.malloc(query_distance_scratch_bytes(positions)) if own_scratch else scratch_ptr
+        table = out_ptr
+        try:
+            if out_ptr is None:
+                table = self.malloc(max(8, 4 * cells))
+                if fill is not None:
+                    self.memset(table, fill, max(8, 4 * cells), stream)
+            _check(self.lib.silo_gpu_query_distances(self.handle, seqstore_id, None if query is None else _ptr(query), table, scratch, stream))
+            self.synchronize(stream)
+            return self.read(table, np.uint32, cells, stream).reshape(-1, 2) if out_ptr is None else None
+        finally:
+            if own_scratch:
+                self.free(scratch)
+            if out_ptr is None and table is not None:
+                self.free(table)
 
     # ---- metadata columns (K5 / K6) and FastaAligned ---------------------------------------------
     VALUE_TYPES = {np.dtype(np.int32): 0, np.dtype(np.uint32): 1, np.dtype(np.float64): 2}
