@@ -115,7 +115,15 @@ int silo_gpu_store_append_sequences(
  * position is "no other symbol and not missing"), then silo_gpu_store_import_position per position; finalize as usual.
  * The containers are expanded on the device.  The Boost archive framing around the payloads is the caller's to strip: it is
  * not read here (nothing in this image to pin it against), and the portable format itself is restated from its published
- * specification — parity unpinned.  SILO_GPU_SYMBOL_NONE = no flipped / deleted symbol. */
+ * specification — parity unpinned.  SILO_GPU_SYMBOL_NONE = no flipped / deleted symbol.
+ * Two rules of silo_gpu_store_import_position, both refused with SILO_GPU_ERR_INVALID_ARGUMENT:
+ *   - a position takes ONE import.  A row has one symbol at a position: bitmaps of one call that share a row are refused, and so
+ *     is any further call for a position whose planes an earlier call has written, whatever symbols it names (scan symbols,
+ *     sparsely stored ambiguity codes and extra-plane symbols alike).  A call refused for its arguments or for a malformed first
+ *     payload has written nothing and may be repeated; after any other refusal the position's content is undefined.
+ *   - the flipped symbol's bitmap has to be among the payloads, EMPTY included: flipped, an empty bitmap stands for every row.
+ *     A flipped_symbol without a payload is refused rather than read as "no row" (the deleted symbol, by contrast, needs none).
+ * Ids at or past sequence_count inside a payload (positions at or past the store's, for the missing rows) are ignored. */
 typedef struct silo_gpu_roaring_payload {
    uint32_t symbol;    /* reference enum value; ignored by silo_gpu_store_import_missing_rows */
    const void* bytes;  /* portable-format roaring bitmap, host memory */

@@ -369,6 +369,23 @@ int silo_gpu_store_import_position(
    if (const int rc = ensureBuildPlanes(store, seqstore); rc != SILO_GPU_OK) {
       return rc;
    }
+   // a row has ONE symbol at a position.  Within a call the union of the rows seen so far (d_import_union) finds a second claim;
+   // across calls nothing on the device does for a sparsely stored or extra-plane symbol (their rows are no code bits), so the
+   // host keeps the record: a position whose planes an import has touched takes no second import, whatever the symbols
+   if (position < seqstore.imported_positions.size() && seqstore.imported_positions[position] != 0) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_store_import_position: the position was imported before (a second import would overlap the first)");
+   }
+   // a flipped bitmap that is EMPTY means every row: it has to be among the payloads, a caller that drops empty bitmaps would
+   // otherwise get a position where the symbol has no row at all
+   if (flipped_symbol != SILO_GPU_SYMBOL_NONE && flipped_symbol != deleted_symbol) {
+      bool present = false;
+      for (uint32_t k = 0; k < n_bitmaps; ++k) {
+         present = present || bitmaps[k].symbol == flipped_symbol;
+      }
+      if (!present) {
+         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_store_import_position: the flipped symbol has no bitmap among the payloads (an empty flipped bitmap stands for every row and has to be passed)");
+      }
+   }
    seqstore.finalized = false;
    seqstore.totals_ready = false;
    const size_t row_bytes = static_cast<size_t>(store->row_words) * sizeof(uint64_t);
@@ -387,6 +404,8 @@ int silo_gpu_store_import_position(
             return rc;
          }
       }
+      seqstore.imported_positions.resize(dev.positions, 0);
+      seqstore.imported_positions[position] = 1;  // the first launch that writes the planes of the position: it has had its import
       k_merge_symbol_row<<<blocks, 256>>>(
          seqstore.dev, position, symbol, store->d_import_row, store->d_import_union, seqstore.d_sparse, seqstore.d_sparse_count, seqstore.sparse_capacity,
          store->d_error_flag

@@ -1966,6 +1966,7 @@ int finishLayout(silo_gpu_store* store, SeqStoreHost& seqstore, SeqStoreHost::La
       (void)hipFree(dev.scan);
       dev.scan = nullptr;
       store->device_bytes -= build_bytes;
+      std::vector<uint8_t>().swap(seqstore.imported_positions);
    }
    layout.planes = work.d_planes;
    layout.d_row_of = work.d_row_of;

@@ -248,6 +248,9 @@ struct SeqStoreHost {
    // rows that received a sequence (append / generate; an import counts none: its bitmaps may leave rows without a symbol).  Only
    // a store whose every row has a symbol at every position may derive a symbol as "the rest" (LAYOUT_IMPLICIT).
    uint64_t rows_filled = 0;
+   // positions whose build-time planes silo_gpu_store_import_position has written: each takes one import (empty until the first
+   // import, cleared where the build-time planes are released)
+   std::vector<uint8_t> imported_positions;
    // counts of the unfiltered store, [positions][n_scan]: what the reference reads from stored
    // cardinalities for a full filter (mutations.cpp:98-136); computed by one scan on first use
    uint32_t* d_totals = nullptr;
