@@ -597,7 +597,16 @@ int silo_gpu_distance_pairs(int alphabet, const uint64_t* planes_dev, uint32_t n
  * the same arguments give the same output.  scratch_dev: SILO_GPU_NEAREST_ROWS_SCRATCH_BYTES bytes, 16-byte aligned.  Launches on
  * `stream` and returns without waiting.
  * Both fail with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL store, query, table, output or scratch, a seqstore_id
- * out of range, a store or table without rows, k == 0 or k > SILO_GPU_MAX_NEAREST_ROWS. */
+ * out of range, a store or table without rows, k == 0 or k > SILO_GPU_MAX_NEAREST_ROWS.
+ * silo_gpu_bitset_from_distances takes such a table of row_words * 64 rows (no store either) and WRITES every one of the row_words
+ * words of out_bitset_dev — the caller never clears it, nothing past row_words is touched:
+ *     bit r = r < sequence_count && distance[r] <= max_distance && compared[r] >= min_compared
+ * max_distance == UINT32_MAX: no bound on the distance; min_compared == 0: none on the compared positions.  Rows at or past
+ * sequence_count are 0 whatever the table holds there (the filter kernels and the derived-symbol count rely on clean padding).
+ * This is the leaf of the filter expression WithinDistance: the 8 bytes per row of the table never leave the device.  One launch
+ * on `stream` (a thread per row, one 8-byte load each, a wave's ballot is a word; no atomics: the same arguments give the same
+ * words), returns without waiting.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL table or output,
+ * row_words == 0, sequence_count == 0 or sequence_count > row_words * 64. */
 #define SILO_GPU_MAX_NEAREST_ROWS 1024
 #define SILO_GPU_QUERY_DISTANCE_COUNTER_PLANES 12 /* a vertical counter is unpacked after 2^12 - 1 adds */
 #define SILO_GPU_QUERY_DISTANCE_SCRATCH_BYTES(positions)                                                                    \
@@ -609,6 +618,10 @@ int silo_gpu_query_distances(
 int silo_gpu_nearest_rows(
    const uint32_t* table_dev, const uint64_t* filter_dev, uint32_t sequence_count, uint32_t exclude_row, uint32_t max_distance, uint32_t k,
    uint32_t* out_dev, uint32_t* out_count_dev, void* scratch_dev, void* stream
+);
+int silo_gpu_bitset_from_distances(
+   const uint32_t* table_dev, uint32_t sequence_count, uint32_t row_words, uint32_t max_distance, uint32_t min_compared, uint64_t* out_bitset_dev,
+   void* stream
 );
 
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to

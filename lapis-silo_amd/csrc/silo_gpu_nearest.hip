@@ -16,6 +16,9 @@
 // the rows at or below it are exactly the answer, ties at the k-th distance broken by the lowest row ids:
 //   k_nearest_compact     appends them in any order
 //   k_nearest_finish      one block sorts the <= SILO_GPU_MAX_NEAREST_ROWS keys and writes the list
+// silo_gpu_bitset_from_distances: the rows of such a table within a distance of the query, as a row bitset (the filter expression
+// WithinDistance):
+//   k_bitset_from_distances  a thread per row, a wave's ballot per word
 #include <algorithm>
 #include <cstring>
 
@@ -434,9 +437,52 @@ __global__ __launch_bounds__(FINISH_THREADS) void k_nearest_finish(const SelectA
    }
 }
 
+// ---- the rows within a distance -------------------------------------------------------------------------
+constexpr uint32_t BITSET_THREADS = 256;  // four waves, four output words
+static_assert(BITSET_THREADS % 64u == 0);
+
+/// A thread per row of the table, a wave per word of the bitset: one 8-byte load per lane (a wave reads 512 consecutive bytes), the
+/// wave's ballot of the predicate is the word, stored by its first lane.  A wave whose word is at or past row_words neither loads
+/// nor stores (the grid is rounded up to whole blocks); rows at or past sequence_count give 0 whatever their cell holds.
+__global__ __launch_bounds__(BITSET_THREADS) void k_bitset_from_distances(
+   const uint2* __restrict__ table, uint32_t sequence_count, uint32_t row_words, uint32_t max_distance, uint32_t min_compared,
+   uint64_t* __restrict__ out
+) {
+   const size_t row = static_cast<size_t>(blockIdx.x) * BITSET_THREADS + threadIdx.x;
+   const size_t word = row >> 6;  // (uniform over the wave)
+   if (word >= row_words) {
+      return;
+   }
+   const uint2 cell = table[row];  // .x = distance, .y = compared
+   const bool selected = row < sequence_count && cell.x <= max_distance && cell.y >= min_compared;
+   const uint64_t bits = __ballot(selected);
+   if ((threadIdx.x & 63u) == 0) {
+      out[word] = bits;
+   }
+}
+
 }  // namespace
 
 extern "C" {
+
+int silo_gpu_bitset_from_distances(
+   const uint32_t* table_dev, uint32_t sequence_count, uint32_t row_words, uint32_t max_distance, uint32_t min_compared, uint64_t* out_bitset_dev,
+   void* stream
+) {
+   if (table_dev == nullptr || out_bitset_dev == nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_bitset_from_distances: bad arguments");
+   }
+   if (row_words == 0 || sequence_count == 0 || sequence_count > static_cast<uint64_t>(row_words) * 64u) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_bitset_from_distances: the table has no rows, or fewer than sequence_count");
+   }
+   constexpr uint32_t WORDS_PER_BLOCK = BITSET_THREADS / 64u;
+   const uint32_t blocks = row_words / WORDS_PER_BLOCK + (row_words % WORDS_PER_BLOCK != 0 ? 1u : 0u);
+   k_bitset_from_distances<<<blocks, BITSET_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+      reinterpret_cast<const uint2*>(table_dev), sequence_count, row_words, max_distance, min_compared, out_bitset_dev
+   );
+   HIP_TRY(hipGetLastError());
+   return SILO_GPU_OK;
+}
 
 int silo_gpu_query_distances(
    const silo_gpu_store* store, uint32_t seqstore_id, const char* query_chars, uint32_t* out_dev, void* scratch_dev, void* stream

@@ -853,6 +853,86 @@ std::unique_ptr<Expression> parseInsertionContains(const json::Value& json) {  /
 
 }  // namespace
 
+// ---- WithinDistance (no counterpart in the reference) ---------------------------------------------------
+std::string WithinDistance::toString(const Database& /*database*/) const {
+   const std::string sequence_string = sequence_name.has_value() ? "The sequence '" + sequence_name.value() + "'" : "The default nucleotide sequence";
+   const std::string query_string = primary_key.has_value() ? "the sequence with the primary key " + primary_key->dump() : "a literal sequence";
+   return sequence_string + " is within distance " + std::to_string(max_distance) + " of " + query_string + " (compared positions >= " +
+          std::to_string(min_compared_positions) + ")";
+}
+
+std::unique_ptr<Operator> WithinDistance::compile(const Database& database, const DatabasePartition& database_partition, AmbiguityMode /*mode*/) const {
+   // distance and compared are exact numbers of the stored symbols: there is no upper or lower bound of them to take
+   const RowSpace rows = rowsOf(database_partition);
+   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+   const bool is_amino_acid = database.nuc_sequences.count(name) == 0;
+   CHECK_SILO_QUERY(
+      !is_amino_acid || database.aa_sequences.count(name) != 0,
+      "WithinDistance: the field sequenceName: Database does not contain a sequence with name: '" + name + "'"
+   )
+   CHECK_SILO_QUERY(
+      database.shard_world <= 1, "WithinDistance is not supported on a sharded database yet: the table of distances of a position shard is partial, "
+                                 "and the row of a primary key may live on another rank"
+   )
+   // resolved for every partition compiled (the parsed expression is kept by query text, whatever the database holds): a lookup in the
+   // host copy of the key column and a gather of one row per partition of the database
+   const actions::QuerySequence query = actions::resolveQuerySequence(database, name, is_amino_acid, primary_key, sequence, "WithinDistance");
+   if (database_partition.sequence_count == 0) {
+      return std::make_unique<operators::Empty>(rows);
+   }
+   if (query.characters.empty()) {  // a sequence without positions: every row is at distance 0 with nothing compared
+      if (min_compared_positions == 0) {
+         return std::make_unique<operators::Full>(rows);
+      }
+      return std::make_unique<operators::Empty>(rows);
+   }
+   const uint32_t seqstore_id = is_amino_acid ? database_partition.aa_sequences.at(name).seqstore_id : database_partition.nuc_sequences.at(name).seqstore_id;
+   return std::make_unique<operators::DistanceSelection>(seqstore_id, query.characters, max_distance, min_compared_positions, rows);
+}
+
+namespace {
+
+std::unique_ptr<Expression> parseWithinDistance(const json::Value& json) {
+   std::optional<std::string> sequence_name;
+   if (json.contains("sequenceName")) {
+      CHECK_SILO_QUERY(json["sequenceName"].is_string(), "The field 'sequenceName' in a WithinDistance expression, if present, needs to be a string")
+      sequence_name = json["sequenceName"].as_string();
+   }
+   CHECK_SILO_QUERY(
+      json.contains("primaryKey") != json.contains("sequence"), "Exactly one of the fields 'primaryKey' and 'sequence' is required in a WithinDistance expression"
+   )
+   std::optional<json::Value> primary_key;
+   std::optional<std::string> sequence;
+   if (json.contains("primaryKey")) {
+      CHECK_SILO_QUERY(
+         json["primaryKey"].is_string() || json["primaryKey"].is_number_integer(),
+         "The field 'primaryKey' in a WithinDistance expression needs to be a string or an integer"
+      )
+      primary_key = json["primaryKey"];
+   } else {
+      CHECK_SILO_QUERY(json["sequence"].is_string(), "The field 'sequence' in a WithinDistance expression needs to be a string")
+      sequence = json["sequence"].as_string();
+   }
+   CHECK_SILO_QUERY(json.contains("maxDistance"), "The field 'maxDistance' is required in a WithinDistance expression")
+   CHECK_SILO_QUERY(
+      json["maxDistance"].is_number_unsigned() && json["maxDistance"].as_int64() <= INT32_MAX,
+      "The field 'maxDistance' in a WithinDistance expression needs to be a non-negative integer"
+   )
+   uint32_t min_compared_positions = 0;
+   if (json.contains("minComparedPositions")) {
+      CHECK_SILO_QUERY(
+         json["minComparedPositions"].is_number_unsigned() && json["minComparedPositions"].as_int64() <= INT32_MAX,
+         "The field 'minComparedPositions' in a WithinDistance expression, if present, needs to be a non-negative integer"
+      )
+      min_compared_positions = json["minComparedPositions"].as_uint32();
+   }
+   return std::make_unique<WithinDistance>(
+      std::move(sequence_name), std::move(primary_key), std::move(sequence), json["maxDistance"].as_uint32(), min_compared_positions
+   );
+}
+
+}  // namespace
+
 // ---- JSON -> Expression (the from_json functions) ------------------------------------------------------
 namespace {
 
@@ -1083,6 +1163,9 @@ std::unique_ptr<Expression> parseExpression(const json::Value& json) {  // expre
    }
    if (expression_type == "AminoAcidInsertionContains") {
       return parseInsertionContains<AminoAcid>(json);
+   }
+   if (expression_type == "WithinDistance") {
+      return parseWithinDistance(json);
    }
    throw QueryParseException("Unknown object filter type '" + expression_type + "'");
 }

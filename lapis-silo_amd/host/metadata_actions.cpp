@@ -710,10 +710,10 @@ std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json) {
 // device (K11), with its parser.  No counterpart in the reference.
 namespace {
 
-/// The row of a partition whose primary key is `key`, read off the host copy of the column.
-std::optional<uint32_t> rowOfKey(const MetadataColumnPartition& column, const json::Value& key) {
+/// The row of a partition whose primary key is `key`, read off the host copy of the column.  `what`: who asks, for the messages.
+std::optional<uint32_t> rowOfKey(const MetadataColumnPartition& column, const json::Value& key, const std::string& what) {
    if (column.isStringLike()) {
-      CHECK_SILO_QUERY(key.is_string(), "NearestNeighbours action: the primary key column holds strings, primaryKey is " + key.dump())
+      CHECK_SILO_QUERY(key.is_string(), what + ": the primary key column holds strings, primaryKey is " + key.dump())
       const std::optional<uint32_t> id = column.lookupId(key.as_string());
       if (!id.has_value()) {
          return std::nullopt;
@@ -721,16 +721,64 @@ std::optional<uint32_t> rowOfKey(const MetadataColumnPartition& column, const js
       const auto found = std::find(column.words.begin(), column.words.end(), *id);
       return found == column.words.end() ? std::nullopt : std::optional<uint32_t>(static_cast<uint32_t>(found - column.words.begin()));
    }
-   CHECK_SILO_QUERY(column.type == config::ColumnType::INT, "NearestNeighbours action: the primary key column is neither a string nor an int column")
+   CHECK_SILO_QUERY(column.type == config::ColumnType::INT, what + ": the primary key column is neither a string nor an int column")
    CHECK_SILO_QUERY(
       key.is_number_integer() && key.as_int64() > INT32_MIN && key.as_int64() <= INT32_MAX,
-      "NearestNeighbours action: the primary key column holds integers, primaryKey is " + key.dump()
+      what + ": the primary key column holds integers, primaryKey is " + key.dump()
    )
    const auto found = std::find(column.ints.begin(), column.ints.end(), static_cast<int32_t>(key.as_int64()));
    return found == column.ints.end() ? std::nullopt : std::optional<uint32_t>(static_cast<uint32_t>(found - column.ints.begin()));
 }
 
 }  // namespace
+
+QuerySequence resolveQuerySequence(
+   const Database& database, const std::string& name, bool is_amino_acid, const std::optional<json::Value>& primary_key,
+   const std::optional<std::string>& sequence, const std::string& what
+) {
+   const size_t positions = is_amino_acid ? database.aa_sequences.at(name).reference_sequence.size() : database.nuc_sequences.at(name).reference_sequence.size();
+   QuerySequence query;
+   if (sequence.has_value()) {
+      CHECK_SILO_QUERY(
+         sequence->size() == positions, what + ": the field sequence has " + std::to_string(sequence->size()) + " characters, the sequence '" + name +
+                                           "' has " + std::to_string(positions)
+      )
+      query.characters = *sequence;
+      return query;
+   }
+   const std::string& primary_key_column = database.database_config.primary_key;
+   for (size_t partition_id = 0; partition_id < database.partitions.size() && query.own_partition == SIZE_MAX; ++partition_id) {
+      const DatabasePartition& partition = database.partitions[partition_id];
+      if (partition.sequence_count == 0) {
+         continue;
+      }
+      if (const std::optional<uint32_t> row = rowOfKey(columnOf(partition, primary_key_column), *primary_key, what); row.has_value()) {
+         query.own_partition = partition_id;
+         query.own_row = *row;
+      }
+   }
+   CHECK_SILO_QUERY(query.own_partition != SIZE_MAX, what + ": no sequence has the primary key " + primary_key->dump())
+   query.characters.resize(positions);
+   if (positions != 0) {
+      const DatabasePartition& partition = database.partitions[query.own_partition];
+      const uint32_t seqstore_id = is_amino_acid ? partition.aa_sequences.at(name).seqstore_id : partition.nuc_sequences.at(name).seqstore_id;
+      // the two buffers return to the pool when the gather has been waited for: the copy to the host is synchronous
+      DeviceBuffer device_row = partition.pool.acquire(sizeof(uint32_t));
+      DeviceBuffer device_chars = partition.pool.acquire(positions);
+      try {
+         checkGpu(silo_gpu_memcpy_h2d(device_row.get(), &query.own_row, sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
+         checkGpu(
+            silo_gpu_reconstruct_sequences(partition.store, seqstore_id, device_row.as<uint32_t>(), 1, device_chars.as<char>(), queryStream()),
+            "silo_gpu_reconstruct_sequences"
+         );
+         checkGpu(silo_gpu_memcpy_d2h(query.characters.data(), device_chars.get(), positions, queryStream()), "silo_gpu_memcpy_d2h");
+      } catch (...) {
+         (void)silo_gpu_stream_synchronize(queryStream());  // the gather may be in flight
+         throw;
+      }
+   }
+   return query;
+}
 
 void NearestNeighbours::validateOrderByFields(const Database& /*database*/) const {
    checkOrderByFields({"primaryKey", "distance", "comparedPositions"});
@@ -759,40 +807,10 @@ QueryResult NearestNeighbours::execute(const Database& database, std::vector<Ope
       std::vector<DeviceBuffer> live;
       try {
          // the query's characters: the literal string, or the row of that key gathered from its partition (and left out there)
-         std::string query;
-         size_t own_partition = SIZE_MAX;
-         uint32_t own_row = UINT32_MAX;
-         if (sequence.has_value()) {
-            CHECK_SILO_QUERY(
-               sequence->size() == positions, "NearestNeighbours action: the field sequence has " + std::to_string(sequence->size()) +
-                                                 " characters, the sequence '" + name + "' has " + std::to_string(positions)
-            )
-            query = *sequence;
-         } else {
-            for (size_t partition_id = 0; partition_id < database.partitions.size() && own_partition == SIZE_MAX; ++partition_id) {
-               const DatabasePartition& partition = database.partitions[partition_id];
-               if (partition.sequence_count == 0) {
-                  continue;
-               }
-               if (const std::optional<uint32_t> row = rowOfKey(columnOf(partition, primary_key_column), *primary_key); row.has_value()) {
-                  own_partition = partition_id;
-                  own_row = *row;
-               }
-            }
-            CHECK_SILO_QUERY(own_partition != SIZE_MAX, "NearestNeighbours action: no sequence has the primary key " + primary_key->dump())
-            query.resize(positions);
-            if (positions != 0) {
-               const DatabasePartition& partition = database.partitions[own_partition];
-               auto* device_row = live.emplace_back(partition.pool.acquire(sizeof(uint32_t))).as<uint32_t>();
-               checkGpu(silo_gpu_memcpy_h2d(device_row, &own_row, sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
-               auto* device_chars = live.emplace_back(partition.pool.acquire(positions)).as<char>();
-               checkGpu(
-                  silo_gpu_reconstruct_sequences(partition.store, seqstoreOf(partition), device_row, 1, device_chars, queryStream()),
-                  "silo_gpu_reconstruct_sequences"
-               );
-               checkGpu(silo_gpu_memcpy_d2h(query.data(), device_chars, positions, queryStream()), "silo_gpu_memcpy_d2h");
-            }
-         }
+         const QuerySequence resolved = resolveQuerySequence(database, name, is_amino_acid, primary_key, sequence, "NearestNeighbours action");
+         const std::string& query = resolved.characters;
+         const size_t own_partition = resolved.own_partition;
+         const uint32_t own_row = resolved.own_row;
 
          const size_t list_words = static_cast<size_t>(neighbours) * 3u + 1u;  // the list, then its length
          for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {

@@ -258,6 +258,21 @@ const uint64_t* ProgramBuilder::sparsePointer(uint32_t seqstore_id, uint32_t pos
    return pointer;
 }
 
+void* ProgramBuilder::temporaryBuffer(size_t bytes) {
+   DeviceBuffer buffer = rows.partition->pool.acquire(bytes);
+   void* pointer = buffer.get();
+   temporaries.push_back(std::move(buffer));
+   buffer_stream = queryStream();
+   has_buffers = true;
+   return pointer;
+}
+
+ProgramBuilder::~ProgramBuilder() {
+   if (has_buffers) {
+      (void)silo_gpu_stream_synchronize(buffer_stream);
+   }
+}
+
 uint64_t* ProgramBuilder::temporaryBitset() {
    const DatabasePartition& partition = *rows.partition;
    DeviceBuffer buffer = partition.pool.acquire(static_cast<size_t>(partition.rowWords()) * sizeof(uint64_t));
@@ -305,6 +320,7 @@ void ProgramBuilder::run(uint32_t result_slot, uint64_t* out_bitset, uint64_t* o
    if (!temporaries.empty() || !materialized_children.empty()) {
       // temporaries go back to the pool when the builder dies: make sure the kernel is done with them
       checkGpu(silo_gpu_stream_synchronize(stream), "silo_gpu_stream_synchronize");
+      has_buffers = has_buffers && stream != buffer_stream;
    }
 }
 
@@ -328,6 +344,7 @@ uint32_t ProgramBuilder::runCounting(uint32_t result_slot, uint64_t* out_bitset,
    // the total arrives when the last block is done: every block has read its leaves by then, so the temporaries of
    // this builder may go back to the pool without a stream synchronisation
    checkGpu(silo_gpu_count_slot_wait(slot, &count, stream), "silo_gpu_count_slot_wait");
+   has_buffers = has_buffers && stream != buffer_stream;  // what wrote and read them ran ahead of the program on that stream
    return static_cast<uint32_t>(count);
 }
 
@@ -510,6 +527,32 @@ uint32_t BitmapProducer::lower(ProgramBuilder& builder) const {
          membership.data(), static_cast<uint32_t>(membership.size()), queryStream()
       ),
       "silo_gpu_bitset_from_pairs"
+   );
+   return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
+}
+
+// ---- DistanceSelection (no counterpart in the reference) -----------------------------------------------
+std::string DistanceSelection::toString() const {
+   return "DistanceSelection[<= " + std::to_string(max_distance) + ", compared >= " + std::to_string(min_compared) + "]";
+}
+std::unique_ptr<Operator> DistanceSelection::copy() const {
+   return std::make_unique<DistanceSelection>(seqstore_id, query, max_distance, min_compared, rows);
+}
+std::unique_ptr<Operator> DistanceSelection::negate() const {
+   return std::make_unique<Complement>(this->copy(), rows);
+}
+uint32_t DistanceSelection::lower(ProgramBuilder& builder) const {
+   // 8 bytes per row that never leave the device: the table is written by K11's first entry and read once by the kernel that
+   // makes the bitset, all on the query's stream ahead of the fused program; the three buffers live as long as the builder
+   const DatabasePartition& partition = *rows.partition;
+   const uint32_t row_words = partition.rowWords();
+   auto* table = static_cast<uint32_t*>(builder.temporaryBuffer(static_cast<size_t>(row_words) * 64u * 2u * sizeof(uint32_t)));
+   void* scratch = builder.temporaryBuffer(SILO_GPU_QUERY_DISTANCE_SCRATCH_BYTES(query.size()));
+   uint64_t* bitset = builder.temporaryBitset();
+   checkGpu(silo_gpu_query_distances(partition.store, seqstore_id, query.data(), table, scratch, queryStream()), "silo_gpu_query_distances");
+   checkGpu(
+      silo_gpu_bitset_from_distances(table, partition.sequence_count, row_words, max_distance, min_compared, bitset, queryStream()),
+      "silo_gpu_bitset_from_distances"
    );
    return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
 }

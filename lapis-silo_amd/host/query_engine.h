@@ -103,6 +103,11 @@ class OperatorResult {
 class ProgramBuilder {
   public:
    explicit ProgramBuilder(RowSpace rows) : rows(rows) {}
+   ProgramBuilder(const ProgramBuilder&) = delete;
+   ProgramBuilder& operator=(const ProgramBuilder&) = delete;
+   /// Waits for the stream that temporaryBuffer()s were handed out on, unless run() / runCounting() has: a lowering that throws half
+   /// way leaves launches in flight that read and write them.
+   ~ProgramBuilder();
 
    uint32_t allocSlot();
    uint32_t allocRun(uint32_t count);
@@ -115,6 +120,9 @@ class ProgramBuilder {
    const uint64_t* sparsePointer(uint32_t seqstore_id, uint32_t position, uint32_t symbol);
    /// A row bitset from the partition's pool that lives as long as this builder (filled by the caller before run()).
    uint64_t* temporaryBitset();
+   /// `bytes` of device memory from the partition's pool with the same lifetime, for a lowering whose launches on queryStream()
+   /// need more than a bitset (DistanceSelection: the table of distances and its scratch).  queuedDeviceWork() holds for it too.
+   void* temporaryBuffer(size_t bytes);
    /// Appends `columns` as consecutive leaves; returns the imm of an n-ary instruction (first | count << 16).
    uint32_t leafRun(const std::vector<const uint64_t*>& columns);
    /// Children that are stored columns (foldable by one n-ary instruction) vs composite sub-trees.
@@ -146,6 +154,8 @@ class ProgramBuilder {
    std::vector<const uint64_t*> leaves;
    std::vector<DeviceBuffer> temporaries;
    std::vector<OperatorResult> materialized_children;
+   void* buffer_stream = nullptr;  // the stream of temporaryBuffer()s nobody has waited for yet
+   bool has_buffers = false;
    uint32_t used_slots = 0;  // bit mask
    uint32_t high_water = 0;
 };
@@ -153,7 +163,7 @@ class ProgramBuilder {
 namespace operators {
 
 enum Type {
-   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER
+   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION
 };
 
 struct Cost {
@@ -345,6 +355,28 @@ class BitmapProducer : public Operator {
    std::vector<uint8_t> membership;  // per distinct insertion id of the index
 };
 
+/// The rows within a distance of one query sequence (the filter expression WithinDistance; no counterpart in the reference): a
+/// bitmap computed at evaluation time like BitmapProducer's.  lower() leaves (distance, compared) of every row of the partition in
+/// a pooled table (silo_gpu_query_distances, K11) and turns it into a row bitset on the device (silo_gpu_bitset_from_distances),
+/// both on the lowering thread's stream ahead of the fused program, which reads the bitset as a leaf.  The table, its scratch and
+/// the bitset belong to the builder: nothing returns to the pool before the stream has been waited for.
+class DistanceSelection : public Operator {
+  public:
+   DistanceSelection(uint32_t seqstore_id, std::string query, uint32_t max_distance, uint32_t min_compared, RowSpace rows)
+       : Operator(rows), seqstore_id(seqstore_id), query(std::move(query)), max_distance(max_distance), min_compared(min_compared) {}
+   Type type() const override { return DISTANCE_SELECTION; }
+   std::string toString() const override;
+   std::unique_ptr<Operator> copy() const override;
+   std::unique_ptr<Operator> negate() const override;
+   uint32_t lower(ProgramBuilder& builder) const override;
+   Cost cost() const override { return {1, 1}; }
+
+   uint32_t seqstore_id;
+   std::string query;  // the aligned query sequence, one character per position of the sequence store
+   uint32_t max_distance;
+   uint32_t min_compared;
+};
+
 class Threshold : public Operator {
   public:
    Threshold(OperatorVector&& non_negated_children, OperatorVector&& negated_children, uint32_t number_of_matchers, bool match_exactly, RowSpace rows);
@@ -507,6 +539,27 @@ struct InsertionContains : public Expression {  // insertion_contains.cpp
    uint32_t position;
    std::string value;
 };
+/// WithinDistance (no counterpart in the reference): the rows at most maxDistance away from one query sequence — a row named by its
+/// primary key (which the selection contains: it is at distance 0 from itself) or a literal aligned string — with at least
+/// minComparedPositions positions compared, by the distance of DistanceMatrix / NearestNeighbours on one aligned sequence.  The
+/// parsed expression holds only what the query text says: compile resolves the query's characters against the database it is given.
+struct WithinDistance : public Expression {
+   WithinDistance(
+      std::optional<std::string> sequence_name, std::optional<json::Value> primary_key, std::optional<std::string> sequence, uint32_t max_distance,
+      uint32_t min_compared_positions
+   )
+       : sequence_name(std::move(sequence_name)),
+         primary_key(std::move(primary_key)),
+         sequence(std::move(sequence)),
+         max_distance(max_distance),
+         min_compared_positions(min_compared_positions) {}
+   SILO_DECLARE_EXPRESSION_METHODS
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   std::optional<json::Value> primary_key;    // exactly one of the two
+   std::optional<std::string> sequence;
+   uint32_t max_distance;
+   uint32_t min_compared_positions;
+};
 struct DateBetween : public Expression {  // date_between.cpp
    DateBetween(std::string column, std::optional<common::Date> date_from, std::optional<common::Date> date_to)
        : column(std::move(column)), date_from(date_from), date_to(date_to) {}
@@ -630,6 +683,20 @@ std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json);
 
 /// Refuses a sharded database on behalf of an action whose counts are not all-reduced across ranks (table_actions.cpp).
 void requireUnsharded(const Database& database, const std::string& action_name);
+
+/// The aligned sequence that NearestNeighbours and WithinDistance compare every row with (metadata_actions.cpp).
+struct QuerySequence {
+   std::string characters;             // one per position of the sequence
+   size_t own_partition = SIZE_MAX;    // where the row named by a primary key lives; a literal sequence has none
+   uint32_t own_row = UINT32_MAX;
+};
+/// The literal `sequence` (which must have the length of the sequence `name`), or the row whose primary key is `primary_key`:
+/// looked up in the host copies of the key column of every partition and gathered from its store (silo_gpu_reconstruct_sequences,
+/// n = 1) on the calling thread's queryStream(), which is waited for.  `what` opens every message ("NearestNeighbours action").
+QuerySequence resolveQuerySequence(
+   const Database& database, const std::string& name, bool is_amino_acid, const std::optional<json::Value>& primary_key,
+   const std::optional<std::string>& sequence, const std::string& what
+);
 
 class Aggregated : public Action {
    std::vector<std::string> group_by_fields;

@@ -111,7 +111,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules", "silo_gpu_store_scan_prunable_rows",
     "silo_gpu_filters_grouped", "silo_gpu_filters_cross",
     "silo_gpu_distance_pack", "silo_gpu_distance_pairs",
-    "silo_gpu_query_distances", "silo_gpu_nearest_rows",
+    "silo_gpu_query_distances", "silo_gpu_nearest_rows", "silo_gpu_bitset_from_distances",
 ]
 
 _lib = None
@@ -181,6 +181,7 @@ def load_library():
     lib.silo_gpu_distance_pairs.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_query_distances.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_nearest_rows.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
+    lib.silo_gpu_bitset_from_distances.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -572,6 +573,33 @@ def nearest_rows(table, filter_words, sequence_count, k, exclude_row=NO_ROW, max
         for ptr in (table_dev, filter_dev, out, count, scratch):
             if ptr is not None:
                 device_free(ptr)
+
+
+def bitset_from_distances_call(table_ptr, sequence_count, row_words, max_distance, min_compared, out_ptr, stream=None):
+    """silo_gpu_bitset_from_distances (K11) on the caller's device buffers, waited for."""
+    lib = load_library()
+    _check(lib.silo_gpu_bitset_from_distances(table_ptr, sequence_count, row_words, max_distance, min_compared, out_ptr, stream))
+    _check(lib.silo_gpu_stream_synchronize(stream))
+
+
+def bitset_from_distances(table, sequence_count, row_words, max_distance=NO_ROW, min_compared=0, fill=None, stream=None, guard_words=0):
+    """silo_gpu_bitset_from_distances (K11) over a host table uint32 [row_words * 64][2] (distance, compared) as
+    silo_gpu_query_distances leaves it: bit r = r < sequence_count and distance <= max_distance and compared >= min_compared.
+    Returns the row_words words the call writes, followed by `guard_words` words behind them that it must not touch: those hold
+    the byte `fill` repeated (the whole allocation is filled with it before the launch), or whatever the allocation held."""
+    lib = load_library()
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    words = int(row_words) + int(guard_words)
+    table_dev = device_malloc(table.nbytes)
+    out = device_malloc(words * 8, fill, stream)
+    try:
+        if table.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(table_dev, _ptr(table), table.nbytes, stream))
+        bitset_from_distances_call(table_dev, sequence_count, row_words, max_distance, min_compared, out, stream)
+        return device_read(out, np.uint64, words, stream)
+    finally:
+        device_free(table_dev)
+        device_free(out)
 
 
 class GpuStore:
