@@ -576,6 +576,47 @@ int silo_gpu_filters_cross(
 int silo_gpu_distance_pack(int alphabet, const char* chars_dev, uint32_t n_rows, uint32_t positions, uint64_t* planes_dev, void* stream);
 int silo_gpu_distance_pairs(int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, uint32_t* out_dev, void* stream);
 
+/* ---- K12: which pairs are within a bound, and the connected components of that relation (Clusters) ---
+ * Neither entry takes a store.  silo_gpu_distance_within reads planes as silo_gpu_distance_pack leaves them (that entry keeps its
+ * own limit of SILO_GPU_MAX_DISTANCE_ROWS rows per call: the caller packs in batches into one plane buffer) and WRITES a bit matrix
+ * of AW = SILO_GPU_ADJACENCY_WORDS(n_rows) words per row, adjacency_dev[i * AW + (j >> 6)] bit (j & 63):
+ *     bit (i, j) = i != j && i < n_rows && j < n_rows && differing(i, j) <= max_distance && compared(i, j) >= min_compared
+ * with differing / compared as silo_gpu_distance_pairs counts them.  max_distance == UINT32_MAX: no bound on the distance;
+ * min_compared == 0: none on the compared positions.  The matrix is symmetric, its diagonal is clear and the bits at or past n_rows
+ * are zero.  Every one of the n_rows * AW words is written once and nothing behind them is touched: the caller never clears the
+ * buffer.  No atomics: the words do not depend on how the blocks are scheduled.
+ * Two launches on `stream`, no waiting.  k_distance_within: a block of 256 threads owns a tile of SILO_GPU_WITHIN_TILE_ROWS rows x
+ * SILO_GPU_WITHIN_TILE_COLS columns (= one word of 4 rows per wave, four pairs per thread in registers) and stages
+ * SILO_GPU_WITHIN_CHUNK_WORDS words of every plane of its 16 + 64 rows in LDS at a time; only the tiles whose word is at or right
+ * of the word that holds the diagonal are launched, and a wave's ballot is the finished word.  After every chunk the block stops if
+ * none of its pairs can still be linked (differing only grows along the row; a pair with a row at or past n_rows and a pair i == j
+ * count as out from the start): its words are then zeros.  The words are exact either way; only the time depends on the data.
+ * k_adjacency_mirror fills the words left of the diagonal's word from the transposed 64 x 64 blocks right of it.
+ * n_rows == 0: success, nothing launched.  positions == 0: every pair has compared = differing = 0, and the matrix of that is
+ * written.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for an alphabet other than the two, a NULL buffer or more
+ * than SILO_GPU_MAX_CLUSTER_ROWS rows.
+ * silo_gpu_adjacency_components takes such a matrix, which must be symmetric (bits at or past n_rows in a row's last word are
+ * ignored: they never index the labels), and WRITES labels_dev[i] = the lowest j in the connected component of i, for i < n_rows,
+ * and, unless rounds_dev is NULL, *rounds_dev = the rounds it ran (at most n_rows).  One launch of ONE block of
+ * SILO_GPU_COMPONENTS_THREADS threads on `stream`, no waiting: the labels live in LDS (4 bytes per row); a round gives every row
+ * to a wave, which takes the lowest label among the row's neighbours and lowers (atomicMin in LDS) the row's label and the label
+ * of the row's old label to it, then every label jumps to its label's label until none changes; a round that lowers nothing ends
+ * the loop, which n_rows bounds whatever the input.  Labels only fall and every label is a row of its row's own component, so the
+ * labels at the end do not depend on the order of the atomics (the round count may).  The matrix is read once per round.
+ * n_rows == 0: success, nothing launched or written.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL
+ * matrix, NULL labels or more than SILO_GPU_MAX_CLUSTER_ROWS rows. */
+#define SILO_GPU_MAX_CLUSTER_ROWS 8192
+#define SILO_GPU_ADJACENCY_WORDS(n_rows) (((n_rows) + 63u) / 64u)
+#define SILO_GPU_WITHIN_TILE_ROWS 16
+#define SILO_GPU_WITHIN_TILE_COLS 64
+#define SILO_GPU_WITHIN_CHUNK_WORDS 16
+#define SILO_GPU_COMPONENTS_THREADS 1024
+int silo_gpu_distance_within(
+   int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, uint32_t max_distance, uint32_t min_compared,
+   uint64_t* adjacency_dev, void* stream
+);
+int silo_gpu_adjacency_components(const uint64_t* adjacency_dev, uint32_t n_rows, uint32_t* labels_dev, uint32_t* rounds_dev, void* stream);
+
 /* ---- K11: the rows of the whole store nearest to a query (NearestNeighbours) --------------------------
  * silo_gpu_query_distances compares one query — query_chars, `positions` characters in HOST memory — with EVERY row of a sequence
  * store, read off the store's own layout (identity / code planes with escape keys, one-hot rows with a derived symbol, runs of the

@@ -8,6 +8,11 @@
 //   k_distance_pairs   an AND / XOR-popcount "GEMM" over the planes (silo_gpu_distance_pairs): a block owns a tile of
 //                      DISTANCE_TILE x DISTANCE_TILE pairs on or above the diagonal, stages the words of its 2 x DISTANCE_TILE
 //                      rows in LDS chunk by chunk, and WRITES each pair's two counts once
+// and the same comparison as a yes / no per pair behind Clusters (K12):
+//   k_distance_within  "differing <= max_distance and compared >= min_compared" as one BIT per pair (silo_gpu_distance_within): a
+//                      block owns WITHIN_TILE_ROWS x WITHIN_TILE_COLS pairs at or right of the diagonal's word, four pairs per
+//                      thread in registers, a wave's ballot is a finished word; it stops once no pair of its tile can be linked
+//   k_adjacency_mirror the words left of the diagonal's word, transposed from the 64 x 64 bit blocks right of it
 #include "store_internal.h"
 
 using namespace silo_gpu_detail;
@@ -20,6 +25,13 @@ constexpr uint32_t DISTANCE_CHUNK_WORDS = SILO_GPU_DISTANCE_CHUNK_WORDS;  // wor
 constexpr uint32_t DISTANCE_PACK_WAVES = DISTANCE_THREADS / 64;           // words of a row per block of k_distance_pack
 constexpr uint8_t NOT_VALID = 0xFF;
 static_assert(DISTANCE_TILE * DISTANCE_TILE == DISTANCE_THREADS);
+constexpr uint32_t WITHIN_TILE_ROWS = SILO_GPU_WITHIN_TILE_ROWS;      // rows of a block's tile: WITHIN_ROWS_PER_WAVE per wave
+constexpr uint32_t WITHIN_TILE_COLS = SILO_GPU_WITHIN_TILE_COLS;      // columns of a block's tile: one per lane, one adjacency word
+constexpr uint32_t WITHIN_CHUNK_WORDS = SILO_GPU_WITHIN_CHUNK_WORDS;  // words of every plane of a row that are staged at a time
+constexpr uint32_t WITHIN_ROWS_PER_WAVE = WITHIN_TILE_ROWS / (DISTANCE_THREADS / 64u);  // pairs per thread
+constexpr uint32_t WITHIN_ROW_TILES_PER_WORD = WITHIN_TILE_COLS / WITHIN_TILE_ROWS;     // row tiles that share a diagonal word
+static_assert(WITHIN_TILE_COLS == 64 && WITHIN_ROWS_PER_WAVE * (DISTANCE_THREADS / 64u) == WITHIN_TILE_ROWS);
+static_assert(WITHIN_ROW_TILES_PER_WORD * WITHIN_TILE_ROWS == WITHIN_TILE_COLS);
 
 /// The valid mutation symbols of an alphabet as characters, in the order of Nucleotide / AminoAcid::VALID_MUTATION_SYMBOLS
 /// (host/symbols.h): the index of a character in here is the code the planes hold.
@@ -157,16 +169,164 @@ __global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_pairs(
    }
 }
 
-/// What both entries refuse; nullptr if nothing.
-const char* distanceComplaint(int alphabet, const void* in_dev, const void* out_dev, uint32_t n_rows) {
+/// A row of the tile that k_distance_within stages: WITHIN_CHUNK_WORDS words of each plane, and one word of padding.  The stride
+/// is an odd number of 8-byte words, so the 32 lanes that an 8-byte LDS read serves together, which read 32 consecutive rows at
+/// the same (plane, word), fall on 32 different pairs of banks.
+template <uint32_t PLANES>
+constexpr uint32_t withinRowWords() {
+   return PLANES * WITHIN_CHUNK_WORDS + 1u;
+}
+static_assert(withinRowWords<4>() % 2u == 1u && withinRowWords<6>() % 2u == 1u);
+
+/// grid = the tiles (ti, tj) with tj >= the word of the diagonal of row tile ti, row tile by row tile: the row tiles 4 g .. 4 g + 3
+/// (WITHIN_ROW_TILES_PER_WORD of them share the diagonal word g) have adjacency_words - g tiles each.  Wave v owns rows
+/// ti * 16 + 4 v .. + 3 of the tile, lane l its column tj * 64 + l.  Per chunk of WITHIN_CHUNK_WORDS words the block copies the words
+/// of all planes of its 16 + 64 rows into LDS — a row at or past n_rows is staged as zeros, so nothing past the buffer is read — and
+/// every thread walks the chunk with its column's words (one LDS read per plane and word) against its four rows' (the same address
+/// for the whole wave: broadcast).  A pair is `open` while it can still be linked: never a pair with a row at or past n_rows or
+/// with i == j, and no longer once differing > max_distance.  After each chunk the block leaves the loop if no pair is open.  At
+/// the end the ballot of "open and compared >= min_compared" over a wave is word (row, tj); one lane stores it, for rows < n_rows.
+template <uint32_t PLANES>
+__global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_within(
+   const uint64_t* __restrict__ planes, uint32_t n_rows, uint32_t words, uint32_t row_tiles, uint32_t adjacency_words, uint32_t max_distance,
+   uint32_t min_compared, uint64_t* __restrict__ adjacency
+) {
+   constexpr uint32_t ROW_WORDS = withinRowWords<PLANES>();
+   constexpr uint32_t STAGED_ROWS = WITHIN_TILE_ROWS + WITHIN_TILE_COLS;
+   constexpr uint32_t STAGED = STAGED_ROWS * PLANES * WITHIN_CHUNK_WORDS;  // words copied per chunk
+   static_assert(STAGED % DISTANCE_THREADS == 0);
+   __shared__ uint64_t s_rows[STAGED_ROWS * ROW_WORDS];
+
+   // the tile of this block (uniform, at most adjacency_words steps)
+   uint32_t ti = 0;
+   uint32_t tj = 0;
+   {
+      uint32_t index = blockIdx.x;
+      for (uint32_t group = 0; group < adjacency_words; ++group) {
+         const uint32_t tiles_per_row_tile = adjacency_words - group;
+         const uint32_t group_row_tiles = min(WITHIN_ROW_TILES_PER_WORD, row_tiles - group * WITHIN_ROW_TILES_PER_WORD);
+         if (index < group_row_tiles * tiles_per_row_tile) {
+            ti = group * WITHIN_ROW_TILES_PER_WORD + index / tiles_per_row_tile;
+            tj = group + index % tiles_per_row_tile;
+            break;
+         }
+         index -= group_row_tiles * tiles_per_row_tile;
+      }
+   }
+   const uint32_t wave = threadIdx.x / 64u;
+   const uint32_t lane = threadIdx.x & 63u;
+   const uint32_t first_row = ti * WITHIN_TILE_ROWS + wave * WITHIN_ROWS_PER_WAVE;
+   const uint32_t column = tj * WITHIN_TILE_COLS + lane;
+   const uint64_t* mine = s_rows + wave * WITHIN_ROWS_PER_WAVE * ROW_WORDS;
+   const uint64_t* other = s_rows + (WITHIN_TILE_ROWS + lane) * ROW_WORDS;
+   uint32_t compared[WITHIN_ROWS_PER_WAVE];
+   uint32_t differing[WITHIN_ROWS_PER_WAVE];
+   bool open[WITHIN_ROWS_PER_WAVE];
+#pragma unroll
+   for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
+      compared[r] = 0;
+      differing[r] = 0;
+      open[r] = first_row + r < n_rows && column < n_rows && first_row + r != column;
+   }
+   for (uint32_t chunk_begin = 0; chunk_begin < words; chunk_begin += WITHIN_CHUNK_WORDS) {
+      const uint32_t chunk_words = min(words - chunk_begin, WITHIN_CHUNK_WORDS);
+      uint64_t staged[STAGED / DISTANCE_THREADS];
+#pragma unroll
+      for (uint32_t k = 0; k < STAGED / DISTANCE_THREADS; ++k) {  // all loads in flight
+         const uint32_t element = k * DISTANCE_THREADS + threadIdx.x;
+         const uint32_t word = element % WITHIN_CHUNK_WORDS;
+         const uint32_t row_plane = element / WITHIN_CHUNK_WORDS;  // (row of the tile's 16, then column of its 64) * PLANES + plane
+         const uint32_t local_row = row_plane / PLANES;
+         const uint32_t row = local_row < WITHIN_TILE_ROWS ? ti * WITHIN_TILE_ROWS + local_row : tj * WITHIN_TILE_COLS + (local_row - WITHIN_TILE_ROWS);
+         staged[k] = 0;
+         if (row < n_rows && word < chunk_words) {
+            staged[k] = planes[(static_cast<size_t>(row) * PLANES + row_plane % PLANES) * words + chunk_begin + word];
+         }
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < STAGED / DISTANCE_THREADS; ++k) {
+         const uint32_t element = k * DISTANCE_THREADS + threadIdx.x;
+         const uint32_t row_plane = element / WITHIN_CHUNK_WORDS;
+         s_rows[(row_plane / PLANES) * ROW_WORDS + (row_plane % PLANES) * WITHIN_CHUNK_WORDS + element % WITHIN_CHUNK_WORDS] = staged[k];
+      }
+      __syncthreads();
+      for (uint32_t word = 0; word < chunk_words; ++word) {
+         uint64_t theirs[PLANES];
+#pragma unroll
+         for (uint32_t k = 0; k < PLANES; ++k) {
+            theirs[k] = other[k * WITHIN_CHUNK_WORDS + word];
+         }
+#pragma unroll
+         for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
+            const uint64_t* row = mine + r * ROW_WORDS;
+            const uint64_t both = row[word] & theirs[0];
+            uint64_t unequal = 0;
+#pragma unroll
+            for (uint32_t k = 1; k < PLANES; ++k) {
+               unequal |= row[k * WITHIN_CHUNK_WORDS + word] ^ theirs[k];
+            }
+            compared[r] += static_cast<uint32_t>(__popcll(both));
+            differing[r] += static_cast<uint32_t>(__popcll(both & unequal));
+         }
+      }
+      bool any_open = false;
+#pragma unroll
+      for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
+         open[r] = open[r] && differing[r] <= max_distance;
+         any_open = any_open || open[r];
+      }
+      // the barrier that lets the next chunk overwrite what was just read, and the vote: differing only grows along the row
+      if (__syncthreads_or(any_open) == 0) {
+         break;
+      }
+   }
+#pragma unroll
+   for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
+      const uint64_t linked = __ballot(open[r] && differing[r] <= max_distance && compared[r] >= min_compared);
+      if (lane == 0 && first_row + r < n_rows) {
+         adjacency[static_cast<size_t>(first_row + r) * adjacency_words + tj] = linked;
+      }
+   }
+}
+
+/// grid = (adjacency_words / 4 rounded up, adjacency_words), a wave per 64 x 64 bit block (wi, wj) with wj < wi, the blocks left of
+/// the diagonal's: lane l reads word (64 wj + l, wi) — right of its row's diagonal word, so k_distance_within wrote it, and
+/// 64 wj + l < 64 wi < n_rows — the ballot of bit b over the wave is word (64 wi + b, wj), which lane b keeps and stores where its
+/// row is < n_rows.  Reads words right of the diagonal only and writes words left of it only.
+__global__ __launch_bounds__(DISTANCE_THREADS) void k_adjacency_mirror(uint64_t* adjacency, uint32_t n_rows, uint32_t adjacency_words) {
+   const uint32_t wi = blockIdx.y;
+   const uint32_t wj = blockIdx.x * (DISTANCE_THREADS / 64u) + threadIdx.x / 64u;  // the same for the whole wave
+   if (wj >= wi) {
+      return;
+   }
+   const uint32_t lane = threadIdx.x & 63u;
+   const uint64_t column_bits = adjacency[static_cast<size_t>(wj * 64u + lane) * adjacency_words + wi];
+   uint64_t row_bits = 0;
+   for (uint32_t bit = 0; bit < 64u; ++bit) {
+      const uint64_t transposed = __ballot(((column_bits >> bit) & 1u) != 0);
+      if (lane == bit) {
+         row_bits = transposed;
+      }
+   }
+   const uint32_t row = wi * 64u + lane;
+   if (row < n_rows) {
+      adjacency[static_cast<size_t>(row) * adjacency_words + wj] = row_bits;
+   }
+}
+
+constexpr const char* MORE_THAN_DISTANCE_ROWS = "more rows than SILO_GPU_MAX_DISTANCE_ROWS";
+constexpr const char* MORE_THAN_CLUSTER_ROWS = "more rows than SILO_GPU_MAX_CLUSTER_ROWS";
+
+/// What the entries refuse; nullptr if nothing.  limit_complaint: what to say of more than max_rows rows.
+const char* distanceComplaint(int alphabet, const void* in_dev, const void* out_dev, uint32_t n_rows, uint32_t max_rows, const char* limit_complaint) {
    if (alphabet != SILO_GPU_ALPHABET_NUCLEOTIDE && alphabet != SILO_GPU_ALPHABET_AMINO_ACID) {
       return "the alphabet is neither SILO_GPU_ALPHABET_NUCLEOTIDE nor SILO_GPU_ALPHABET_AMINO_ACID";
    }
    if (in_dev == nullptr || out_dev == nullptr) {
       return "a buffer is NULL";
    }
-   if (n_rows > SILO_GPU_MAX_DISTANCE_ROWS) {
-      return "more rows than SILO_GPU_MAX_DISTANCE_ROWS";
+   if (n_rows > max_rows) {
+      return limit_complaint;
    }
    return nullptr;
 }
@@ -176,7 +336,7 @@ const char* distanceComplaint(int alphabet, const void* in_dev, const void* out_
 extern "C" {
 
 int silo_gpu_distance_pack(int alphabet, const char* chars_dev, uint32_t n_rows, uint32_t positions, uint64_t* planes_dev, void* stream) {
-   if (const char* complaint = distanceComplaint(alphabet, chars_dev, planes_dev, n_rows); complaint != nullptr) {
+   if (const char* complaint = distanceComplaint(alphabet, chars_dev, planes_dev, n_rows, SILO_GPU_MAX_DISTANCE_ROWS, MORE_THAN_DISTANCE_ROWS); complaint != nullptr) {
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_distance_pack: ") + complaint);
    }
    if (n_rows == 0 || positions == 0) {
@@ -198,7 +358,7 @@ int silo_gpu_distance_pack(int alphabet, const char* chars_dev, uint32_t n_rows,
 }
 
 int silo_gpu_distance_pairs(int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, uint32_t* out_dev, void* stream) {
-   if (const char* complaint = distanceComplaint(alphabet, planes_dev, out_dev, n_rows); complaint != nullptr) {
+   if (const char* complaint = distanceComplaint(alphabet, planes_dev, out_dev, n_rows, SILO_GPU_MAX_DISTANCE_ROWS, MORE_THAN_DISTANCE_ROWS); complaint != nullptr) {
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_distance_pairs: ") + complaint);
    }
    if (n_rows == 0 || positions == 0) {
@@ -216,6 +376,43 @@ int silo_gpu_distance_pairs(int alphabet, const uint64_t* planes_dev, uint32_t n
          <<<grid, DISTANCE_THREADS, 0, hip_stream>>>(planes_dev, n_rows, words, tiles_per_side, out_dev);
    }
    HIP_TRY(hipGetLastError());
+   return SILO_GPU_OK;
+}
+
+int silo_gpu_distance_within(
+   int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, uint32_t max_distance, uint32_t min_compared,
+   uint64_t* adjacency_dev, void* stream
+) {
+   if (const char* complaint = distanceComplaint(alphabet, planes_dev, adjacency_dev, n_rows, SILO_GPU_MAX_CLUSTER_ROWS, MORE_THAN_CLUSTER_ROWS);
+       complaint != nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_distance_within: ") + complaint);
+   }
+   if (n_rows == 0) {
+      return SILO_GPU_OK;
+   }
+   const uint32_t words = SILO_GPU_DISTANCE_WORDS(positions);  // 0 positions: no chunk is walked, every pair has (0, 0)
+   const uint32_t adjacency_words = SILO_GPU_ADJACENCY_WORDS(n_rows);
+   const uint32_t row_tiles = (n_rows + WITHIN_TILE_ROWS - 1) / WITHIN_TILE_ROWS;
+   uint32_t grid = 0;
+   for (uint32_t group = 0; group < adjacency_words; ++group) {
+      grid += std::min(WITHIN_ROW_TILES_PER_WORD, row_tiles - group * WITHIN_ROW_TILES_PER_WORD) * (adjacency_words - group);
+   }
+   auto hip_stream = static_cast<hipStream_t>(stream);
+   if (alphabet == SILO_GPU_ALPHABET_NUCLEOTIDE) {
+      k_distance_within<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_NUCLEOTIDE)><<<grid, DISTANCE_THREADS, 0, hip_stream>>>(
+         planes_dev, n_rows, words, row_tiles, adjacency_words, max_distance, min_compared, adjacency_dev
+      );
+   } else {
+      k_distance_within<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_AMINO_ACID)><<<grid, DISTANCE_THREADS, 0, hip_stream>>>(
+         planes_dev, n_rows, words, row_tiles, adjacency_words, max_distance, min_compared, adjacency_dev
+      );
+   }
+   HIP_TRY(hipGetLastError());
+   if (adjacency_words > 1) {
+      const dim3 mirror_grid((adjacency_words + DISTANCE_THREADS / 64u - 1) / (DISTANCE_THREADS / 64u), adjacency_words);
+      k_adjacency_mirror<<<mirror_grid, DISTANCE_THREADS, 0, hip_stream>>>(adjacency_dev, n_rows, adjacency_words);
+      HIP_TRY(hipGetLastError());
+   }
    return SILO_GPU_OK;
 }
 

@@ -799,6 +799,7 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"QueriesOverTime", parseQueriesOverTime},
    {"CrossTabulation", parseCrossTabulation},
    {"DistanceMatrix", parseDistanceMatrix},
+   {"Clusters", parseClusters},
    {"NearestNeighbours", parseNearestNeighbours},
 };
 

@@ -3,6 +3,8 @@
 //   Details                         src/silo/query_engine/actions/details.cpp
 //   FastaAligned                    src/silo/query_engine/actions/fasta_aligned.cpp
 //   DistanceMatrix                  (not in the reference) the rows FastaAligned would return, compared pairwise on the device (K10)
+//   Clusters                        (not in the reference) the same rows, linked where they are within a distance bound; the connected
+//                                   components of the links on the device (K12)
 //   NearestNeighbours               (not in the reference) the rows of the whole database closest to one query sequence (K11)
 #include <algorithm>
 #include <tuple>
@@ -703,6 +705,173 @@ std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json) {
       max_distance = json["maxDistance"].as_uint32();
    }
    return std::make_unique<DistanceMatrix>(std::move(sequence_name), max_distance);
+}
+
+// ---- Clusters --------------------------------------------------------------------------------------------
+// The single-linkage clusters of the selected sequences at a distance bound: the connected components of "distance <= maxDistance
+// and comparedPositions >= minComparedPositions", from the bit-per-pair kernel and the components kernel (K12), with its parser.
+// No counterpart in the reference.
+void Clusters::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"key", "cluster", "clusterSize"});
+}
+
+QueryResult Clusters::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+   const bool is_amino_acid = database.nuc_sequences.count(name) == 0;
+   CHECK_SILO_QUERY(!is_amino_acid || database.aa_sequences.count(name) != 0, "Database does not contain a sequence with name: '" + name + "'")
+   size_t total_count = 0;
+   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+      total_count += database.partitions[partition_id].sequence_count == 0 ? 0 : bitmap_filter[partition_id].cardinality();
+   }
+   CHECK_SILO_QUERY(total_count <= SEQUENCE_LIMIT, "Clusters action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences")
+   requireUnsharded(database, "Clusters");
+   QueryResult results;
+   if (total_count == 0) {
+      return results;
+   }
+   const auto n = static_cast<uint32_t>(total_count);
+   const int alphabet = is_amino_acid ? SILO_GPU_ALPHABET_AMINO_ACID : SILO_GPU_ALPHABET_NUCLEOTIDE;
+   const auto positions =
+      static_cast<uint32_t>(is_amino_acid ? database.aa_sequences.at(name).reference_sequence.size() : database.nuc_sequences.at(name).reference_sequence.size());
+   const size_t row_plane_words = static_cast<size_t>(SILO_GPU_DISTANCE_PLANES(alphabet)) * SILO_GPU_DISTANCE_WORDS(positions);
+   constexpr uint32_t BATCH_ROWS = SILO_GPU_MAX_DISTANCE_ROWS;  // what one silo_gpu_distance_pack takes
+
+   const std::string& primary_key_column = database.database_config.primary_key;
+   std::vector<JsonValue> keys;  // of sequence 0 .. n - 1: partition order, then ascending row id, as DistanceMatrix numbers them
+   keys.reserve(n);
+   // (a sequence without positions: nothing to compare, nothing launched — every pair has distance 0 and 0 positions compared)
+   std::vector<uint32_t> labels(n, min_compared_positions == 0 ? 0u : UINT32_MAX);
+   {
+      // nothing in here returns to the pool before the stream has been waited for: the launches read it
+      DevicePool& pool = database.partitions.front().pool;
+      DeviceBuffer device_planes = pool.acquire(std::max<size_t>(8, n * row_plane_words * sizeof(uint64_t)));
+      DeviceBuffer device_chars = pool.acquire(std::max<size_t>(1, static_cast<size_t>(std::min(n, BATCH_ROWS)) * positions));
+      DeviceBuffer device_adjacency = pool.acquire(static_cast<size_t>(n) * SILO_GPU_ADJACENCY_WORDS(n) * sizeof(uint64_t));
+      DeviceBuffer device_labels = pool.acquire(n * sizeof(uint32_t));
+      std::vector<DeviceBuffer> live;  // per partition: its row ids
+      try {
+         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+            const DatabasePartition& partition = database.partitions[partition_id];
+            if (partition.sequence_count == 0) {
+               continue;
+            }
+            const std::vector<uint32_t> rows = selectedRows(partition, bitmap_filter[partition_id]);
+            if (rows.empty()) {
+               continue;
+            }
+            const size_t first_sequence = keys.size();
+            const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
+            for (const uint32_t row : rows) {
+               keys.push_back(primary_key.jsonOfRow(row));
+            }
+            if (keys.size() > n) {
+               throw std::runtime_error("Clusters: a filter selects more rows than its cardinality says");
+            }
+            if (positions == 0) {
+               continue;
+            }
+            const uint32_t seqstore_id = is_amino_acid ? partition.aa_sequences.at(name).seqstore_id : partition.nuc_sequences.at(name).seqstore_id;
+            auto* device_rows = live.emplace_back(partition.pool.acquire(rows.size() * sizeof(uint32_t))).as<uint32_t>();
+            checkGpu(silo_gpu_memcpy_h2d(device_rows, rows.data(), rows.size() * sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
+            // every batch gathers into the SAME character buffer: the batches are in order on queryStream(), so a batch's gather
+            // starts after the pack of the batch before it has read the characters
+            for (size_t begin = 0; begin < rows.size(); begin += BATCH_ROWS) {
+               const auto batch_rows = static_cast<uint32_t>(std::min<size_t>(BATCH_ROWS, rows.size() - begin));
+               checkGpu(
+                  silo_gpu_reconstruct_sequences(partition.store, seqstore_id, device_rows + begin, batch_rows, device_chars.as<char>(), queryStream()),
+                  "silo_gpu_reconstruct_sequences"
+               );
+               checkGpu(
+                  silo_gpu_distance_pack(
+                     alphabet, device_chars.as<char>(), batch_rows, positions, device_planes.as<uint64_t>() + (first_sequence + begin) * row_plane_words,
+                     queryStream()
+                  ),
+                  "silo_gpu_distance_pack"
+               );
+            }
+         }
+         if (keys.size() != n) {
+            throw std::runtime_error("Clusters: a filter selects fewer rows than its cardinality says");
+         }
+         if (positions != 0) {
+            // rows of different partitions are linked with each other: one bit matrix over all of them, one labelling, n labels fetched
+            checkGpu(
+               silo_gpu_distance_within(
+                  alphabet, device_planes.as<uint64_t>(), n, positions, max_distance, min_compared_positions, device_adjacency.as<uint64_t>(), queryStream()
+               ),
+               "silo_gpu_distance_within"
+            );
+            checkGpu(
+               silo_gpu_adjacency_components(device_adjacency.as<uint64_t>(), n, device_labels.as<uint32_t>(), nullptr, queryStream()),
+               "silo_gpu_adjacency_components"
+            );
+            HostFetch fetch(device_labels.get(), n * sizeof(uint32_t), queryStream());
+            const auto* host = static_cast<const uint32_t*>(fetch.wait());
+            labels.assign(host, host + n);
+         }
+         // the copy was the last thing enqueued, but say it: nothing of this query runs any more when its buffers go back
+         checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+      } catch (...) {
+         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+         (void)silo_gpu_stream_synchronize(queryStream());
+         throw;
+      }
+   }
+
+   std::vector<uint32_t> sizes(n, 0);
+   for (uint32_t i = 0; i < n; ++i) {
+      if (labels[i] == UINT32_MAX) {  // (no positions and a bound on the compared positions: nothing is linked)
+         labels[i] = i;
+      }
+      if (labels[i] >= n) {
+         throw std::runtime_error("Clusters: a label names no selected sequence");
+      }
+      ++sizes[labels[i]];
+   }
+   // minClusterSize is applied here, before a row is built
+   for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t size = sizes[labels[i]];
+      if (size < min_cluster_size) {
+         continue;
+      }
+      QueryResultEntry& entry = results.query_result.emplace_back();
+      entry.fields.emplace("key", keys[i]);
+      entry.fields.emplace("cluster", keys[labels[i]]);
+      entry.fields.emplace("clusterSize", static_cast<int32_t>(size));
+   }
+   return results;
+}
+
+std::unique_ptr<Action> parseClusters(const json::Value& json) {
+   std::optional<std::string> sequence_name;
+   if (json.contains("sequenceName")) {
+      CHECK_SILO_QUERY(json["sequenceName"].is_string(), "Clusters action: the field sequenceName, if present, must be of type string")
+      sequence_name = json["sequenceName"].as_string();
+   }
+   CHECK_SILO_QUERY(json.contains("maxDistance"), "Clusters action: the field maxDistance is required")
+   CHECK_SILO_QUERY(
+      json["maxDistance"].is_number_unsigned() && json["maxDistance"].as_int64() >= 0 && json["maxDistance"].as_int64() <= INT32_MAX,
+      "Clusters action: the field maxDistance must be a non-negative integer"
+   )
+   const uint32_t max_distance = json["maxDistance"].as_uint32();
+   uint32_t min_compared_positions = 0;
+   if (json.contains("minComparedPositions")) {
+      CHECK_SILO_QUERY(
+         json["minComparedPositions"].is_number_unsigned() && json["minComparedPositions"].as_int64() >= 0 &&
+            json["minComparedPositions"].as_int64() <= INT32_MAX,
+         "Clusters action: the field minComparedPositions, if present, must be a non-negative integer"
+      )
+      min_compared_positions = json["minComparedPositions"].as_uint32();
+   }
+   uint32_t min_cluster_size = 1;
+   if (json.contains("minClusterSize")) {
+      CHECK_SILO_QUERY(
+         json["minClusterSize"].is_number_unsigned() && json["minClusterSize"].as_int64() >= 1 && json["minClusterSize"].as_int64() <= INT32_MAX,
+         "Clusters action: the field minClusterSize, if present, must be an integer of at least 1"
+      )
+      min_cluster_size = json["minClusterSize"].as_uint32();
+   }
+   return std::make_unique<Clusters>(std::move(sequence_name), max_distance, min_compared_positions, min_cluster_size);
 }
 
 // ---- NearestNeighbours -----------------------------------------------------------------------------------

@@ -678,6 +678,8 @@ std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json);
 std::unique_ptr<Action> parseCrossTabulation(const json::Value& json);
 /// The parser of DistanceMatrix (metadata_actions.cpp).
 std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json);
+/// The parser of Clusters (metadata_actions.cpp).
+std::unique_ptr<Action> parseClusters(const json::Value& json);
 /// The parser of NearestNeighbours (metadata_actions.cpp).
 std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json);
 
@@ -775,6 +777,29 @@ class DistanceMatrix : public Action {
    static constexpr uint32_t SEQUENCE_LIMIT = SILO_GPU_MAX_DISTANCE_ROWS;
    DistanceMatrix(std::optional<std::string> sequence_name, std::optional<uint32_t> max_distance)
        : sequence_name(std::move(sequence_name)), max_distance(max_distance) {}
+};
+
+/// Clusters (metadata_actions.cpp): the single-linkage clusters of the selected sequences — numbered as DistanceMatrix numbers them —
+/// at a bound on DistanceMatrix's distance on one aligned sequence: two sequences are linked iff their distance is <= maxDistance
+/// and they compare at >= minComparedPositions positions, and a cluster is a connected component of the links.  One row per
+/// sequence: its key, the key of the lowest-numbered member of its cluster, the cluster's size; minClusterSize drops the rows of
+/// smaller clusters.  The rows are gathered and packed in batches of SILO_GPU_MAX_DISTANCE_ROWS into ONE plane buffer; then one
+/// silo_gpu_distance_within (a bit per pair, K12), one silo_gpu_adjacency_components, and n labels are fetched.
+class Clusters : public Action {
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   uint32_t max_distance;
+   uint32_t min_compared_positions;
+   uint32_t min_cluster_size;
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+
+  public:
+   static constexpr uint32_t SEQUENCE_LIMIT = SILO_GPU_MAX_CLUSTER_ROWS;
+   Clusters(std::optional<std::string> sequence_name, uint32_t max_distance, uint32_t min_compared_positions, uint32_t min_cluster_size)
+       : sequence_name(std::move(sequence_name)),
+         max_distance(max_distance),
+         min_compared_positions(min_compared_positions),
+         min_cluster_size(min_cluster_size) {}
 };
 
 /// NearestNeighbours (metadata_actions.cpp): the `neighbours` rows of the WHOLE database closest to one query sequence — a row named

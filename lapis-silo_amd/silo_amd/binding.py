@@ -110,7 +110,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_allreduce_counts", "silo_gpu_broadcast_bytes",
     "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules", "silo_gpu_store_scan_prunable_rows",
     "silo_gpu_filters_grouped", "silo_gpu_filters_cross",
-    "silo_gpu_distance_pack", "silo_gpu_distance_pairs",
+    "silo_gpu_distance_pack", "silo_gpu_distance_pairs", "silo_gpu_distance_within", "silo_gpu_adjacency_components",
     "silo_gpu_query_distances", "silo_gpu_nearest_rows", "silo_gpu_bitset_from_distances",
 ]
 
@@ -179,6 +179,8 @@ def load_library():
                                            ctypes.c_uint32, ctypes.c_uint32, vp]
     lib.silo_gpu_distance_pack.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_distance_pairs.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_distance_within.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_adjacency_components.argtypes = [vp, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_query_distances.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_nearest_rows.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_bitset_from_distances.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
@@ -527,6 +529,79 @@ def distance_pairs(alphabet_id, planes_ptr, n_rows, positions, fill=None, stream
         return device_read(out, np.uint32, cells, stream).reshape(n_rows, n_rows, 2)
     finally:
         device_free(out)
+
+
+MAX_CLUSTER_ROWS = 8192        # SILO_GPU_MAX_CLUSTER_ROWS
+WITHIN_TILE_ROWS = 16          # SILO_GPU_WITHIN_TILE_ROWS: rows of the pair tile that a block of K12 owns
+WITHIN_TILE_COLS = 64          # SILO_GPU_WITHIN_TILE_COLS: its columns, one adjacency word
+WITHIN_CHUNK_WORDS = 16        # SILO_GPU_WITHIN_CHUNK_WORDS: words of every plane of a row that a block of K12 stages at a time
+COMPONENTS_THREADS = 1024      # SILO_GPU_COMPONENTS_THREADS: the one block of silo_gpu_adjacency_components
+
+
+def adjacency_words(n_rows):
+    """SILO_GPU_ADJACENCY_WORDS: 64-bit words per row of the bit matrix of K12."""
+    return (n_rows + 63) // 64
+
+
+def distance_pack_rows(alphabet_id, chars, fill=None, stream=None):
+    """distance_pack for any number of rows: silo_gpu_distance_pack in batches of at most MAX_DISTANCE_ROWS rows into the rows of
+    ONE plane buffer uint64 [n][PLANES][WORDS], as the Clusters action packs (free with device_free)."""
+    lib = load_library()
+    chars = np.ascontiguousarray(chars, dtype=np.uint8)
+    n_rows, positions = chars.shape
+    abi = _abi_alphabet(alphabet_id)
+    row_bytes = distance_planes(abi) * distance_words(positions) * 8
+    planes = device_malloc(n_rows * row_bytes, fill, stream)
+    chars_dev = device_malloc(min(n_rows, MAX_DISTANCE_ROWS) * positions)
+    try:
+        for begin in range(0, n_rows, MAX_DISTANCE_ROWS):
+            batch = chars[begin:begin + MAX_DISTANCE_ROWS]
+            if batch.size:
+                _check(lib.silo_gpu_memcpy_h2d(chars_dev, _ptr(batch), batch.size, stream))
+            _check(lib.silo_gpu_distance_pack(abi, chars_dev, len(batch), positions, ctypes.c_void_p(planes.value + begin * row_bytes), stream))
+            _check(lib.silo_gpu_stream_synchronize(stream))  # the next batch overwrites the characters
+    except Exception:
+        device_free(planes)
+        raise
+    finally:
+        device_free(chars_dev)
+    return planes
+
+
+def distance_within(alphabet_id, planes_ptr, n_rows, positions, max_distance, min_compared, fill=None, guard_words=0, stream=None):
+    """silo_gpu_distance_within (K12) over planes as distance_pack / distance_pack_rows leave them: the n_rows * adjacency_words(n_rows)
+    words of the bit matrix, bit (i, j) = i != j and differing <= max_distance and compared >= min_compared, followed by
+    `guard_words` words behind them that the call must not touch: those hold the byte `fill` repeated (the whole allocation is
+    filled with it before the launch), or whatever the allocation held."""
+    lib = load_library()
+    words = n_rows * adjacency_words(n_rows) + int(guard_words)
+    out = device_malloc(words * 8, fill, stream)
+    try:
+        _check(lib.silo_gpu_distance_within(_abi_alphabet(alphabet_id), planes_ptr, n_rows, positions, max_distance, min_compared, out, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(out, np.uint64, words, stream)
+    finally:
+        device_free(out)
+
+
+def adjacency_components(adjacency, n_rows, fill=None, stream=None):
+    """silo_gpu_adjacency_components (K12) over a host bit matrix uint64 [n_rows * adjacency_words(n_rows)] as
+    silo_gpu_distance_within leaves it: (labels uint32 [n_rows], rounds) — labels[i] the lowest row of i's component.  The labels
+    and the round count are filled with the byte `fill` before the launch."""
+    lib = load_library()
+    adjacency = np.ascontiguousarray(adjacency, dtype=np.uint64).reshape(-1)
+    adjacency_dev = device_malloc(adjacency.nbytes)
+    labels = device_malloc(n_rows * 4, fill, stream)
+    rounds = device_malloc(4, fill, stream)
+    try:
+        if adjacency.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(adjacency_dev, _ptr(adjacency), adjacency.nbytes, stream))
+        _check(lib.silo_gpu_adjacency_components(adjacency_dev, n_rows, labels, rounds, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(labels, np.uint32, n_rows, stream), int(device_read(rounds, np.uint32, 1, stream)[0])
+    finally:
+        for ptr in (adjacency_dev, labels, rounds):
+            device_free(ptr)
 
 
 MAX_NEAREST_ROWS = 1024              # SILO_GPU_MAX_NEAREST_ROWS

@@ -56,6 +56,8 @@ def build_gpu(force=False):
     target = os.path.join(LIB, "libsilo_gpu.so")
     sources = _glob(CSRC, (".hip",))
     headers = _glob(CSRC, (".h",)) + _glob(INCLUDE, (".h",))
+    if not force and not _newer(target, sources + headers):
+        return target  # up to date, whether or not the objects it was linked from are still there
     # one object per translation unit (lib/obj/, git-ignored), so that touching one kernel file recompiles only it
     obj_dir = os.path.join(LIB, "obj")
     os.makedirs(obj_dir, exist_ok=True)
