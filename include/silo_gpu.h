@@ -474,6 +474,15 @@ int silo_gpu_store_scan_prunable_granules(
 int silo_gpu_store_scan_prunable_rows(
    const silo_gpu_store* store, uint32_t seqstore_id, uint32_t cardinality, double min_proportion, uint64_t* out_skippable, uint64_t* out_total
 );
+/* The end runs of the gap symbol '-' (a sequence that has not begun yet, or has already ended), which a Mutations scan counts
+ * instead of reading the one-hot rows of '-' at the alignment's ragged ends (SILO_GPU_TUNE_END_RUNS): the one-hot rows the scan
+ * leaves out (covered rows), the end events it streams instead (one where a sequence's leading run ends, one where its trailing
+ * run begins) and the residual keys (set bits of the covered rows outside every end run: interior deletions).  All 0 for a store
+ * without them: built in two passes, imported, of more than 67 M rows, without derived symbols, or where no row is covered.
+ * The store itself keeps the rows: every other reader finds them where they are. */
+uint64_t silo_gpu_store_scan_covered_rows(const silo_gpu_store* store, uint32_t seqstore_id);
+uint64_t silo_gpu_store_scan_end_events(const silo_gpu_store* store, uint32_t seqstore_id);
+uint64_t silo_gpu_store_scan_residual_keys(const silo_gpu_store* store, uint32_t seqstore_id);
 
 /* ---- K7: grouped mutation counts (MutationsOverTime) -------------------------------------------------
  * For each of n_mutations listed cells (positions[m] 0-based in the store, symbols[m] a VALID mutation symbol id of the
@@ -691,6 +700,9 @@ enum { SILO_GPU_TUNE_SCAN_ROWS_PER_BLOCK = 0, SILO_GPU_TUNE_SCAN_VARIANT = 1, SI
                                         and stores of more than 67 M rows always do */,
        SILO_GPU_TUNE_PRUNE_KEYS = 11 /* silo_gpu_mutations_scan_ranges_min_proportion: 0 (default) skips the granules of escape keys and the one-hot
                                         plane rows that cannot reach a filter's proportion; 1 skips keys only; < 0 skips nothing (the exact scan) — for A/B runs */,
+       SILO_GPU_TUNE_END_RUNS = 12 /* a Mutations scan over a store with end runs of the gap symbol (silo_gpu_store_scan_covered_rows): 0 (default) counts
+                                      the covered one-hot rows of '-' from the sequences' end events and residual keys in the escape-key pass; 1 counts
+                                      them in a launch of their own behind the row launch; < 0 reads the rows — the same tables either way, for A/B runs */,
        SILO_GPU_TUNE_SCAN_SPARSE_DIVISOR = 3 /* a filter with a set bit in <= row_words / divisor of its 64-byte sectors takes the gather scan (K1s); 0 = default 16, < 0 = off */ };
 int silo_gpu_tune(int knob, int value);
 
@@ -735,7 +747,9 @@ const char* silo_gpu_last_scan_kernel(void);
 typedef struct silo_gpu_scan_timing {
    char kernel[64];       /* e.g. "k_scan_sliced<2, 2, 8, 1, 2>", as rocprofv3 names it; ", pruning" behind k_scan_escapes_sliced<N> where the
                              launch may skip granules of keys and behind k_scan_sliced<2, 2, ..., 2> where it may skip one-hot rows
-                             (silo_gpu_mutations_scan_ranges_min_proportion); plane_rows and bytes stay those of ALL its rows */
+                             (silo_gpu_mutations_scan_ranges_min_proportion); ", ends" behind either where a range of the launch counts the
+                             end runs of the gap symbol (k_scan_sliced leaves the covered rows out, k_scan_escapes_sliced streams the end
+                             events and the residual keys); plane_rows and bytes stay those of ALL its rows */
    uint64_t plane_rows;   /* plane rows a k_scan_sliced launch streams (0 for the other kernels) */
    uint64_t bytes;        /* what the launch has to read, each byte once: plane rows + filter rows; 8 bytes per escape key (+ a filter
                              slice per block); 12 bytes per run of the missing symbol; 8 per sparse key */

@@ -28,6 +28,29 @@ constexpr uint64_t LAUNCH_COST_BYTES = 192ull << 20;
 // one-hot rows: not at all / a row for every stored symbol / the most numerous symbol derived (LAYOUT_IMPLICIT)
 enum OneHotMode : int { ONE_HOT_OFF = 0, ONE_HOT_ROWS = 1, ONE_HOT_IMPLICIT = 2 };
 
+/// May the Mutations scan count the one-hot row of the gap symbol at a position from the alignment's end runs instead of
+/// reading it?  The position has to derive a symbol (LAYOUT_IMPLICIT: only then does the scan complete its tables at the end),
+/// another one than the gap symbol, and the row's bits outside every end run — `residual` of them, each a key of the scan —
+/// have to cost less than the row by the rule the layouts are chosen by.
+inline bool endRunCovers(uint8_t layout, uint8_t derived_symbol, uint32_t gap_symbol, uint64_t residual, uint64_t row_bytes, uint64_t key_cost = KEY_COST_BYTES) {
+   return (layout & LAYOUT_ONE_HOT) != 0 && (layout & LAYOUT_IMPLICIT) != 0 && derived_symbol != gap_symbol && key_cost * residual < row_bytes;
+}
+
+/// The residual bits of a position's gap row: its set bits less the rows inside an end run there.  ends_before[p] = sequences
+/// whose leading run ends at or before p (lead <= p), trails_from[p] = sequences whose trailing run has begun by p
+/// (trail_start <= p); a sequence that is the gap symbol throughout has lead = trail_start = P and counts once.
+inline uint64_t endRunResidual(uint64_t row_bits, uint64_t sequences, uint64_t ends_before, uint64_t trails_from) {
+   const uint64_t inside = sequences - ends_before + trails_from;
+   return row_bits >= inside ? row_bits - inside : 0;
+}
+
+/// Does the end stream of a store pay at all?  A scan that counts end runs streams every end event and every residual key, each
+/// at the cost of a key, whatever the number of rows it no longer reads: a gene with four covered rows would pay 10 M events for
+/// them.  By the same rule as everything else: the keys have to cost less than the rows they replace.
+inline bool endRunsPay(uint64_t covered_rows, uint64_t row_bytes, uint64_t end_events, uint64_t residual_keys, uint64_t key_cost = KEY_COST_BYTES) {
+   return key_cost * (end_events + residual_keys) < covered_rows * row_bytes;
+}
+
 /// The layout of every position of a sequence store (see "The adaptive code planes" above) from the unfiltered totals:
 /// code_map[p][0] = code planes (| LAYOUT_IDENTITY) or one-hot rows (| LAYOUT_ONE_HOT, | LAYOUT_IMPLICIT), code_map[p][c] = the
 /// scan symbol of code c (of one-hot row c - 1); escape_count[p][s] = rows of symbol s at p that get neither.  A small dynamic

@@ -2,7 +2,7 @@
 // by-value argument structs of their kernels, the pieces a scan is cut into, and the one host function each pass exports.
 //   silo_gpu_scan.hip          the scan over ranges: pieces, timing log, scratch pool, side streams, the C entries
 //   silo_gpu_scan_planes.hip   the plane rows: k_scan_sliced, k_scan_sliced_rowwave, k_compact_filter (prepare), k_scan_gather
-//   silo_gpu_scan_keys.hip     the escape keys and the gap events: k_scan_escapes_sliced, k_scan_escapes, k_scan_escapes_overflow
+//   silo_gpu_scan_keys.hip     the escape keys, the gap events, the end events: k_scan_escapes_sliced, k_scan_escapes, k_scan_escapes_overflow
 //   silo_gpu_scan_derived.hip  derived symbols: k_scan_missing_runs, k_sum_run_parts, k_count_sparse_keys, k_finish_scan
 // A kernel lives in the anonymous namespace of its file and is launched only from there.
 #pragma once
@@ -22,6 +22,8 @@ constexpr uint32_t SCAN_MAX_RANGES = 32;
 constexpr uint32_t SPARSE_COUNTER_STRIDE = 64;
 constexpr uint32_t SECTOR_WORDS = 8;        // a 64-byte sector of a filter row
 constexpr uint32_t COMPACT_THREADS = 1024;   // words per block of k_compact_filter
+// rows of a run of one-hot rows whose live rows a block of k_scan_sliced can list in LDS (4 KiB); a run of more rows is scanned in full
+constexpr uint32_t ROW_LIST_MAX = 1024;
 
 /// Which scan serves a filter, from the counters k_compact_filter left for it: [0] sectors with a set bit, [1] stretches of
 /// COMPACT_THREADS words with one.  The gather pays while the sectors fit its list AND cost less than the column tiles the
@@ -54,6 +56,9 @@ struct ScanBatchArgs {
    const uint8_t* code_map[SCAN_MAX_RANGES];
    uint32_t target_base[SCAN_MAX_RANGES];
    uint32_t out_symbols;
+   // one-hot rows of a range that counts the gap symbol's end runs (DerivedPlan::end_runs): one byte per row from the range's first
+   // row on (SeqStoreHost::Layout::d_row_covered), non-zero = the row is not read, by k_scan_sliced and k_scan_gather alike; else nullptr
+   const uint8_t* row_covered[SCAN_MAX_RANGES];
 };
 
 // what a run of plane rows holds
@@ -85,6 +90,7 @@ struct ScanPiece {
    uint32_t target_base;      // one-hot rows: first position of the piece * n_scan
    const uint32_t* row_heaviest;  // one-hot rows: the bounds of the piece's rows from its first row on (RowPruneArgs), or nullptr
    const uint32_t* row_without;
+   const uint8_t* row_covered;    // one-hot rows of a range that counts end runs: the flags of the piece's rows from its first row on, or nullptr
    uint32_t* counts[SILO_GPU_MAX_SCAN_BATCH];  // tables at the piece's first position
 };
 
@@ -95,7 +101,9 @@ enum ScanLayout { SCAN_2_PLANES = 0, SCAN_3_PLANES_MAPPED, SCAN_FULL_NUCLEOTIDE,
 constexpr uint32_t DERIVED_MAX_RANGES = 16;
 
 /// A range of a scan with derived symbols.  Its private tables: per filter `stride` words of scratch — counts[n][n_scan], then
-/// diff[n + 1] (selected rows entering / leaving a run of the missing symbol at each position), then ambiguous[n].
+/// diff[n + 1] (selected rows entering / leaving a run of the missing symbol at each position), then ambiguous[n]; with gap events
+/// gaps[n][2] instead of the two, and behind it, in a range that counts end runs (position_covered != nullptr), ends[n][2]: the
+/// selected rows whose leading run of the gap symbol ends ([0]) and whose trailing run begins ([1]) at each position.
 struct DerivedRange {
    uint32_t* scratch;        // of filter 0
    uint32_t stride;          // words per filter
@@ -103,6 +111,8 @@ struct DerivedRange {
    uint32_t n_scan;
    uint32_t pos_begin;
    const uint8_t* code_map;  // of the store's position 0; nullptr: no position of this store derives a symbol
+   const uint8_t* position_covered;  // of the store's position 0: the gap symbol's cell takes its end runs from ends[n][2]; nullptr: no end runs
+   uint32_t end_symbol;              // the gap symbol's scan index
    const uint64_t* run_keys;
    const uint32_t* run_ends;
    const uint32_t* run_slice_first;  // [n_run_slices + 1]
@@ -135,6 +145,14 @@ struct DerivedPlan {
    // range, seqstore null where it has none) and none of the passes of the runs and the sparse keys runs
    bool events = false;
    std::vector<ScanRange> gap_ranges;
+   // Which ranges count the end runs of the gap symbol instead of reading its covered rows (SeqStoreHost::Layout::d_ends_sliced):
+   // decided ONCE per scan and range (usesEndRuns), whatever the proportions, the partitions or the entry — the counts are exact.
+   // The row kernel and the gather kernel leave the covered rows out, the escape pass counts the end events into end_ranges (counts =
+   // the range's ends tables; seqstore null where the range reads its rows) and the residual keys into the private tables,
+   // k_finish_scan adds the end runs to the gap symbol's cell at the covered positions.
+   std::vector<uint8_t> end_runs;
+   std::vector<ScanRange> end_ranges;
+   bool ends_apart = false;  // SILO_GPU_TUNE_END_RUNS = 1: the end events and residual keys in a launch of their own behind the row launch
    std::vector<std::array<uint64_t, DERIVED_MAX_RANGES>> run_counts;  // [launch][range] runs of the missing symbol of the range's store (for the timing log)
    size_t table_words = 0;       // zeroed by the prepare step: the tables, then the flags of the run parts
    size_t part_words = 0;        // behind them, not zeroed: the run parts (k_scan_missing_runs -> k_sum_run_parts)
@@ -168,7 +186,8 @@ int scanPiecesGather(const std::vector<ScanPiece> (&pieces)[N_SCAN_LAYOUTS], con
    const uint32_t* sparse_sectors, uint32_t sparse_capacity, const uint32_t* sector_index, uint32_t stride, hipStream_t hip_stream);
 
 // silo_gpu_scan_keys.hip
-int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream, const std::vector<ScanRange>* gaps, const ScanPruning* pruning);
+int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream, const std::vector<ScanRange>* gaps, const ScanPruning* pruning,
+   const std::vector<ScanRange>* ends = nullptr, bool only_ends = false);
 
 // silo_gpu_scan_derived.hip
 void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, DerivedPlan& plan);

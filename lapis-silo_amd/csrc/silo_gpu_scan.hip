@@ -42,9 +42,12 @@ ScanLayout layoutOfRun(const SeqStoreDev& dev, uint32_t bits, bool identity, boo
    return dev.n_bits == 3 ? SCAN_FULL_NUCLEOTIDE : SCAN_FULL_AMINO_ACID;
 }
 
-/// Cuts the ranges along the runs of their stores; pieces[layout] collects what one kind of launch takes.
-void cutIntoPieces(const std::vector<ScanRange>& ranges, uint32_t q_count, std::vector<ScanPiece> (&pieces)[N_SCAN_LAYOUTS]) {
+/// Cuts the ranges along the runs of their stores; pieces[layout] collects what one kind of launch takes.  end_runs (or nullptr):
+/// per range, whether the scan counts the end runs of the gap symbol there (DerivedPlan::end_runs) — its runs of one-hot rows
+/// then carry the flags of the rows to leave out.
+void cutIntoPieces(const std::vector<ScanRange>& ranges, uint32_t q_count, std::vector<ScanPiece> (&pieces)[N_SCAN_LAYOUTS], const std::vector<uint8_t>* end_runs) {
    for (const ScanRange& range : ranges) {
+      const bool covered = end_runs != nullptr && (*end_runs)[static_cast<size_t>(&range - ranges.data())] != 0;
       const SeqStoreHost& seqstore = *range.seqstore;
       const SeqStoreDev& dev = seqstore.dev;
       const auto add = [&](uint32_t begin, uint32_t end, uint32_t bits, bool identity, bool one_hot) {
@@ -66,6 +69,7 @@ void cutIntoPieces(const std::vector<ScanRange>& ranges, uint32_t q_count, std::
                piece.row_heaviest = seqstore.layout.d_row_heaviest + first_row;
                piece.row_without = seqstore.layout.d_row_without + first_row;
             }
+            piece.row_covered = covered ? seqstore.layout.d_row_covered + first_row : nullptr;
             if (piece.n_positions == 0) {
                return;  // positions whose only stored symbol is derived: no rows
             }
@@ -291,8 +295,9 @@ int forkSidePasses(
    if (!any_escapes && derived == nullptr) {
       return SILO_GPU_OK;
    }
-   if (derived != nullptr && derived->events) {  // one pass over the keys and the gap events, on the caller's stream
-      return scanEscapes(ranges, filters, q_count, hip_stream, &derived->gap_ranges, pruning);
+   if (derived != nullptr && derived->events) {  // one pass over the keys, the gap events and the end events, on the caller's stream
+      // (SILO_GPU_TUNE_END_RUNS = 1: the end events in a launch of their own behind the row launch — scanRanges; measured, not faster)
+      return scanEscapes(ranges, filters, q_count, hip_stream, &derived->gap_ranges, pruning, derived->ends_apart ? nullptr : &derived->end_ranges);
    }
    const int mode = g_tune_side_stream.load();
    SideStreams* side = mode == 2 ? nullptr : sideStreams();
@@ -350,7 +355,7 @@ int silo_gpu_detail::scanRanges(
    const bool routing = divisor >= 0;
    if (!routing && !any_derived) {
       std::vector<ScanPiece> pieces[N_SCAN_LAYOUTS];
-      cutIntoPieces(caller_ranges, q_count, pieces);
+      cutIntoPieces(caller_ranges, q_count, pieces, nullptr);
       int rc = forkSidePasses(caller_ranges, filters, q_count, nullptr, hip_stream, nullptr);
       if (rc == SILO_GPU_OK) {
          rc = scanPiecesDense(pieces, any_store, filters, q_count, nullptr, 0, hip_stream, nullptr);
@@ -371,7 +376,7 @@ int silo_gpu_detail::scanRanges(
    }
    const std::vector<ScanRange>& ranges = any_derived ? plan.private_ranges : caller_ranges;
    std::vector<ScanPiece> pieces[N_SCAN_LAYOUTS];
-   cutIntoPieces(ranges, q_count, pieces);
+   cutIntoPieces(ranges, q_count, pieces, any_derived ? &plan.end_runs : nullptr);  // (planDerived decided where the end runs are counted)
    // what the passes may leave out (ScanPruning: the one place that decides it)
    bool some_proportion = false;
    for (uint32_t q = 0; min_proportion != nullptr && q < q_count; ++q) {
@@ -394,6 +399,9 @@ int silo_gpu_detail::scanRanges(
    if (rc == SILO_GPU_OK) {
       // (the rows are left out where the keys are: one pass over keys and gap events, the tables completed by k_finish_scan)
       rc = scanPiecesDense(pieces, any_store, filters, q_count, routing ? counters : nullptr, capacity, hip_stream, pruned);
+   }
+   if (rc == SILO_GPU_OK && any_derived && plan.events && plan.ends_apart) {
+      rc = scanEscapes(ranges, filters, q_count, hip_stream, &plan.gap_ranges, nullptr, &plan.end_ranges, true);
    }
    if (rc == SILO_GPU_OK && routing) {
       rc = scanPiecesGather(pieces, any_store, filters, q_count, counters, capacity, scratch->sector_index, stride, hip_stream);
@@ -601,6 +609,18 @@ int silo_gpu_store_scan_prunable_rows(
       }
    }
    return SILO_GPU_OK;
+}
+
+uint64_t silo_gpu_store_scan_covered_rows(const silo_gpu_store* store, uint32_t seqstore_id) {
+   return store == nullptr || seqstore_id >= store->seqstores.size() ? 0 : store->seqstores[seqstore_id].layout.covered_rows;
+}
+
+uint64_t silo_gpu_store_scan_end_events(const silo_gpu_store* store, uint32_t seqstore_id) {
+   return store == nullptr || seqstore_id >= store->seqstores.size() ? 0 : store->seqstores[seqstore_id].layout.end_events;
+}
+
+uint64_t silo_gpu_store_scan_residual_keys(const silo_gpu_store* store, uint32_t seqstore_id) {
+   return store == nullptr || seqstore_id >= store->seqstores.size() ? 0 : store->seqstores[seqstore_id].layout.residual_keys;
 }
 
 uint64_t silo_gpu_store_scan_escapes(const silo_gpu_store* store, uint32_t seqstore_id) {

@@ -264,10 +264,13 @@ __global__ __launch_bounds__(256) void k_count_sparse_keys(const DerivedArgs arg
 /// derived symbol's count.  The private table is added to the caller's.
 /// EVENTS: the private table holds gaps[n][2] (the selected rows' gap events that start and end at a position) behind the
 /// counts instead of diff and ambiguous; the rows without a valid symbol at p are the starts up to p less the ends up to p.
+/// A range that counts the end runs of the gap symbol (DerivedRange::position_covered) has ends[n][2] behind that: at a covered
+/// position the gap symbol's cell gets, on top of its residual keys, the selected rows inside an end run — |F| less the lead-end
+/// events up to p plus the trail-start events up to p — before the derived count is formed; elsewhere ends is ignored.
 template <bool EVENTS>
 __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedArgs args) {
-   __shared__ uint32_t s_before[DERIVED_THREADS / 64];
-   __shared__ uint32_t s_own[DERIVED_THREADS / 64];
+   __shared__ uint32_t s_before[2][DERIVED_THREADS / 64];  // [0] the gaps, [1] the end runs
+   __shared__ uint32_t s_own[2][DERIVED_THREADS / 64];
    const uint32_t q = blockIdx.y;
    const uint32_t lane = threadIdx.x & 63u;
    const uint32_t wave = threadIdx.x >> 6;
@@ -290,35 +293,52 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
          return diff[j];
       }
    };
+   // a range that counts end runs: trailing runs beginning less leading runs ending at j — summed up to p and added to |F|, the rows
+   // of the filter inside an end run at p.  Both sums are taken in ONE sweep over the positions before the block's (the sweep is
+   // a chain of memory latencies: 16.3 us for the genome, 19.7 with a sweep per sum, 10.9 without the end runs)
+   const bool with_ends = EVENTS && range.code_map != nullptr && range.position_covered != nullptr;  // (uniform)
+   const uint32_t* __restrict__ ends = diff + 2u * static_cast<size_t>(n);
+   const auto endAt = [&](uint32_t j) { return ends[2u * j + 1u] - ends[2u * j]; };
    uint32_t without_symbol = 0;  // rows of the filter that have no valid symbol at p
+   uint32_t in_end_run = 0;      // rows of the filter inside a leading or trailing run of the gap symbol at p
    if (range.code_map != nullptr) {  // (uniform)
-      uint32_t before = 0;
+      uint32_t before[2] = {0, 0};
       for (uint32_t j = threadIdx.x; j < first_position; j += DERIVED_THREADS) {
-         before += diffAt(j);
+         before[0] += diffAt(j);
+         before[1] += with_ends ? endAt(j) : 0u;
       }
-      const uint32_t scanned = waveSumToLane63(p < n ? diffAt(p) : 0u);  // inclusive over the wave
-      before = waveSumToLane63(before);
-      if (lane == 63u) {
-         s_before[wave] = before;
-         s_own[wave] = scanned;
+      const uint32_t scanned[2] = {waveSumToLane63(p < n ? diffAt(p) : 0u), waveSumToLane63(with_ends && p < n ? endAt(p) : 0u)};  // inclusive over the wave
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+         before[t] = waveSumToLane63(before[t]);
+         if (lane == 63u) {
+            s_before[t][wave] = before[t];
+            s_own[t][wave] = scanned[t];
+         }
       }
       __syncthreads();
-      without_symbol = scanned;
+      without_symbol = scanned[0];
+      in_end_run = scanned[1];
       for (uint32_t k = 0; k < DERIVED_THREADS / 64; ++k) {
-         without_symbol += s_before[k] + (k < wave ? s_own[k] : 0u);
+         without_symbol += s_before[0][k] + (k < wave ? s_own[0][k] : 0u);
+         in_end_run += s_before[1][k] + (k < wave ? s_own[1][k] : 0u);
       }
       if (!EVENTS && p < n) {
          without_symbol += ambiguous[p];
       }
+      in_end_run += args.counters[q * SPARSE_COUNTER_STRIDE + 2];
    }
    if (p >= n) {
       return;
+   }
+   if (!with_ends || range.position_covered[range.pos_begin + p] == 0) {  // only the covered positions take their gap rows from the end runs: everywhere else the row was read
+      in_end_run = 0;
    }
    uint32_t* __restrict__ out = range.caller_counts[q] + static_cast<size_t>(p) * n_scan;
    const uint32_t* __restrict__ cell = counts + static_cast<size_t>(p) * n_scan;
    uint32_t others = 0;
    for (uint32_t symbol = 0; symbol < n_scan; ++symbol) {
-      const uint32_t count = cell[symbol];
+      const uint32_t count = cell[symbol] + (symbol == range.end_symbol ? in_end_run : 0u);
       others += count;
       if (count != 0) {
          out[symbol] += count;  // scans of one table are ordered on a stream: no atomic needed
@@ -341,6 +361,23 @@ uint32_t runBlocksPerSlice(const DerivedArgs& launch, uint32_t q_count) {
    return std::min<uint32_t>(8, std::max<uint32_t>(1, 240 / run_units));
 }
 
+/// Does a scan of `range` count the end runs of the gap symbol instead of reading its covered rows?  The store has them, the knob
+/// (SILO_GPU_TUNE_END_RUNS, read once per scan) allows it, and every run of one-hot rows of the range fits the row kernel's list of live rows.
+bool usesEndRuns(const ScanRange& range, int knob) {
+   const SeqStoreHost::Layout& layout = range.seqstore->layout;
+   if (layout.d_ends_sliced == nullptr || layout.d_row_covered == nullptr || knob < 0) {
+      return false;
+   }
+   for (const SeqStoreHost::Run& run : layout.runs) {
+      const uint32_t begin = std::max(run.begin, range.pos_begin);
+      const uint32_t end = std::min(run.end, range.pos_end);
+      if (run.one_hot && begin < end && layout.row_of[end] - layout.row_of[begin] > ROW_LIST_MAX) {
+         return false;
+      }
+   }
+   return true;
+}
+
 }  // namespace
 
 namespace silo_gpu_detail {
@@ -355,6 +392,10 @@ void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& rang
       plan.events = plan.events && (!range.seqstore->layout.has_implicit || range.seqstore->layout.gap_stream);
    }
    plan.gap_ranges.assign(plan.events ? ranges.size() : 0, ScanRange{});
+   const int end_knob = g_tune_end_runs.load();
+   plan.ends_apart = end_knob == 1;
+   plan.end_runs.assign(ranges.size(), 0);
+   plan.end_ranges.assign(ranges.size(), ScanRange{});
    size_t offset = 0;
    for (size_t r = 0; r < ranges.size(); ++r) {
       const ScanRange& range = ranges[r];
@@ -365,8 +406,13 @@ void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& rang
       entry.n_positions = n;
       entry.n_scan = seqstore.dev.n_scan;
       entry.pos_begin = range.pos_begin;
-      // counts[n][n_scan], then gaps[n][2] (the events: starts, ends) or diff[n + 1] and ambiguous[n]
-      const size_t rows_without = plan.events ? 2u * static_cast<size_t>(n) : static_cast<size_t>(n) + 1 + n;
+      // counts[n][n_scan], then gaps[n][2] (the events: starts, ends) — and ends[n][2] where the range counts end runs — or
+      // diff[n + 1] and ambiguous[n]
+      const bool end_runs = plan.events && seqstore.layout.has_implicit && usesEndRuns(range, end_knob);
+      plan.end_runs[r] = end_runs ? 1 : 0;
+      entry.position_covered = end_runs ? seqstore.layout.d_position_covered : nullptr;
+      entry.end_symbol = seqstore.layout.end_symbol;
+      const size_t rows_without = plan.events ? (end_runs ? 4u : 2u) * static_cast<size_t>(n) : static_cast<size_t>(n) + 1 + n;
       entry.stride = static_cast<uint32_t>((static_cast<size_t>(n) * seqstore.dev.n_scan + rows_without + 3) / 4 * 4);
       entry.scratch = reinterpret_cast<uint32_t*>(offset * sizeof(uint32_t));  // + the scratch block's tables (bindDerived)
       offset += static_cast<size_t>(entry.stride) * q_count;
@@ -428,6 +474,13 @@ void bindDerived(DerivedPlan& plan, uint32_t* tables, const uint32_t* counters, 
             gap = plan.private_ranges[r];
             for (uint32_t q = 0; q < q_count; ++q) {
                gap.counts[q] = entry.scratch + static_cast<size_t>(q) * entry.stride + static_cast<size_t>(entry.n_positions) * entry.n_scan;
+            }
+         }
+         if (plan.end_runs[r] != 0) {
+            ScanRange& end = plan.end_ranges[r];
+            end = plan.private_ranges[r];
+            for (uint32_t q = 0; q < q_count; ++q) {
+               end.counts[q] = entry.scratch + static_cast<size_t>(q) * entry.stride + static_cast<size_t>(entry.n_positions) * (entry.n_scan + 2u);
             }
          }
       }

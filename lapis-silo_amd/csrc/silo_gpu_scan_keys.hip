@@ -1,6 +1,7 @@
 // silo_gpu_scan_keys.hip — the escape keys of K1, the Mutations scan ("The escape pass", "Keys that cannot reach
 // minProportion"): the rows the plane rows do not carry, one key per (position, symbol, sequence); and, in the same launches, the
-// gap events of a store with derived symbols.
+// gap events of a store with derived symbols and — where a range counts them — the end events of the gap symbol and the residual
+// keys of its covered rows ("The gap symbol's end runs instead of its rows").
 //
 // Kernels:
 //   k_scan_escapes_sliced<FILTERS>   the slice-major 4-byte keys against a slice of 1, 2, 4 or 8 filters in LDS
@@ -527,9 +528,13 @@ namespace silo_gpu_detail {
 /// null where it has none) also the gap events of their stores, in the same launches.
 /// With `gaps` and pruning->keys the pass may skip the granules of keys that no Mutations row of the filters' proportions can come
 /// from, where the store has the bounds for it (EscapeSliceArgs::counters); the gap events and the overflow keys are always counted.
+/// With `ends` (one entry per range: counts = the range's ends tables, seqstore null where the range reads its rows) two more
+/// entries per such range in the same launches: the end events of the gap symbol, counted like gap events, and the residual keys
+/// of the covered rows, counted into the range's count tables like escape keys; neither is ever skipped.  only_ends: nothing but
+/// these entries (SILO_GPU_TUNE_END_RUNS = 1: the end events in a launch of their own, for comparisons).
 int scanEscapes(
    const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream, const std::vector<ScanRange>* gaps,
-   const ScanPruning* pruning
+   const ScanPruning* pruning, const std::vector<ScanRange>* ends, bool only_ends
 ) {
    // the ranges whose stores have slice-major keys go ESCAPE_MAX_RANGES at a time into one launch of k_scan_escapes_sliced
    EscapeSliceArgs sliced{};
@@ -542,6 +547,7 @@ int scanEscapes(
    uint32_t n_sliced = 0;
    std::array<uint32_t, ESCAPE_MAX_RANGES> most_keys{};  // of one (range, slice)
    uint64_t total_keys = 0;  // of the ranges of the launch
+   bool end_entries = false;  // the launch has end events or residual keys (", ends" behind the kernel's name in the timing log)
    const auto launchSliced = [&]() -> int {
       if (n_sliced == 0) {
          return SILO_GPU_OK;
@@ -574,7 +580,7 @@ int scanEscapes(
       for (uint32_t k = 0; k < n_sliced; ++k) {
          bounds = bounds || sliced.ranges[k].heaviest != nullptr;
       }
-      std::snprintf(name, sizeof(name), "k_scan_escapes_sliced<%u>%s", per_block, bounds ? ", pruning" : "");
+      std::snprintf(name, sizeof(name), "k_scan_escapes_sliced<%u>%s%s", per_block, bounds ? ", pruning" : "", end_entries ? ", ends" : "");
       // bytes: the keys and gap events (4 each) once per pass of `per_block` filters, plus a 16 KiB filter slice per block and filter
       ScanLaunchTiming* timing = startLaunchTiming(
          name, 0, total_keys * sizeof(uint32_t) * grid.z + static_cast<uint64_t>(grid.x) * q_count * ESCAPE_SLICE_WORDS32 * sizeof(uint32_t), q_count,
@@ -591,6 +597,7 @@ int scanEscapes(
       n_sliced = 0;
       most_keys.fill(0);
       total_keys = 0;
+      end_entries = false;
       return SILO_GPU_OK;
    };
    // one entry of a launch: the packed keys (or gap events) of a store over [key_from, pos_end) of its positions
@@ -633,9 +640,37 @@ int scanEscapes(
       }
       return addSliced((*gaps)[r], layout.gap_slices, layout.d_gaps_sliced, layout.d_gap_granule_base, layout.d_gap_slice_first, layout.gap_slice_first, 2, 0);
    };
+   // the end events of a range that counts the end runs of the gap symbol — from position 0 on, clamped like the gap events: a
+   // leading run that ended before the range's first position has ended there — and the residual keys of its covered rows
+   const auto addEnds = [&](size_t r) -> int {
+      const SeqStoreHost::Layout& layout = ranges[r].seqstore->layout;
+      if (ends == nullptr || (*ends)[r].seqstore == nullptr || layout.d_ends_sliced == nullptr) {
+         return SILO_GPU_OK;
+      }
+      if (const int rc = addSliced((*ends)[r], layout.end_slices, layout.d_ends_sliced, layout.d_end_granule_base, layout.d_end_slice_first, layout.end_slice_first, 2, 0);
+          rc != SILO_GPU_OK) {
+         return rc;
+      }
+      end_entries = true;
+      if (layout.d_residual_sliced == nullptr) {
+         return SILO_GPU_OK;
+      }
+      const int rc = addSliced(
+         ranges[r], layout.end_slices, layout.d_residual_sliced, layout.d_residual_granule_base, layout.d_residual_slice_first, layout.residual_slice_first,
+         ranges[r].seqstore->dev.n_scan, ranges[r].pos_begin
+      );
+      end_entries = true;
+      return rc;
+   };
    for (size_t r = 0; r < ranges.size(); ++r) {
       const ScanRange& range = ranges[r];
       const SeqStoreHost::Layout& layout = range.seqstore->layout;
+      if (const int rc = addEnds(r); rc != SILO_GPU_OK) {
+         return rc;
+      }
+      if (only_ends) {
+         continue;
+      }
       const uint32_t begin = layout.built && layout.d_escapes != nullptr ? layout.escape_first[range.pos_begin] : 0;
       const uint32_t count = layout.built && layout.d_escapes != nullptr ? layout.escape_first[range.pos_end] - begin : 0;
       if (count == 0) {

@@ -44,9 +44,6 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 constexpr int SCAN_WAVES = SCAN_THREADS / 64;
 
-// rows of a range whose live rows a block can list in LDS (4 KiB); a range of more rows is scanned in full
-constexpr uint32_t ROW_LIST_MAX = 1024;
-
 // positions whose partial counts sit in LDS between two flushes: ~16 KiB of LDS whatever NSYM * Q is
 template <int NSYM, int Q>
 constexpr int scanPositionsBatch() {
@@ -139,35 +136,48 @@ __global__ __launch_bounds__(SCAN_THREADS, (scanMinBlocks<BITS, NSYM, WPT, Q>())
       // EVERY filter this launch counts allows it (granulePrunable, the escape pass's rule; a filter routed to the gather kernel is
       // counted exactly there and has no say) — while the filter tile is on its way; the barrier below publishes the list.
       // Lane l looks at rows l, l + 64, ...: a row's place in the list is the live rows of the ballots before plus those of
-      // the lanes below in its own.
+      // the lanes below in its own.  A range that counts the end runs of the gap symbol (batch.row_covered) lists its rows as well,
+      // pruning or not: the covered rows are left out for every filter — the escape pass counts them from the end events.
       if constexpr (KIND == KIND_ROWS) {
-         if (rows.heaviest[range] != nullptr && n_rows <= ROW_LIST_MAX && tid < 64u) {  // (uniform per wave)
+         const bool by_bounds = rows.heaviest[range] != nullptr;       // (uniform)
+         const uint8_t* __restrict__ covered = batch.row_covered[range];  // (uniform)
+         if ((by_bounds || covered != nullptr) && n_rows <= ROW_LIST_MAX && tid < 64u) {  // (uniform per wave)
             constexpr uint32_t PER_LANE = ROW_LIST_MAX / 64u;
             uint32_t heaviest[PER_LANE];
             uint32_t without[PER_LANE];
+            // the flags first, folded into one register before the bounds are asked for (flags and bounds in flight together
+            // would be 48 registers, more than the pipeline of the narrow instantiations needs anywhere else)
+            uint32_t left_out = 0;  // bit k: row k * 64 + tid is covered
+            if (covered != nullptr) {
+#pragma unroll
+               for (uint32_t k = 0; k < PER_LANE; ++k) {
+                  left_out |= (covered[min(k * 64u + tid, n_rows - 1u)] != 0 ? 1u : 0u) << k;
+               }
+            }
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (uint32_t k = 0; k < PER_LANE; ++k) {  // (unconditional, clamped: all in flight at once)
                const uint32_t row = min(k * 64u + tid, n_rows - 1u);
-               heaviest[k] = rows.heaviest[range][row];
-               without[k] = rows.without[range][row];
+               heaviest[k] = by_bounds ? rows.heaviest[range][row] : 0xFFFFFFFFu;
+               without[k] = by_bounds ? rows.without[range][row] : 0xFFFFFFFFu;
             }
             uint32_t cardinality[Q];
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
-               cardinality[q] = rows.counters[q * SPARSE_COUNTER_STRIDE + 2u];
+               cardinality[q] = by_bounds ? rows.counters[q * SPARSE_COUNTER_STRIDE + 2u] : 0u;
             }
             uint32_t n_live = 0;
 #pragma unroll
             for (uint32_t k = 0; k < PER_LANE; ++k) {
                const uint32_t row = k * 64u + tid;
-               bool skip = true;
+               bool skip = by_bounds;
 #pragma unroll
                for (int q = 0; q < Q; ++q) {
                   if (dense[q]) {
                      skip = skip && granulePrunable(cardinality[q], without[k], heaviest[k], rows.min_proportion[q]);
                   }
                }
-               const bool live = row < n_rows && !skip;
+               const bool live = row < n_rows && !skip && ((left_out >> k) & 1u) == 0;
                const uint64_t live_lanes = __ballot(live);
                if (live) {
                   s_live_rows[n_live + static_cast<uint32_t>(__popcll(live_lanes & ((uint64_t{1} << tid) - 1u)))] = row;
@@ -188,7 +198,7 @@ __global__ __launch_bounds__(SCAN_THREADS, (scanMinBlocks<BITS, NSYM, WPT, Q>())
    [[maybe_unused]] uint32_t n_live = n_rows;
    bool listed = false;  // (uniform) the block walks the list of live rows, not rows 0 .. n_rows
    if constexpr (KIND == KIND_ROWS) {
-      listed = rows.heaviest[range] != nullptr && n_rows <= ROW_LIST_MAX;
+      listed = (rows.heaviest[range] != nullptr || batch.row_covered[range] != nullptr) && n_rows <= ROW_LIST_MAX;
       if (listed) {
          // The position groups of the range take even shares of the LIVE pairs, not of all pairs: the rows left out cluster (the
          // flanks of an alignment's ragged ends), all blocks of a launch are resident together, and the launch ends with its
@@ -532,6 +542,21 @@ __global__ __launch_bounds__(256, (BITS <= 3 ? (NSYM <= 5 ? 5 : 4) : 4)) void k_
    const uint32_t* index = sector_index + static_cast<size_t>(q) * capacity;
    const uint64_t* filter = batch.filters[q];
    const size_t position_stride = static_cast<size_t>(BITS) * row_words;
+   // one-hot rows of a range that counts the end runs of the gap symbol: the covered rows are left out here as k_scan_sliced
+   // leaves them out (the same flags; uniform per wave)
+   [[maybe_unused]] uint32_t left_out = 0;  // bit g: row pos_begin + g is covered
+   if constexpr (KIND == KIND_ROWS) {
+      if (batch.row_covered[range] != nullptr) {
+#pragma unroll
+         for (int g = 0; g < POSG; ++g) {
+            left_out |= (batch.row_covered[range][min(pos_begin + g, last_pos)] != 0 ? 1u : 0u) << g;
+         }
+         left_out = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(left_out)));
+         if (left_out == (1u << POSG) - 1u) {
+            return;
+         }
+      }
+   }
 
    uint32_t acc[POSG][NSYM];
 #pragma unroll
@@ -551,7 +576,7 @@ __global__ __launch_bounds__(256, (BITS <= 3 ? (NSYM <= 5 ? 5 : 4) : 4)) void k_
          const uint64_t* base = planes + static_cast<size_t>(min(pos_begin + g, last_pos)) * position_stride + w;
 #pragma unroll
          for (int bit = 0; bit < BITS; ++bit) {
-            bits[g][bit] = base[static_cast<size_t>(bit) * row_words];
+            bits[g][bit] = KIND == KIND_ROWS && ((left_out >> g) & 1u) != 0 ? 0ull : base[static_cast<size_t>(bit) * row_words];
          }
       }
 #pragma unroll
@@ -658,12 +683,14 @@ int launchSlicedScan(ScanBatchArgs& batch, const RowPruneArgs& rows, uint32_t ro
       for (uint32_t r = 0; r < batch.n_ranges; ++r) {
          plane_rows += KIND == KIND_ROWS ? batch.n_positions[r] : static_cast<uint64_t>(batch.n_positions[r]) * BITS;
       }
-      bool bounds = false;
+      bool bounds = false, ends = false;
       for (uint32_t r = 0; r < batch.n_ranges; ++r) {
          bounds = bounds || (KIND == KIND_ROWS && rows.heaviest[r] != nullptr);
+         ends = ends || (KIND == KIND_ROWS && batch.row_covered[r] != nullptr);
       }
       char name[64];
-      std::snprintf(name, sizeof(name), "k_scan_sliced<%d, %d, %d, %u, %d>%s", BITS, NSYM, wide ? 8 : 4, wide ? 1u : std::min(q_count, 8u), KIND, bounds ? ", pruning" : "");
+      std::snprintf(name, sizeof(name), "k_scan_sliced<%d, %d, %d, %u, %d>%s%s", BITS, NSYM, wide ? 8 : 4, wide ? 1u : std::min(q_count, 8u), KIND, bounds ? ", pruning" : "",
+                    ends ? ", ends" : "");
       timing = startLaunchTiming(name, plane_rows, (plane_rows + q_count) * row_words * sizeof(uint64_t), q_count, grid.x, hip_stream);
    }
 #define SILO_LAUNCH_SLICED(WPT, Q) \
@@ -727,6 +754,7 @@ ScanBatchArgs pieceBatch(
       batch.planes[r] = piece.planes;
       batch.code_map[r] = piece.code_map;
       batch.target_base[r] = piece.target_base;
+      batch.row_covered[r] = piece.row_covered;
       batch.n_positions[r] = piece.n_positions;
       std::copy_n(piece.counts + first_filter, n_filters, batch.counts[r]);
    }

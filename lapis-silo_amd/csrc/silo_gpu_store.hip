@@ -576,6 +576,108 @@ __global__ __launch_bounds__(RUN_BLOCK_THREADS) void k_missing_runs(
    }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The end runs of the gap symbol (SeqStoreHost::Layout::d_ends_sliced).  k_end_runs walks the build-time code planes
+// [P][BITS][Wp] in the manner of k_missing_runs — a wave per word column, a lane per sequence — forward from position 0 and
+// backward from P - 1, each walk stopping when no lane is still inside its run: lead[r] = the length of the maximal prefix of
+// cells whose code is `code` (the gap symbol's), trail_start[r] = the first cell of the maximal suffix of them (P: none; a
+// sequence that is the gap symbol throughout has lead = trail_start = P).  A run ends at the first cell that is anything else.
+// ------------------------------------------------------------------------------------------------
+template <int BITS>
+__global__ __launch_bounds__(RUN_BLOCK_THREADS) void k_end_runs(
+   const uint64_t* __restrict__ planes, uint32_t positions, uint32_t row_words, uint32_t sequence_count, uint32_t code, uint32_t* __restrict__ lead,
+   uint32_t* __restrict__ trail_start
+) {
+   const uint32_t lane = threadIdx.x & 63u;
+   const uint32_t word = blockIdx.x * (RUN_BLOCK_THREADS / 64) + (threadIdx.x >> 6);
+   if (word >= row_words) {
+      return;  // (uniform per wave)
+   }
+   const uint32_t sequence = word * 64u + lane;
+   const auto hasCode = [&](uint32_t p) {
+      const uint64_t* base = planes + static_cast<size_t>(p) * BITS * row_words + word;
+      bool match = true;
+#pragma unroll
+      for (int bit = 0; bit < BITS; ++bit) {
+         match = match && ((base[static_cast<size_t>(bit) * row_words] >> lane) & 1ull) == ((code >> bit) & 1u);
+      }
+      return match;
+   };
+   bool inside = sequence < sequence_count;
+   uint32_t n_lead = 0;
+   for (uint32_t p = 0; p < positions && __ballot(inside) != 0; ++p) {
+      inside = inside && hasCode(p);
+      n_lead += inside ? 1u : 0u;
+   }
+   inside = sequence < sequence_count && n_lead < positions;
+   uint32_t n_trail = 0;
+   for (uint32_t p = positions; p-- > 0 && __ballot(inside) != 0;) {
+      inside = inside && hasCode(p);
+      n_trail += inside ? 1u : 0u;
+   }
+   if (sequence < sequence_count) {
+      lead[sequence] = n_lead;
+      trail_start[sequence] = positions - n_trail;
+   }
+}
+
+/// hist[lead[r]] += 1 and hist[P + 1 + trail_start[r]] += 1 for every sequence (both arrays [P + 1]).
+__global__ void k_end_histogram(const uint32_t* __restrict__ lead, const uint32_t* __restrict__ trail_start, uint32_t sequence_count, uint32_t positions, uint32_t* __restrict__ hist) {
+   const uint32_t sequence = blockIdx.x * blockDim.x + threadIdx.x;
+   if (sequence < sequence_count) {
+      atomicAdd(&hist[lead[sequence]], 1u);
+      atomicAdd(&hist[positions + 1u + trail_start[sequence]], 1u);
+   }
+}
+
+/// The two end events of every sequence as 8-byte keys: kind 0 at lead, kind 1 at trail_start (those at P are left out later).
+__global__ void k_end_events(const uint32_t* __restrict__ lead, const uint32_t* __restrict__ trail_start, uint32_t sequence_count, uint64_t* __restrict__ events) {
+   const uint32_t sequence = blockIdx.x * blockDim.x + threadIdx.x;
+   if (sequence < sequence_count) {
+      events[2u * static_cast<size_t>(sequence)] = (static_cast<uint64_t>(lead[sequence]) << 37) | sequence;
+      events[2u * static_cast<size_t>(sequence) + 1u] = (static_cast<uint64_t>(trail_start[sequence]) << 37) | (uint64_t{1} << 32) | sequence;
+   }
+}
+
+/// The residual keys of the covered rows: a wave per word column, a lane per sequence, along the list of covered rows
+/// (`rows`: their plane rows, `row_positions`: their positions) — a set bit outside the sequence's end runs gives the key
+/// position << 37 | symbol << 32 | sequence, through one atomic cursor.
+__global__ __launch_bounds__(RUN_BLOCK_THREADS) void k_residual_keys(
+   const uint64_t* __restrict__ planes, uint32_t row_words, uint32_t sequence_count, const uint32_t* __restrict__ rows, const uint32_t* __restrict__ row_positions,
+   uint32_t n_rows, uint32_t symbol, const uint32_t* __restrict__ lead, const uint32_t* __restrict__ trail_start, unsigned long long* __restrict__ cursor,
+   uint64_t* __restrict__ keys, unsigned long long capacity
+) {
+   const uint32_t lane = threadIdx.x & 63u;
+   const uint32_t word = blockIdx.x * (RUN_BLOCK_THREADS / 64) + (threadIdx.x >> 6);
+   if (word >= row_words) {
+      return;  // (uniform per wave)
+   }
+   const uint32_t sequence = word * 64u + lane;
+   const bool real = sequence < sequence_count;
+   const uint32_t own_lead = real ? lead[sequence] : 0u;
+   const uint32_t own_trail = real ? trail_start[sequence] : 0u;
+   for (uint32_t k = 0; k < n_rows; ++k) {
+      const uint64_t bits = planes[static_cast<size_t>(rows[k]) * row_words + word];
+      if (bits == 0) {
+         continue;  // (uniform)
+      }
+      const uint32_t position = row_positions[k];
+      const bool residual = real && ((bits >> lane) & 1ull) != 0 && own_lead <= position && position < own_trail;
+      const uint64_t emitting = __ballot(residual);
+      if (emitting != 0) {
+         unsigned long long first = 0;
+         if (lane == static_cast<uint32_t>(__builtin_ctzll(emitting))) {
+            first = atomicAdd(cursor, static_cast<unsigned long long>(__popcll(emitting)));
+         }
+         first = __shfl(first, __builtin_ctzll(emitting));
+         const unsigned long long slot = first + static_cast<unsigned long long>(__popcll(emitting & ((1ull << lane) - 1ull)));
+         if (residual && slot < capacity) {
+            keys[slot] = (static_cast<uint64_t>(position) << 37) | (static_cast<uint64_t>(symbol) << 32) | sequence;
+         }
+      }
+   }
+}
+
 
 }  // namespace
 
@@ -796,6 +898,16 @@ void silo_gpu_store_destroy(silo_gpu_store* store) {
       (void)hipFree(seqstore.layout.d_gaps_sliced);
       (void)hipFree(seqstore.layout.d_gap_granule_base);
       (void)hipFree(seqstore.layout.d_gap_slice_first);
+      (void)hipFree(seqstore.layout.d_end_lead);
+      (void)hipFree(seqstore.layout.d_end_trail);
+      (void)hipFree(seqstore.layout.d_ends_sliced);
+      (void)hipFree(seqstore.layout.d_end_granule_base);
+      (void)hipFree(seqstore.layout.d_end_slice_first);
+      (void)hipFree(seqstore.layout.d_residual_sliced);
+      (void)hipFree(seqstore.layout.d_residual_granule_base);
+      (void)hipFree(seqstore.layout.d_residual_slice_first);
+      (void)hipFree(seqstore.layout.d_row_covered);
+      (void)hipFree(seqstore.layout.d_position_covered);
       (void)hipFree(seqstore.layout.d_granule_heaviest);
       (void)hipFree(seqstore.layout.d_granule_without);
       (void)hipFree(seqstore.layout.d_row_heaviest);
@@ -1628,6 +1740,202 @@ int buildRowBounds(silo_gpu_store* store, SeqStoreHost& seqstore) {
    return SILO_GPU_OK;
 }
 
+/// The scan symbol of the gap symbol ('-', symbol 0 of both alphabets), or 0xFF where it is no scan symbol of the store.
+uint32_t gapScanSymbol(const SeqStoreDev& dev) {
+   return dev.n_symbols != 0 && dev.kind[0] == PLANE_SCAN ? dev.index[0] : 0xFFu;
+}
+
+void freeEndWalk(SeqStoreHost::Layout& layout) {
+   (void)hipFree(layout.d_end_lead);
+   (void)hipFree(layout.d_end_trail);
+   layout.d_end_lead = nullptr;
+   layout.d_end_trail = nullptr;
+}
+
+/// finalize(), while the build-time planes are still there: where every sequence's leading run of the gap symbol ends and its
+/// trailing run begins (k_end_runs), for buildEndRuns.  Only for a store that derives symbols — no other store gets gap events.
+int walkEndRuns(silo_gpu_store* store, SeqStoreHost& seqstore, bool has_implicit) {
+   const SeqStoreDev& dev = seqstore.dev;
+   SeqStoreHost::Layout& layout = seqstore.layout;
+   const uint32_t n_slices = (store->sequence_count + (1u << ESCAPE_SLICE_SHIFT) - 1) >> ESCAPE_SLICE_SHIFT;
+   const uint32_t symbol = gapScanSymbol(dev);
+   if (!has_implicit || dev.scan == nullptr || symbol == 0xFFu || n_slices > ESCAPE_MAX_SLICES || dev.positions == 0 || layout.d_end_lead != nullptr ||
+       (dev.n_bits != 3 && dev.n_bits != 5)) {
+      return SILO_GPU_OK;
+   }
+   const size_t bytes = static_cast<size_t>(store->sequence_count) * sizeof(uint32_t);
+   hipError_t status = hipMalloc(&layout.d_end_lead, bytes);
+   status = status != hipSuccess ? status : hipMalloc(&layout.d_end_trail, bytes);
+   if (status == hipSuccess) {
+      const uint32_t blocks = (dev.row_words + RUN_BLOCK_THREADS / 64 - 1) / (RUN_BLOCK_THREADS / 64);
+      if (dev.n_bits == 3) {
+         k_end_runs<3><<<blocks, RUN_BLOCK_THREADS>>>(dev.scan, dev.positions, dev.row_words, store->sequence_count, symbol + 1u, layout.d_end_lead, layout.d_end_trail);
+      } else {
+         k_end_runs<5><<<blocks, RUN_BLOCK_THREADS>>>(dev.scan, dev.positions, dev.row_words, store->sequence_count, symbol + 1u, layout.d_end_lead, layout.d_end_trail);
+      }
+      status = hipGetLastError();
+   }
+   status = status != hipSuccess ? status : hipStreamSynchronize(nullptr);  // the planes are released next
+   if (status != hipSuccess) {
+      freeEndWalk(layout);
+      HIP_TRY(status);
+   }
+   return SILO_GPU_OK;
+}
+
+/// The end runs of the gap symbol for the Mutations scan (SeqStoreHost::Layout::d_ends_sliced and what goes with it): which
+/// one-hot rows of the gap symbol the scan may count from the sequences' ends instead (endRunCovers), the end events, and the
+/// residual keys of the covered rows.  Built where the store has its gap events and finalize walked the build-time planes
+/// (walkEndRuns); every other store — two-pass builds, imports, more than ESCAPE_MAX_SLICES slices, nothing derived — has none
+/// and is scanned row by row.  Nothing of the store itself changes.
+int buildEndRuns(silo_gpu_store* store, SeqStoreHost& seqstore) {
+   SeqStoreHost::Layout& layout = seqstore.layout;
+   const SeqStoreDev& dev = seqstore.dev;
+   struct Scratch {
+      SeqStoreHost::Layout& layout;
+      uint32_t* d_hist = nullptr;
+      uint32_t* d_rows = nullptr;  // the covered rows, then their positions
+      uint64_t* d_keys = nullptr;
+      unsigned long long* d_cursor = nullptr;
+      ~Scratch() {
+         (void)hipFree(d_hist);
+         (void)hipFree(d_rows);
+         (void)hipFree(d_keys);
+         (void)hipFree(d_cursor);
+         freeEndWalk(layout);
+      }
+   } scratch{layout};
+   const uint32_t positions = dev.positions;
+   const uint32_t sequences = store->sequence_count;
+   const uint32_t symbol = gapScanSymbol(dev);
+   if (layout.d_end_lead == nullptr || !layout.built || !layout.has_implicit || !layout.gap_stream || layout.d_row_target == nullptr || layout.planes == nullptr ||
+       seqstore.d_totals == nullptr || !seqstore.totals_ready || layout.row_of.size() != static_cast<size_t>(positions) + 1 || layout.d_ends_sliced != nullptr) {
+      return SILO_GPU_OK;
+   }
+   const uint32_t n_slices = (sequences + (1u << ESCAPE_SLICE_SHIFT) - 1) >> ESCAPE_SLICE_SHIFT;
+   // how many leading runs end, and trailing runs begin, at every position
+   std::vector<uint32_t> hist(2 * (static_cast<size_t>(positions) + 1));
+   HIP_TRY(hipMalloc(&scratch.d_hist, hist.size() * sizeof(uint32_t)));
+   HIP_TRY(hipMemset(scratch.d_hist, 0, hist.size() * sizeof(uint32_t)));
+   k_end_histogram<<<(sequences + 255) / 256, 256>>>(layout.d_end_lead, layout.d_end_trail, sequences, positions, scratch.d_hist);
+   HIP_TRY(hipGetLastError());
+   HIP_TRY(hipMemcpy(hist.data(), scratch.d_hist, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   std::vector<uint32_t> totals(static_cast<size_t>(positions) * dev.n_scan);
+   HIP_TRY(hipMemcpy(totals.data(), seqstore.d_totals, totals.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   // the covered rows
+   const uint64_t row_bytes = static_cast<uint64_t>(dev.row_words) * sizeof(uint64_t);
+   const uint64_t key_cost = keyCostOption(store) > 0 ? static_cast<uint64_t>(keyCostOption(store)) : KEY_COST_BYTES;
+   const size_t n_rows = layout.row_of[positions];
+   std::vector<uint8_t> row_covered(n_rows, 0), position_covered(positions, 0);
+   std::vector<uint32_t> covered_list, covered_positions;
+   uint64_t ends_before = 0, trails_from = 0, residual_total = 0, events = 0;
+   for (uint32_t p = 0; p < positions; ++p) {
+      ends_before += hist[p];
+      trails_from += hist[static_cast<size_t>(positions) + 1 + p];
+      events += hist[p] + hist[static_cast<size_t>(positions) + 1 + p];
+      const uint8_t* map = layout.code_map.data() + static_cast<size_t>(p) * CODE_MAP_STRIDE;
+      for (uint32_t row = layout.row_of[p]; (map[0] & LAYOUT_ONE_HOT) != 0 && row < layout.row_of[p + 1]; ++row) {
+         if (map[1 + (row - layout.row_of[p])] != symbol) {
+            continue;
+         }
+         const uint64_t residual = silo_gpu_layout::endRunResidual(totals[static_cast<size_t>(p) * dev.n_scan + symbol], sequences, ends_before, trails_from);
+         if (silo_gpu_layout::endRunCovers(map[0], map[IMPLICIT_SLOT], symbol, residual, row_bytes, key_cost)) {
+            row_covered[row] = 1;
+            position_covered[p] = 1;
+            covered_list.push_back(row);
+            covered_positions.push_back(p);
+            residual_total += residual;
+         }
+      }
+   }
+   if (!silo_gpu_layout::endRunsPay(covered_list.size(), row_bytes, events, residual_total, key_cost) || 2u * static_cast<uint64_t>(sequences) >= (uint64_t{1} << 31) ||
+       residual_total >= (uint64_t{1} << 31)) {
+      return SILO_GPU_OK;  // nothing to gain (a few covered rows against an event per sequence end): the scan reads every row
+   }
+   // the residual keys: the bits of the covered rows outside every end run
+   SliceMajorKeys residual;
+   if (residual_total != 0) {
+      const size_t n_covered = covered_list.size();
+      unsigned long long written = 0;
+      HIP_TRY(hipMalloc(&scratch.d_rows, 2 * n_covered * sizeof(uint32_t)));
+      HIP_TRY(hipMalloc(&scratch.d_keys, residual_total * sizeof(uint64_t)));
+      HIP_TRY(hipMalloc(&scratch.d_cursor, sizeof(unsigned long long)));
+      HIP_TRY(hipMemset(scratch.d_cursor, 0, sizeof(unsigned long long)));
+      HIP_TRY(hipMemcpy(scratch.d_rows, covered_list.data(), n_covered * sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(scratch.d_rows + n_covered, covered_positions.data(), n_covered * sizeof(uint32_t), hipMemcpyHostToDevice));
+      const uint32_t blocks = (dev.row_words + RUN_BLOCK_THREADS / 64 - 1) / (RUN_BLOCK_THREADS / 64);
+      k_residual_keys<<<blocks, RUN_BLOCK_THREADS>>>(
+         layout.planes, dev.row_words, sequences, scratch.d_rows, scratch.d_rows + n_covered, static_cast<uint32_t>(n_covered), symbol, layout.d_end_lead,
+         layout.d_end_trail, scratch.d_cursor, scratch.d_keys, residual_total
+      );
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpy(&written, scratch.d_cursor, sizeof(written), hipMemcpyDeviceToHost));
+      if (written != residual_total) {
+         return fail(SILO_GPU_ERR_HIP, "end runs: the covered rows hold other bits outside the end runs than their totals say");
+      }
+      if (const int rc = silo_gpu_internal_sort_keys(scratch.d_keys, residual_total); rc != SILO_GPU_OK) {  // ascending: (position, symbol, sequence)
+         return rc;
+      }
+      // (granules that end early instead of an overflow list, as the gap events have them: the keys lie hundreds to a position
+      // at the two ends of the alignment and nowhere between, and an overflow list would be a launch of its own in every scan)
+      const uint32_t max_span = (ESCAPE_MAX_RELATIVE + 1u - dev.n_scan) / dev.n_scan;
+      if (const int rc = packSliceMajor(scratch.d_keys, residual_total, dev.n_scan, positions, n_slices, max_span, residual); rc != SILO_GPU_OK) {
+         return rc;
+      }
+      (void)hipFree(scratch.d_keys);
+      scratch.d_keys = nullptr;
+   }
+   // the end events
+   const uint64_t n_events = 2u * static_cast<uint64_t>(sequences);
+   SliceMajorKeys ends;
+   hipError_t status = hipMalloc(&scratch.d_keys, n_events * sizeof(uint64_t));
+   if (status == hipSuccess) {
+      k_end_events<<<(sequences + 255) / 256, 256>>>(layout.d_end_lead, layout.d_end_trail, sequences, scratch.d_keys);
+      status = hipGetLastError();
+   }
+   int rc = status == hipSuccess ? SILO_GPU_OK : fail(status == hipErrorOutOfMemory ? SILO_GPU_ERR_OUT_OF_MEMORY : SILO_GPU_ERR_HIP, std::string("end events: ") + hipGetErrorString(status));
+   rc = rc != SILO_GPU_OK ? rc : silo_gpu_internal_sort_keys(scratch.d_keys, n_events);  // ascending: (position, kind, sequence)
+   rc = rc != SILO_GPU_OK ? rc : packSliceMajor(scratch.d_keys, n_events, 2, positions, n_slices, GAP_MAX_SPAN, ends);
+   uint8_t* d_row_covered = nullptr;
+   uint8_t* d_position_covered = nullptr;
+   if (rc == SILO_GPU_OK) {
+      status = hipMalloc(&d_row_covered, std::max<size_t>(n_rows, 1));
+      status = status != hipSuccess ? status : hipMalloc(&d_position_covered, positions);
+      status = status != hipSuccess ? status : hipMemcpy(d_row_covered, row_covered.data(), n_rows, hipMemcpyHostToDevice);
+      status = status != hipSuccess ? status : hipMemcpy(d_position_covered, position_covered.data(), positions, hipMemcpyHostToDevice);
+      if (status != hipSuccess) {
+         (void)hipGetLastError();
+         rc = fail(status == hipErrorOutOfMemory ? SILO_GPU_ERR_OUT_OF_MEMORY : SILO_GPU_ERR_HIP, std::string("end runs: ") + hipGetErrorString(status));
+      }
+   }
+   if (rc != SILO_GPU_OK) {
+      (void)hipFree(d_row_covered);
+      (void)hipFree(d_position_covered);
+      residual.discard();
+      ends.discard();
+      return rc;
+   }
+   layout.d_ends_sliced = ends.d_keys;
+   layout.d_end_granule_base = ends.d_granule_base;
+   layout.d_end_slice_first = ends.d_slice_first;
+   layout.end_slice_first = std::move(ends.slice_first);
+   layout.end_events = events;
+   layout.d_residual_sliced = residual.d_keys;
+   layout.d_residual_granule_base = residual.d_granule_base;
+   layout.d_residual_slice_first = residual.d_slice_first;
+   layout.residual_slice_first = std::move(residual.slice_first);
+   layout.residual_keys = residual_total;
+   layout.d_row_covered = d_row_covered;
+   layout.d_position_covered = d_position_covered;
+   layout.row_covered = std::move(row_covered);
+   layout.position_covered = std::move(position_covered);
+   layout.covered_rows = covered_list.size();
+   layout.end_symbol = symbol;
+   layout.end_slices = n_slices;
+   // (not charged to device_bytes, as the gap events are not: scan-side copies of what the rows hold)
+   return SILO_GPU_OK;
+}
+
 int finalizeSeqStore(silo_gpu_store* store, SeqStoreHost& seqstore) {
    if (seqstore.layout.built) {
       return SILO_GPU_OK;
@@ -1669,7 +1977,10 @@ int finalizeSeqStore(silo_gpu_store* store, SeqStoreHost& seqstore) {
    if (const int rc = buildPruneBounds(store, seqstore); rc != SILO_GPU_OK) {
       return rc;
    }
-   return buildRowBounds(store, seqstore);
+   if (const int rc = buildRowBounds(store, seqstore); rc != SILO_GPU_OK) {
+      return rc;
+   }
+   return buildEndRuns(store, seqstore);
 }
 }  // namespace
 
@@ -2119,6 +2430,10 @@ int buildLayout(silo_gpu_store* store, SeqStoreHost& seqstore) {
       }
       SILO_LAYOUT_TRY(hipGetLastError());
       SILO_LAYOUT_TRY(hipDeviceSynchronize());
+   }
+   if (const int rc = walkEndRuns(store, seqstore, work.has_implicit); rc != SILO_GPU_OK) {  // (the build-time planes go in finishLayout)
+      work.discard();
+      return rc;
    }
    return finishLayout(store, seqstore, work);
 }

@@ -32,6 +32,7 @@ extern std::atomic<int> g_tune_eval_leaf_batch;
 extern std::atomic<int> g_tune_compact_index;   // < 0: finalize keeps the build-time identity planes; 2 / 3: see SILO_GPU_TUNE_COMPACT_INDEX
 extern std::atomic<int> g_tune_gap_events;      // < 0: scans of derived symbols take the runs and the sparse keys by themselves (planDerived)
 extern std::atomic<int> g_tune_prune_keys;      // silo_gpu_mutations_scan_ranges_min_proportion: < 0 skips nothing, 0 granules of escape keys and one-hot rows, 1 keys only (ScanPruning, scan_internal.h)
+extern std::atomic<int> g_tune_end_runs;        // < 0: a Mutations scan reads the covered rows of the gap symbol instead of counting its end runs (DerivedPlan::end_runs)
 extern std::atomic<int> g_tune_side_stream;     // the side passes of a scan: see forkSidePasses (silo_gpu_scan.hip)
 extern std::atomic<int> g_tune_scan_timing;     // 1: HIP events around every launch of a scan (silo_gpu_scan_timings)
 extern std::atomic<int> g_tune_missing_runs;    // < 0: finalize keeps the plane of the missing symbol instead of turning it into runs
@@ -335,6 +336,35 @@ struct SeqStoreHost {
       uint32_t* d_row_without = nullptr;
       std::vector<uint32_t> row_heaviest;  // host copies
       std::vector<uint32_t> row_without;
+      // the END RUNS of the gap symbol ('-': a sequence that has not begun yet, or has already ended), for the Mutations scan
+      // alone (buildEndRuns; every other reader keeps reading the rows).  Per sequence lead = the length of its maximal prefix
+      // of gap cells and trail_start >= lead = the first cell of its maximal suffix of them (P: none).  As events, packed like
+      // d_gaps_sliced (counter = position * 2 + kind): kind 0 at lead (every row, also lead = 0; an event at P is left out),
+      // kind 1 at trail_start (none at P).  The selected rows inside an end run at p: |F| - sum_{q<=p} kind 0 + sum_{q<=p} kind 1.
+      // A one-hot row of the gap symbol is COVERED — not read by the scan — where its position is LAYOUT_IMPLICIT, derives
+      // another symbol, and the row's bits outside every end run (interior deletions, gap cells cut off from their run by an N)
+      // cost less as keys than the row (silo_gpu_layout::endRunCovers); those bits are the residual keys, packed like
+      // d_escapes_sliced but in a stream of their own (the other readers would count them on top of the row).
+      // Built only beside the gap events and while finalize still has the build-time planes; nullptr / empty otherwise.
+      uint32_t* d_end_lead = nullptr;   // [sequences] between the walk of the build-time planes and buildEndRuns only
+      uint32_t* d_end_trail = nullptr;
+      uint32_t* d_ends_sliced = nullptr;
+      uint32_t* d_end_granule_base = nullptr;
+      uint32_t* d_end_slice_first = nullptr;  // [end_slices][P + 1]
+      uint32_t end_slices = 0;
+      std::vector<uint32_t> end_slice_first;
+      uint64_t end_events = 0;                // events at a position < P
+      uint32_t* d_residual_sliced = nullptr;
+      uint32_t* d_residual_granule_base = nullptr;
+      uint32_t* d_residual_slice_first = nullptr;
+      std::vector<uint32_t> residual_slice_first;
+      uint64_t residual_keys = 0;
+      uint8_t* d_row_covered = nullptr;       // [rows] in the order of d_row_target
+      uint8_t* d_position_covered = nullptr;  // [P]
+      std::vector<uint8_t> row_covered;       // host copies
+      std::vector<uint8_t> position_covered;
+      uint64_t covered_rows = 0;
+      uint32_t end_symbol = 0;                // scan index of the gap symbol
    } layout;
 };
 

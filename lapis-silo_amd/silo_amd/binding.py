@@ -109,6 +109,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_comm_unique_id", "silo_gpu_comm_create", "silo_gpu_comm_destroy", "silo_gpu_comm_rank", "silo_gpu_comm_world",
     "silo_gpu_allreduce_counts", "silo_gpu_broadcast_bytes",
     "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules", "silo_gpu_store_scan_prunable_rows",
+    "silo_gpu_store_scan_covered_rows", "silo_gpu_store_scan_end_events", "silo_gpu_store_scan_residual_keys",
     "silo_gpu_filters_grouped", "silo_gpu_filters_cross",
     "silo_gpu_distance_pack", "silo_gpu_distance_pairs", "silo_gpu_distance_within", "silo_gpu_adjacency_components",
     "silo_gpu_query_distances", "silo_gpu_nearest_rows", "silo_gpu_bitset_from_distances",
@@ -173,6 +174,9 @@ def load_library():
     lib.silo_gpu_store_scan_prunable_granules.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64),
                                                           ctypes.POINTER(ctypes.c_uint64)]
     lib.silo_gpu_store_scan_prunable_rows.argtypes = lib.silo_gpu_store_scan_prunable_granules.argtypes
+    for name in ("silo_gpu_store_scan_covered_rows", "silo_gpu_store_scan_end_events", "silo_gpu_store_scan_residual_keys"):
+        getattr(lib, name).argtypes = [vp, ctypes.c_uint32]
+        getattr(lib, name).restype = ctypes.c_uint64
     lib.silo_gpu_mutations_grouped.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_filters_grouped.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_filters_cross.argtypes = [vp, vp, ctypes.POINTER(vp), vp, ctypes.c_uint32, ctypes.POINTER(vp), vp, ctypes.c_uint32, vp, vp,
@@ -949,6 +953,12 @@ class GpuStore:
         _check(self.lib.silo_gpu_store_scan_prunable_granules(self.handle, seqstore_id, int(cardinality), ctypes.c_double(min_proportion),
                                                               ctypes.byref(skippable), ctypes.byref(total)))
         return skippable.value, total.value
+
+    def scan_end_runs(self, seqstore_id):
+        """The end runs of the gap symbol a Mutations scan counts instead of reading rows: (covered one-hot rows, end events,
+        residual keys) of a sequence store; all 0 where the store has none."""
+        return (int(self.lib.silo_gpu_store_scan_covered_rows(self.handle, seqstore_id)), int(self.lib.silo_gpu_store_scan_end_events(self.handle, seqstore_id)),
+                int(self.lib.silo_gpu_store_scan_residual_keys(self.handle, seqstore_id)))
 
     def scan_prunable_rows(self, seqstore_id, cardinality, min_proportion):
         """(skippable, total) one-hot plane rows of the store for one filter of `cardinality` rows."""

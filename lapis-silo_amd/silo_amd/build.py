@@ -4,6 +4,7 @@
   lib/libsilo_engine.so  C++ host mirror of silo::query_engine (include/silo_engine.h), links libsilo_gpu
   lib/silo_query         CLI: load a data set directory (reference input formats), answer /query bodies from stdin
   lib/libbitprog_host.so g++ build of the bit-program interpreter for host-logic unit tests
+  lib/libend_runs_host.so g++ build of the end-run cost rule (layout_choice.h) for its unit tests
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container and the resulting
 .so files travel to the GPU box with the repo snapshot.
@@ -118,6 +119,11 @@ def build_host_tools(force=False):
     if os.path.exists(logic_src) and os.path.exists(engine_lib) and (force or _newer(logic_target, [logic_src, engine_lib, os.path.join(CSRC, "layout_choice.h")])):
         _run(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", INCLUDE, "-I", HOST, logic_src, "-o", logic_target, "-L", LIB,
               "-lsilo_engine", "-lsilo_gpu", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + LIB])
+    # the host rule of the end runs of the gap symbol (layout_choice.h)
+    ends_src = os.path.join(ROOT, "tests", "host_tools", "end_runs_host.cpp")
+    ends_target = os.path.join(LIB, "libend_runs_host.so")
+    if os.path.exists(ends_src) and (force or _newer(ends_target, [ends_src, os.path.join(CSRC, "layout_choice.h")])):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-I", INCLUDE, ends_src, "-o", ends_target])
     return target
 
 
