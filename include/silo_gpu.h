@@ -626,6 +626,52 @@ int silo_gpu_distance_within(
 );
 int silo_gpu_adjacency_components(const uint64_t* adjacency_dev, uint32_t n_rows, uint32_t* labels_dev, uint32_t* rounds_dev, void* stream);
 
+/* ---- K13: the distances of the pairs within a bound, and the minimum spanning forest of that graph (MinimumSpanningTree) ---
+ * No entry takes a store.  An EDGE is a pair i != j of rows < n_rows with differing(i, j) <= max_distance and compared(i, j) >=
+ * min_compared, both as silo_gpu_distance_pairs counts them (max_distance == UINT32_MAX: no bound; min_compared == 0: none): the
+ * pairs whose bit silo_gpu_distance_within sets.
+ * silo_gpu_distance_weights reads planes as silo_gpu_distance_pack leaves them and WRITES the full symmetric matrix
+ *     weights_dev[i * n_rows + j] = differing(i, j) where (i, j) is an edge, UINT32_MAX where it is not and on the diagonal.
+ * Every one of the n_rows * n_rows cells is written once and nothing behind them is touched: the caller never clears the buffer.
+ * No atomics: the cells do not depend on how the blocks are scheduled.  One launch on `stream`, no waiting: the tiles, the LDS
+ * staging and the early exit are those of k_distance_within (the two kernels share the walk); a block whose pairs have all passed
+ * the bound stops, and its cells are UINT32_MAX.  Only the tiles at or right of the diagonal's 64 x 64 block are launched; a tile
+ * right of it writes its transpose as well.  n_rows == 0: success, nothing launched.  positions == 0: every pair has compared =
+ * differing = 0, and the matrix of that is written.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for an alphabet
+ * other than the two, a NULL buffer or more than SILO_GPU_MAX_SPANNING_ROWS rows.
+ * silo_gpu_spanning_forest takes such a matrix (UINT32_MAX: no edge; the diagonal is ignored) and WRITES *count_dev = the number
+ * of edges of its minimum spanning forest and edges_dev[0 .. count) = their keys
+ *     SILO_GPU_SPANNING_KEY(weight, i, j) = weight << 26 | i << 13 | j,   i < j,
+ * ASCENDING.  Edges are ordered by that key, a strict order, so the forest is unique and the output a pure function of the
+ * matrix; cutting it at any d leaves the single-linkage clusters at d.  Entries at or past the count are untouched (room for
+ * n_rows - 1 keys is enough).  One launch of ONE block of SILO_GPU_SPANNING_THREADS threads on `stream`, no waiting: Prim's
+ * algorithm with a restart — a thread keeps the best key of each of its <= 8 vertices in registers, a step reads one row of the
+ * matrix, takes the block-wide minimum and moves one vertex into the forest (with no key left, the lowest vertex outside it,
+ * without an edge) — then a bitonic sort of the keys in LDS.  Exactly n_rows - 1 steps whatever the matrix holds, and nothing read
+ * from the matrix is used as an index; for an asymmetric matrix the output is unspecified (but count <= n_rows - 1 and i < j <
+ * n_rows hold).  n_rows == 0: success, nothing launched or written.  n_rows == 1: count 0.  Fails with
+ * SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer or more than SILO_GPU_MAX_SPANNING_ROWS rows.
+ * silo_gpu_distance_listed_pairs WRITES for every e < min(*count_dev, max_pairs), with (i, j) the low 26 bits of edges_dev[e],
+ *     out_dev[2 e] = differing(i, j),   out_dev[2 e + 1] = compared(i, j)
+ * — a wave per pair — and (UINT32_MAX, UINT32_MAX), without reading a plane, where i or j is >= n_rows.  Entries at or past the
+ * count are untouched.  One launch on `stream`, no waiting (none for max_pairs == 0).  Fails with SILO_GPU_ERR_INVALID_ARGUMENT,
+ * nothing written, for an alphabet other than the two, a NULL buffer or more than SILO_GPU_MAX_SPANNING_ROWS rows. */
+#define SILO_GPU_MAX_SPANNING_ROWS 8192
+#define SILO_GPU_SPANNING_THREADS 1024
+#define SILO_GPU_SPANNING_KEY_ROW_BITS 13    /* a row of the key: SILO_GPU_MAX_SPANNING_ROWS == 1 << 13 */
+#define SILO_GPU_SPANNING_KEY_WEIGHT_SHIFT 26 /* two rows below the weight */
+#define SILO_GPU_SPANNING_KEY(weight, i, j) \
+   (((uint64_t)(weight) << SILO_GPU_SPANNING_KEY_WEIGHT_SHIFT) | ((uint64_t)(i) << SILO_GPU_SPANNING_KEY_ROW_BITS) | (uint64_t)(j))
+int silo_gpu_distance_weights(
+   int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, uint32_t max_distance, uint32_t min_compared,
+   uint32_t* weights_dev, void* stream
+);
+int silo_gpu_spanning_forest(const uint32_t* weights_dev, uint32_t n_rows, uint64_t* edges_dev, uint32_t* count_dev, void* stream);
+int silo_gpu_distance_listed_pairs(
+   int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, const uint64_t* edges_dev, const uint32_t* count_dev,
+   uint32_t max_pairs, uint32_t* out_dev, void* stream
+);
+
 /* ---- K11: the rows of the whole store nearest to a query (NearestNeighbours) --------------------------
  * silo_gpu_query_distances compares one query — query_chars, `positions` characters in HOST memory — with EVERY row of a sequence
  * store, read off the store's own layout (identity / code planes with escape keys, one-hot rows with a derived symbol, runs of the

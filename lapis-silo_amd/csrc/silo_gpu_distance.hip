@@ -13,6 +13,11 @@
 //                      block owns WITHIN_TILE_ROWS x WITHIN_TILE_COLS pairs at or right of the diagonal's word, four pairs per
 //                      thread in registers, a wave's ballot is a finished word; it stops once no pair of its tile can be linked
 //   k_adjacency_mirror the words left of the diagonal's word, transposed from the 64 x 64 bit blocks right of it
+// and as a full matrix of weights behind MinimumSpanningTree (K13):
+//   k_distance_weights the same tiles and the same walk as k_distance_within (withinTileWalk), but a pair that is linked keeps its
+//                      `differing` and every other cell is UINT32_MAX (silo_gpu_distance_weights); a tile writes its transpose too
+//   k_distance_listed_pairs  a wave per pair of a list of keys: both counts of the pairs a spanning forest kept
+//                      (silo_gpu_distance_listed_pairs)
 #include "store_internal.h"
 
 using namespace silo_gpu_detail;
@@ -178,50 +183,57 @@ constexpr uint32_t withinRowWords() {
 }
 static_assert(withinRowWords<4>() % 2u == 1u && withinRowWords<6>() % 2u == 1u);
 
-/// grid = the tiles (ti, tj) with tj >= the word of the diagonal of row tile ti, row tile by row tile: the row tiles 4 g .. 4 g + 3
-/// (WITHIN_ROW_TILES_PER_WORD of them share the diagonal word g) have adjacency_words - g tiles each.  Wave v owns rows
-/// ti * 16 + 4 v .. + 3 of the tile, lane l its column tj * 64 + l.  Per chunk of WITHIN_CHUNK_WORDS words the block copies the words
-/// of all planes of its 16 + 64 rows into LDS — a row at or past n_rows is staged as zeros, so nothing past the buffer is read — and
-/// every thread walks the chunk with its column's words (one LDS read per plane and word) against its four rows' (the same address
-/// for the whole wave: broadcast).  A pair is `open` while it can still be linked: never a pair with a row at or past n_rows or
-/// with i == j, and no longer once differing > max_distance.  After each chunk the block leaves the loop if no pair is open.  At
-/// the end the ballot of "open and compared >= min_compared" over a wave is word (row, tj); one lane stores it, for rows < n_rows.
+/// The tile (ti, tj) of block `index` among the tiles with tj >= the word of the diagonal of row tile ti, row tile by row tile: the
+/// row tiles 4 g .. 4 g + 3 (WITHIN_ROW_TILES_PER_WORD of them share the diagonal word g) have adjacency_words - g tiles each.
+/// Uniform over the block, at most adjacency_words steps.
+__device__ __forceinline__ void withinTileOf(uint32_t index, uint32_t row_tiles, uint32_t adjacency_words, uint32_t& ti, uint32_t& tj) {
+   ti = 0;
+   tj = 0;
+   for (uint32_t group = 0; group < adjacency_words; ++group) {
+      const uint32_t tiles_per_row_tile = adjacency_words - group;
+      const uint32_t group_row_tiles = min(WITHIN_ROW_TILES_PER_WORD, row_tiles - group * WITHIN_ROW_TILES_PER_WORD);
+      if (index < group_row_tiles * tiles_per_row_tile) {
+         ti = group * WITHIN_ROW_TILES_PER_WORD + index / tiles_per_row_tile;
+         tj = group + index % tiles_per_row_tile;
+         break;
+      }
+      index -= group_row_tiles * tiles_per_row_tile;
+   }
+}
+
+/// The pairs of one thread of a WITHIN_TILE_ROWS x WITHIN_TILE_COLS tile: its column against its wave's four rows.
+struct WithinPairs {
+   uint32_t compared[WITHIN_ROWS_PER_WAVE];
+   uint32_t differing[WITHIN_ROWS_PER_WAVE];
+   bool open[WITHIN_ROWS_PER_WAVE];  // still linkable: rows < n_rows, i != j, differing <= max_distance so far
+};
+
+/// The walk of tile (ti, tj) that k_distance_within and k_distance_weights share; the whole block calls it, s_rows is its LDS of
+/// (WITHIN_TILE_ROWS + WITHIN_TILE_COLS) * withinRowWords<PLANES>() words.  Wave v owns rows ti * 16 + 4 v .. + 3 of the tile, lane l
+/// its column tj * 64 + l.  Per chunk of WITHIN_CHUNK_WORDS words the block copies the words of all planes of its 16 + 64 rows into
+/// LDS — a row at or past n_rows is staged as zeros, so nothing past the buffer is read — and every thread walks the chunk with its
+/// column's words (one LDS read per plane and word) against its four rows' (the same address for the whole wave: broadcast).  A
+/// pair is `open` while it can still be linked: never a pair with a row at or past n_rows or with i == j, and no longer once
+/// differing > max_distance.  After each chunk the block leaves the loop if no pair is open.  Every path out of here ends with a
+/// barrier after the last read of s_rows (or never touched it): the caller may reuse it at once.
 template <uint32_t PLANES>
-__global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_within(
-   const uint64_t* __restrict__ planes, uint32_t n_rows, uint32_t words, uint32_t row_tiles, uint32_t adjacency_words, uint32_t max_distance,
-   uint32_t min_compared, uint64_t* __restrict__ adjacency
+__device__ __forceinline__ void withinTileWalk(
+   const uint64_t* __restrict__ planes, uint32_t n_rows, uint32_t words, uint32_t ti, uint32_t tj, uint32_t max_distance, uint64_t* s_rows,
+   WithinPairs& pairs
 ) {
    constexpr uint32_t ROW_WORDS = withinRowWords<PLANES>();
    constexpr uint32_t STAGED_ROWS = WITHIN_TILE_ROWS + WITHIN_TILE_COLS;
    constexpr uint32_t STAGED = STAGED_ROWS * PLANES * WITHIN_CHUNK_WORDS;  // words copied per chunk
    static_assert(STAGED % DISTANCE_THREADS == 0);
-   __shared__ uint64_t s_rows[STAGED_ROWS * ROW_WORDS];
-
-   // the tile of this block (uniform, at most adjacency_words steps)
-   uint32_t ti = 0;
-   uint32_t tj = 0;
-   {
-      uint32_t index = blockIdx.x;
-      for (uint32_t group = 0; group < adjacency_words; ++group) {
-         const uint32_t tiles_per_row_tile = adjacency_words - group;
-         const uint32_t group_row_tiles = min(WITHIN_ROW_TILES_PER_WORD, row_tiles - group * WITHIN_ROW_TILES_PER_WORD);
-         if (index < group_row_tiles * tiles_per_row_tile) {
-            ti = group * WITHIN_ROW_TILES_PER_WORD + index / tiles_per_row_tile;
-            tj = group + index % tiles_per_row_tile;
-            break;
-         }
-         index -= group_row_tiles * tiles_per_row_tile;
-      }
-   }
    const uint32_t wave = threadIdx.x / 64u;
    const uint32_t lane = threadIdx.x & 63u;
    const uint32_t first_row = ti * WITHIN_TILE_ROWS + wave * WITHIN_ROWS_PER_WAVE;
    const uint32_t column = tj * WITHIN_TILE_COLS + lane;
    const uint64_t* mine = s_rows + wave * WITHIN_ROWS_PER_WAVE * ROW_WORDS;
    const uint64_t* other = s_rows + (WITHIN_TILE_ROWS + lane) * ROW_WORDS;
-   uint32_t compared[WITHIN_ROWS_PER_WAVE];
-   uint32_t differing[WITHIN_ROWS_PER_WAVE];
-   bool open[WITHIN_ROWS_PER_WAVE];
+   uint32_t (&compared)[WITHIN_ROWS_PER_WAVE] = pairs.compared;
+   uint32_t (&differing)[WITHIN_ROWS_PER_WAVE] = pairs.differing;
+   bool (&open)[WITHIN_ROWS_PER_WAVE] = pairs.open;
 #pragma unroll
    for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
       compared[r] = 0;
@@ -280,12 +292,130 @@ __global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_within(
          break;
       }
    }
+}
+
+/// grid = the tiles of withinTileOf.  After the walk the ballot of "open and compared >= min_compared" over a wave is word (row, tj);
+/// one lane stores it, for rows < n_rows.
+template <uint32_t PLANES>
+__global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_within(
+   const uint64_t* __restrict__ planes, uint32_t n_rows, uint32_t words, uint32_t row_tiles, uint32_t adjacency_words, uint32_t max_distance,
+   uint32_t min_compared, uint64_t* __restrict__ adjacency
+) {
+   __shared__ uint64_t s_rows[(WITHIN_TILE_ROWS + WITHIN_TILE_COLS) * withinRowWords<PLANES>()];
+   uint32_t ti;
+   uint32_t tj;
+   withinTileOf(blockIdx.x, row_tiles, adjacency_words, ti, tj);
+   WithinPairs pairs;
+   withinTileWalk<PLANES>(planes, n_rows, words, ti, tj, max_distance, s_rows, pairs);
+   const uint32_t lane = threadIdx.x & 63u;
+   const uint32_t first_row = ti * WITHIN_TILE_ROWS + (threadIdx.x / 64u) * WITHIN_ROWS_PER_WAVE;
 #pragma unroll
    for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
-      const uint64_t linked = __ballot(open[r] && differing[r] <= max_distance && compared[r] >= min_compared);
+      const uint64_t linked = __ballot(pairs.open[r] && pairs.differing[r] <= max_distance && pairs.compared[r] >= min_compared);
       if (lane == 0 && first_row + r < n_rows) {
          adjacency[static_cast<size_t>(first_row + r) * adjacency_words + tj] = linked;
       }
+   }
+}
+
+/// A row of the tile of weights that k_distance_weights transposes through LDS: WITHIN_TILE_COLS cells and one of padding, so the
+/// 16 cells of a column that consecutive lanes read lie in different banks.
+constexpr uint32_t WEIGHTS_TILE_STRIDE = WITHIN_TILE_COLS + 1u;
+static_assert(WITHIN_TILE_ROWS * WEIGHTS_TILE_STRIDE * sizeof(uint32_t) <= (WITHIN_TILE_ROWS + WITHIN_TILE_COLS) * withinRowWords<4>() * sizeof(uint64_t));
+
+/// grid = the tiles of withinTileOf, the walk of withinTileWalk.  Afterwards a pair's cell is its `differing` if it is an edge (open,
+/// differing <= max_distance, compared >= min_compared) and UINT32_MAX if not — the diagonal and the pairs of a block that stopped
+/// early included.  Every thread stores its four cells (row, column) where both are < n_rows: consecutive lanes, consecutive cells.
+/// A tile right of the diagonal's 64 x 64 block also owns the transposed cells (column, row), which no launched tile covers: the
+/// cells go through LDS (s_rows is free after the walk) and 16 consecutive threads store the 16 consecutive cells of a column.
+/// The four row tiles of the diagonal's block cover both halves of it themselves.  So every cell has one writer.
+template <uint32_t PLANES>
+__global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_weights(
+   const uint64_t* __restrict__ planes, uint32_t n_rows, uint32_t words, uint32_t row_tiles, uint32_t adjacency_words, uint32_t max_distance,
+   uint32_t min_compared, uint32_t* __restrict__ weights
+) {
+   __shared__ uint64_t s_rows[(WITHIN_TILE_ROWS + WITHIN_TILE_COLS) * withinRowWords<PLANES>()];
+   uint32_t ti;
+   uint32_t tj;
+   withinTileOf(blockIdx.x, row_tiles, adjacency_words, ti, tj);
+   WithinPairs pairs;
+   withinTileWalk<PLANES>(planes, n_rows, words, ti, tj, max_distance, s_rows, pairs);
+   const uint32_t wave = threadIdx.x / 64u;
+   const uint32_t lane = threadIdx.x & 63u;
+   const uint32_t first_row = ti * WITHIN_TILE_ROWS + wave * WITHIN_ROWS_PER_WAVE;
+   const uint32_t column = tj * WITHIN_TILE_COLS + lane;
+   const bool mirrored = tj > ti / WITHIN_ROW_TILES_PER_WORD;  // uniform
+   auto* s_tile = reinterpret_cast<uint32_t*>(s_rows);
+#pragma unroll
+   for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
+      const bool edge = pairs.open[r] && pairs.differing[r] <= max_distance && pairs.compared[r] >= min_compared;
+      const uint32_t weight = edge ? pairs.differing[r] : UINT32_MAX;
+      if (first_row + r < n_rows && column < n_rows) {
+         weights[static_cast<size_t>(first_row + r) * n_rows + column] = weight;
+      }
+      if (mirrored) {
+         s_tile[(wave * WITHIN_ROWS_PER_WAVE + r) * WEIGHTS_TILE_STRIDE + lane] = weight;
+      }
+   }
+   if (!mirrored) {
+      return;
+   }
+   __syncthreads();
+#pragma unroll
+   for (uint32_t k = 0; k < WITHIN_TILE_ROWS * WITHIN_TILE_COLS / DISTANCE_THREADS; ++k) {
+      const uint32_t cell = k * DISTANCE_THREADS + threadIdx.x;
+      const uint32_t tile_row = cell % WITHIN_TILE_ROWS;
+      const uint32_t tile_column = cell / WITHIN_TILE_ROWS;
+      const uint32_t row = ti * WITHIN_TILE_ROWS + tile_row;
+      const uint32_t mirrored_row = tj * WITHIN_TILE_COLS + tile_column;
+      if (row < n_rows && mirrored_row < n_rows) {
+         weights[static_cast<size_t>(mirrored_row) * n_rows + row] = s_tile[tile_row * WEIGHTS_TILE_STRIDE + tile_column];
+      }
+   }
+}
+
+/// grid = max_pairs / 4 rounded up, a wave per listed pair e < min(*count, max_pairs): (i, j) from the low 26 bits of keys[e]; a
+/// key that names a row at or past n_rows gets (UINT32_MAX, UINT32_MAX) and reads no plane.  Lane l takes the words l, l + 64, ...
+/// of the two rows, one reduction over the wave, lane 0 stores the two counts.
+template <uint32_t PLANES>
+__global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_listed_pairs(
+   const uint64_t* __restrict__ planes, uint32_t n_rows, uint32_t words, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ count,
+   uint32_t max_pairs, uint32_t* __restrict__ out
+) {
+   const uint32_t pair = blockIdx.x * (DISTANCE_THREADS / 64u) + threadIdx.x / 64u;  // the same for the whole wave
+   if (pair >= min(*count, max_pairs)) {
+      return;
+   }
+   const uint32_t lane = threadIdx.x & 63u;
+   const uint64_t key = keys[pair];
+   const uint32_t i = static_cast<uint32_t>(key >> SILO_GPU_SPANNING_KEY_ROW_BITS) & (SILO_GPU_MAX_SPANNING_ROWS - 1u);
+   const uint32_t j = static_cast<uint32_t>(key) & (SILO_GPU_MAX_SPANNING_ROWS - 1u);
+   uint32_t compared = UINT32_MAX;
+   uint32_t differing = UINT32_MAX;
+   if (i < n_rows && j < n_rows) {
+      const uint64_t* mine = planes + static_cast<size_t>(i) * PLANES * words;
+      const uint64_t* other = planes + static_cast<size_t>(j) * PLANES * words;
+      compared = 0;
+      differing = 0;
+      for (uint32_t word = lane; word < words; word += 64u) {
+         const uint64_t both = mine[word] & other[word];
+         uint64_t unequal = 0;
+#pragma unroll
+         for (uint32_t k = 1; k < PLANES; ++k) {
+            unequal |= mine[static_cast<size_t>(k) * words + word] ^ other[static_cast<size_t>(k) * words + word];
+         }
+         compared += static_cast<uint32_t>(__popcll(both));
+         differing += static_cast<uint32_t>(__popcll(both & unequal));
+      }
+#pragma unroll
+      for (uint32_t offset = 32; offset > 0; offset >>= 1) {
+         compared += static_cast<uint32_t>(__shfl_xor(static_cast<int>(compared), static_cast<int>(offset)));
+         differing += static_cast<uint32_t>(__shfl_xor(static_cast<int>(differing), static_cast<int>(offset)));
+      }
+   }
+   if (lane == 0) {
+      out[static_cast<size_t>(pair) * 2u] = differing;
+      out[static_cast<size_t>(pair) * 2u + 1u] = compared;
    }
 }
 
@@ -316,6 +446,17 @@ __global__ __launch_bounds__(DISTANCE_THREADS) void k_adjacency_mirror(uint64_t*
 
 constexpr const char* MORE_THAN_DISTANCE_ROWS = "more rows than SILO_GPU_MAX_DISTANCE_ROWS";
 constexpr const char* MORE_THAN_CLUSTER_ROWS = "more rows than SILO_GPU_MAX_CLUSTER_ROWS";
+constexpr const char* MORE_THAN_SPANNING_ROWS = "more rows than SILO_GPU_MAX_SPANNING_ROWS";
+static_assert(SILO_GPU_MAX_SPANNING_ROWS == SILO_GPU_MAX_CLUSTER_ROWS && SILO_GPU_MAX_SPANNING_ROWS == 1u << SILO_GPU_SPANNING_KEY_ROW_BITS);
+
+/// Blocks of k_distance_within / k_distance_weights: the tiles withinTileOf numbers.
+uint32_t withinTiles(uint32_t row_tiles, uint32_t adjacency_words) {
+   uint32_t grid = 0;
+   for (uint32_t group = 0; group < adjacency_words; ++group) {
+      grid += std::min(WITHIN_ROW_TILES_PER_WORD, row_tiles - group * WITHIN_ROW_TILES_PER_WORD) * (adjacency_words - group);
+   }
+   return grid;
+}
 
 /// What the entries refuse; nullptr if nothing.  limit_complaint: what to say of more than max_rows rows.
 const char* distanceComplaint(int alphabet, const void* in_dev, const void* out_dev, uint32_t n_rows, uint32_t max_rows, const char* limit_complaint) {
@@ -393,10 +534,7 @@ int silo_gpu_distance_within(
    const uint32_t words = SILO_GPU_DISTANCE_WORDS(positions);  // 0 positions: no chunk is walked, every pair has (0, 0)
    const uint32_t adjacency_words = SILO_GPU_ADJACENCY_WORDS(n_rows);
    const uint32_t row_tiles = (n_rows + WITHIN_TILE_ROWS - 1) / WITHIN_TILE_ROWS;
-   uint32_t grid = 0;
-   for (uint32_t group = 0; group < adjacency_words; ++group) {
-      grid += std::min(WITHIN_ROW_TILES_PER_WORD, row_tiles - group * WITHIN_ROW_TILES_PER_WORD) * (adjacency_words - group);
-   }
+   const uint32_t grid = withinTiles(row_tiles, adjacency_words);
    auto hip_stream = static_cast<hipStream_t>(stream);
    if (alphabet == SILO_GPU_ALPHABET_NUCLEOTIDE) {
       k_distance_within<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_NUCLEOTIDE)><<<grid, DISTANCE_THREADS, 0, hip_stream>>>(
@@ -413,6 +551,63 @@ int silo_gpu_distance_within(
       k_adjacency_mirror<<<mirror_grid, DISTANCE_THREADS, 0, hip_stream>>>(adjacency_dev, n_rows, adjacency_words);
       HIP_TRY(hipGetLastError());
    }
+   return SILO_GPU_OK;
+}
+
+int silo_gpu_distance_weights(
+   int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, uint32_t max_distance, uint32_t min_compared,
+   uint32_t* weights_dev, void* stream
+) {
+   if (const char* complaint = distanceComplaint(alphabet, planes_dev, weights_dev, n_rows, SILO_GPU_MAX_SPANNING_ROWS, MORE_THAN_SPANNING_ROWS);
+       complaint != nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_distance_weights: ") + complaint);
+   }
+   if (n_rows == 0) {
+      return SILO_GPU_OK;
+   }
+   const uint32_t words = SILO_GPU_DISTANCE_WORDS(positions);  // 0 positions: no chunk is walked, every pair has (0, 0)
+   const uint32_t adjacency_words = SILO_GPU_ADJACENCY_WORDS(n_rows);
+   const uint32_t row_tiles = (n_rows + WITHIN_TILE_ROWS - 1) / WITHIN_TILE_ROWS;
+   const uint32_t grid = withinTiles(row_tiles, adjacency_words);
+   auto hip_stream = static_cast<hipStream_t>(stream);
+   if (alphabet == SILO_GPU_ALPHABET_NUCLEOTIDE) {
+      k_distance_weights<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_NUCLEOTIDE)><<<grid, DISTANCE_THREADS, 0, hip_stream>>>(
+         planes_dev, n_rows, words, row_tiles, adjacency_words, max_distance, min_compared, weights_dev
+      );
+   } else {
+      k_distance_weights<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_AMINO_ACID)><<<grid, DISTANCE_THREADS, 0, hip_stream>>>(
+         planes_dev, n_rows, words, row_tiles, adjacency_words, max_distance, min_compared, weights_dev
+      );
+   }
+   HIP_TRY(hipGetLastError());
+   return SILO_GPU_OK;
+}
+
+int silo_gpu_distance_listed_pairs(
+   int alphabet, const uint64_t* planes_dev, uint32_t n_rows, uint32_t positions, const uint64_t* edges_dev, const uint32_t* count_dev,
+   uint32_t max_pairs, uint32_t* out_dev, void* stream
+) {
+   if (const char* complaint = distanceComplaint(alphabet, planes_dev, out_dev, n_rows, SILO_GPU_MAX_SPANNING_ROWS, MORE_THAN_SPANNING_ROWS);
+       complaint != nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_distance_listed_pairs: ") + complaint);
+   }
+   if (edges_dev == nullptr || count_dev == nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_distance_listed_pairs: a buffer is NULL");
+   }
+   if (max_pairs == 0) {
+      return SILO_GPU_OK;
+   }
+   const uint32_t words = SILO_GPU_DISTANCE_WORDS(positions);  // 0 positions: every listed pair has (0, 0)
+   const uint32_t grid = (max_pairs + DISTANCE_THREADS / 64u - 1) / (DISTANCE_THREADS / 64u);
+   auto hip_stream = static_cast<hipStream_t>(stream);
+   if (alphabet == SILO_GPU_ALPHABET_NUCLEOTIDE) {
+      k_distance_listed_pairs<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_NUCLEOTIDE)>
+         <<<grid, DISTANCE_THREADS, 0, hip_stream>>>(planes_dev, n_rows, words, edges_dev, count_dev, max_pairs, out_dev);
+   } else {
+      k_distance_listed_pairs<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_AMINO_ACID)>
+         <<<grid, DISTANCE_THREADS, 0, hip_stream>>>(planes_dev, n_rows, words, edges_dev, count_dev, max_pairs, out_dev);
+   }
+   HIP_TRY(hipGetLastError());
    return SILO_GPU_OK;
 }
 

@@ -800,6 +800,7 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"CrossTabulation", parseCrossTabulation},
    {"DistanceMatrix", parseDistanceMatrix},
    {"Clusters", parseClusters},
+   {"MinimumSpanningTree", parseMinimumSpanningTree},
    {"NearestNeighbours", parseNearestNeighbours},
 };
 

@@ -5,8 +5,11 @@
 //   DistanceMatrix                  (not in the reference) the rows FastaAligned would return, compared pairwise on the device (K10)
 //   Clusters                        (not in the reference) the same rows, linked where they are within a distance bound; the connected
 //                                   components of the links on the device (K12)
+//   MinimumSpanningTree             (not in the reference) the same rows again: the minimum spanning forest of their distances within a
+//                                   bound, the tree that answers Clusters at every bound at once, on the device (K13)
 //   NearestNeighbours               (not in the reference) the rows of the whole database closest to one query sequence (K11)
 #include <algorithm>
+#include <cstring>
 #include <tuple>
 #include <type_traits>
 #include <unordered_map>
@@ -577,6 +580,112 @@ QueryResult FastaAligned::execute(const Database& database, std::vector<Operator
    return results;
 }
 
+// ---- what DistanceMatrix, Clusters and MinimumSpanningTree share -----------------------------------------
+namespace {
+
+/// A sequence by name, as the three actions take it: none is the default nucleotide sequence.
+struct ComparedSequence {
+   std::string name;
+   bool is_amino_acid;
+   int alphabet;
+   uint32_t positions;
+   size_t row_plane_words;  // of one row in the plane buffer of silo_gpu_distance_pack
+};
+
+ComparedSequence comparedSequence(const Database& database, const std::optional<std::string>& sequence_name) {
+   ComparedSequence sequence;
+   sequence.name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+   sequence.is_amino_acid = database.nuc_sequences.count(sequence.name) == 0;
+   CHECK_SILO_QUERY(
+      !sequence.is_amino_acid || database.aa_sequences.count(sequence.name) != 0,
+      "Database does not contain a sequence with name: '" + sequence.name + "'"
+   )
+   sequence.alphabet = sequence.is_amino_acid ? SILO_GPU_ALPHABET_AMINO_ACID : SILO_GPU_ALPHABET_NUCLEOTIDE;
+   sequence.positions = static_cast<uint32_t>(
+      sequence.is_amino_acid ? database.aa_sequences.at(sequence.name).reference_sequence.size()
+                             : database.nuc_sequences.at(sequence.name).reference_sequence.size()
+   );
+   sequence.row_plane_words = static_cast<size_t>(SILO_GPU_DISTANCE_PLANES(sequence.alphabet)) * SILO_GPU_DISTANCE_WORDS(sequence.positions);
+   return sequence;
+}
+
+/// The rows the filters select, over all partitions that hold rows.
+size_t selectedCount(const Database& database, const std::vector<OperatorResult>& bitmap_filter) {
+   size_t total_count = 0;
+   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+      total_count += database.partitions[partition_id].sequence_count == 0 ? 0 : bitmap_filter[partition_id].cardinality();
+   }
+   return total_count;
+}
+
+constexpr uint32_t PACK_BATCH_ROWS = SILO_GPU_MAX_DISTANCE_ROWS;  // what one silo_gpu_distance_pack takes
+
+/// Bytes of the character buffer packSelectedSequences gathers into, for n selected rows.
+size_t packCharsBytes(uint32_t n, uint32_t positions) {
+   return std::max<size_t>(1, static_cast<size_t>(std::min(n, PACK_BATCH_ROWS)) * positions);
+}
+
+/// The selected rows of every partition, numbered in partition order, then by ascending row id: reconstructs them in batches of
+/// PACK_BATCH_ROWS into device_chars (packCharsBytes) and packs every batch into its rows of the ONE plane buffer device_planes
+/// (n * row_plane_words words), all enqueued on queryStream(); returns the primary keys of sequence 0 .. n - 1.  Every batch gathers
+/// into the SAME character buffer: the batches are in order on the stream, so a batch's gather starts after the pack of the batch
+/// before it has read the characters.  `live` receives the row ids of every partition: like the two buffers, it must outlive the
+/// wait for the stream.  A sequence without positions: only the keys are collected, nothing is launched.  `what`: who asks, for
+/// the messages.
+std::vector<JsonValue> packSelectedSequences(
+   const Database& database, const std::vector<OperatorResult>& bitmap_filter, const ComparedSequence& sequence, uint32_t n, uint64_t* device_planes,
+   char* device_chars, std::vector<DeviceBuffer>& live, const std::string& what
+) {
+   const std::string& primary_key_column = database.database_config.primary_key;
+   std::vector<JsonValue> keys;
+   keys.reserve(n);
+   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+      const DatabasePartition& partition = database.partitions[partition_id];
+      if (partition.sequence_count == 0) {
+         continue;
+      }
+      const std::vector<uint32_t> rows = selectedRows(partition, bitmap_filter[partition_id]);
+      if (rows.empty()) {
+         continue;
+      }
+      const size_t first_sequence = keys.size();
+      const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
+      for (const uint32_t row : rows) {
+         keys.push_back(primary_key.jsonOfRow(row));
+      }
+      if (keys.size() > n) {
+         throw std::runtime_error(what + ": a filter selects more rows than its cardinality says");
+      }
+      if (sequence.positions == 0) {
+         continue;
+      }
+      const uint32_t seqstore_id =
+         sequence.is_amino_acid ? partition.aa_sequences.at(sequence.name).seqstore_id : partition.nuc_sequences.at(sequence.name).seqstore_id;
+      auto* device_rows = live.emplace_back(partition.pool.acquire(rows.size() * sizeof(uint32_t))).as<uint32_t>();
+      checkGpu(silo_gpu_memcpy_h2d(device_rows, rows.data(), rows.size() * sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
+      for (size_t begin = 0; begin < rows.size(); begin += PACK_BATCH_ROWS) {
+         const auto batch_rows = static_cast<uint32_t>(std::min<size_t>(PACK_BATCH_ROWS, rows.size() - begin));
+         checkGpu(
+            silo_gpu_reconstruct_sequences(partition.store, seqstore_id, device_rows + begin, batch_rows, device_chars, queryStream()),
+            "silo_gpu_reconstruct_sequences"
+         );
+         checkGpu(
+            silo_gpu_distance_pack(
+               sequence.alphabet, device_chars, batch_rows, sequence.positions, device_planes + (first_sequence + begin) * sequence.row_plane_words,
+               queryStream()
+            ),
+            "silo_gpu_distance_pack"
+         );
+      }
+   }
+   if (keys.size() != n) {
+      throw std::runtime_error(what + ": a filter selects fewer rows than its cardinality says");
+   }
+   return keys;
+}
+
+}  // namespace
+
 // ---- DistanceMatrix --------------------------------------------------------------------------------------
 // The pairwise distances of the selected sequences from the pair kernel (K10), with its parser.  No counterpart in the reference:
 // its clients fetch FastaAligned and compare the strings themselves.
@@ -585,13 +694,8 @@ void DistanceMatrix::validateOrderByFields(const Database& /*database*/) const {
 }
 
 QueryResult DistanceMatrix::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
-   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
-   const bool is_amino_acid = database.nuc_sequences.count(name) == 0;
-   CHECK_SILO_QUERY(!is_amino_acid || database.aa_sequences.count(name) != 0, "Database does not contain a sequence with name: '" + name + "'")
-   size_t total_count = 0;
-   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-      total_count += database.partitions[partition_id].sequence_count == 0 ? 0 : bitmap_filter[partition_id].cardinality();
-   }
+   const ComparedSequence sequence = comparedSequence(database, sequence_name);
+   const size_t total_count = selectedCount(database, bitmap_filter);
    CHECK_SILO_QUERY(total_count <= SEQUENCE_LIMIT, "DistanceMatrix action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences")
    requireUnsharded(database, "DistanceMatrix");
    QueryResult results;
@@ -599,64 +703,24 @@ QueryResult DistanceMatrix::execute(const Database& database, std::vector<Operat
       return results;
    }
    const auto n = static_cast<uint32_t>(total_count);
-   const int alphabet = is_amino_acid ? SILO_GPU_ALPHABET_AMINO_ACID : SILO_GPU_ALPHABET_NUCLEOTIDE;
-   const auto positions =
-      static_cast<uint32_t>(is_amino_acid ? database.aa_sequences.at(name).reference_sequence.size() : database.nuc_sequences.at(name).reference_sequence.size());
-   const size_t row_plane_words = static_cast<size_t>(SILO_GPU_DISTANCE_PLANES(alphabet)) * SILO_GPU_DISTANCE_WORDS(positions);
+   const uint32_t positions = sequence.positions;
    const size_t table_words = static_cast<size_t>(n) * n * 2u;
 
-   const std::string& primary_key_column = database.database_config.primary_key;
    std::vector<JsonValue> keys;  // of sequence 0 .. n - 1: partition order, then ascending row id
-   keys.reserve(n);
    std::vector<uint32_t> table(positions == 0 ? table_words : 0u, 0u);  // (a sequence without positions: nothing to compare, nothing launched)
    {
       // nothing in here returns to the pool before the stream has been waited for: the launches read it
       DevicePool& pool = database.partitions.front().pool;
-      DeviceBuffer device_planes = pool.acquire(std::max<size_t>(8, n * row_plane_words * sizeof(uint64_t)));
+      DeviceBuffer device_planes = pool.acquire(std::max<size_t>(8, n * sequence.row_plane_words * sizeof(uint64_t)));
+      DeviceBuffer device_chars = pool.acquire(packCharsBytes(n, positions));
       DeviceBuffer device_table = pool.acquire(table_words * sizeof(uint32_t));
-      std::vector<DeviceBuffer> live;  // per partition: its row ids and its characters
+      std::vector<DeviceBuffer> live;  // per partition: its row ids
       try {
-         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-            const DatabasePartition& partition = database.partitions[partition_id];
-            if (partition.sequence_count == 0) {
-               continue;
-            }
-            const std::vector<uint32_t> rows = selectedRows(partition, bitmap_filter[partition_id]);
-            if (rows.empty()) {
-               continue;
-            }
-            const size_t first_sequence = keys.size();
-            const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
-            for (const uint32_t row : rows) {
-               keys.push_back(primary_key.jsonOfRow(row));
-            }
-            if (keys.size() > n) {
-               throw std::runtime_error("DistanceMatrix: a filter selects more rows than its cardinality says");
-            }
-            if (positions == 0) {
-               continue;
-            }
-            const auto n_rows = static_cast<uint32_t>(rows.size());
-            const uint32_t seqstore_id = is_amino_acid ? partition.aa_sequences.at(name).seqstore_id : partition.nuc_sequences.at(name).seqstore_id;
-            auto* device_rows = live.emplace_back(partition.pool.acquire(rows.size() * sizeof(uint32_t))).as<uint32_t>();
-            checkGpu(silo_gpu_memcpy_h2d(device_rows, rows.data(), rows.size() * sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
-            auto* device_chars = live.emplace_back(partition.pool.acquire(rows.size() * static_cast<size_t>(positions))).as<char>();
-            checkGpu(
-               silo_gpu_reconstruct_sequences(partition.store, seqstore_id, device_rows, n_rows, device_chars, queryStream()),
-               "silo_gpu_reconstruct_sequences"
-            );
-            checkGpu(
-               silo_gpu_distance_pack(alphabet, device_chars, n_rows, positions, device_planes.as<uint64_t>() + first_sequence * row_plane_words, queryStream()),
-               "silo_gpu_distance_pack"
-            );
-         }
-         if (keys.size() != n) {
-            throw std::runtime_error("DistanceMatrix: a filter selects fewer rows than its cardinality says");
-         }
+         keys = packSelectedSequences(database, bitmap_filter, sequence, n, device_planes.as<uint64_t>(), device_chars.as<char>(), live, "DistanceMatrix");
          if (positions != 0) {
             // rows of different partitions are compared with each other: one call over all of them, one table fetched
             checkGpu(
-               silo_gpu_distance_pairs(alphabet, device_planes.as<uint64_t>(), n, positions, device_table.as<uint32_t>(), queryStream()),
+               silo_gpu_distance_pairs(sequence.alphabet, device_planes.as<uint64_t>(), n, positions, device_table.as<uint32_t>(), queryStream()),
                "silo_gpu_distance_pairs"
             );
             HostFetch fetch(device_table.get(), table_words * sizeof(uint32_t), queryStream());
@@ -716,13 +780,8 @@ void Clusters::validateOrderByFields(const Database& /*database*/) const {
 }
 
 QueryResult Clusters::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
-   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
-   const bool is_amino_acid = database.nuc_sequences.count(name) == 0;
-   CHECK_SILO_QUERY(!is_amino_acid || database.aa_sequences.count(name) != 0, "Database does not contain a sequence with name: '" + name + "'")
-   size_t total_count = 0;
-   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-      total_count += database.partitions[partition_id].sequence_count == 0 ? 0 : bitmap_filter[partition_id].cardinality();
-   }
+   const ComparedSequence sequence = comparedSequence(database, sequence_name);
+   const size_t total_count = selectedCount(database, bitmap_filter);
    CHECK_SILO_QUERY(total_count <= SEQUENCE_LIMIT, "Clusters action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences")
    requireUnsharded(database, "Clusters");
    QueryResult results;
@@ -730,74 +789,27 @@ QueryResult Clusters::execute(const Database& database, std::vector<OperatorResu
       return results;
    }
    const auto n = static_cast<uint32_t>(total_count);
-   const int alphabet = is_amino_acid ? SILO_GPU_ALPHABET_AMINO_ACID : SILO_GPU_ALPHABET_NUCLEOTIDE;
-   const auto positions =
-      static_cast<uint32_t>(is_amino_acid ? database.aa_sequences.at(name).reference_sequence.size() : database.nuc_sequences.at(name).reference_sequence.size());
-   const size_t row_plane_words = static_cast<size_t>(SILO_GPU_DISTANCE_PLANES(alphabet)) * SILO_GPU_DISTANCE_WORDS(positions);
-   constexpr uint32_t BATCH_ROWS = SILO_GPU_MAX_DISTANCE_ROWS;  // what one silo_gpu_distance_pack takes
+   const uint32_t positions = sequence.positions;
 
-   const std::string& primary_key_column = database.database_config.primary_key;
    std::vector<JsonValue> keys;  // of sequence 0 .. n - 1: partition order, then ascending row id, as DistanceMatrix numbers them
-   keys.reserve(n);
    // (a sequence without positions: nothing to compare, nothing launched — every pair has distance 0 and 0 positions compared)
    std::vector<uint32_t> labels(n, min_compared_positions == 0 ? 0u : UINT32_MAX);
    {
       // nothing in here returns to the pool before the stream has been waited for: the launches read it
       DevicePool& pool = database.partitions.front().pool;
-      DeviceBuffer device_planes = pool.acquire(std::max<size_t>(8, n * row_plane_words * sizeof(uint64_t)));
-      DeviceBuffer device_chars = pool.acquire(std::max<size_t>(1, static_cast<size_t>(std::min(n, BATCH_ROWS)) * positions));
+      DeviceBuffer device_planes = pool.acquire(std::max<size_t>(8, n * sequence.row_plane_words * sizeof(uint64_t)));
+      DeviceBuffer device_chars = pool.acquire(packCharsBytes(n, positions));
       DeviceBuffer device_adjacency = pool.acquire(static_cast<size_t>(n) * SILO_GPU_ADJACENCY_WORDS(n) * sizeof(uint64_t));
       DeviceBuffer device_labels = pool.acquire(n * sizeof(uint32_t));
       std::vector<DeviceBuffer> live;  // per partition: its row ids
       try {
-         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-            const DatabasePartition& partition = database.partitions[partition_id];
-            if (partition.sequence_count == 0) {
-               continue;
-            }
-            const std::vector<uint32_t> rows = selectedRows(partition, bitmap_filter[partition_id]);
-            if (rows.empty()) {
-               continue;
-            }
-            const size_t first_sequence = keys.size();
-            const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
-            for (const uint32_t row : rows) {
-               keys.push_back(primary_key.jsonOfRow(row));
-            }
-            if (keys.size() > n) {
-               throw std::runtime_error("Clusters: a filter selects more rows than its cardinality says");
-            }
-            if (positions == 0) {
-               continue;
-            }
-            const uint32_t seqstore_id = is_amino_acid ? partition.aa_sequences.at(name).seqstore_id : partition.nuc_sequences.at(name).seqstore_id;
-            auto* device_rows = live.emplace_back(partition.pool.acquire(rows.size() * sizeof(uint32_t))).as<uint32_t>();
-            checkGpu(silo_gpu_memcpy_h2d(device_rows, rows.data(), rows.size() * sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
-            // every batch gathers into the SAME character buffer: the batches are in order on queryStream(), so a batch's gather
-            // starts after the pack of the batch before it has read the characters
-            for (size_t begin = 0; begin < rows.size(); begin += BATCH_ROWS) {
-               const auto batch_rows = static_cast<uint32_t>(std::min<size_t>(BATCH_ROWS, rows.size() - begin));
-               checkGpu(
-                  silo_gpu_reconstruct_sequences(partition.store, seqstore_id, device_rows + begin, batch_rows, device_chars.as<char>(), queryStream()),
-                  "silo_gpu_reconstruct_sequences"
-               );
-               checkGpu(
-                  silo_gpu_distance_pack(
-                     alphabet, device_chars.as<char>(), batch_rows, positions, device_planes.as<uint64_t>() + (first_sequence + begin) * row_plane_words,
-                     queryStream()
-                  ),
-                  "silo_gpu_distance_pack"
-               );
-            }
-         }
-         if (keys.size() != n) {
-            throw std::runtime_error("Clusters: a filter selects fewer rows than its cardinality says");
-         }
+         keys = packSelectedSequences(database, bitmap_filter, sequence, n, device_planes.as<uint64_t>(), device_chars.as<char>(), live, "Clusters");
          if (positions != 0) {
             // rows of different partitions are linked with each other: one bit matrix over all of them, one labelling, n labels fetched
             checkGpu(
                silo_gpu_distance_within(
-                  alphabet, device_planes.as<uint64_t>(), n, positions, max_distance, min_compared_positions, device_adjacency.as<uint64_t>(), queryStream()
+                  sequence.alphabet, device_planes.as<uint64_t>(), n, positions, max_distance, min_compared_positions, device_adjacency.as<uint64_t>(),
+                  queryStream()
                ),
                "silo_gpu_distance_within"
             );
@@ -872,6 +884,146 @@ std::unique_ptr<Action> parseClusters(const json::Value& json) {
       min_cluster_size = json["minClusterSize"].as_uint32();
    }
    return std::make_unique<Clusters>(std::move(sequence_name), max_distance, min_compared_positions, min_cluster_size);
+}
+
+// ---- MinimumSpanningTree ---------------------------------------------------------------------------------
+// The minimum spanning forest of the selected sequences under DistanceMatrix's distance — the single-linkage tree: cut at any d it
+// leaves the clusters of Clusters at d — from the weights kernel, the one-block forest kernel and the listed-pairs kernel (K13),
+// with its parser.  No counterpart in the reference.
+void MinimumSpanningTree::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"firstKey", "secondKey", "distance", "comparedPositions"});
+}
+
+QueryResult MinimumSpanningTree::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const ComparedSequence sequence = comparedSequence(database, sequence_name);
+   const size_t total_count = selectedCount(database, bitmap_filter);
+   CHECK_SILO_QUERY(
+      total_count <= SEQUENCE_LIMIT, "MinimumSpanningTree action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences"
+   )
+   requireUnsharded(database, "MinimumSpanningTree");
+   QueryResult results;
+   if (total_count < 2) {
+      return results;
+   }
+   const auto n = static_cast<uint32_t>(total_count);
+   const uint32_t positions = sequence.positions;
+   const size_t max_edges = n - 1u;
+
+   struct Edge {
+      uint32_t first;
+      uint32_t second;
+      uint32_t distance;
+      uint32_t compared;
+   };
+   std::vector<Edge> edges;  // of the forest, by ascending key
+   std::vector<JsonValue> keys;  // of sequence 0 .. n - 1: partition order, then ascending row id, as DistanceMatrix numbers them
+   {
+      // nothing in here returns to the pool before the stream has been waited for: the launches read it
+      DevicePool& pool = database.partitions.front().pool;
+      DeviceBuffer device_planes = pool.acquire(std::max<size_t>(8, n * sequence.row_plane_words * sizeof(uint64_t)));
+      DeviceBuffer device_chars = pool.acquire(packCharsBytes(n, positions));
+      // (a sequence without positions: nothing to compare, nothing launched, no matrix)
+      DeviceBuffer device_weights = pool.acquire(positions == 0 ? sizeof(uint32_t) : static_cast<size_t>(n) * n * sizeof(uint32_t));
+      // what is fetched, in one piece: the keys of the edges, then the two counts of every edge, then the number of edges
+      const size_t pairs_offset = max_edges * sizeof(uint64_t);
+      const size_t count_offset = pairs_offset + max_edges * 2u * sizeof(uint32_t);
+      const size_t result_bytes = count_offset + sizeof(uint64_t);
+      DeviceBuffer device_result = pool.acquire(result_bytes);
+      auto* device_edges = device_result.as<uint64_t>();
+      auto* device_pairs = reinterpret_cast<uint32_t*>(device_result.as<char>() + pairs_offset);
+      auto* device_count = reinterpret_cast<uint32_t*>(device_result.as<char>() + count_offset);
+      std::vector<DeviceBuffer> live;  // per partition: its row ids
+      try {
+         keys = packSelectedSequences(database, bitmap_filter, sequence, n, device_planes.as<uint64_t>(), device_chars.as<char>(), live, "MinimumSpanningTree");
+         if (positions == 0) {
+            // every pair has distance 0 and 0 positions compared: the star of sequence 0, or nothing at all
+            for (uint32_t j = 1; min_compared_positions == 0 && j < n; ++j) {
+               edges.push_back({0, j, 0, 0});
+            }
+         } else {
+            // rows of different partitions are linked with each other: one matrix over all of them, one forest, its edges fetched
+            checkGpu(
+               silo_gpu_distance_weights(
+                  sequence.alphabet, device_planes.as<uint64_t>(), n, positions, max_distance.value_or(UINT32_MAX), min_compared_positions,
+                  device_weights.as<uint32_t>(), queryStream()
+               ),
+               "silo_gpu_distance_weights"
+            );
+            checkGpu(silo_gpu_spanning_forest(device_weights.as<uint32_t>(), n, device_edges, device_count, queryStream()), "silo_gpu_spanning_forest");
+            checkGpu(
+               silo_gpu_distance_listed_pairs(
+                  sequence.alphabet, device_planes.as<uint64_t>(), n, positions, device_edges, device_count, static_cast<uint32_t>(max_edges), device_pairs,
+                  queryStream()
+               ),
+               "silo_gpu_distance_listed_pairs"
+            );
+            HostFetch fetch(device_result.get(), result_bytes, queryStream());
+            const auto* host = static_cast<const char*>(fetch.wait());
+            uint32_t count = 0;
+            std::memcpy(&count, host + count_offset, sizeof(count));
+            if (count > max_edges) {
+               throw std::runtime_error("MinimumSpanningTree: more edges than a forest has");
+            }
+            edges.reserve(count);
+            for (uint32_t e = 0; e < count; ++e) {
+               uint64_t key = 0;
+               uint32_t counts[2];
+               std::memcpy(&key, host + e * sizeof(uint64_t), sizeof(key));
+               std::memcpy(counts, host + pairs_offset + e * sizeof(counts), sizeof(counts));
+               const auto first = static_cast<uint32_t>(key >> SILO_GPU_SPANNING_KEY_ROW_BITS) & (SILO_GPU_MAX_SPANNING_ROWS - 1u);
+               const auto second = static_cast<uint32_t>(key) & (SILO_GPU_MAX_SPANNING_ROWS - 1u);
+               if (!(first < second && second < n)) {
+                  throw std::runtime_error("MinimumSpanningTree: an edge names no pair of selected sequences");
+               }
+               if (key >> SILO_GPU_SPANNING_KEY_WEIGHT_SHIFT != counts[0]) {
+                  throw std::runtime_error("MinimumSpanningTree: an edge's weight is not the distance of its pair");
+               }
+               edges.push_back({first, second, counts[0], counts[1]});
+            }
+         }
+         // the copy was the last thing enqueued, but say it: nothing of this query runs any more when its buffers go back
+         checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+      } catch (...) {
+         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+         (void)silo_gpu_stream_synchronize(queryStream());
+         throw;
+      }
+   }
+
+   for (const Edge& edge : edges) {
+      QueryResultEntry& entry = results.query_result.emplace_back();
+      entry.fields.emplace("firstKey", keys[edge.first]);
+      entry.fields.emplace("secondKey", keys[edge.second]);
+      entry.fields.emplace("distance", static_cast<int32_t>(edge.distance));
+      entry.fields.emplace("comparedPositions", static_cast<int32_t>(edge.compared));
+   }
+   return results;
+}
+
+std::unique_ptr<Action> parseMinimumSpanningTree(const json::Value& json) {
+   std::optional<std::string> sequence_name;
+   if (json.contains("sequenceName")) {
+      CHECK_SILO_QUERY(json["sequenceName"].is_string(), "MinimumSpanningTree action: the field sequenceName, if present, must be of type string")
+      sequence_name = json["sequenceName"].as_string();
+   }
+   std::optional<uint32_t> max_distance;
+   if (json.contains("maxDistance")) {
+      CHECK_SILO_QUERY(
+         json["maxDistance"].is_number_unsigned() && json["maxDistance"].as_int64() >= 0 && json["maxDistance"].as_int64() <= INT32_MAX,
+         "MinimumSpanningTree action: the field maxDistance, if present, must be a non-negative integer"
+      )
+      max_distance = json["maxDistance"].as_uint32();
+   }
+   uint32_t min_compared_positions = 0;
+   if (json.contains("minComparedPositions")) {
+      CHECK_SILO_QUERY(
+         json["minComparedPositions"].is_number_unsigned() && json["minComparedPositions"].as_int64() >= 0 &&
+            json["minComparedPositions"].as_int64() <= INT32_MAX,
+         "MinimumSpanningTree action: the field minComparedPositions, if present, must be a non-negative integer"
+      )
+      min_compared_positions = json["minComparedPositions"].as_uint32();
+   }
+   return std::make_unique<MinimumSpanningTree>(std::move(sequence_name), max_distance, min_compared_positions);
 }
 
 // ---- NearestNeighbours -----------------------------------------------------------------------------------

@@ -680,6 +680,8 @@ std::unique_ptr<Action> parseCrossTabulation(const json::Value& json);
 std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json);
 /// The parser of Clusters (metadata_actions.cpp).
 std::unique_ptr<Action> parseClusters(const json::Value& json);
+/// The parser of MinimumSpanningTree (metadata_actions.cpp).
+std::unique_ptr<Action> parseMinimumSpanningTree(const json::Value& json);
 /// The parser of NearestNeighbours (metadata_actions.cpp).
 std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json);
 
@@ -800,6 +802,26 @@ class Clusters : public Action {
          max_distance(max_distance),
          min_compared_positions(min_compared_positions),
          min_cluster_size(min_cluster_size) {}
+};
+
+/// MinimumSpanningTree (metadata_actions.cpp): the minimum spanning forest of the selected sequences — numbered as DistanceMatrix
+/// numbers them — over the graph whose edges are the pairs i < j with distance <= maxDistance (absent: no bound) and >=
+/// minComparedPositions positions compared, ordered by the key distance * 2^26 + i * 2^13 + j.  The order is strict, so the forest is
+/// unique; cut at any d it leaves the clusters of Clusters at d.  One row per edge of the forest: the two keys, the distance, the
+/// compared positions, by ascending key; a sequence without an edge is in no row.  The rows are gathered and packed as for Clusters;
+/// then one silo_gpu_distance_weights (the n x n matrix of the edges' distances: 4 n^2 bytes, 256 MB at the limit), one
+/// silo_gpu_spanning_forest, one silo_gpu_distance_listed_pairs (K13), and ONE fetch of the count, the keys and the edges' counts.
+class MinimumSpanningTree : public Action {
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   std::optional<uint32_t> max_distance;
+   uint32_t min_compared_positions;
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+
+  public:
+   static constexpr uint32_t SEQUENCE_LIMIT = SILO_GPU_MAX_SPANNING_ROWS;
+   MinimumSpanningTree(std::optional<std::string> sequence_name, std::optional<uint32_t> max_distance, uint32_t min_compared_positions)
+       : sequence_name(std::move(sequence_name)), max_distance(max_distance), min_compared_positions(min_compared_positions) {}
 };
 
 /// NearestNeighbours (metadata_actions.cpp): the `neighbours` rows of the WHOLE database closest to one query sequence — a row named

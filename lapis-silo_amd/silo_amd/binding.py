@@ -112,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_store_scan_covered_rows", "silo_gpu_store_scan_end_events", "silo_gpu_store_scan_residual_keys",
     "silo_gpu_filters_grouped", "silo_gpu_filters_cross",
     "silo_gpu_distance_pack", "silo_gpu_distance_pairs", "silo_gpu_distance_within", "silo_gpu_adjacency_components",
+    "silo_gpu_distance_weights", "silo_gpu_spanning_forest", "silo_gpu_distance_listed_pairs",
     "silo_gpu_query_distances", "silo_gpu_nearest_rows", "silo_gpu_bitset_from_distances",
 ]
 
@@ -185,6 +186,9 @@ def load_library():
     lib.silo_gpu_distance_pairs.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_distance_within.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_adjacency_components.argtypes = [vp, ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_distance_weights.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_spanning_forest.argtypes = [vp, ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_distance_listed_pairs.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_query_distances.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_nearest_rows.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_bitset_from_distances.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
@@ -605,6 +609,87 @@ def adjacency_components(adjacency, n_rows, fill=None, stream=None):
         return device_read(labels, np.uint32, n_rows, stream), int(device_read(rounds, np.uint32, 1, stream)[0])
     finally:
         for ptr in (adjacency_dev, labels, rounds):
+            device_free(ptr)
+
+
+MAX_SPANNING_ROWS = 8192       # SILO_GPU_MAX_SPANNING_ROWS
+SPANNING_THREADS = 1024        # SILO_GPU_SPANNING_THREADS: the one block of silo_gpu_spanning_forest
+SPANNING_KEY_ROW_BITS = 13     # SILO_GPU_SPANNING_KEY_ROW_BITS: a row of an edge's key
+SPANNING_KEY_WEIGHT_SHIFT = 26  # SILO_GPU_SPANNING_KEY_WEIGHT_SHIFT: the weight lies above the two rows
+NO_EDGE = 0xFFFFFFFF           # a cell of the matrix of K13 that is no edge; as max_distance: no bound
+
+
+def spanning_key(weight, i, j):
+    """SILO_GPU_SPANNING_KEY: weight << 26 | i << 13 | j for the edge i < j."""
+    return (int(weight) << SPANNING_KEY_WEIGHT_SHIFT) | (int(i) << SPANNING_KEY_ROW_BITS) | int(j)
+
+
+def spanning_key_fields(keys):
+    """(weight, i, j) of keys as silo_gpu_spanning_forest writes them (uint64 arrays in, uint64 arrays out)."""
+    keys = np.asarray(keys, dtype=np.uint64)
+    row_mask = np.uint64(MAX_SPANNING_ROWS - 1)
+    return keys >> np.uint64(SPANNING_KEY_WEIGHT_SHIFT), (keys >> np.uint64(SPANNING_KEY_ROW_BITS)) & row_mask, keys & row_mask
+
+
+def distance_weights(alphabet_id, planes_ptr, n_rows, positions, max_distance, min_compared, fill=None, guard_words=0, stream=None):
+    """silo_gpu_distance_weights (K13) over planes as distance_pack / distance_pack_rows leave them: the n_rows * n_rows cells uint32
+    of the matrix, cell (i, j) = differing where i != j and differing <= max_distance and compared >= min_compared, NO_EDGE
+    elsewhere, followed by `guard_words` uint32 behind them that the call must not touch: those hold the byte `fill` repeated (the
+    whole allocation is filled with it before the launch), or whatever the allocation held."""
+    lib = load_library()
+    cells = n_rows * n_rows + int(guard_words)
+    out = device_malloc(cells * 4, fill, stream)
+    try:
+        _check(lib.silo_gpu_distance_weights(_abi_alphabet(alphabet_id), planes_ptr, n_rows, positions, max_distance, min_compared, out, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(out, np.uint32, cells, stream)
+    finally:
+        device_free(out)
+
+
+def spanning_forest(weights, n_rows, fill=None, guard_words=0, stream=None):
+    """silo_gpu_spanning_forest (K13) over a host matrix uint32 [n_rows * n_rows] as silo_gpu_distance_weights leaves it: (edges
+    uint64 [max(n_rows - 1, 0) + guard_words], count uint32 [1]) — edges[:count] the keys of the forest, ascending; the entries at or
+    past the count, and the count where nothing is written, hold the byte `fill` repeated (both are filled with it before the
+    launch)."""
+    lib = load_library()
+    weights = np.ascontiguousarray(weights, dtype=np.uint32).reshape(-1)
+    slots = max(n_rows - 1, 0) + int(guard_words)
+    weights_dev = device_malloc(weights.nbytes)
+    edges = device_malloc(slots * 8, fill, stream)
+    count = device_malloc(4, fill, stream)
+    try:
+        if weights.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(weights_dev, _ptr(weights), weights.nbytes, stream))
+        _check(lib.silo_gpu_spanning_forest(weights_dev, n_rows, edges, count, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(edges, np.uint64, slots, stream), device_read(count, np.uint32, 1, stream)
+    finally:
+        for ptr in (weights_dev, edges, count):
+            device_free(ptr)
+
+
+def distance_listed_pairs(alphabet_id, planes_ptr, n_rows, positions, edges, count, max_pairs, fill=None, guard_words=0, stream=None):
+    """silo_gpu_distance_listed_pairs (K13) over planes as distance_pack / distance_pack_rows leave them, for the host keys `edges`
+    uint64 and the count `count`: uint32 [max_pairs + guard_words][2] — row e = (differing, compared) of the pair in the low 26 bits
+    of edges[e], for e < min(count, max_pairs); the rows at or past that hold the byte `fill` repeated (the whole allocation is
+    filled with it before the launch)."""
+    lib = load_library()
+    edges = np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1)
+    count = np.array([count], dtype=np.uint32)
+    rows = int(max_pairs) + int(guard_words)
+    edges_dev = device_malloc(edges.nbytes)
+    count_dev = device_malloc(4)
+    out = device_malloc(rows * 8, fill, stream)
+    try:
+        if edges.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(edges_dev, _ptr(edges), edges.nbytes, stream))
+        _check(lib.silo_gpu_memcpy_h2d(count_dev, _ptr(count), 4, stream))
+        _check(lib.silo_gpu_distance_listed_pairs(_abi_alphabet(alphabet_id), planes_ptr, n_rows, positions, edges_dev, count_dev, max_pairs, out, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(out, np.uint32, rows * 2, stream).reshape(rows, 2)
+    finally:
+        for ptr in (edges_dev, count_dev, out):
             device_free(ptr)
 
 
