@@ -672,6 +672,48 @@ int silo_gpu_distance_listed_pairs(
    uint32_t max_pairs, uint32_t* out_dev, void* stream
 );
 
+/* ---- K14: the distances of one set of rows against another, and the k lowest of every row (NearestAmong) ---
+ * Neither entry takes a store.  A column j is ELIGIBLE for a row i when j != self_column_dev[i], differing(i, j) <= max_distance
+ * and compared(i, j) >= min_compared, both as silo_gpu_distance_pairs counts them for row i of the row planes and row j of the
+ * column planes (max_distance == UINT32_MAX: no bound; min_compared == 0: none).
+ * silo_gpu_distance_cross reads two plane buffers as silo_gpu_distance_pack leaves them — n_rows <= SILO_GPU_MAX_CROSS_ROWS rows of
+ * the one, n_columns <= SILO_GPU_MAX_CROSS_COLUMNS rows of the other, the same alphabet and positions; the same buffer may stand on
+ * both sides — and WRITES the rectangle
+ *     cells_dev[(i * n_columns + j) * 2 + 0 .. 1] = (differing, compared)       where j is eligible for i,
+ *                                                   (UINT32_MAX, UINT32_MAX)   where it is not.
+ * self_column_dev: n_rows values in device memory, the column that is the same row as row i and is never eligible for it; NULL:
+ * none; a value at or past n_columns names no column.  Every one of the n_rows * n_columns cells is written once and nothing behind
+ * them is touched: the caller never clears the buffer.  No atomics: the cells do not depend on how the blocks are scheduled.  One
+ * launch on `stream`, no waiting: the plain grid of n_rows / 16 x n_columns / 64 tiles (rounded up; no symmetry, no transpose), the
+ * tile, the LDS staging and the early exit of k_distance_within (the kernels share the walk); a block whose pairs have all passed
+ * max_distance stops, and its cells are the UINT32_MAX pairs.  A thread stores its four cells as 8-byte stores: cells_dev is 8-byte
+ * aligned.  n_rows == 0 or n_columns == 0: success, nothing launched.  positions == 0: every pair has compared = differing = 0, and
+ * the cells of that are written.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for an alphabet other than the two, a
+ * NULL plane or cell buffer, or either count above its limit.
+ * silo_gpu_nearest_columns takes such cells (a cell whose first word is UINT32_MAX is not eligible) and WRITES per row i < n_rows
+ *     counts_dev[i] = min(k, eligible cells of row i)
+ *     out_dev[(i * k + r) * 3 + 0 .. 2] = column, distance, compared     for r < counts_dev[i], ascending by (distance, column)
+ * — a strict order, so the lists are unique and two calls give the same output.  Entries of a row's list at or past its count are
+ * untouched.  One launch on `stream`, no waiting: a block of SILO_GPU_NEIGHBOUR_THREADS threads per row keeps the keys
+ *     distance << SILO_GPU_NEIGHBOUR_KEY_COLUMN_BITS | column
+ * of its <= 8 cells per thread in registers (UINT64_MAX: not eligible) and runs exactly min(k, n_columns) rounds of a block-wide
+ * minimum (the forest kernel's reduction); a round lists one column, whose owner retires its key, or nothing at all.  Nothing read
+ * from the cells is used as an index; no atomics, no spin.  n_rows == 0: success, nothing launched.  n_columns == 0: the counts are
+ * written as 0.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer, k == 0, k >
+ * SILO_GPU_MAX_NEIGHBOUR_COLUMNS or either count above its limit. */
+#define SILO_GPU_MAX_CROSS_ROWS 2048      /* the rows of the rectangle: == SILO_GPU_MAX_DISTANCE_ROWS */
+#define SILO_GPU_MAX_CROSS_COLUMNS 8192   /* its columns: == SILO_GPU_MAX_CLUSTER_ROWS */
+#define SILO_GPU_MAX_NEIGHBOUR_COLUMNS 64 /* k of silo_gpu_nearest_columns */
+#define SILO_GPU_NEIGHBOUR_THREADS 1024
+#define SILO_GPU_NEIGHBOUR_KEY_COLUMN_BITS 13 /* the column of a key: SILO_GPU_MAX_CROSS_COLUMNS == 1 << 13 */
+int silo_gpu_distance_cross(
+   int alphabet, const uint64_t* row_planes_dev, uint32_t n_rows, const uint64_t* column_planes_dev, uint32_t n_columns, uint32_t positions,
+   const uint32_t* self_column_dev, uint32_t max_distance, uint32_t min_compared, uint32_t* cells_dev, void* stream
+);
+int silo_gpu_nearest_columns(
+   const uint32_t* cells_dev, uint32_t n_rows, uint32_t n_columns, uint32_t k, uint32_t* out_dev, uint32_t* counts_dev, void* stream
+);
+
 /* ---- K11: the rows of the whole store nearest to a query (NearestNeighbours) --------------------------
  * silo_gpu_query_distances compares one query — query_chars, `positions` characters in HOST memory — with EVERY row of a sequence
  * store, read off the store's own layout (identity / code planes with escape keys, one-hot rows with a derived symbol, runs of the

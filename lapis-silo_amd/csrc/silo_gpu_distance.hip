@@ -18,6 +18,10 @@
 //                      `differing` and every other cell is UINT32_MAX (silo_gpu_distance_weights); a tile writes its transpose too
 //   k_distance_listed_pairs  a wave per pair of a list of keys: both counts of the pairs a spanning forest kept
 //                      (silo_gpu_distance_listed_pairs)
+// and as a rectangle, one set of rows against another, behind NearestAmong (K14):
+//   k_distance_cross   the same walk over the plain grid of 16 x 64 tiles of n_rows x n_columns pairs, each side with a plane buffer
+//                      of its own; a pair that is eligible keeps both counts and every other cell is (UINT32_MAX, UINT32_MAX)
+//                      (silo_gpu_distance_cross)
 #include "store_internal.h"
 
 using namespace silo_gpu_detail;
@@ -205,21 +209,35 @@ __device__ __forceinline__ void withinTileOf(uint32_t index, uint32_t row_tiles,
 struct WithinPairs {
    uint32_t compared[WITHIN_ROWS_PER_WAVE];
    uint32_t differing[WITHIN_ROWS_PER_WAVE];
-   bool open[WITHIN_ROWS_PER_WAVE];  // still linkable: rows < n_rows, i != j, differing <= max_distance so far
+   bool open[WITHIN_ROWS_PER_WAVE];  // still linkable: the caller's start (row and column in range, not the same row), then differing <= max_distance so far
 };
 
-/// The walk of tile (ti, tj) that k_distance_within and k_distance_weights share; the whole block calls it, s_rows is its LDS of
-/// (WITHIN_TILE_ROWS + WITHIN_TILE_COLS) * withinRowWords<PLANES>() words.  Wave v owns rows ti * 16 + 4 v .. + 3 of the tile, lane l
-/// its column tj * 64 + l.  Per chunk of WITHIN_CHUNK_WORDS words the block copies the words of all planes of its 16 + 64 rows into
-/// LDS — a row at or past n_rows is staged as zeros, so nothing past the buffer is read — and every thread walks the chunk with its
-/// column's words (one LDS read per plane and word) against its four rows' (the same address for the whole wave: broadcast).  A
-/// pair is `open` while it can still be linked: never a pair with a row at or past n_rows or with i == j, and no longer once
-/// differing > max_distance.  After each chunk the block leaves the loop if no pair is open.  Every path out of here ends with a
-/// barrier after the last read of s_rows (or never touched it): the caller may reuse it at once.
+/// Where the pairs of this thread start: in range on both sides and not what `excluded(row, column)` names.
+template <typename Excluded>
+__device__ __forceinline__ void withinOpen(WithinPairs& pairs, uint32_t ti, uint32_t tj, uint32_t n_rows, uint32_t n_columns, Excluded excluded) {
+   const uint32_t first_row = ti * WITHIN_TILE_ROWS + (threadIdx.x / 64u) * WITHIN_ROWS_PER_WAVE;
+   const uint32_t column = tj * WITHIN_TILE_COLS + (threadIdx.x & 63u);
+#pragma unroll
+   for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
+      pairs.open[r] = first_row + r < n_rows && column < n_columns && !excluded(first_row + r, column);
+   }
+}
+
+/// The walk of tile (ti, tj) that k_distance_within, k_distance_weights and k_distance_cross share; the whole block calls it, s_rows
+/// is its LDS of (WITHIN_TILE_ROWS + WITHIN_TILE_COLS) * withinRowWords<PLANES>() words.  The row side (row_planes, n_rows) and the
+/// column side (column_planes, n_columns) each have a plane buffer and a row count of their own; the square kernels pass the same
+/// buffer and count twice.  Wave v owns rows ti * 16 + 4 v .. + 3 of the tile, lane l its column tj * 64 + l.  Per chunk of
+/// WITHIN_CHUNK_WORDS words the block copies the words of all planes of its 16 + 64 rows into LDS — a row at or past its side's
+/// count is staged as zeros, so nothing past either buffer is read — and every thread walks the chunk with its column's words (one
+/// LDS read per plane and word) against its four rows' (the same address for the whole wave: broadcast).  The CALLER sets
+/// pairs.open before the walk (withinOpen): a pair is `open` while it can still be linked — never a pair with a row at or past
+/// n_rows, a column at or past n_columns or the caller's own exclusion (i == j, self[i] == j), and no longer once differing >
+/// max_distance.  The walk clears the two counts.  After each chunk the block leaves the loop if no pair is open.  Every path out of
+/// here ends with a barrier after the last read of s_rows (or never touched it): the caller may reuse it at once.
 template <uint32_t PLANES>
 __device__ __forceinline__ void withinTileWalk(
-   const uint64_t* __restrict__ planes, uint32_t n_rows, uint32_t words, uint32_t ti, uint32_t tj, uint32_t max_distance, uint64_t* s_rows,
-   WithinPairs& pairs
+   const uint64_t* __restrict__ row_planes, uint32_t n_rows, const uint64_t* __restrict__ column_planes, uint32_t n_columns, uint32_t words,
+   uint32_t ti, uint32_t tj, uint32_t max_distance, uint64_t* s_rows, WithinPairs& pairs
 ) {
    constexpr uint32_t ROW_WORDS = withinRowWords<PLANES>();
    constexpr uint32_t STAGED_ROWS = WITHIN_TILE_ROWS + WITHIN_TILE_COLS;
@@ -227,8 +245,6 @@ __device__ __forceinline__ void withinTileWalk(
    static_assert(STAGED % DISTANCE_THREADS == 0);
    const uint32_t wave = threadIdx.x / 64u;
    const uint32_t lane = threadIdx.x & 63u;
-   const uint32_t first_row = ti * WITHIN_TILE_ROWS + wave * WITHIN_ROWS_PER_WAVE;
-   const uint32_t column = tj * WITHIN_TILE_COLS + lane;
    const uint64_t* mine = s_rows + wave * WITHIN_ROWS_PER_WAVE * ROW_WORDS;
    const uint64_t* other = s_rows + (WITHIN_TILE_ROWS + lane) * ROW_WORDS;
    uint32_t (&compared)[WITHIN_ROWS_PER_WAVE] = pairs.compared;
@@ -238,7 +254,6 @@ __device__ __forceinline__ void withinTileWalk(
    for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
       compared[r] = 0;
       differing[r] = 0;
-      open[r] = first_row + r < n_rows && column < n_rows && first_row + r != column;
    }
    for (uint32_t chunk_begin = 0; chunk_begin < words; chunk_begin += WITHIN_CHUNK_WORDS) {
       const uint32_t chunk_words = min(words - chunk_begin, WITHIN_CHUNK_WORDS);
@@ -249,10 +264,11 @@ __device__ __forceinline__ void withinTileWalk(
          const uint32_t word = element % WITHIN_CHUNK_WORDS;
          const uint32_t row_plane = element / WITHIN_CHUNK_WORDS;  // (row of the tile's 16, then column of its 64) * PLANES + plane
          const uint32_t local_row = row_plane / PLANES;
-         const uint32_t row = local_row < WITHIN_TILE_ROWS ? ti * WITHIN_TILE_ROWS + local_row : tj * WITHIN_TILE_COLS + (local_row - WITHIN_TILE_ROWS);
+         const bool row_side = local_row < WITHIN_TILE_ROWS;
+         const uint32_t row = row_side ? ti * WITHIN_TILE_ROWS + local_row : tj * WITHIN_TILE_COLS + (local_row - WITHIN_TILE_ROWS);
          staged[k] = 0;
-         if (row < n_rows && word < chunk_words) {
-            staged[k] = planes[(static_cast<size_t>(row) * PLANES + row_plane % PLANES) * words + chunk_begin + word];
+         if (row < (row_side ? n_rows : n_columns) && word < chunk_words) {
+            staged[k] = (row_side ? row_planes : column_planes)[(static_cast<size_t>(row) * PLANES + row_plane % PLANES) * words + chunk_begin + word];
          }
       }
 #pragma unroll
@@ -306,7 +322,8 @@ __global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_within(
    uint32_t tj;
    withinTileOf(blockIdx.x, row_tiles, adjacency_words, ti, tj);
    WithinPairs pairs;
-   withinTileWalk<PLANES>(planes, n_rows, words, ti, tj, max_distance, s_rows, pairs);
+   withinOpen(pairs, ti, tj, n_rows, n_rows, [](uint32_t i, uint32_t j) { return i == j; });
+   withinTileWalk<PLANES>(planes, n_rows, planes, n_rows, words, ti, tj, max_distance, s_rows, pairs);
    const uint32_t lane = threadIdx.x & 63u;
    const uint32_t first_row = ti * WITHIN_TILE_ROWS + (threadIdx.x / 64u) * WITHIN_ROWS_PER_WAVE;
 #pragma unroll
@@ -339,7 +356,8 @@ __global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_weights(
    uint32_t tj;
    withinTileOf(blockIdx.x, row_tiles, adjacency_words, ti, tj);
    WithinPairs pairs;
-   withinTileWalk<PLANES>(planes, n_rows, words, ti, tj, max_distance, s_rows, pairs);
+   withinOpen(pairs, ti, tj, n_rows, n_rows, [](uint32_t i, uint32_t j) { return i == j; });
+   withinTileWalk<PLANES>(planes, n_rows, planes, n_rows, words, ti, tj, max_distance, s_rows, pairs);
    const uint32_t wave = threadIdx.x / 64u;
    const uint32_t lane = threadIdx.x & 63u;
    const uint32_t first_row = ti * WITHIN_TILE_ROWS + wave * WITHIN_ROWS_PER_WAVE;
@@ -370,6 +388,39 @@ __global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_weights(
       const uint32_t mirrored_row = tj * WITHIN_TILE_COLS + tile_column;
       if (row < n_rows && mirrored_row < n_rows) {
          weights[static_cast<size_t>(mirrored_row) * n_rows + row] = s_tile[tile_row * WEIGHTS_TILE_STRIDE + tile_column];
+      }
+   }
+}
+
+/// grid = (n_columns / 64 rounded up, n_rows / 16 rounded up): the plain rectangle, no symmetry and no transpose.  self_column
+/// (NULL: none) names per row the column that is the same database row; a value at or past n_columns excludes nothing.  After the
+/// walk a pair's cell is (differing, compared) if it is eligible (open, differing <= max_distance, compared >= min_compared) and
+/// (UINT32_MAX, UINT32_MAX) if not — self and the pairs of a block that stopped early included.  Every thread stores its four cells
+/// (row, column) where row < n_rows and column < n_columns as 8-byte stores: consecutive lanes, consecutive cells.
+template <uint32_t PLANES>
+__global__ __launch_bounds__(DISTANCE_THREADS) void k_distance_cross(
+   const uint64_t* __restrict__ row_planes, uint32_t n_rows, const uint64_t* __restrict__ column_planes, uint32_t n_columns, uint32_t words,
+   const uint32_t* __restrict__ self_column, uint32_t max_distance, uint32_t min_compared, uint32_t* __restrict__ cells
+) {
+   __shared__ uint64_t s_rows[(WITHIN_TILE_ROWS + WITHIN_TILE_COLS) * withinRowWords<PLANES>()];
+   const uint32_t ti = blockIdx.y;
+   const uint32_t tj = blockIdx.x;
+   const uint32_t first_row = ti * WITHIN_TILE_ROWS + (threadIdx.x / 64u) * WITHIN_ROWS_PER_WAVE;
+   const uint32_t column = tj * WITHIN_TILE_COLS + (threadIdx.x & 63u);
+   uint32_t self[WITHIN_ROWS_PER_WAVE];
+#pragma unroll
+   for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
+      self[r] = self_column != nullptr && first_row + r < n_rows ? self_column[first_row + r] : UINT32_MAX;
+   }
+   WithinPairs pairs;
+   withinOpen(pairs, ti, tj, n_rows, n_columns, [&](uint32_t i, uint32_t j) { return self[i - first_row] == j; });
+   withinTileWalk<PLANES>(row_planes, n_rows, column_planes, n_columns, words, ti, tj, max_distance, s_rows, pairs);
+#pragma unroll
+   for (uint32_t r = 0; r < WITHIN_ROWS_PER_WAVE; ++r) {
+      const bool eligible = pairs.open[r] && pairs.differing[r] <= max_distance && pairs.compared[r] >= min_compared;
+      if (first_row + r < n_rows && column < n_columns) {
+         *reinterpret_cast<uint2*>(cells + (static_cast<size_t>(first_row + r) * n_columns + column) * 2u) =
+            eligible ? make_uint2(pairs.differing[r], pairs.compared[r]) : make_uint2(UINT32_MAX, UINT32_MAX);
       }
    }
 }
@@ -448,6 +499,7 @@ constexpr const char* MORE_THAN_DISTANCE_ROWS = "more rows than SILO_GPU_MAX_DIS
 constexpr const char* MORE_THAN_CLUSTER_ROWS = "more rows than SILO_GPU_MAX_CLUSTER_ROWS";
 constexpr const char* MORE_THAN_SPANNING_ROWS = "more rows than SILO_GPU_MAX_SPANNING_ROWS";
 static_assert(SILO_GPU_MAX_SPANNING_ROWS == SILO_GPU_MAX_CLUSTER_ROWS && SILO_GPU_MAX_SPANNING_ROWS == 1u << SILO_GPU_SPANNING_KEY_ROW_BITS);
+static_assert(SILO_GPU_MAX_CROSS_ROWS == SILO_GPU_MAX_DISTANCE_ROWS && SILO_GPU_MAX_CROSS_COLUMNS == SILO_GPU_MAX_CLUSTER_ROWS);
 
 /// Blocks of k_distance_within / k_distance_weights: the tiles withinTileOf numbers.
 uint32_t withinTiles(uint32_t row_tiles, uint32_t adjacency_words) {
@@ -577,6 +629,39 @@ int silo_gpu_distance_weights(
    } else {
       k_distance_weights<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_AMINO_ACID)><<<grid, DISTANCE_THREADS, 0, hip_stream>>>(
          planes_dev, n_rows, words, row_tiles, adjacency_words, max_distance, min_compared, weights_dev
+      );
+   }
+   HIP_TRY(hipGetLastError());
+   return SILO_GPU_OK;
+}
+
+int silo_gpu_distance_cross(
+   int alphabet, const uint64_t* row_planes_dev, uint32_t n_rows, const uint64_t* column_planes_dev, uint32_t n_columns, uint32_t positions,
+   const uint32_t* self_column_dev, uint32_t max_distance, uint32_t min_compared, uint32_t* cells_dev, void* stream
+) {
+   if (const char* complaint = distanceComplaint(alphabet, row_planes_dev, cells_dev, n_rows, SILO_GPU_MAX_CROSS_ROWS, "more rows than SILO_GPU_MAX_CROSS_ROWS");
+       complaint != nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string("silo_gpu_distance_cross: ") + complaint);
+   }
+   if (column_planes_dev == nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_distance_cross: a buffer is NULL");
+   }
+   if (n_columns > SILO_GPU_MAX_CROSS_COLUMNS) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_distance_cross: more columns than SILO_GPU_MAX_CROSS_COLUMNS");
+   }
+   if (n_rows == 0 || n_columns == 0) {
+      return SILO_GPU_OK;
+   }
+   const uint32_t words = SILO_GPU_DISTANCE_WORDS(positions);  // 0 positions: no chunk is walked, every pair has (0, 0)
+   const dim3 grid((n_columns + WITHIN_TILE_COLS - 1) / WITHIN_TILE_COLS, (n_rows + WITHIN_TILE_ROWS - 1) / WITHIN_TILE_ROWS);
+   auto hip_stream = static_cast<hipStream_t>(stream);
+   if (alphabet == SILO_GPU_ALPHABET_NUCLEOTIDE) {
+      k_distance_cross<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_NUCLEOTIDE)><<<grid, DISTANCE_THREADS, 0, hip_stream>>>(
+         row_planes_dev, n_rows, column_planes_dev, n_columns, words, self_column_dev, max_distance, min_compared, cells_dev
+      );
+   } else {
+      k_distance_cross<SILO_GPU_DISTANCE_PLANES(SILO_GPU_ALPHABET_AMINO_ACID)><<<grid, DISTANCE_THREADS, 0, hip_stream>>>(
+         row_planes_dev, n_rows, column_planes_dev, n_columns, words, self_column_dev, max_distance, min_compared, cells_dev
       );
    }
    HIP_TRY(hipGetLastError());

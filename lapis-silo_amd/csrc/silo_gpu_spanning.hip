@@ -6,6 +6,7 @@
 //   k_spanning_forest   ONE block: Prim's algorithm with a restart — the best key of every vertex in a register of its thread, per
 //                       step one row of the matrix and one block-wide minimum — then a bitonic sort of the keys in LDS
 //                       (silo_gpu_spanning_forest)
+#include "block_minimum.h"
 #include "store_internal.h"
 
 using namespace silo_gpu_detail;
@@ -30,9 +31,9 @@ static_assert(SPANNING_WAVES <= 64 && (SPANNING_WAVES & (SPANNING_WAVES - 1u)) =
 /// the forest (NO_KEY: none), in_forest its vertices that are in.  Vertex 0 starts the forest.  A step, n_rows - 1 of them: the
 /// block reads row u of the matrix, u the vertex that entered last — consecutive threads, consecutive cells, all loads of a thread
 /// in flight — and lowers best[] of its vertices outside the forest with one compare each; the minimum of what these vertices
-/// offer (see RESTART) goes through a wave reduction and SPANNING_WAVES partials in LDS, two sets of them in turn so that one
-/// barrier per step is enough.  Every thread then holds the same minimum: a key — thread 0 appends it to s_keys, and the key's end
-/// outside the forest, which the low bit names, enters — or no key at all, and the lowest vertex outside enters without an edge.
+/// offer (see RESTART) goes through a wave reduction and SPANNING_WAVES partials in LDS (blockMinimum, block_minimum.h), two sets
+/// of them in turn so that one barrier per step is enough.  Every thread then holds the same minimum: a key — thread 0 appends it
+/// to s_keys, and the key's end outside the forest, which the low bit names, enters — or no key at all, and the lowest vertex outside enters without an edge.
 /// Keys are distinct (an unordered pair has one), so the order is strict and Prim's choice is the unique forest's.  Every vertex
 /// index comes from threadIdx and the loop counters, never from the matrix, whose cells only become the high bits of a key; every
 /// loop has a trip count fixed by n_rows.  Then s_keys, padded with NO_KEY to a power of two, is sorted (bitonic, a barrier per
@@ -42,8 +43,6 @@ __global__ __launch_bounds__(SPANNING_THREADS) void k_spanning_forest(
 ) {
    __shared__ uint64_t s_keys[SPANNING_MAX_ROWS];
    __shared__ uint64_t s_partial[2][SPANNING_WAVES];
-   const uint32_t wave = threadIdx.x / 64u;
-   const uint32_t lane = threadIdx.x & 63u;
    uint64_t best[SPANNING_OWNED];
 #pragma unroll
    for (uint32_t k = 0; k < SPANNING_OWNED; ++k) {
@@ -72,19 +71,7 @@ __global__ __launch_bounds__(SPANNING_THREADS) void k_spanning_forest(
             offer = min(offer, mine);
          }
       }
-#pragma unroll
-      for (uint32_t offset = 32; offset > 0; offset >>= 1) {
-         offer = min(offer, static_cast<uint64_t>(__shfl_xor(static_cast<unsigned long long>(offer), static_cast<int>(offset))));
-      }
-      if (lane == 0) {
-         s_partial[step & 1u][wave] = offer;
-      }
-      __syncthreads();
-      offer = s_partial[step & 1u][lane & (SPANNING_WAVES - 1u)];
-#pragma unroll
-      for (uint32_t offset = SPANNING_WAVES / 2u; offset > 0; offset >>= 1) {
-         offer = min(offer, static_cast<uint64_t>(__shfl_xor(static_cast<unsigned long long>(offer), static_cast<int>(offset))));
-      }
+      offer = blockMinimum<SPANNING_WAVES>(offer, s_partial[step & 1u]);
       // step < n_rows: a vertex is outside the forest, so `offer` is a key's or a restart's, the same in every thread
       if (offer < RESTART) {
          const uint64_t key = offer >> 1;

@@ -801,6 +801,7 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"DistanceMatrix", parseDistanceMatrix},
    {"Clusters", parseClusters},
    {"MinimumSpanningTree", parseMinimumSpanningTree},
+   {"NearestAmong", parseNearestAmong},
    {"NearestNeighbours", parseNearestNeighbours},
 };
 

@@ -5,6 +5,7 @@
 //   DistanceMatrix                  (not in the reference) the rows FastaAligned would return, compared pairwise on the device (K10)
 //   Clusters                        (not in the reference) the same rows, linked where they are within a distance bound; the connected
 //                                   components of the links on the device (K12)
+//   NearestAmong                    (not in the reference) two selections: per row of the one its nearest rows of the other (K14)
 //   MinimumSpanningTree             (not in the reference) the same rows again: the minimum spanning forest of their distances within a
 //                                   bound, the tree that answers Clusters at every bound at once, on the device (K13)
 //   NearestNeighbours               (not in the reference) the rows of the whole database closest to one query sequence (K11)
@@ -580,7 +581,7 @@ QueryResult FastaAligned::execute(const Database& database, std::vector<Operator
    return results;
 }
 
-// ---- what DistanceMatrix, Clusters and MinimumSpanningTree share -----------------------------------------
+// ---- what DistanceMatrix, Clusters, MinimumSpanningTree and NearestAmong share -----------------------------------------
 namespace {
 
 /// A sequence by name, as the three actions take it: none is the default nucleotide sequence.
@@ -631,10 +632,11 @@ size_t packCharsBytes(uint32_t n, uint32_t positions) {
 /// into the SAME character buffer: the batches are in order on the stream, so a batch's gather starts after the pack of the batch
 /// before it has read the characters.  `live` receives the row ids of every partition: like the two buffers, it must outlive the
 /// wait for the stream.  A sequence without positions: only the keys are collected, nothing is launched.  `what`: who asks, for
-/// the messages.
+/// the messages.  `numbered`, unless null, receives the (partition, row id) of sequence 0 .. n - 1: ascending.
+using PartitionRow = std::pair<uint32_t, uint32_t>;
 std::vector<JsonValue> packSelectedSequences(
    const Database& database, const std::vector<OperatorResult>& bitmap_filter, const ComparedSequence& sequence, uint32_t n, uint64_t* device_planes,
-   char* device_chars, std::vector<DeviceBuffer>& live, const std::string& what
+   char* device_chars, std::vector<DeviceBuffer>& live, const std::string& what, std::vector<PartitionRow>* numbered = nullptr
 ) {
    const std::string& primary_key_column = database.database_config.primary_key;
    std::vector<JsonValue> keys;
@@ -652,6 +654,9 @@ std::vector<JsonValue> packSelectedSequences(
       const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
       for (const uint32_t row : rows) {
          keys.push_back(primary_key.jsonOfRow(row));
+         if (numbered != nullptr) {
+            numbered->emplace_back(static_cast<uint32_t>(partition_id), row);
+         }
       }
       if (keys.size() > n) {
          throw std::runtime_error(what + ": a filter selects more rows than its cardinality says");
@@ -1024,6 +1029,186 @@ std::unique_ptr<Action> parseMinimumSpanningTree(const json::Value& json) {
       min_compared_positions = json["minComparedPositions"].as_uint32();
    }
    return std::make_unique<MinimumSpanningTree>(std::move(sequence_name), max_distance, min_compared_positions);
+}
+
+// ---- NearestAmong ----------------------------------------------------------------------------------------
+// For every selected sequence (a subject) its `neighbours` closest sequences among those a second filter selects (the candidates),
+// under DistanceMatrix's distance, from the rectangle kernel and the per-row selection (K14), with its parser.  No counterpart in
+// the reference.
+void NearestAmong::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"key", "neighbourKey", "rank", "distance", "comparedPositions"});
+}
+
+QueryResult NearestAmong::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const ComparedSequence sequence = comparedSequence(database, sequence_name);
+   requireUnsharded(database, "NearestAmong");
+   // the candidates: `among`, compiled and evaluated per partition as the top-level filter is; absent, the query's own filter
+   std::vector<OperatorResult> among_filter;
+   if (among != nullptr) {
+      among_filter.reserve(database.partitions.size());
+      for (const DatabasePartition& partition : database.partitions) {
+         among_filter.push_back(operators::Operator::evaluate(among->compile(database, partition, filter_expressions::Expression::AmbiguityMode::NONE)));
+      }
+   }
+   const std::vector<OperatorResult>& candidate_filter = among != nullptr ? among_filter : bitmap_filter;
+   const size_t subject_count = selectedCount(database, bitmap_filter);
+   const size_t candidate_count = selectedCount(database, candidate_filter);
+   // both limits before anything is allocated
+   CHECK_SILO_QUERY(subject_count <= SUBJECT_LIMIT, "NearestAmong action currently limited to " + std::to_string(SUBJECT_LIMIT) + " subjects")
+   CHECK_SILO_QUERY(candidate_count <= CANDIDATE_LIMIT, "NearestAmong action currently limited to " + std::to_string(CANDIDATE_LIMIT) + " candidates")
+   QueryResult results;
+   if (subject_count == 0 || candidate_count == 0) {
+      return results;
+   }
+   const auto m = static_cast<uint32_t>(subject_count);
+   const auto n = static_cast<uint32_t>(candidate_count);
+   const uint32_t k = neighbours;
+   const uint32_t positions = sequence.positions;
+   const size_t result_words = static_cast<size_t>(m) + static_cast<size_t>(m) * k * 3u;  // the counts, then the lists
+
+   std::vector<JsonValue> subject_keys;    // of subject 0 .. m - 1: partition order, then ascending row id, as DistanceMatrix numbers a selection
+   std::vector<JsonValue> candidate_keys;  // of candidate 0 .. n - 1, numbered on its own in the same way
+   std::vector<uint32_t> self(m, UINT32_MAX);  // the candidate that is the same database row as subject s
+   std::vector<uint32_t> result;           // a copy of what is fetched
+   {
+      // nothing in here returns to the pool before the stream has been waited for: the launches read it
+      DevicePool& pool = database.partitions.front().pool;
+      DeviceBuffer device_subject_planes = pool.acquire(std::max<size_t>(8, m * sequence.row_plane_words * sizeof(uint64_t)));
+      DeviceBuffer device_candidate_planes = pool.acquire(std::max<size_t>(8, n * sequence.row_plane_words * sizeof(uint64_t)));
+      DeviceBuffer device_chars = pool.acquire(packCharsBytes(std::max(m, n), positions));
+      // (a sequence without positions: nothing to compare, nothing launched, no cells)
+      DeviceBuffer device_cells = pool.acquire(positions == 0 ? sizeof(uint64_t) : static_cast<size_t>(m) * n * 2u * sizeof(uint32_t));
+      DeviceBuffer device_self = pool.acquire(m * sizeof(uint32_t));
+      DeviceBuffer device_result = pool.acquire(result_words * sizeof(uint32_t));
+      std::vector<DeviceBuffer> live;  // per side and partition: its row ids
+      try {
+         // both sides gather into the ONE character buffer: they are in order on the stream
+         std::vector<PartitionRow> subject_rows;
+         std::vector<PartitionRow> candidate_rows;
+         subject_keys = packSelectedSequences(
+            database, bitmap_filter, sequence, m, device_subject_planes.as<uint64_t>(), device_chars.as<char>(), live, "NearestAmong", &subject_rows
+         );
+         candidate_keys = packSelectedSequences(
+            database, candidate_filter, sequence, n, device_candidate_planes.as<uint64_t>(), device_chars.as<char>(), live, "NearestAmong", &candidate_rows
+         );
+         // both lists ascend by (partition, row id): one merge
+         for (uint32_t s = 0, c = 0; s < m && c < n;) {
+            if (subject_rows[s] == candidate_rows[c]) {
+               self[s++] = c++;
+            } else if (subject_rows[s] < candidate_rows[c]) {
+               ++s;
+            } else {
+               ++c;
+            }
+         }
+         if (positions != 0) {
+            checkGpu(silo_gpu_memcpy_h2d(device_self.get(), self.data(), m * sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
+            // rows of different partitions are compared with each other: one rectangle over both sides; it never leaves the device
+            checkGpu(
+               silo_gpu_distance_cross(
+                  sequence.alphabet, device_subject_planes.as<uint64_t>(), m, device_candidate_planes.as<uint64_t>(), n, positions,
+                  device_self.as<uint32_t>(), max_distance.value_or(UINT32_MAX), min_compared_positions, device_cells.as<uint32_t>(), queryStream()
+               ),
+               "silo_gpu_distance_cross"
+            );
+            auto* device_counts = device_result.as<uint32_t>();
+            checkGpu(
+               silo_gpu_nearest_columns(device_cells.as<uint32_t>(), m, n, k, device_counts + m, device_counts, queryStream()), "silo_gpu_nearest_columns"
+            );
+            HostFetch fetch(device_result.get(), result_words * sizeof(uint32_t), queryStream());
+            const auto* host = static_cast<const uint32_t*>(fetch.wait());
+            result.assign(host, host + result_words);
+         }
+         // the copy was the last thing enqueued, but say it: nothing of this query runs any more when its buffers go back
+         checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+      } catch (...) {
+         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+         (void)silo_gpu_stream_synchronize(queryStream());
+         throw;
+      }
+   }
+
+   const auto addRow = [&](uint32_t subject, uint32_t rank, uint32_t candidate, uint32_t distance, uint32_t compared) {
+      QueryResultEntry& entry = results.query_result.emplace_back();
+      entry.fields.emplace("key", subject_keys[subject]);
+      entry.fields.emplace("neighbourKey", candidate_keys[candidate]);
+      entry.fields.emplace("rank", static_cast<int32_t>(rank));
+      entry.fields.emplace("distance", static_cast<int32_t>(distance));
+      entry.fields.emplace("comparedPositions", static_cast<int32_t>(compared));
+   };
+   if (positions == 0) {
+      // every pair has distance 0 and 0 positions compared: the first candidates by number other than the subject, or nothing at all
+      for (uint32_t s = 0; min_compared_positions == 0 && s < m; ++s) {
+         uint32_t rank = 0;
+         for (uint32_t c = 0; c < n && rank < k; ++c) {
+            if (c != self[s]) {
+               addRow(s, ++rank, c, 0, 0);
+            }
+         }
+      }
+      return results;
+   }
+   for (uint32_t s = 0; s < m; ++s) {
+      const uint32_t count = result[s];
+      if (count > k) {
+         throw std::runtime_error("NearestAmong: a subject lists more candidates than neighbours");
+      }
+      const uint32_t* list = result.data() + m + static_cast<size_t>(s) * k * 3u;
+      for (uint32_t r = 0; r < count; ++r) {
+         const uint32_t* entry = list + r * 3u;
+         if (entry[0] >= n || entry[0] == self[s]) {
+            throw std::runtime_error("NearestAmong: a listed candidate names no candidate, or the subject itself");
+         }
+         if (r != 0 && !(std::tie(entry[-2], entry[-3]) < std::tie(entry[1], entry[0]))) {
+            throw std::runtime_error("NearestAmong: a subject's list does not ascend by (distance, candidate)");
+         }
+         addRow(s, r + 1u, entry[0], entry[1], entry[2]);
+      }
+   }
+   return results;
+}
+
+std::unique_ptr<Action> parseNearestAmong(const json::Value& json) {
+   std::optional<std::string> sequence_name;
+   if (json.contains("sequenceName")) {
+      CHECK_SILO_QUERY(json["sequenceName"].is_string(), "NearestAmong action: the field sequenceName, if present, must be of type string")
+      sequence_name = json["sequenceName"].as_string();
+   }
+   std::unique_ptr<filter_expressions::Expression> among;
+   if (json.contains("among")) {
+      CHECK_SILO_QUERY(json["among"].is_object(), "NearestAmong action: the field among, if present, must be a filter expression")
+      try {
+         among = filter_expressions::parseExpression(json["among"]);
+      } catch (const QueryParseException& error) {
+         throw QueryParseException(std::string("NearestAmong action: the field among is no filter expression: ") + error.what());
+      }
+   }
+   uint32_t neighbours = NearestAmong::DEFAULT_NEIGHBOURS;
+   if (json.contains("neighbours")) {
+      CHECK_SILO_QUERY(
+         json["neighbours"].is_number_unsigned() && json["neighbours"].as_int64() >= 1 && json["neighbours"].as_int64() <= NearestAmong::NEIGHBOUR_LIMIT,
+         "NearestAmong action: the field neighbours, if present, must be an integer from 1 to " + std::to_string(NearestAmong::NEIGHBOUR_LIMIT)
+      )
+      neighbours = json["neighbours"].as_uint32();
+   }
+   std::optional<uint32_t> max_distance;
+   if (json.contains("maxDistance")) {
+      CHECK_SILO_QUERY(
+         json["maxDistance"].is_number_unsigned() && json["maxDistance"].as_int64() >= 0 && json["maxDistance"].as_int64() <= INT32_MAX,
+         "NearestAmong action: the field maxDistance, if present, must be a non-negative integer"
+      )
+      max_distance = json["maxDistance"].as_uint32();
+   }
+   uint32_t min_compared_positions = 0;
+   if (json.contains("minComparedPositions")) {
+      CHECK_SILO_QUERY(
+         json["minComparedPositions"].is_number_unsigned() && json["minComparedPositions"].as_int64() >= 0 &&
+            json["minComparedPositions"].as_int64() <= INT32_MAX,
+         "NearestAmong action: the field minComparedPositions, if present, must be a non-negative integer"
+      )
+      min_compared_positions = json["minComparedPositions"].as_uint32();
+   }
+   return std::make_unique<NearestAmong>(std::move(sequence_name), std::move(among), neighbours, max_distance, min_compared_positions);
 }
 
 // ---- NearestNeighbours -----------------------------------------------------------------------------------

@@ -682,6 +682,8 @@ std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json);
 std::unique_ptr<Action> parseClusters(const json::Value& json);
 /// The parser of MinimumSpanningTree (metadata_actions.cpp).
 std::unique_ptr<Action> parseMinimumSpanningTree(const json::Value& json);
+/// The parser of NearestAmong (metadata_actions.cpp).
+std::unique_ptr<Action> parseNearestAmong(const json::Value& json);
 /// The parser of NearestNeighbours (metadata_actions.cpp).
 std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json);
 
@@ -822,6 +824,40 @@ class MinimumSpanningTree : public Action {
    static constexpr uint32_t SEQUENCE_LIMIT = SILO_GPU_MAX_SPANNING_ROWS;
    MinimumSpanningTree(std::optional<std::string> sequence_name, std::optional<uint32_t> max_distance, uint32_t min_compared_positions)
        : sequence_name(std::move(sequence_name)), max_distance(max_distance), min_compared_positions(min_compared_positions) {}
+};
+
+/// NearestAmong (metadata_actions.cpp): for every sequence the filter selects (a subject) its `neighbours` closest sequences among
+/// those `among` selects (the candidates; absent: the query's own filter), by DistanceMatrix's distance on one aligned sequence.
+/// Each side is numbered on its own as DistanceMatrix numbers a selection.  A candidate is eligible for a subject when it is another
+/// database row, >= minComparedPositions positions are compared and the distance is <= maxDistance (absent: no bound); a subject
+/// lists its lowest eligible candidates by (distance, candidate number), a strict order.  One row per (subject, listed candidate):
+/// the two keys, the 1-based rank, the distance, the compared positions, by subject, then rank; a subject without an eligible
+/// candidate is in no row.  Both sides are gathered and packed as for Clusters, each into its own plane buffer; then one
+/// silo_gpu_distance_cross (the m x n cells: 8 m n bytes, 128 MB at the limit, which never leave the device), one
+/// silo_gpu_nearest_columns (K14), and ONE fetch of the counts and the lists.
+class NearestAmong : public Action {
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   std::unique_ptr<filter_expressions::Expression> among;  // null: the query's own filter
+   uint32_t neighbours;
+   std::optional<uint32_t> max_distance;
+   uint32_t min_compared_positions;
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+
+  public:
+   static constexpr uint32_t SUBJECT_LIMIT = SILO_GPU_MAX_CROSS_ROWS;
+   static constexpr uint32_t CANDIDATE_LIMIT = SILO_GPU_MAX_CROSS_COLUMNS;
+   static constexpr uint32_t NEIGHBOUR_LIMIT = SILO_GPU_MAX_NEIGHBOUR_COLUMNS;
+   static constexpr uint32_t DEFAULT_NEIGHBOURS = 1;
+   NearestAmong(
+      std::optional<std::string> sequence_name, std::unique_ptr<filter_expressions::Expression> among, uint32_t neighbours,
+      std::optional<uint32_t> max_distance, uint32_t min_compared_positions
+   )
+       : sequence_name(std::move(sequence_name)),
+         among(std::move(among)),
+         neighbours(neighbours),
+         max_distance(max_distance),
+         min_compared_positions(min_compared_positions) {}
 };
 
 /// NearestNeighbours (metadata_actions.cpp): the `neighbours` rows of the WHOLE database closest to one query sequence — a row named

@@ -113,6 +113,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_filters_grouped", "silo_gpu_filters_cross",
     "silo_gpu_distance_pack", "silo_gpu_distance_pairs", "silo_gpu_distance_within", "silo_gpu_adjacency_components",
     "silo_gpu_distance_weights", "silo_gpu_spanning_forest", "silo_gpu_distance_listed_pairs",
+    "silo_gpu_distance_cross", "silo_gpu_nearest_columns",
     "silo_gpu_query_distances", "silo_gpu_nearest_rows", "silo_gpu_bitset_from_distances",
 ]
 
@@ -189,6 +190,9 @@ def load_library():
     lib.silo_gpu_distance_weights.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_spanning_forest.argtypes = [vp, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_distance_listed_pairs.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_distance_cross.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32,
+                                            ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_nearest_columns.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_query_distances.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_nearest_rows.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_bitset_from_distances.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
@@ -690,6 +694,64 @@ def distance_listed_pairs(alphabet_id, planes_ptr, n_rows, positions, edges, cou
         return device_read(out, np.uint32, rows * 2, stream).reshape(rows, 2)
     finally:
         for ptr in (edges_dev, count_dev, out):
+            device_free(ptr)
+
+
+MAX_CROSS_ROWS = 2048          # SILO_GPU_MAX_CROSS_ROWS: the rows (subjects) of the rectangle of K14
+MAX_CROSS_COLUMNS = 8192       # SILO_GPU_MAX_CROSS_COLUMNS: its columns (candidates)
+MAX_NEIGHBOUR_COLUMNS = 64     # SILO_GPU_MAX_NEIGHBOUR_COLUMNS: k of silo_gpu_nearest_columns
+NEIGHBOUR_THREADS = 1024       # SILO_GPU_NEIGHBOUR_THREADS: the block that owns a row in silo_gpu_nearest_columns
+NEIGHBOUR_KEY_COLUMN_BITS = 13  # SILO_GPU_NEIGHBOUR_KEY_COLUMN_BITS: the column of a key, below the distance
+NOT_ELIGIBLE = 0xFFFFFFFF      # both words of a cell of K14 that is not eligible; as a self column: none; as max_distance: no bound
+
+
+def distance_cross(alphabet_id, row_planes_ptr, n_rows, column_planes_ptr, n_columns, positions, self_columns, max_distance, min_compared,
+                   fill=None, guard_words=0, stream=None):
+    """silo_gpu_distance_cross (K14) over two plane buffers as distance_pack / distance_pack_rows leave them: the n_rows * n_columns
+    cells uint32 [2] of the rectangle, cell (i, j) = (differing, compared) where j != self_columns[i] and differing <= max_distance
+    and compared >= min_compared, (NOT_ELIGIBLE, NOT_ELIGIBLE) elsewhere, followed by `guard_words` uint32 behind them that the call
+    must not touch: those hold the byte `fill` repeated (the whole allocation is filled with it before the launch), or whatever the
+    allocation held.  self_columns: None (NULL) or n_rows uint32."""
+    lib = load_library()
+    words = n_rows * n_columns * 2 + int(guard_words)
+    out = device_malloc(words * 4, fill, stream)
+    self_dev = None
+    try:
+        if self_columns is not None:
+            self_columns = np.ascontiguousarray(self_columns, dtype=np.uint32).reshape(-1)
+            self_dev = device_malloc(self_columns.nbytes)
+            if self_columns.nbytes:
+                _check(lib.silo_gpu_memcpy_h2d(self_dev, _ptr(self_columns), self_columns.nbytes, stream))
+        _check(lib.silo_gpu_distance_cross(_abi_alphabet(alphabet_id), row_planes_ptr, n_rows, column_planes_ptr, n_columns, positions, self_dev,
+                                           max_distance, min_compared, out, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(out, np.uint32, words, stream)
+    finally:
+        device_free(out)
+        if self_dev is not None:
+            device_free(self_dev)
+
+
+def nearest_columns(cells, n_rows, n_columns, k, fill=None, guard_words=0, stream=None):
+    """silo_gpu_nearest_columns (K14) over host cells uint32 [n_rows * n_columns * 2] as silo_gpu_distance_cross leaves them: (lists
+    uint32 [n_rows * k * 3 + guard_words], counts uint32 [n_rows + guard_words]) — entry r < counts[i] of row i = (column, distance,
+    compared), ascending by (distance, column); the entries at or past a row's count, the guard words and everything where nothing
+    is written hold the byte `fill` repeated (both are filled with it before the launch)."""
+    lib = load_library()
+    cells = np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1)
+    list_words = n_rows * int(k) * 3 + int(guard_words)
+    count_words = n_rows + int(guard_words)
+    cells_dev = device_malloc(cells.nbytes)
+    lists = device_malloc(list_words * 4, fill, stream)
+    counts = device_malloc(count_words * 4, fill, stream)
+    try:
+        if cells.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(cells_dev, _ptr(cells), cells.nbytes, stream))
+        _check(lib.silo_gpu_nearest_columns(cells_dev, n_rows, n_columns, k, lists, counts, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(lists, np.uint32, list_words, stream), device_read(counts, np.uint32, count_words, stream)
+    finally:
+        for ptr in (cells_dev, lists, counts):
             device_free(ptr)
 
 
