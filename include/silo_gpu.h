@@ -464,6 +464,31 @@ int silo_gpu_mutations_scan_ranges_min_proportion(
    const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
    const double* min_proportion /* [n_filters] or NULL */, uint32_t* const* counts_out_dev, void* stream
 );
+/* That scan and the row selection (K4) in one call, for a caller whose scan is the ONLY writer of each filter's count table and
+ * whose only reader is the selection: a Mutations query over one partition.  Per filter a sink: its table (total_positions x
+ * n_symbols words; every counts_out_dev[r * n_filters + q] points into table q), the reference symbols of the table's
+ * positions (as silo_gpu_mutations_select), and the row slot its rows go to.  min_proportion[q] serves the scan's pruning and
+ * the selection alike (NULL = 0 for every filter).
+ * The tables are OVERWRITTEN, not accumulated into: on return (in stream order) table q holds exactly this call's counts — as
+ * silo_gpu_mutations_scan_ranges_min_proportion into a cleared table —, whatever it held before; the caller does not clear it.
+ * The rows of filter q arrive in its slot as from silo_gpu_mutations_select_to_slot (silo_gpu_row_slot_wait; the number of
+ * selected cells may exceed the capacity, the table is then complete for the caller's fallback).
+ * Where every range goes through the finish kernel of a scan with derived symbols (k_finish_scan: one alphabet, rows of at least
+ * 1 024 words, a store with derived symbols and gap events) and the ranges of the call tile [0, total_positions) of every
+ * table exactly and alike, that kernel stores the cells and selects the rows from the registers it holds them in: no fill
+ * launch, no selection launch.  Otherwise — and with SILO_GPU_TUNE_FUSED_SELECT < 0 — the call clears the tables, scans and
+ * launches the selection, as a caller of the other entries would. */
+typedef struct silo_gpu_select_sink {
+   uint32_t* table_dev;
+   uint32_t total_positions;
+   uint32_t n_symbols;
+   const uint8_t* reference_index_dev; /* [total_positions] */
+   silo_gpu_row_slot* slot;
+} silo_gpu_select_sink;
+int silo_gpu_mutations_scan_select(
+   const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
+   const double* min_proportion /* [n_filters] or NULL */, uint32_t* const* counts_out_dev, const silo_gpu_select_sink* sinks /* [n_filters] */, void* stream
+);
 /* How many granules (4 096 keys) of the store's slice-major escape keys the scan above skips for ONE filter of `cardinality`
  * rows at `min_proportion`, and how many there are: the kernel's rule applied to the host copies of the store's bounds. */
 int silo_gpu_store_scan_prunable_granules(
@@ -791,6 +816,8 @@ enum { SILO_GPU_TUNE_SCAN_ROWS_PER_BLOCK = 0, SILO_GPU_TUNE_SCAN_VARIANT = 1, SI
        SILO_GPU_TUNE_END_RUNS = 12 /* a Mutations scan over a store with end runs of the gap symbol (silo_gpu_store_scan_covered_rows): 0 (default) counts
                                       the covered one-hot rows of '-' from the sequences' end events and residual keys in the escape-key pass; 1 counts
                                       them in a launch of their own behind the row launch; < 0 reads the rows — the same tables either way, for A/B runs */,
+       SILO_GPU_TUNE_FUSED_SELECT = 13 /* silo_gpu_mutations_scan_select: 0 (default) lets the finish kernel of the scan overwrite the tables and select the
+                                          rows where the call allows it, < 0 always clears, scans and selects in launches of their own (comparisons) */,
        SILO_GPU_TUNE_SCAN_SPARSE_DIVISOR = 3 /* a filter with a set bit in <= row_words / divisor of its 64-byte sectors takes the gather scan (K1s); 0 = default 16, < 0 = off */ };
 int silo_gpu_tune(int knob, int value);
 

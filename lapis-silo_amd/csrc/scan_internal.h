@@ -110,6 +110,9 @@ struct DerivedRange {
    uint32_t n_positions;
    uint32_t n_scan;
    uint32_t pos_begin;
+   uint32_t gaps_offset;     // words from a filter's counts to its gaps (its diff): n_positions * n_scan rounded up to 16 bytes
+   uint32_t ends_offset;     // words from a filter's counts to its ends, rounded up likewise (a range that counts end runs)
+   uint32_t table_offset;    // a scan that selects (SelectSink): the range's first position in the filters' count tables
    const uint8_t* code_map;  // of the store's position 0; nullptr: no position of this store derives a symbol
    const uint8_t* position_covered;  // of the store's position 0: the gap symbol's cell takes its end runs from ends[n][2]; nullptr: no end runs
    uint32_t end_symbol;              // the gap symbol's scan index
@@ -120,6 +123,19 @@ struct DerivedRange {
    uint32_t sparse_begin;            // the keys of the range's positions
    uint32_t sparse_end;
    uint32_t* caller_counts[SILO_GPU_MAX_SCAN_BATCH];  // at the range's first position
+};
+/// Where k_finish_scan delivers the Mutations rows of one filter of a scan that selects (silo_gpu_mutations_scan_select): the
+/// filter's row slot (silo_gpu_row_slot: cursor and ticket on the device, rows and header word in page-locked host memory), what
+/// the selection needs beside the counts, and how many blocks of the scan's finish launches take a ticket for this filter.
+struct SelectSink {
+   const uint8_t* reference_index;  // of the table's position 0
+   uint32_t* cursor_and_ticket;
+   silo_gpu_mutation_row* host_rows;
+   unsigned long long* host_header;
+   double min_proportion;
+   uint32_t capacity;
+   uint32_t epoch;
+   uint32_t total_blocks;
 };
 struct DerivedArgs {
    const uint64_t* filters[SILO_GPU_MAX_SCAN_BATCH];
@@ -135,7 +151,9 @@ struct DerivedArgs {
    uint32_t part_stride;
    uint32_t run_blocks_per_slice;
    DerivedRange ranges[DERIVED_MAX_RANGES];
+   SelectSink sinks[SILO_GPU_MAX_SCAN_BATCH];  // k_finish_scan<true, n_scan> only
 };
+static_assert(sizeof(DerivedArgs) <= 4096, "the kernels of the derived symbols take their arguments by value: the kernel-argument segment holds 4 KiB");
 
 /// The private tables of a scan with derived symbols and what its extra passes read, DERIVED_MAX_RANGES ranges at a time.
 struct DerivedPlan {
@@ -157,6 +175,14 @@ struct DerivedPlan {
    size_t table_words = 0;       // zeroed by the prepare step: the tables, then the flags of the run parts
    size_t part_words = 0;        // behind them, not zeroed: the run parts (k_scan_missing_runs -> k_sum_run_parts)
    uint32_t most_positions = 0;  // of a range with derived symbols
+   bool select = false;          // the finish launches overwrite the callers' tables and deliver the selected rows (SelectSink)
+};
+
+/// What a scan that selects (silo_gpu_mutations_scan_select, fused route) hands to scanRanges: per filter of the scan its sink
+/// (total_blocks is filled in by planDerived), per range its first position in the filters' tables.
+struct ScanSelect {
+   SelectSink sinks[SILO_GPU_MAX_SCAN_BATCH];
+   std::vector<uint32_t> table_offset;  // [range]
 };
 
 /// What a scan for Mutations rows of at least a proportion (silo_gpu_mutations_scan_ranges_min_proportion) may leave out: the keys
@@ -190,7 +216,9 @@ int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* fil
    const std::vector<ScanRange>* ends = nullptr, bool only_ends = false);
 
 // silo_gpu_scan_derived.hip
-void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, DerivedPlan& plan);
+bool derivedCountsEvents(const std::vector<ScanRange>& ranges);
+void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, DerivedPlan& plan,
+   const ScanSelect* select = nullptr);
 void bindDerived(DerivedPlan& plan, uint32_t* tables, const uint32_t* counters, uint32_t q_count);
 int scanRowsWithoutSymbol(DerivedPlan& plan, uint32_t q_count, hipStream_t hip_stream);
 int finishDerived(DerivedPlan& plan, uint32_t q_count, hipStream_t hip_stream);

@@ -29,6 +29,7 @@ std::atomic<int> g_tune_sparse_divisor{0};
 std::atomic<int> g_tune_gap_events{0};
 std::atomic<int> g_tune_prune_keys{0};
 std::atomic<int> g_tune_end_runs{0};
+std::atomic<int> g_tune_fused_select{0};
 
 namespace {
 thread_local std::string g_last_error;
@@ -86,6 +87,9 @@ int silo_gpu_tune(int knob, int value) {
    }
    if (knob == SILO_GPU_TUNE_END_RUNS) {
       return g_tune_end_runs.exchange(value);
+   }
+   if (knob == SILO_GPU_TUNE_FUSED_SELECT) {
+      return g_tune_fused_select.exchange(value);
    }
    return -1;
 }

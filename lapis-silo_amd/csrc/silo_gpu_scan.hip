@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "fused_select_rule.h"
 #include "scan_internal.h"
 
 using namespace silo_gpu_detail;
@@ -327,7 +328,7 @@ int forkSidePasses(
 /// `min_proportion` (nullptr, or one per filter): see silo_gpu_mutations_scan_ranges_min_proportion.
 int silo_gpu_detail::scanRanges(
    const silo_gpu_store* store, const std::vector<ScanRange>& caller_ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream,
-   const double* min_proportion
+   const double* min_proportion, const ScanSelect* select
 ) {
    const SeqStoreDev& any_store = caller_ranges.front().seqstore->dev;
    const bool nucleotide = any_store.n_bits == 3 && any_store.n_scan == 5;
@@ -335,6 +336,9 @@ int silo_gpu_detail::scanRanges(
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "mutations scan: unsupported set of scan symbols (5 nucleotide or 22 amino-acid symbols)");
    }
    if (any_store.row_words < SCAN_THREADS * 4) {
+      if (select != nullptr) {
+         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "mutations scan: short rows do not go through the finish kernel");
+      }
       const int rc = scanShortRows(caller_ranges, nucleotide, filters, q_count, hip_stream);
       if (rc == SILO_GPU_OK) {
          g_last_scan_kernel = "k_scan_sliced_rowwave";
@@ -349,7 +353,10 @@ int silo_gpu_detail::scanRanges(
    }
    DerivedPlan plan;
    if (any_derived) {
-      planDerived(store, caller_ranges, filters, q_count, plan);
+      planDerived(store, caller_ranges, filters, q_count, plan, select);
+   }
+   if (select != nullptr && !plan.select) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "mutations scan: this scan cannot select its rows in the finish kernel");  // (canFuseSelect decides the same way)
    }
    const int divisor = g_tune_sparse_divisor.load();
    const bool routing = divisor >= 0;
@@ -414,10 +421,63 @@ int silo_gpu_detail::scanRanges(
    return rc != SILO_GPU_OK ? rc : joined;
 }
 
-/// silo_gpu_mutations_scan_ranges and silo_gpu_mutations_scan_ranges_min_proportion (`entry`: the one called, for its error messages).
+/// May the finish kernel of the scan behind silo_gpu_mutations_scan_select overwrite the sinks' tables and select their rows?
+/// (The arguments have passed the entry's checks.)  Every range goes through k_finish_scan<true, .> — one alphabet, rows long
+/// enough for k_scan_sliced, a store with derived symbols, gap events counted — and the ranges tile every filter's table, at the
+/// same offsets for all filters (DerivedRange::table_offset); table_offset gets them, per range.
+static bool canFuseSelect(
+   const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, uint32_t n_filters, uint32_t* const* counts_out_dev,
+   const silo_gpu_select_sink* sinks, std::vector<uint32_t>& table_offset
+) {
+   if (g_tune_fused_select.load() < 0 || n_ranges == 0 || n_filters == 0) {
+      return false;
+   }
+   const uint32_t n_symbols = sinks[0].n_symbols;
+   if (n_symbols != 5 && n_symbols != 22) {
+      return false;
+   }
+   std::vector<ScanRange> group;
+   std::vector<TableSpan> spans;
+   bool any_derived = false;
+   table_offset.assign(n_ranges, 0);
+   for (uint32_t r = 0; r < n_ranges; ++r) {
+      const SeqStoreHost& seqstore = store->seqstores[ranges[r].seqstore_id];
+      const uint32_t n = ranges[r].pos_end - ranges[r].pos_begin;
+      if (n == 0) {
+         continue;  // (not scanned)
+      }
+      if (seqstore.dev.n_scan != n_symbols || seqstore.dev.planes == nullptr || seqstore.dev.row_words < static_cast<uint32_t>(SCAN_THREADS) * 4) {
+         return false;
+      }
+      any_derived = any_derived || seqstore.layout.has_implicit;
+      group.push_back(ScanRange{&seqstore, ranges[r].pos_begin, ranges[r].pos_end, {}});
+      for (uint32_t q = 0; q < n_filters; ++q) {
+         const silo_gpu_select_sink& sink = sinks[q];
+         const uint32_t* at = counts_out_dev[static_cast<size_t>(r) * n_filters + q];
+         if (sink.n_symbols != n_symbols || sink.total_positions != sinks[0].total_positions || at < sink.table_dev) {
+            return false;
+         }
+         const size_t words = static_cast<size_t>(at - sink.table_dev);
+         if (words % n_symbols != 0 || words / n_symbols >= sink.total_positions) {
+            return false;
+         }
+         const auto offset = static_cast<uint32_t>(words / n_symbols);
+         if (q != 0 && offset != table_offset[r]) {
+            return false;
+         }
+         table_offset[r] = offset;
+      }
+      spans.push_back({table_offset[r], n});
+   }
+   return any_derived && derivedCountsEvents(group) && spansTileTable(spans, sinks[0].total_positions);
+}
+
+/// silo_gpu_mutations_scan_ranges, silo_gpu_mutations_scan_ranges_min_proportion and silo_gpu_mutations_scan_select (`entry`: the
+/// one called, for its error messages).  sinks (or nullptr), table_offset: the finish kernel overwrites the tables and selects (canFuseSelect).
 static int scanRangesEntry(
    const char* entry, const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
-   const double* min_proportion, uint32_t* const* counts_out_dev, void* stream
+   const double* min_proportion, uint32_t* const* counts_out_dev, void* stream, const silo_gpu_select_sink* sinks = nullptr,
+   const std::vector<uint32_t>* table_offset = nullptr
 ) {
    if (store == nullptr || (n_ranges != 0 && ranges == nullptr) || (n_filters != 0 && filters_dev == nullptr) ||
        (n_ranges != 0 && n_filters != 0 && counts_out_dev == nullptr)) {
@@ -452,6 +512,7 @@ static int scanRangesEntry(
       // ranges of one layout (3 code planes / 5 code planes) share launches
       for (const uint32_t n_bits : {3u, 5u}) {
          std::vector<ScanRange> group;
+         ScanSelect select;
          for (uint32_t r = 0; r < n_ranges; ++r) {
             const SeqStoreDev& dev = store->seqstores[ranges[r].seqstore_id].dev;
             if (ranges[r].pos_begin == ranges[r].pos_end || dev.n_scan == 0 || (dev.n_bits == 3 ? 3u : 5u) != n_bits) {
@@ -466,9 +527,24 @@ static int scanRangesEntry(
                range.counts[q] = counts_out_dev[static_cast<size_t>(r) * n_filters + first + q];
             }
             group.push_back(range);
+            if (sinks != nullptr) {
+               select.table_offset.push_back((*table_offset)[r]);
+            }
+         }
+         for (uint32_t q = 0; sinks != nullptr && !group.empty() && q < q_count; ++q) {  // (one alphabet: one group per filter)
+            const silo_gpu_select_sink& sink = sinks[first + q];
+            silo_gpu_row_slot* slot = sink.slot;
+            slot->epoch += 1;
+            if (slot->epoch == 0) {
+               slot->epoch = 1;
+            }
+            select.sinks[q] = SelectSink{
+               sink.reference_index_dev, slot->d_cursor_and_ticket, reinterpret_cast<silo_gpu_mutation_row*>(static_cast<char*>(slot->host_dev) + 16),
+               static_cast<unsigned long long*>(slot->host_dev), min_proportion != nullptr ? min_proportion[first + q] : 0.0, slot->capacity, slot->epoch, 0};
          }
          if (!group.empty()) {
-            const int rc = scanRanges(store, group, filters_dev + first, q_count, hip_stream, min_proportion != nullptr ? min_proportion + first : nullptr);
+            const int rc = scanRanges(store, group, filters_dev + first, q_count, hip_stream, min_proportion != nullptr ? min_proportion + first : nullptr,
+                                      sinks != nullptr ? &select : nullptr);
             if (rc != SILO_GPU_OK) {
                return rc;
             }
@@ -496,6 +572,64 @@ int silo_gpu_mutations_scan_ranges_min_proportion(
    const double* min_proportion, uint32_t* const* counts_out_dev, void* stream
 ) {
    return scanRangesEntry("silo_gpu_mutations_scan_ranges_min_proportion", store, ranges, n_ranges, filters_dev, n_filters, min_proportion, counts_out_dev, stream);
+}
+
+int silo_gpu_mutations_scan_select(
+   const silo_gpu_store* store, const silo_gpu_scan_range* ranges, uint32_t n_ranges, const uint64_t* const* filters_dev, uint32_t n_filters,
+   const double* min_proportion, uint32_t* const* counts_out_dev, const silo_gpu_select_sink* sinks, void* stream
+) {
+   const char* entry = "silo_gpu_mutations_scan_select";
+   if (store == nullptr || sinks == nullptr || n_filters == 0 || filters_dev == nullptr || n_ranges == 0 || ranges == nullptr || counts_out_dev == nullptr) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": bad arguments");
+   }
+   for (uint32_t q = 0; q < n_filters; ++q) {
+      const silo_gpu_select_sink& sink = sinks[q];
+      if (filters_dev[q] == nullptr || sink.table_dev == nullptr || sink.reference_index_dev == nullptr || sink.slot == nullptr || sink.total_positions == 0 ||
+          sink.n_symbols == 0 || sink.n_symbols > 32) {
+         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": bad filter or sink");
+      }
+      for (uint32_t other = 0; other < q; ++other) {
+         if (sinks[other].slot == sink.slot || sinks[other].table_dev == sink.table_dev) {
+            return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": two filters share a table or a row slot");
+         }
+      }
+   }
+   // (the checks both routes share come first: a call that fails them has launched nothing)
+   for (uint32_t r = 0; r < n_ranges; ++r) {
+      if (ranges[r].seqstore_id >= store->seqstores.size()) {
+         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": no such sequence store");
+      }
+      if (ranges[r].pos_begin > ranges[r].pos_end || ranges[r].pos_end > store->seqstores[ranges[r].seqstore_id].dev.positions) {
+         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "position range out of bounds");
+      }
+      for (uint32_t q = 0; q < n_filters; ++q) {
+         if (counts_out_dev[static_cast<size_t>(r) * n_filters + q] == nullptr) {
+            return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(entry) + ": null counts buffer");
+         }
+      }
+   }
+   std::vector<uint32_t> table_offset;
+   if (canFuseSelect(store, ranges, n_ranges, n_filters, counts_out_dev, sinks, table_offset)) {
+      return scanRangesEntry(entry, store, ranges, n_ranges, filters_dev, n_filters, min_proportion, counts_out_dev, stream, sinks, &table_offset);
+   }
+   // otherwise what a caller of the other entries does: clear the tables, scan into them, select from them (K4)
+   HIP_TRY(hipSetDevice(store->device));
+   for (uint32_t q = 0; q < n_filters; ++q) {
+      HIP_TRY(hipMemsetAsync(sinks[q].table_dev, 0, static_cast<size_t>(sinks[q].total_positions) * sinks[q].n_symbols * sizeof(uint32_t), static_cast<hipStream_t>(stream)));
+   }
+   if (const int rc = scanRangesEntry(entry, store, ranges, n_ranges, filters_dev, n_filters, min_proportion, counts_out_dev, stream); rc != SILO_GPU_OK) {
+      return rc;
+   }
+   for (uint32_t q = 0; q < n_filters; ++q) {
+      const int rc = silo_gpu_mutations_select_to_slot(
+         sinks[q].table_dev, sinks[q].reference_index_dev, sinks[q].total_positions, sinks[q].n_symbols, min_proportion != nullptr ? min_proportion[q] : 0.0,
+         sinks[q].slot, stream
+      );
+      if (rc != SILO_GPU_OK) {
+         return rc;
+      }
+   }
+   return SILO_GPU_OK;
 }
 
 int silo_gpu_scan_timings(silo_gpu_scan_timing* out, uint32_t capacity, uint32_t* n_out) {

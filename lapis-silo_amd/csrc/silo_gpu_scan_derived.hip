@@ -4,7 +4,7 @@
 // Kernels:
 //   k_scan_missing_runs<LDS_DIFF>, k_sum_run_parts   rows of the filter inside a run of the missing symbol, per position
 //   k_count_sparse_keys                              rows of the filter with an ambiguity code, per position
-//   k_finish_scan<EVENTS>                            derived counts; the scan's private tables into the caller's
+//   k_finish_scan<EVENTS, SELECT>                    derived counts; the scan's private tables into the caller's — or over them, with K4's row selection
 // (k_scan_missing_runs and k_count_sparse_keys run only where a store has no gap events: SILO_GPU_TUNE_GAP_EVENTS < 0.)
 // Exported (scan_internal.h): planDerived, bindDerived, scanRowsWithoutSymbol, finishDerived.
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "fused_select_rule.h"
 #include "scan_internal.h"
 
 using namespace silo_gpu_detail;
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_scan_missing_runs(const Der
    if (__syncthreads_or(any_bit != 0 ? 1 : 0) == 0) {
       return;  // no row of this slice is selected
    }
-   uint32_t* __restrict__ diff = range.scratch + static_cast<size_t>(q) * range.stride + static_cast<size_t>(n) * range.n_scan;
+   uint32_t* __restrict__ diff = range.scratch + static_cast<size_t>(q) * range.stride + range.gaps_offset;
    const uint32_t slice_first_row = slice << ESCAPE_SLICE_SHIFT;
    const uint32_t pos_end = range.pos_begin + n;
    uint32_t from_the_first = 0;  // selected runs that begin at or before the range's first position (sequences that begin with the missing symbol: every lane on one counter otherwise)
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256) void k_sum_run_parts(const DerivedArgs args) {
    if (j > n) {
       return;
    }
-   uint32_t* __restrict__ diff = range.scratch + static_cast<size_t>(q) * range.stride + static_cast<size_t>(n) * range.n_scan;
+   uint32_t* __restrict__ diff = range.scratch + static_cast<size_t>(q) * range.stride + range.gaps_offset;
    const uint32_t values[4] = {sum.x, sum.y, sum.z, sum.w};
 #pragma unroll
    for (uint32_t c = 0; c < 4; ++c) {
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(256) void k_count_sparse_keys(const DerivedArgs arg
    }
    const DerivedRange& range = args.ranges[r];
    const uint32_t n = range.n_positions;
-   uint32_t* __restrict__ ambiguous = range.scratch + static_cast<size_t>(q) * range.stride + static_cast<size_t>(n) * range.n_scan + n + 1u;
+   uint32_t* __restrict__ ambiguous = range.scratch + static_cast<size_t>(q) * range.stride + range.gaps_offset + n + 1u;
    const uint32_t first = range.sparse_begin + (blockIdx.x - args.first_unit[r]) * (256u * SPARSE_KEYS_PER_THREAD) + threadIdx.x;
    uint64_t key[SPARSE_KEYS_PER_THREAD];
 #pragma unroll
@@ -267,8 +268,15 @@ __global__ __launch_bounds__(256) void k_count_sparse_keys(const DerivedArgs arg
 /// A range that counts the end runs of the gap symbol (DerivedRange::position_covered) has ends[n][2] behind that: at a covered
 /// position the gap symbol's cell gets, on top of its residual keys, the selected rows inside an end run — |F| less the lead-end
 /// events up to p plus the trail-start events up to p — before the derived count is formed; elsewhere ends is ignored.
-template <bool EVENTS>
+/// SELECT (0, or the n_scan of every range of the launch; EVENTS only): the scan is the only writer of the caller's tables and
+/// their only reader is the row selection of a Mutations query (silo_gpu_mutations_scan_select).  The thread then STORES every
+/// cell of its position, zeros included, and applies K4's arithmetic (k_mutations_select_to_host) to the cells it holds: the
+/// rows go straight into the filter's row slot, and the block that takes the last ticket of the scan's finish launches for
+/// the filter publishes the header word.  No block waits for another.
+constexpr uint32_t PREFIX_IN_FLIGHT = 4;  // 16-byte loads per array and thread in flight together in the sweep before the block's positions
+template <bool EVENTS, uint32_t SELECT>
 __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedArgs args) {
+   static_assert(SELECT == 0 || EVENTS, "the selection is fused into the finish of a scan that counts gap events");
    __shared__ uint32_t s_before[2][DERIVED_THREADS / 64];  // [0] the gaps, [1] the end runs
    __shared__ uint32_t s_own[2][DERIVED_THREADS / 64];
    const uint32_t q = blockIdx.y;
@@ -280,11 +288,11 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
    }
    const DerivedRange& range = args.ranges[r];
    const uint32_t n = range.n_positions;
-   const uint32_t n_scan = range.n_scan;
+   const uint32_t n_scan = SELECT != 0 ? SELECT : range.n_scan;
    const uint32_t first_position = (blockIdx.x - args.first_unit[r]) * DERIVED_THREADS;
    const uint32_t p = first_position + threadIdx.x;
    const uint32_t* __restrict__ counts = range.scratch + static_cast<size_t>(q) * range.stride;
-   const uint32_t* __restrict__ diff = counts + static_cast<size_t>(n) * n_scan;
+   const uint32_t* __restrict__ diff = counts + range.gaps_offset;
    const uint32_t* __restrict__ ambiguous = diff + n + 1u;
    const auto diffAt = [&](uint32_t j) {  // rows entering less rows leaving the gaps at j
       if constexpr (EVENTS) {
@@ -294,20 +302,38 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
       }
    };
    // a range that counts end runs: trailing runs beginning less leading runs ending at j — summed up to p and added to |F|, the rows
-   // of the filter inside an end run at p.  Both sums are taken in ONE sweep over the positions before the block's (the sweep is
-   // a chain of memory latencies: 16.3 us for the genome, 19.7 with a sweep per sum, 10.9 without the end runs)
+   // of the filter inside an end run at p.  Both sums are taken in ONE sweep over the positions before the block's.  The sweep
+   // was a chain of memory latencies (a 4-byte load per thread and turn, 29 turns in the genome's last block: 16.3 us); both
+   // arrays are 16-byte aligned (gaps_offset, ends_offset) and first_position is a multiple of 1024, so a thread takes whole
+   // uint4 — two positions of gaps or ends, four of diff — and has PREFIX_IN_FLIGHT of them per array in flight before the
+   // first is consumed: 15 per array and thread at 29 903 positions, four turns.
    const bool with_ends = EVENTS && range.code_map != nullptr && range.position_covered != nullptr;  // (uniform)
-   const uint32_t* __restrict__ ends = diff + 2u * static_cast<size_t>(n);
+   const uint32_t* __restrict__ ends = counts + range.ends_offset;
    const auto endAt = [&](uint32_t j) { return ends[2u * j + 1u] - ends[2u * j]; };
    uint32_t without_symbol = 0;  // rows of the filter that have no valid symbol at p
    uint32_t in_end_run = 0;      // rows of the filter inside a leading or trailing run of the gap symbol at p
    if (range.code_map != nullptr) {  // (uniform)
       uint32_t before[2] = {0, 0};
-      for (uint32_t j = threadIdx.x; j < first_position; j += DERIVED_THREADS) {
-         before[0] += diffAt(j);
-         before[1] += with_ends ? endAt(j) : 0u;
+      const uint4* __restrict__ diff16 = reinterpret_cast<const uint4*>(diff);
+      const uint4* __restrict__ ends16 = reinterpret_cast<const uint4*>(ends);
+      const uint32_t own[2] = {p < n ? diffAt(p) : 0u, with_ends && p < n ? endAt(p) : 0u};  // (in flight beside the sweep's first loads)
+      const uint32_t n16 = EVENTS ? first_position / 2u : first_position / 4u;  // (exact: first_position is a multiple of 1024)
+      for (uint32_t base = 0; base < n16; base += DERIVED_THREADS * PREFIX_IN_FLIGHT) {  // (uniform)
+         uint4 d[PREFIX_IN_FLIGHT];
+         uint4 e[PREFIX_IN_FLIGHT];
+#pragma unroll
+         for (uint32_t k = 0; k < PREFIX_IN_FLIGHT; ++k) {
+            const uint32_t i = base + k * DERIVED_THREADS + threadIdx.x;
+            d[k] = i < n16 ? diff16[i] : make_uint4(0, 0, 0, 0);
+            e[k] = with_ends && i < n16 ? ends16[i] : make_uint4(0, 0, 0, 0);
+         }
+#pragma unroll
+         for (uint32_t k = 0; k < PREFIX_IN_FLIGHT; ++k) {
+            before[0] += EVENTS ? d[k].x - d[k].y + d[k].z - d[k].w : d[k].x + d[k].y + d[k].z + d[k].w;
+            before[1] += e[k].y - e[k].x + e[k].w - e[k].z;
+         }
       }
-      const uint32_t scanned[2] = {waveSumToLane63(p < n ? diffAt(p) : 0u), waveSumToLane63(with_ends && p < n ? endAt(p) : 0u)};  // inclusive over the wave
+      const uint32_t scanned[2] = {waveSumToLane63(own[0]), waveSumToLane63(own[1])};  // inclusive over the wave
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
          before[t] = waveSumToLane63(before[t]);
@@ -328,28 +354,98 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
       }
       in_end_run += args.counters[q * SPARSE_COUNTER_STRIDE + 2];
    }
-   if (p >= n) {
-      return;
-   }
-   if (!with_ends || range.position_covered[range.pos_begin + p] == 0) {  // only the covered positions take their gap rows from the end runs: everywhere else the row was read
-      in_end_run = 0;
-   }
-   uint32_t* __restrict__ out = range.caller_counts[q] + static_cast<size_t>(p) * n_scan;
-   const uint32_t* __restrict__ cell = counts + static_cast<size_t>(p) * n_scan;
-   uint32_t others = 0;
-   for (uint32_t symbol = 0; symbol < n_scan; ++symbol) {
-      const uint32_t count = cell[symbol] + (symbol == range.end_symbol ? in_end_run : 0u);
-      others += count;
-      if (count != 0) {
-         out[symbol] += count;  // scans of one table are ordered on a stream: no atomic needed
+   if constexpr (SELECT == 0) {
+      if (p >= n) {
+         return;
       }
-   }
-   if (range.code_map != nullptr) {
-      const uint8_t* map = range.code_map + static_cast<size_t>(range.pos_begin + p) * CODE_MAP_STRIDE;
-      if ((map[0] & LAYOUT_IMPLICIT) != 0) {
-         const uint32_t derived = args.counters[q * SPARSE_COUNTER_STRIDE + 2] - without_symbol - others;
-         if (derived != 0) {
-            out[map[IMPLICIT_SLOT]] += derived;
+      if (!with_ends || range.position_covered[range.pos_begin + p] == 0) {  // only the covered positions take their gap rows from the end runs: everywhere else the row was read
+         in_end_run = 0;
+      }
+      uint32_t* __restrict__ out = range.caller_counts[q] + static_cast<size_t>(p) * n_scan;
+      const uint32_t* __restrict__ cell = counts + static_cast<size_t>(p) * n_scan;
+      uint32_t others = 0;
+      for (uint32_t symbol = 0; symbol < n_scan; ++symbol) {
+         const uint32_t count = cell[symbol] + (symbol == range.end_symbol ? in_end_run : 0u);
+         others += count;
+         if (count != 0) {
+            out[symbol] += count;  // scans of one table are ordered on a stream: no atomic needed
+         }
+      }
+      if (range.code_map != nullptr) {
+         const uint8_t* map = range.code_map + static_cast<size_t>(range.pos_begin + p) * CODE_MAP_STRIDE;
+         if ((map[0] & LAYOUT_IMPLICIT) != 0) {
+            const uint32_t derived = args.counters[q * SPARSE_COUNTER_STRIDE + 2] - without_symbol - others;
+            if (derived != 0) {
+               out[map[IMPLICIT_SLOT]] += derived;
+            }
+         }
+      }
+   } else {
+      const SelectSink& sink = args.sinks[q];
+      uint32_t selected = 0;  // bit s: symbol s passes
+      if (p < n) {
+         if (!with_ends || range.position_covered[range.pos_begin + p] == 0) {
+            in_end_run = 0;
+         }
+         const uint32_t* __restrict__ cell = counts + static_cast<size_t>(p) * SELECT;
+         uint32_t count[SELECT];
+         uint32_t others = 0;
+#pragma unroll
+         for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
+            count[symbol] = cell[symbol] + (symbol == range.end_symbol ? in_end_run : 0u);
+            others += count[symbol];
+         }
+         uint32_t covered = others;  // the sum of the position's final cells (uint32 wrap-around as in K4)
+         if (range.code_map != nullptr) {
+            const uint8_t* map = range.code_map + static_cast<size_t>(range.pos_begin + p) * CODE_MAP_STRIDE;
+            if ((map[0] & LAYOUT_IMPLICIT) != 0) {
+               const uint32_t derived = args.counters[q * SPARSE_COUNTER_STRIDE + 2] - without_symbol - others;
+               const uint32_t slot = map[IMPLICIT_SLOT];
+#pragma unroll
+               for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
+                  count[symbol] += symbol == slot ? derived : 0u;
+               }
+               covered += derived;
+            }
+         }
+         uint32_t* __restrict__ out = range.caller_counts[q] + static_cast<size_t>(p) * SELECT;
+#pragma unroll
+         for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
+            out[symbol] = count[symbol];  // the only writer of the cell: whatever the table held is gone
+         }
+         // K4 (k_mutations_select_to_host) on the cells at hand
+         const uint32_t position = range.table_offset + p;
+         if (covered != 0) {
+            const uint32_t threshold_count =
+               sink.min_proportion == 0 ? 0u : static_cast<uint32_t>(ceil(static_cast<double>(covered) * sink.min_proportion) - 1);
+            const uint32_t reference = sink.reference_index[position];
+#pragma unroll
+            for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
+               if (symbol != reference && count[symbol] > threshold_count) {
+                  selected |= 1u << symbol;
+               }
+            }
+         }
+         if (selected != 0) {
+            uint32_t slot = atomicAdd(&sink.cursor_and_ticket[0], static_cast<uint32_t>(__popc(selected)));
+#pragma unroll
+            for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
+               if ((selected >> symbol) & 1u) {
+                  if (slot < sink.capacity) {
+                     sink.host_rows[slot] = silo_gpu_mutation_row{position, symbol, count[symbol], covered};
+                  }
+                  ++slot;
+               }
+            }
+         }
+      }
+      __threadfence_system();  // this thread's rows are in host memory ...
+      __syncthreads();         // ... and so are those of the whole block, before its ticket is taken
+      if (threadIdx.x == 0) {
+         if (atomicAdd(&sink.cursor_and_ticket[1], 1u) == sink.total_blocks - 1) {  // the last block of the scan's finish launches for this filter
+            const uint32_t n_selected = atomicExch(&sink.cursor_and_ticket[0], 0u);
+            atomicExch(&sink.cursor_and_ticket[1], 0u);
+            __hip_atomic_store(sink.host_header, (static_cast<unsigned long long>(sink.epoch) << 32) | n_selected, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
          }
       }
    }
@@ -382,14 +478,37 @@ bool usesEndRuns(const ScanRange& range, int knob) {
 
 namespace silo_gpu_detail {
 
-/// Lays the private tables of `ranges` out (offsets only: `tables` may still be null) .
-void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, DerivedPlan& plan) {
+/// Does a scan of `ranges` count the gap events of its stores (DerivedPlan::events)?  The knobs allow it and every store with
+/// derived symbols has them.
+bool derivedCountsEvents(const std::vector<ScanRange>& ranges) {
+   bool events = g_tune_gap_events.load() >= 0 && g_tune_side_stream.load() != 3;
+   for (const ScanRange& range : ranges) {
+      events = events && (!range.seqstore->layout.has_implicit || range.seqstore->layout.gap_stream);
+   }
+   return events;
+}
+
+/// Lays the private tables of `ranges` out (offsets only: `tables` may still be null).  `select` (or nullptr): the finish
+/// launches overwrite the callers' tables and deliver the selected rows (the caller has checked that the scan counts gap events).
+void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, DerivedPlan& plan,
+   const ScanSelect* select) {
    plan.private_ranges = ranges;
    plan.launches.assign((ranges.size() + DERIVED_MAX_RANGES - 1) / DERIVED_MAX_RANGES, DerivedArgs{});
    plan.run_counts.assign(plan.launches.size(), {});
-   plan.events = g_tune_gap_events.load() >= 0 && g_tune_side_stream.load() != 3;
-   for (const ScanRange& range : ranges) {
-      plan.events = plan.events && (!range.seqstore->layout.has_implicit || range.seqstore->layout.gap_stream);
+   plan.events = derivedCountsEvents(ranges);
+   plan.select = select != nullptr && plan.events;
+   if (plan.select) {
+      std::vector<uint32_t> n_positions;
+      for (const ScanRange& range : ranges) {
+         n_positions.push_back(range.pos_end - range.pos_begin);
+      }
+      const uint32_t total_blocks = finishBlocks(n_positions.data(), n_positions.size(), DERIVED_THREADS);
+      for (DerivedArgs& launch : plan.launches) {
+         std::copy_n(select->sinks, q_count, launch.sinks);
+         for (uint32_t q = 0; q < q_count; ++q) {
+            launch.sinks[q].total_blocks = total_blocks;
+         }
+      }
    }
    plan.gap_ranges.assign(plan.events ? ranges.size() : 0, ScanRange{});
    const int end_knob = g_tune_end_runs.load();
@@ -406,14 +525,19 @@ void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& rang
       entry.n_positions = n;
       entry.n_scan = seqstore.dev.n_scan;
       entry.pos_begin = range.pos_begin;
+      entry.table_offset = plan.select ? select->table_offset[r] : 0;
       // counts[n][n_scan], then gaps[n][2] (the events: starts, ends) — and ends[n][2] where the range counts end runs — or
-      // diff[n + 1] and ambiguous[n]
+      // diff[n + 1] and ambiguous[n]; gaps / diff and ends begin at a multiple of 16 bytes (the sweep of k_finish_scan)
       const bool end_runs = plan.events && seqstore.layout.has_implicit && usesEndRuns(range, end_knob);
       plan.end_runs[r] = end_runs ? 1 : 0;
       entry.position_covered = end_runs ? seqstore.layout.d_position_covered : nullptr;
       entry.end_symbol = seqstore.layout.end_symbol;
-      const size_t rows_without = plan.events ? (end_runs ? 4u : 2u) * static_cast<size_t>(n) : static_cast<size_t>(n) + 1 + n;
-      entry.stride = static_cast<uint32_t>((static_cast<size_t>(n) * seqstore.dev.n_scan + rows_without + 3) / 4 * 4);
+      const auto rounded = [](size_t words) { return (words + 3) / 4 * 4; };
+      const size_t gaps_offset = rounded(static_cast<size_t>(n) * seqstore.dev.n_scan);
+      const size_t ends_offset = rounded(gaps_offset + 2 * static_cast<size_t>(n));
+      entry.gaps_offset = static_cast<uint32_t>(gaps_offset);
+      entry.ends_offset = static_cast<uint32_t>(ends_offset);
+      entry.stride = static_cast<uint32_t>(rounded(plan.events ? ends_offset + (end_runs ? 2 * static_cast<size_t>(n) : 0) : gaps_offset + n + 1 + n));
       entry.scratch = reinterpret_cast<uint32_t*>(offset * sizeof(uint32_t));  // + the scratch block's tables (bindDerived)
       offset += static_cast<size_t>(entry.stride) * q_count;
       if (seqstore.layout.has_implicit) {
@@ -473,14 +597,14 @@ void bindDerived(DerivedPlan& plan, uint32_t* tables, const uint32_t* counters, 
             ScanRange& gap = plan.gap_ranges[r];
             gap = plan.private_ranges[r];
             for (uint32_t q = 0; q < q_count; ++q) {
-               gap.counts[q] = entry.scratch + static_cast<size_t>(q) * entry.stride + static_cast<size_t>(entry.n_positions) * entry.n_scan;
+               gap.counts[q] = entry.scratch + static_cast<size_t>(q) * entry.stride + entry.gaps_offset;
             }
          }
          if (plan.end_runs[r] != 0) {
             ScanRange& end = plan.end_ranges[r];
             end = plan.private_ranges[r];
             for (uint32_t q = 0; q < q_count; ++q) {
-               end.counts[q] = entry.scratch + static_cast<size_t>(q) * entry.stride + static_cast<size_t>(entry.n_positions) * (entry.n_scan + 2u);
+               end.counts[q] = entry.scratch + static_cast<size_t>(q) * entry.stride + entry.ends_offset;
             }
          }
       }
@@ -544,10 +668,15 @@ int finishDerived(DerivedPlan& plan, uint32_t q_count, hipStream_t hip_stream) {
          launch.first_unit[k + 1] = launch.first_unit[k] + (launch.ranges[k].n_positions + DERIVED_THREADS - 1) / DERIVED_THREADS;
       }
       if (launch.first_unit[launch.n_ranges] != 0) {
-         if (plan.events) {
-            k_finish_scan<true><<<dim3(launch.first_unit[launch.n_ranges], q_count), DERIVED_THREADS, 0, hip_stream>>>(launch);
+         const dim3 grid(launch.first_unit[launch.n_ranges], q_count);
+         if (plan.select && launch.ranges[0].n_scan == 5) {  // (a scan's ranges are of one alphabet)
+            k_finish_scan<true, 5><<<grid, DERIVED_THREADS, 0, hip_stream>>>(launch);
+         } else if (plan.select) {
+            k_finish_scan<true, 22><<<grid, DERIVED_THREADS, 0, hip_stream>>>(launch);
+         } else if (plan.events) {
+            k_finish_scan<true, 0><<<grid, DERIVED_THREADS, 0, hip_stream>>>(launch);
          } else {
-            k_finish_scan<false><<<dim3(launch.first_unit[launch.n_ranges], q_count), DERIVED_THREADS, 0, hip_stream>>>(launch);
+            k_finish_scan<false, 0><<<grid, DERIVED_THREADS, 0, hip_stream>>>(launch);
          }
          HIP_TRY(hipGetLastError());
       }

@@ -133,14 +133,6 @@ int silo_gpu_mutations_select(
    return SILO_GPU_OK;
 }
 
-struct silo_gpu_row_slot {
-   uint32_t capacity = 0;
-   uint32_t epoch = 0;                       // of the last launch
-   uint32_t* d_cursor_and_ticket = nullptr;  // device: rows appended so far, blocks done so far
-   void* host = nullptr;                     // page-locked: header word (epoch << 32 | selected cells), then the rows from byte 16
-   void* host_dev = nullptr;                 // its device address
-};
-
 int silo_gpu_row_slot_create(uint32_t row_capacity, silo_gpu_row_slot** out_slot) {
    if (out_slot == nullptr || row_capacity == 0) {
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_row_slot_create: bad arguments");

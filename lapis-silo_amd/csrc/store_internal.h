@@ -33,12 +33,23 @@ extern std::atomic<int> g_tune_compact_index;   // < 0: finalize keeps the build
 extern std::atomic<int> g_tune_gap_events;      // < 0: scans of derived symbols take the runs and the sparse keys by themselves (planDerived)
 extern std::atomic<int> g_tune_prune_keys;      // silo_gpu_mutations_scan_ranges_min_proportion: < 0 skips nothing, 0 granules of escape keys and one-hot rows, 1 keys only (ScanPruning, scan_internal.h)
 extern std::atomic<int> g_tune_end_runs;        // < 0: a Mutations scan reads the covered rows of the gap symbol instead of counting its end runs (DerivedPlan::end_runs)
+extern std::atomic<int> g_tune_fused_select;    // < 0: silo_gpu_mutations_scan_select always clears, scans and selects in launches of their own (canFuseSelect, silo_gpu_scan.hip)
 extern std::atomic<int> g_tune_side_stream;     // the side passes of a scan: see forkSidePasses (silo_gpu_scan.hip)
 extern std::atomic<int> g_tune_scan_timing;     // 1: HIP events around every launch of a scan (silo_gpu_scan_timings)
 extern std::atomic<int> g_tune_missing_runs;    // < 0: finalize keeps the plane of the missing symbol instead of turning it into runs
 extern std::atomic<int> g_tune_key_cost;        // > 0: what an escape key costs in plane bytes in the layout choice (default KEY_COST_BYTES)
 extern std::atomic<int> g_tune_launch_cost;     // KiB of plane bytes a further kind of plane-scan launch costs in the layout choice: 0 = default, < 0 = nothing
 extern std::atomic<int> g_tune_sparse_divisor;  // 0 = default (row_words / 16 filter sectors with a set bit), < 0 = sparse-filter path off
+
+/// A row slot (silo_gpu_row_slot_*, silo_gpu_select.hip): written by k_mutations_select_to_host and by the finish kernel of a
+/// scan that selects (silo_gpu_mutations_scan_select).
+struct silo_gpu_row_slot {
+   uint32_t capacity = 0;
+   uint32_t epoch = 0;                       // of the last launch
+   uint32_t* d_cursor_and_ticket = nullptr;  // device: rows appended so far, blocks done so far
+   void* host = nullptr;                     // page-locked: header word (epoch << 32 | selected cells), then the rows from byte 16
+   void* host_dev = nullptr;                 // its device address
+};
 
 namespace silo_gpu_detail {
 
@@ -528,9 +539,12 @@ struct ScanRange {
 /// The Mutations scan of `q_count` filters over position ranges of sequence stores of one alphabet (silo_gpu_scan.hip, its passes: scan_internal.h); finalize
 /// uses it for the unfiltered totals that decide the layout.
 /// min_proportion: nullptr, or one proportion per filter (silo_gpu_mutations_scan_ranges_min_proportion).
+/// select (or nullptr; scan_internal.h): the scan is the only writer of the callers' tables — it overwrites them and delivers each
+/// filter's Mutations rows into its row slot (silo_gpu_mutations_scan_select, which has checked that the scan can).
+struct ScanSelect;
 int scanRanges(
    const silo_gpu_store* store, const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream,
-   const double* min_proportion = nullptr
+   const double* min_proportion = nullptr, const ScanSelect* select = nullptr
 );
 
 // host helpers of the store (silo_gpu_store.hip)

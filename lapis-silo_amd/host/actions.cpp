@@ -169,6 +169,7 @@ void ScanBatcher::flush() {
       silo_gpu_store* store;
       const uint64_t* filter;
       double min_proportion;  // of every range of the entry (Request::min_proportion)
+      silo_gpu_select_sink sink;  // of every range of the entry (Request::sink)
       std::vector<silo_gpu_scan_range> ranges;
       std::vector<uint32_t*> counts;
    };
@@ -188,13 +189,14 @@ void ScanBatcher::flush() {
       FilterScans* entry = nullptr;
       for (FilterScans& candidate : by_filter) {
          if (candidate.store == request.store && candidate.filter == request.filter && candidate.min_proportion == request.min_proportion &&
+             candidate.sink.slot == request.sink.slot &&
              std::none_of(candidate.ranges.begin(), candidate.ranges.end(), [&](const auto& other) { return same_range(other, range); })) {
             entry = &candidate;
             break;
          }
       }
       if (entry == nullptr) {
-         by_filter.push_back({request.store, request.filter, request.min_proportion, {}, {}});
+         by_filter.push_back({request.store, request.filter, request.min_proportion, request.sink, {}, {}});
          entry = &by_filter.back();
       }
       entry->ranges.push_back(range);
@@ -209,7 +211,8 @@ void ScanBatcher::flush() {
       std::vector<size_t> group;
       for (size_t k = i; k < by_filter.size(); ++k) {
          const FilterScans& other = by_filter[k];
-         if (!done[k] && other.store == first.store && other.ranges.size() == first.ranges.size() &&
+         // (entries with a sink and entries without one do not share a call)
+         if (!done[k] && other.store == first.store && (other.sink.slot != nullptr) == (first.sink.slot != nullptr) && other.ranges.size() == first.ranges.size() &&
              std::equal(other.ranges.begin(), other.ranges.end(), first.ranges.begin(), same_range)) {
             done[k] = true;
             group.push_back(k);
@@ -226,6 +229,20 @@ void ScanBatcher::flush() {
          for (const size_t k : group) {
             counts.push_back(by_filter[k].counts[r]);
          }
+      }
+      if (first.sink.slot != nullptr) {  // the scans are their tables' only writers: one call overwrites them and delivers the rows
+         std::vector<silo_gpu_select_sink> sinks;
+         for (const size_t k : group) {
+            sinks.push_back(by_filter[k].sink);
+         }
+         checkGpu(
+            silo_gpu_mutations_scan_select(
+               first.store, first.ranges.data(), static_cast<uint32_t>(first.ranges.size()), filters.data(), static_cast<uint32_t>(filters.size()),
+               proportions.data(), counts.data(), sinks.data(), queryStream()
+            ),
+            "silo_gpu_mutations_scan_select"
+         );
+         continue;
       }
       checkGpu(
          silo_gpu_mutations_scan_ranges_min_proportion(
@@ -312,7 +329,7 @@ std::map<std::string, typename Mutations<SymbolType>::PrefilteredBitmaps> Mutati
 template <typename SymbolType>
 void Mutations<SymbolType>::calculateMutationsPerPosition(
    const Database& database, const SequenceStore<SymbolType>& sequence_store, const PrefilteredBitmaps& bitmap_filter, uint32_t* device_counts,
-   double min_proportion
+   double min_proportion, const silo_gpu_select_sink* sink
 ) {
    // mutations.cpp:139-164 runs and_cardinality(filter, column) per position x symbol under
    // tbb::parallel_for; here each (partition, sequence store) is ONE scan kernel (K1) that accumulates
@@ -330,8 +347,10 @@ void Mutations<SymbolType>::calculateMutationsPerPosition(
    const bool single_scan = bitmap_filter.bitmaps.size() + bitmap_filter.full_bitmaps.size() == 1 && database.all_reduce == nullptr;
    const double prunable = single_scan && min_proportion > 0 ? min_proportion : 0;
    const auto scan = [&](const SequenceStorePartition<SymbolType>& store, const uint64_t* filter) {
-      if (batcher != nullptr) {
-         batcher->add({store.store, store.seqstore_id, filter, 0, local_positions, window, filter != nullptr ? prunable : 0});
+      if (batcher != nullptr && sink != nullptr) {  // (begin has checked: a batcher, one filtered scan per store, the selection with min_proportion)
+         batcher->add({store.store, store.seqstore_id, filter, 0, local_positions, window, min_proportion, *sink});
+      } else if (batcher != nullptr) {
+         batcher->add({store.store, store.seqstore_id, filter, 0, local_positions, window, filter != nullptr ? prunable : 0, {}});
       } else {
          checkGpu(
             silo_gpu_mutations_scan(store.store, store.seqstore_id, filter, 0, local_positions, window, queryStream()), "silo_gpu_mutations_scan"
@@ -436,7 +455,22 @@ std::unique_ptr<Action::Pending> Mutations<SymbolType>::begin(const Database& da
    pending->row_capacity = layout.reference_index_device != nullptr ? database.mutation_row_capacity : 0;
    pending->device_table = database.partitions.front().pool.acquire(pending->table_bytes);
    auto* device_counts = static_cast<uint32_t*>(pending->device_table.get());
-   checkGpu(silo_gpu_memset_async(device_counts, 0, pending->table_bytes, queryStream()), "silo_gpu_memset_async");
+   // Where every requested store has exactly ONE scan, a filtered one, and the table is not summed across ranks — one partition,
+   // or one partition selected — the scans are the only writers of the table and the row selection its only reader: they leave
+   // in one call that overwrites the table and delivers the rows into the row slot (silo_gpu_mutations_scan_select; where the
+   // scanned stores make up the whole table, the finish kernel of the scan does both), with no fill and no selection launch here.
+   bool scans_select = !reduced && pending->row_capacity != 0;
+   for (const auto& sequence_name : pending->sequence_names) {
+      const auto found = bitmaps_to_evaluate.find(sequence_name);
+      scans_select = scans_select && found != bitmaps_to_evaluate.end() && found->second.bitmaps.size() == 1 && found->second.full_bitmaps.empty();
+   }
+   silo_gpu_select_sink sink{};
+   if (scans_select) {
+      pending->row_slot = RowSlot(pending->row_capacity);
+      sink = {device_counts, layout.total_positions, n_symbols, layout.reference_index_device.get(), pending->row_slot.handle()};
+   } else {
+      checkGpu(silo_gpu_memset_async(device_counts, 0, pending->table_bytes, queryStream()), "silo_gpu_memset_async");
+   }
 
    const PrefilteredBitmaps no_bitmaps{};
    std::vector<std::string> scanned;  // a store requested twice is scanned once
@@ -455,7 +489,7 @@ std::unique_ptr<Action::Pending> Mutations<SymbolType>::begin(const Database& da
       const auto found = bitmaps_to_evaluate.find(sequence_name);
       calculateMutationsPerPosition(
          database, sequence_store, found != bitmaps_to_evaluate.end() ? found->second : no_bitmaps,
-         device_counts + static_cast<size_t>(layout.position_offset.at(sequence_name)) * n_symbols, min_proportion
+         device_counts + static_cast<size_t>(layout.position_offset.at(sequence_name)) * n_symbols, min_proportion, scans_select ? &sink : nullptr
       );
    }
    Trace::mark("scan_launched");
@@ -483,7 +517,11 @@ std::unique_ptr<Action::Pending> Mutations<SymbolType>::begin(const Database& da
       appendFingerprint(device_counts, n_counts, scans.fingerprint);
       batcher->addReduction(database, device_counts, n_counts + FINGERPRINT_WORDS);  // the whole query in one collective
    }
-   batcher->afterFlush(select_and_fetch);  // the scans are only recorded so far
+   if (scans_select) {
+      batcher->afterFlush([&scans]() { scans.row_slot.launched(queryStream()); });  // (the call that delivers into the slot leaves with the flush)
+   } else {
+      batcher->afterFlush(select_and_fetch);  // the scans are only recorded so far
+   }
    if (own_batcher) {
       own_batcher->flush();
    }

@@ -132,6 +132,13 @@ class RowSlot {
    ~RowSlot();
    /// k_mutations_select over `counts` with the rows delivered into this slot; enqueued on `stream`.
    void select(const uint32_t* counts, const uint8_t* reference_index, uint32_t n_positions, uint32_t n_symbols, double min_proportion, void* stream);
+   /// The device library's slot, for a launch the caller makes itself (silo_gpu_mutations_scan_select) and reports with launched().
+   [[nodiscard]] silo_gpu_row_slot* handle() const { return slot_; }
+   /// A launch that delivers into this slot has been enqueued on `stream`.
+   void launched(void* stream) {
+      stream_ = stream;
+      in_flight_ = true;
+   }
    /// Blocks (spins) until the launch has delivered: the rows and the number of selected cells (may exceed the capacity).
    std::pair<const silo_gpu_mutation_row*, uint32_t> wait();
    explicit operator bool() const { return slot_ != nullptr; }

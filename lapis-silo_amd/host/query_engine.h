@@ -593,6 +593,10 @@ class ScanBatcher {
       /// other scan adds into this store's part of it — the scan may then leave out escape keys that cannot reach the proportion
       /// (silo_gpu_mutations_scan_ranges_min_proportion).  0: every cell exact.
       double min_proportion = 0;
+      /// slot != nullptr: this scan is the ONLY writer of the query's count table (sink.table_dev, which `counts` points into) and
+      /// the row selection with min_proportion its only reader — the scans of the query leave in a call that overwrites the table
+      /// and delivers the selected rows into the slot (silo_gpu_mutations_scan_select); the table is not cleared beforehand.
+      silo_gpu_select_sink sink{};
    };
    ScanBatcher();
    ~ScanBatcher();
@@ -911,7 +915,7 @@ class Mutations : public Action {
    /// scan may leave out escape keys that cannot reach the proportion (ScanBatcher::Request::min_proportion).
    static void calculateMutationsPerPosition(
       const Database& database, const SequenceStore<SymbolType>& sequence_store, const PrefilteredBitmaps& bitmap_filter,
-      uint32_t* device_counts, double min_proportion = 0
+      uint32_t* device_counts, double min_proportion = 0, const silo_gpu_select_sink* sink = nullptr
    );
 
    /// `counts` = the slice counts[position][valid symbol] of one store, on the host.

@@ -108,6 +108,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_event_destroy", "silo_gpu_event_synchronize", "silo_gpu_host_alloc", "silo_gpu_host_free", "silo_gpu_memcpy_d2h_async", "silo_gpu_mutations_select", "silo_gpu_upload_bytes", "silo_gpu_upload_column", "silo_gpu_bitset_from_compare", "silo_gpu_group_count", "silo_gpu_group_count_hashed", "silo_gpu_reconstruct_sequences", "silo_gpu_bitset_from_pairs", "silo_gpu_count_pairs", "silo_gpu_count_slot_create", "silo_gpu_count_slot_destroy", "silo_gpu_filter_eval_count", "silo_gpu_count_slot_wait", "silo_gpu_tune", "silo_gpu_last_scan_kernel", "silo_gpu_scan_timings", "silo_gpu_stream_read_probe", "silo_gpu_last_error",
     "silo_gpu_comm_unique_id", "silo_gpu_comm_create", "silo_gpu_comm_destroy", "silo_gpu_comm_rank", "silo_gpu_comm_world",
     "silo_gpu_allreduce_counts", "silo_gpu_broadcast_bytes",
+    "silo_gpu_mutations_scan_select",
     "silo_gpu_mutations_scan_ranges_min_proportion", "silo_gpu_store_scan_prunable_granules", "silo_gpu_store_scan_prunable_rows",
     "silo_gpu_store_scan_covered_rows", "silo_gpu_store_scan_end_events", "silo_gpu_store_scan_residual_keys",
     "silo_gpu_filters_grouped", "silo_gpu_filters_cross",
@@ -173,6 +174,8 @@ def load_library():
     lib.silo_gpu_mutations_scan_ranges.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32, ctypes.POINTER(vp), vp]
     lib.silo_gpu_mutations_scan_ranges_min_proportion.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32,
                                                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(vp), vp]
+    lib.silo_gpu_mutations_scan_select.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32,
+                                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(vp), ctypes.POINTER(SelectSink), vp]
     lib.silo_gpu_store_scan_prunable_granules.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64),
                                                           ctypes.POINTER(ctypes.c_uint64)]
     lib.silo_gpu_store_scan_prunable_rows.argtypes = lib.silo_gpu_store_scan_prunable_granules.argtypes
@@ -358,6 +361,12 @@ class CountSlot:
         if getattr(self, "handle", None):
             self.lib.silo_gpu_count_slot_destroy(self.handle)
             self.handle = None
+
+
+class SelectSink(ctypes.Structure):
+    """silo_gpu_select_sink: where silo_gpu_mutations_scan_select leaves one filter's table and rows."""
+    _fields_ = [("table_dev", ctypes.c_void_p), ("total_positions", ctypes.c_uint32), ("n_symbols", ctypes.c_uint32),
+                ("reference_index_dev", ctypes.c_void_p), ("slot", ctypes.c_void_p)]
 
 
 class RowSlot:
@@ -1140,6 +1149,20 @@ class GpuStore:
         for o in outs:
             self.free(o)
         return tables
+
+    def mutations_scan_select(self, ranges, filter_ptrs, min_proportions, tables, table_offsets, total_positions, reference_ptr, slots, stream=None):
+        """silo_gpu_mutations_scan_select: every filter over every (seqstore_id, pos_begin, pos_end) range, range r counted at position
+        table_offsets[r] of the filter's device table tables[q] ([total_positions][scan symbols], overwritten), the selected rows of filter
+        q delivered into slots[q] (RowSlot.wait); reference_ptr: the device array of the table's reference symbol indexes."""
+        n_symbols = len(self.scan_symbols[ranges[0][0]])
+        flat = (ctypes.c_uint32 * (3 * len(ranges)))(*[int(v) for r in ranges for v in r])
+        filters = (ctypes.c_void_p * len(filter_ptrs))(*[(f.value if isinstance(f, ctypes.c_void_p) else f) for f in filter_ptrs])
+        counts = (ctypes.c_void_p * (len(ranges) * len(filter_ptrs)))(
+            *[tables[q].value + 4 * n_symbols * int(table_offsets[r]) for r in range(len(ranges)) for q in range(len(filter_ptrs))])
+        proportions = (ctypes.c_double * len(filter_ptrs))(*[float(p) for p in min_proportions])
+        sinks = (SelectSink * len(filter_ptrs))(
+            *[SelectSink(tables[q].value, total_positions, n_symbols, reference_ptr.value, slots[q].handle.value) for q in range(len(filter_ptrs))])
+        _check(self.lib.silo_gpu_mutations_scan_select(self.handle, flat, len(ranges), filters, len(filter_ptrs), proportions, counts, sinks, stream))
 
     def _count_table_call(self, launch, shape, scratch_bytes, out_ptr, stream, scratch_ptr, return_groups=False):
         """What the three count-table entries (K7, K8, K9) share around launch(scratch, table) -> status: the call's own scratch or
