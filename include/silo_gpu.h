@@ -739,6 +739,34 @@ int silo_gpu_nearest_columns(
    const uint32_t* cells_dev, uint32_t n_rows, uint32_t n_columns, uint32_t k, uint32_t* out_dev, uint32_t* counts_dev, void* stream
 );
 
+/* ---- K15: the consensus call of count tables (Consensus / AminoAcidConsensus) --------------------------
+ * Takes no store.  counts_dev holds n_tables <= SILO_GPU_MAX_CONSENSUS_TABLES tables back to back, n_positions x n_symbols words
+ * each (n_symbols = 5 "-ACGT" / 22 "-ACDEFGHIKLMNPQRSTVWY*"): what silo_gpu_mutations_scan accumulates.  reference_index_dev is as
+ * for silo_gpu_mutations_select, n_positions bytes shared by every table (0xFF: the reference symbol is not a valid one).
+ * Per table and position, with c[s] the counts and depth = sum_s c[s] (no wrap is defined: depth <= UINT32_MAX):
+ *     depth < min_depth                         the missing symbol 'N' / 'X'; the position is LOW COVERAGE
+ *     otherwise need = (uint32_t)ceil((double)depth * threshold)   (IEEE double, as K4 computes its bound), and the call's symbols
+ *     are those with c[s] >= cut, where cut is the highest count whose symbols, with every symbol above it, sum to >= need:
+ *     the shortest prefix by descending count that reaches need, extended by every symbol tied with its last — never a matter of
+ *     symbol order.  cut > 0: a symbol nobody has is never in the call.
+ *       one symbol       its character ('-' included: the position is DELETED)
+ *       several symbols  the position is AMBIGUOUS: nucleotides all of ACGT — the IUPAC code of the set (M AC, R AG, W AT, S CG,
+ *                        Y CT, K GT, V ACG, H ACT, D AGT, B CGT, N ACGT); nucleotides with '-' among them — 'N'; amino acids — 'X'
+ * WRITES out_chars_dev[t * n_positions + p], every character once, and out_summary_dev[t * 4 + 0 .. 3] = the table's ambiguous,
+ * low-coverage and deleted positions and its DIFFERENCES: positions neither low coverage nor ambiguous whose symbol's index is
+ * not reference_index_dev[p].  Nothing is accumulated into: the call clears the summary words itself, on `stream`, and the
+ * blocks add integers to them, so two calls give the same bytes; the caller clears nothing.  One kernel launch serves all tables
+ * (a block of SILO_GPU_CONSENSUS_THREADS threads per as many positions of one table, staged through LDS; a thread per position; no
+ * scratch memory), returns without waiting.  counts_dev is 4-byte aligned (16-byte loads are used where they stay inside the tables).
+ * n_tables == 0 or n_positions == 0: success, nothing written.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for an
+ * alphabet other than the two, a NULL pointer, a threshold outside (0, 1] or NaN, min_depth == 0 or n_tables above the limit. */
+#define SILO_GPU_MAX_CONSENSUS_TABLES 64
+#define SILO_GPU_CONSENSUS_THREADS 256
+int silo_gpu_consensus_call(
+   int alphabet, const uint32_t* counts_dev, uint32_t n_tables, uint32_t n_positions, const uint8_t* reference_index_dev, double threshold,
+   uint32_t min_depth, char* out_chars_dev, uint32_t* out_summary_dev, void* stream
+);
+
 /* ---- K11: the rows of the whole store nearest to a query (NearestNeighbours) --------------------------
  * silo_gpu_query_distances compares one query — query_chars, `positions` characters in HOST memory — with EVERY row of a sequence
  * store, read off the store's own layout (identity / code planes with escape keys, one-hot rows with a derived symbol, runs of the

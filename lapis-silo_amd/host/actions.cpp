@@ -1,5 +1,5 @@
 // actions.cpp — Action base (ordering / limit / offset), Aggregated (count), Mutations<SymbolType> and parseAction.  The actions
-// that answer from a small count table (MutationsOverTime, QueriesOverTime, CrossTabulation) are in table_actions.cpp.
+// that answer from a small count table (MutationsOverTime, QueriesOverTime, CrossTabulation, Consensus) are in table_actions.cpp.
 // Reference: src/silo/query_engine/actions/{action,aggregated,mutations}.cpp.
 #include <algorithm>
 #include <charconv>
@@ -840,6 +840,8 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"Clusters", parseClusters},
    {"MinimumSpanningTree", parseMinimumSpanningTree},
    {"NearestAmong", parseNearestAmong},
+   {"Consensus", parseConsensus<Nucleotide>},
+   {"AminoAcidConsensus", parseConsensus<AminoAcid>},
    {"NearestNeighbours", parseNearestNeighbours},
 };
 

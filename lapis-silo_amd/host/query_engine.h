@@ -680,6 +680,8 @@ template <typename SymbolType>
 std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json);
 std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json);
 std::unique_ptr<Action> parseCrossTabulation(const json::Value& json);
+template <typename SymbolType>
+std::unique_ptr<Action> parseConsensus(const json::Value& json);
 /// The parser of DistanceMatrix (metadata_actions.cpp).
 std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json);
 /// The parser of Clusters (metadata_actions.cpp).
@@ -1078,6 +1080,42 @@ class CrossTabulation : public Action {
    std::vector<uint32_t> row_filters;     // the distinct sub-expressions of each side (indices into filters), in order of first use
    std::vector<uint32_t> column_filters;
    filter_expressions::ExpressionVector filters;  // the distinct sub-expressions of both lists
+
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+};
+
+/// Consensus / AminoAcidConsensus: the consensus sequence of one sequence store over the rows of the query's filter, or over each of
+/// up to MAX_GROUPS named groups — the filter AND the group's own expression, per partition.  Per group and position the counts of
+/// the valid mutation symbols (a cell of a Mutations table) and their sum, the depth: below min_depth the missing symbol (low
+/// coverage); otherwise the symbols, by descending count, up to the one at which they reach ceil(depth * threshold), with every
+/// symbol tied with that one — a single symbol as itself ('-': deleted), several as the IUPAC code of the set (nucleotides, 'N' with
+/// '-' among them) or 'X' (amino acids): ambiguous.  One row per group, in request order: name (null without groups), sequenceName,
+/// count, consensus, ambiguousPositions, lowCoveragePositions, deletedPositions, differences (unambiguous, covered calls that are
+/// not the reference's symbol).  Per partition the exact Mutations scan of all groups' bitsets (silo_gpu_mutations_scan_batch: a
+/// pass over the planes per SILO_GPU_MAX_SCAN_BATCH groups) accumulates into one table per group; one consensus call (K15) and one
+/// fetch of characters and sums: the tables never leave the device.  No counterpart in the reference.
+template <typename SymbolType>
+class Consensus : public Action {
+  public:
+   struct Group {
+      std::optional<std::string> name;                          // none: the one group of a request without groups
+      std::unique_ptr<filter_expressions::Expression> filter;  // null: the query's filter alone
+   };
+   static constexpr uint32_t MAX_GROUPS = SILO_GPU_MAX_CONSENSUS_TABLES;
+   static constexpr double DEFAULT_THRESHOLD = 0.5;
+   static constexpr uint32_t DEFAULT_MIN_DEPTH = 1;
+   static_assert(MAX_GROUPS <= MAX_LIVE_FILTERS);  // the bitsets of every group of a partition are alive at a time
+   static std::string actionName() { return std::is_same_v<SymbolType, Nucleotide> ? "Consensus" : "AminoAcidConsensus"; }
+
+   Consensus(std::optional<std::string> sequence_name, std::vector<Group> groups, double threshold, uint32_t min_depth)
+       : sequence_name(std::move(sequence_name)), groups(std::move(groups)), threshold(threshold), min_depth(min_depth) {}
+
+  private:
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   std::vector<Group> groups;
+   double threshold;
+   uint32_t min_depth;
 
    void validateOrderByFields(const Database& database) const override;
    [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;

@@ -1,8 +1,10 @@
 // table_actions.cpp — the actions that answer from one small table of counts filled on the device: MutationsOverTime<SymbolType>
-// (K7), QueriesOverTime (K8) and CrossTabulation (K9), with their parsers.  Each differs in the kernel call of a partition and in
-// the rows it makes of the table; what stands around that — the refusals, the date column, the table's life on the device, the
-// evaluation of labelled sub-expressions and what has to stay alive while launches run — is here once.
+// (K7), QueriesOverTime (K8) and CrossTabulation (K9), which fetch the table, and Consensus<SymbolType> (K15), which fetches what
+// a last kernel makes of it, with their parsers.  Each differs in the kernel call of a partition and in the rows it makes of the
+// table; what stands around that — the refusals, the date column, the table's life on the device, the evaluation of labelled
+// sub-expressions and what has to stay alive while launches run — is here once.
 #include <algorithm>
+#include <cstring>
 #include <functional>
 #include <set>
 #include <string_view>
@@ -75,6 +77,8 @@ class LiveSet {
       in_flight = true;
       return scratches.back().get();
    }
+   /// Launches that read kept bitsets, but took no scratch, were enqueued: waitAndRelease has something to wait for.
+   void launched() { in_flight = true; }
    /// Keeps the bitset of a sub-expression for the launches that follow.
    const uint64_t* keep(OperatorResult result, size_t side = 0) {
       const uint64_t* bits = result.bitset();
@@ -434,6 +438,215 @@ QueryResult CrossTabulation::execute(const Database& database, std::vector<Opera
    return QueryResult{std::move(result_rows)};
 }
 
+// ---- Consensus -------------------------------------------------------------------------------------------
+// The consensus sequence of the query's filter, or of up to 64 named groups under it, from the exact Mutations scan and the
+// consensus call on the device (K15), with its parser.  No counterpart in the reference.
+namespace {
+
+/// The rows of one group on one partition: how many, and their bitset (nullptr: every row of the partition).
+struct GroupRows {
+   uint32_t cardinality;
+   const uint64_t* bits;
+};
+
+/// `expression` (nullptr: no expression, the base alone) AND the base — the rows of the query's filter on this partition, of which
+/// there are base_selected > 0, base_bits == nullptr where they are all rows.  Compiled as evaluateSubFilter compiles; the AND is an
+/// Intersection with the base's bitset as a stored column, so one fused launch yields the bitset and its cardinality.  A bitset
+/// made here is kept in `live`.  `owner` opens the message when the expression does not compile.
+GroupRows evaluateWithinBase(
+   const Database& database, const DatabasePartition& partition, const filter_expressions::Expression* expression, uint32_t base_selected,
+   const uint64_t* base_bits, LiveSet& live, const std::string& owner
+) {
+   if (expression == nullptr) {
+      return {base_selected, base_bits};
+   }
+   std::unique_ptr<operators::Operator> root;
+   try {
+      root = expression->compile(database, partition, filter_expressions::Expression::AmbiguityMode::NONE);
+   } catch (const QueryParseException& error) {
+      throw QueryParseException(owner + " is not a valid filter expression: " + error.what());
+   }
+   if (root->type() == operators::EMPTY) {
+      return {0, nullptr};
+   }
+   if (root->type() == operators::FULL) {
+      return {base_selected, base_bits};
+   }
+   if (base_bits != nullptr) {
+      const RowSpace rows = root->rows;
+      operators::OperatorVector children;
+      children.push_back(std::move(root));
+      children.push_back(std::make_unique<operators::IndexScan>(base_bits, rows));
+      root = std::make_unique<operators::Intersection>(std::move(children), operators::OperatorVector{}, rows);
+   }
+   OperatorResult result = operators::Operator::evaluate(std::move(root));
+   result.materialize();  // one launch yields both the bitset and its cardinality
+   const uint32_t cardinality = result.cardinality();
+   if (cardinality == 0 || cardinality == partition.sequence_count) {
+      return {cardinality, nullptr};
+   }
+   return {cardinality, live.keep(std::move(result))};
+}
+
+}  // namespace
+
+template <typename SymbolType>
+void Consensus<SymbolType>::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"name", "count", "ambiguousPositions", "lowCoveragePositions", "deletedPositions", "differences"});
+}
+
+template <typename SymbolType>
+QueryResult Consensus<SymbolType>::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string action_name = actionName();
+   requireUnsharded(database, action_name);
+   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+   const auto found = database.getSequenceStores<SymbolType>().find(name);
+   CHECK_SILO_QUERY(
+      found != database.getSequenceStores<SymbolType>().end(),
+      "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + name + "'"
+   )
+   const auto& reference = found->second.reference_sequence;
+   constexpr uint32_t n_symbols = SymbolType::VALID_MUTATION_SYMBOLS.size();
+   constexpr uint32_t summary_words = 4;  // ambiguous, low coverage, deleted, differences
+   const auto positions = static_cast<uint32_t>(reference.size());
+   const auto n_groups = static_cast<uint32_t>(groups.size());
+   const char missing = SymbolType::symbolToChar(SymbolType::SYMBOL_MISSING);
+   const size_t table_words = static_cast<size_t>(positions) * n_symbols;  // of one group
+
+   std::vector<uint32_t> group_rows(n_groups, 0);  // over all partitions
+   // what a group nobody scanned gets: the missing symbol everywhere, every position low coverage
+   std::vector<uint32_t> summary(static_cast<size_t>(n_groups) * summary_words, 0);
+   std::string characters(static_cast<size_t>(n_groups) * positions, missing);
+   for (uint32_t g = 0; g < n_groups; ++g) {
+      summary[g * summary_words + 1] = positions;
+   }
+   {
+      // nothing in here returns to the pool before the stream has been waited for: the launches read it
+      const bool on_device = !database.partitions.empty() && positions != 0;
+      DeviceBuffer device_table;       // n_groups tables back to back: it never leaves the device
+      DeviceBuffer device_result;      // the summaries, then the characters: the one thing fetched
+      DeviceBuffer device_reference;   // only where the database keeps no reference index on the device
+      LiveSet live;                    // the groups' bitsets of one partition at a time
+      try {
+         if (on_device) {
+            DevicePool& pool = database.partitions.front().pool;
+            device_table = pool.acquire(n_groups * table_words * sizeof(uint32_t));
+            device_result = pool.acquire(summary.size() * sizeof(uint32_t) + characters.size());
+            checkGpu(silo_gpu_memset_async(device_table.get(), 0, n_groups * table_words * sizeof(uint32_t), queryStream()), "silo_gpu_memset_async");
+         }
+         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+            const DatabasePartition& partition = database.partitions[partition_id];
+            const OperatorResult& filter = bitmap_filter[partition_id];
+            const uint32_t base_selected = partition.sequence_count == 0 ? 0 : filter.cardinality();
+            if (base_selected == 0) {
+               continue;
+            }
+            // a filter that selects every row is passed as NULL (no all-ones bitset is made for it)
+            const uint64_t* base_bits = base_selected == partition.sequence_count ? nullptr : filter.bitset();
+            live.waitAndRelease();  // the scans of the partition before may still read its groups' bitsets
+            const SequenceStorePartition<SymbolType>& store = partition.getSequenceStores<SymbolType>().at(name);
+            std::vector<const uint64_t*> scan_filters;  // the groups that select some rows of the partition, not all
+            std::vector<uint32_t*> scan_tables;
+            for (uint32_t g = 0; g < n_groups; ++g) {
+               const std::string owner = action_name + " action: the field filterExpression of the group '" + groups[g].name.value_or("") + "'";
+               const GroupRows rows = evaluateWithinBase(database, partition, groups[g].filter.get(), base_selected, base_bits, live, owner);
+               group_rows[g] += rows.cardinality;
+               if (rows.cardinality == 0 || !on_device) {  // empty here: its table stays as it is
+                  continue;
+               }
+               uint32_t* table = device_table.as<uint32_t>() + g * table_words;
+               if (rows.bits == nullptr) {  // every row: the store's cached totals are added, no pass over the planes
+                  checkGpu(silo_gpu_mutations_scan(store.store, store.seqstore_id, nullptr, 0, positions, table, queryStream()), "silo_gpu_mutations_scan");
+                  live.launched();
+               } else {
+                  scan_filters.push_back(rows.bits);
+                  scan_tables.push_back(table);
+               }
+            }
+            if (!scan_filters.empty()) {
+               // the EXACT scan (never a min_proportion variant: a pruned group would land on the derived symbol), every plane row
+               // read once per SILO_GPU_MAX_SCAN_BATCH groups; it accumulates, so partitions sum as they do for Mutations
+               checkGpu(
+                  silo_gpu_mutations_scan_batch(
+                     store.store, store.seqstore_id, scan_filters.data(), static_cast<uint32_t>(scan_filters.size()), 0, positions, scan_tables.data(),
+                     queryStream()
+                  ),
+                  "silo_gpu_mutations_scan_batch"
+               );
+               live.launched();
+            }
+         }
+         if (on_device) {
+            const MutationTableLayout& layout = database.getMutationTableLayout<SymbolType>();
+            const uint8_t* reference_index = nullptr;
+            if (layout.reference_index_device != nullptr) {
+               reference_index = layout.reference_index_device.get() + layout.position_offset.at(name);
+            } else {
+               std::vector<uint8_t> index(positions, 0xFF);
+               for (uint32_t p = 0; p < positions; ++p) {
+                  for (size_t s = 0; s < n_symbols; ++s) {
+                     if (SymbolType::VALID_MUTATION_SYMBOLS[s] == reference[p]) {
+                        index[p] = static_cast<uint8_t>(s);
+                     }
+                  }
+               }
+               device_reference = database.partitions.front().pool.acquire(positions);
+               checkGpu(silo_gpu_memcpy_h2d(device_reference.get(), index.data(), positions, queryStream()), "silo_gpu_memcpy_h2d");
+               reference_index = device_reference.as<uint8_t>();
+            }
+            auto* device_summary = device_result.as<uint32_t>();
+            char* device_characters = device_result.as<char>() + summary.size() * sizeof(uint32_t);
+            checkGpu(
+               silo_gpu_consensus_call(
+                  SymbolType::ABI_ALPHABET, device_table.as<uint32_t>(), n_groups, positions, reference_index, threshold, min_depth, device_characters,
+                  device_summary, queryStream()
+               ),
+               "silo_gpu_consensus_call"
+            );
+            HostFetch fetch(device_result.get(), summary.size() * sizeof(uint32_t) + characters.size(), queryStream());
+            const auto* host = static_cast<const char*>(fetch.wait());
+            std::memcpy(summary.data(), host, summary.size() * sizeof(uint32_t));
+            characters.assign(host + summary.size() * sizeof(uint32_t), characters.size());
+         }
+         // the copy was the last thing enqueued, but say it: nothing of this query runs any more when its buffers go back
+         checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+      } catch (...) {
+         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+         (void)silo_gpu_stream_synchronize(queryStream());
+         throw;
+      }
+   }
+
+   // what came off the device is checked before it becomes a row: every character one the rule can give, the three kinds of
+   // position disjoint
+   const std::string_view callable = std::is_same_v<SymbolType, Nucleotide> ? std::string_view("-ACGTMRWSYKVHDBN") : std::string_view("-ACDEFGHIKLMNPQRSTVWY*X");
+   QueryResult results;
+   results.query_result.reserve(n_groups);
+   for (uint32_t g = 0; g < n_groups; ++g) {
+      const std::string consensus = characters.substr(static_cast<size_t>(g) * positions, positions);
+      const uint32_t* sums = summary.data() + static_cast<size_t>(g) * summary_words;
+      if (consensus.find_first_not_of(callable) != std::string::npos) {
+         throw std::runtime_error(action_name + ": the device called a character that no call can be");
+      }
+      if (static_cast<uint64_t>(sums[0]) + sums[1] + sums[2] > positions || sums[3] > positions) {
+         throw std::runtime_error(action_name + ": the device counted more ambiguous, low-coverage and deleted positions than there are positions");
+      }
+      QueryResultEntry& entry = results.query_result.emplace_back();
+      entry.fields.emplace("name", groups[g].name.has_value() ? JsonValue{*groups[g].name} : JsonValue{std::nullopt});
+      entry.fields.emplace("sequenceName", name);
+      entry.fields.emplace("count", static_cast<int32_t>(group_rows[g]));
+      entry.fields.emplace("consensus", consensus);
+      entry.fields.emplace("ambiguousPositions", static_cast<int32_t>(sums[0]));
+      entry.fields.emplace("lowCoveragePositions", static_cast<int32_t>(sums[1]));
+      entry.fields.emplace("deletedPositions", static_cast<int32_t>(sums[2]));
+      entry.fields.emplace("differences", static_cast<int32_t>(sums[3]));
+   }
+   return results;
+}
+
+template class Consensus<Nucleotide>;
+template class Consensus<AminoAcid>;
+
 // ---- JSON -> the three actions ---------------------------------------------------------------------------
 namespace {
 
@@ -649,5 +862,68 @@ std::unique_ptr<Action> parseCrossTabulation(const json::Value& json) {
       std::move(row_queries), std::move(column_queries), std::move(row_filters), std::move(column_filters), std::move(distinct.filters)
    );
 }
+
+template <typename SymbolType>
+std::unique_ptr<Action> parseConsensus(const json::Value& json) {
+   using ConsensusAction = Consensus<SymbolType>;
+   const std::string action_name = ConsensusAction::actionName();
+   std::optional<std::string> sequence_name;
+   if (json.contains("sequenceName")) {
+      CHECK_SILO_QUERY(json["sequenceName"].is_string(), action_name + " action: the field sequenceName, if present, must be of type string")
+      sequence_name = json["sequenceName"].as_string();
+   }
+   CHECK_SILO_QUERY(
+      (std::is_same_v<SymbolType, Nucleotide>) || sequence_name.has_value(), action_name + " action must contain the field sequenceName of type string (a gene)"
+   )
+   const std::string entry_form = "{\"name\": string, \"filterExpression\": filter expression}";
+   std::vector<typename ConsensusAction::Group> groups;
+   if (json.contains("groups")) {
+      CHECK_SILO_QUERY(json["groups"].is_array(), action_name + " action: the field groups, if present, must be an array of objects " + entry_form)
+      const size_t n_groups = json["groups"].items().size();
+      CHECK_SILO_QUERY(
+         n_groups <= ConsensusAction::MAX_GROUPS,
+         action_name + " action: the field groups holds " + std::to_string(n_groups) + " groups, more than the limit of " + std::to_string(ConsensusAction::MAX_GROUPS)
+      )
+      CHECK_SILO_QUERY(n_groups >= 1, action_name + " action: the field groups, if present, must hold at least one group")
+      std::set<std::string> names;
+      for (const auto& element : json["groups"].items()) {
+         CHECK_SILO_QUERY(element.is_object(), action_name + " action: every entry of groups must be an object " + entry_form)
+         CHECK_SILO_QUERY(
+            element.contains("name") && element["name"].is_string(), action_name + " action: every entry of groups must contain the field name of type string"
+         )
+         const std::string group_name = element["name"].as_string();
+         CHECK_SILO_QUERY(names.insert(group_name).second, action_name + " action: the name '" + group_name + "' occurs more than once in groups")
+         const std::string owner = action_name + " action: the field filterExpression of the group '" + group_name + "'";
+         CHECK_SILO_QUERY(element.contains("filterExpression") && element["filterExpression"].is_object(), owner + " must be of type object (a filter expression)")
+         try {
+            groups.push_back({group_name, filter_expressions::parseExpression(element["filterExpression"])});
+         } catch (const QueryParseException& error) {
+            throw QueryParseException(owner + " is not a valid filter expression: " + error.what());
+         }
+      }
+   } else {
+      groups.push_back({std::nullopt, nullptr});  // the query's filter alone
+   }
+   double threshold = ConsensusAction::DEFAULT_THRESHOLD;
+   if (json.contains("threshold")) {
+      CHECK_SILO_QUERY(
+         json["threshold"].is_number() && json["threshold"].as_double() > 0 && json["threshold"].as_double() <= 1,
+         action_name + " action: the field threshold, if present, must be a number in (0, 1]"
+      )
+      threshold = json["threshold"].as_double();
+   }
+   uint32_t min_depth = ConsensusAction::DEFAULT_MIN_DEPTH;
+   if (json.contains("minDepth")) {
+      CHECK_SILO_QUERY(
+         json["minDepth"].is_number_unsigned() && json["minDepth"].as_int64() >= 1 && json["minDepth"].as_int64() <= UINT32_MAX,
+         action_name + " action: the field minDepth, if present, must be an integer from 1 to " + std::to_string(UINT32_MAX)
+      )
+      min_depth = json["minDepth"].as_uint32();
+   }
+   return std::make_unique<ConsensusAction>(std::move(sequence_name), std::move(groups), threshold, min_depth);
+}
+
+template std::unique_ptr<Action> parseConsensus<Nucleotide>(const json::Value& json);
+template std::unique_ptr<Action> parseConsensus<AminoAcid>(const json::Value& json);
 
 }  // namespace silo::query_engine::actions

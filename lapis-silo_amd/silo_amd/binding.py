@@ -115,6 +115,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_distance_pack", "silo_gpu_distance_pairs", "silo_gpu_distance_within", "silo_gpu_adjacency_components",
     "silo_gpu_distance_weights", "silo_gpu_spanning_forest", "silo_gpu_distance_listed_pairs",
     "silo_gpu_distance_cross", "silo_gpu_nearest_columns",
+    "silo_gpu_consensus_call",
     "silo_gpu_query_distances", "silo_gpu_nearest_rows", "silo_gpu_bitset_from_distances",
 ]
 
@@ -196,6 +197,7 @@ def load_library():
     lib.silo_gpu_distance_cross.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32,
                                             ctypes.c_uint32, vp, vp]
     lib.silo_gpu_nearest_columns.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_consensus_call.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_double, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_query_distances.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_nearest_rows.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_bitset_from_distances.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
@@ -761,6 +763,44 @@ def nearest_columns(cells, n_rows, n_columns, k, fill=None, guard_words=0, strea
         return device_read(lists, np.uint32, list_words, stream), device_read(counts, np.uint32, count_words, stream)
     finally:
         for ptr in (cells_dev, lists, counts):
+            device_free(ptr)
+
+
+MAX_CONSENSUS_TABLES = 64      # SILO_GPU_MAX_CONSENSUS_TABLES: the count tables (groups) of one silo_gpu_consensus_call
+CONSENSUS_THREADS = 256        # SILO_GPU_CONSENSUS_THREADS: positions of one table that a block of K15 owns
+CONSENSUS_SUMMARY_WORDS = 4    # per table: ambiguous, low-coverage and deleted positions, differences from the reference
+
+
+def consensus_call(alphabet_id, counts, reference_index, threshold, min_depth, fill=None, guard_bytes=0, calls=1, null=(), stream=None):
+    """silo_gpu_consensus_call (K15) over host counts uint32 [n_tables][n_positions][n_symbols] and reference_index uint8
+    [n_positions]: (chars uint8 [n_tables * n_positions + guard_bytes], summary uint32 [n_tables * 4 + guard_bytes / 4], the status
+    of the last call).  Both outputs are filled with the byte `fill` before the first of `calls` launches, so a test can see what
+    is written, that nothing behind it is, and that a second call adds nothing.  A status other than 0 is returned, not raised:
+    the refusals leave the outputs as they were.  null: which of "counts", "reference", "chars", "summary" the call gets as NULL."""
+    lib = load_library()
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    n_tables, n_positions = counts.shape[:2]
+    reference_index = np.ascontiguousarray(reference_index, dtype=np.uint8)
+    char_bytes = n_tables * n_positions + int(guard_bytes)
+    summary_words = n_tables * CONSENSUS_SUMMARY_WORDS + int(guard_bytes) // 4
+    counts_dev = device_malloc(counts.nbytes)
+    reference_dev = device_malloc(reference_index.nbytes)
+    chars = device_malloc(char_bytes, fill, stream)
+    summary = device_malloc(summary_words * 4, fill, stream)
+    try:
+        if counts.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(counts_dev, _ptr(counts), counts.nbytes, stream))
+        if reference_index.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(reference_dev, _ptr(reference_index), reference_index.nbytes, stream))
+        status = 0
+        for _ in range(calls):
+            status = lib.silo_gpu_consensus_call(
+                _abi_alphabet(alphabet_id), None if "counts" in null else counts_dev, n_tables, n_positions, None if "reference" in null else reference_dev,
+                threshold, min_depth, None if "chars" in null else chars, None if "summary" in null else summary, stream)
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(chars, np.uint8, char_bytes, stream), device_read(summary, np.uint32, summary_words, stream), status
+    finally:
+        for ptr in (counts_dev, reference_dev, chars, summary):
             device_free(ptr)
 
 
