@@ -767,6 +767,52 @@ int silo_gpu_consensus_call(
    uint32_t min_depth, char* out_chars_dev, uint32_t* out_summary_dev, void* stream
 );
 
+/* ---- K16: the symbols of every row at listed positions, and their tuple ids (Haplotypes / AminoAcidHaplotypes) ---
+ * silo_gpu_position_symbols reads the symbol of EVERY row at n_positions <= SILO_GPU_MAX_HAPLOTYPE_POSITIONS positions (`positions`
+ * in HOST memory, 0-based; the same position may be listed twice) off the store's own layout and WRITES every byte of
+ *     out_symbols_dev[c * row_words * 64 + r] = the symbol id of row r at positions[c]
+ * in the store's own enumeration — the one silo_gpu_store_plane takes: valid symbols, the missing symbol, ambiguity codes.  Rows at
+ * or past sequence_count get SILO_GPU_SYMBOL_NONE.  So does a real row that nothing stored claims at a position without a derived
+ * symbol (an imported store may hold such rows); those cells are counted into *out_unresolved_dev, which the entry clears itself
+ * with a memset on `stream` ahead of its launches: the caller clears nothing, and a second call gives the same bytes.  Work follows
+ * what the store holds, one pass per kind of stored thing (the decomposition of K7 and K11): the plane pass (grid = rows / 256 x
+ * n_positions, a thread per row, a wave per row word: wave-uniform 8-byte plane loads, 64 consecutive bytes stored; codes and
+ * one-hot rows, the derived symbol of a derived position, extra planes), then on the same stream the override passes with plain
+ * byte stores — the escape keys of the listed positions' ranges of the position-major list, the runs of the missing symbol (a
+ * thread per run, a binary search of the sorted listed positions held in the kernel arguments), the sparse keys of the listed
+ * positions' ranges — and the count of the bytes still SILO_GPU_SYMBOL_NONE among real rows (a ballot per wave, one integer add per
+ * block that found any).  A cell holds one symbol and finalize stores it in one place, so no two threads write the same byte.
+ * No index is taken from a key or a run without a check against the listed positions and sequence_count; no spin, no float.  No
+ * table is uploaded (everything per position fits the kernel arguments): all launches go on `stream`, the entry returns without
+ * waiting and never synchronises.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer, a store that is
+ * not finalized, a seqstore_id or a position out of range, n_positions == 0 or above the maximum.
+ * silo_gpu_haplotype_ids takes such columns (no store, like K10 and silo_gpu_nearest_rows) and WRITES ceil(n_positions /
+ * SILO_GPU_HAPLOTYPE_POSITIONS_PER_COLUMN) id columns of row_words * 64 words (out_ids_dev: their device addresses, an array in
+ * HOST memory):
+ *     out_ids_dev[j][r] = sum_{i < m} symbols[6 j + i][r] * n_symbols^(m - 1 - i),     m = min(6, n_positions - 6 j)
+ * the first listed position the most significant digit — columns for silo_gpu_group_count / silo_gpu_group_count_hashed with the
+ * cardinalities n_symbols^m.  A row with a byte at or past n_symbols (SILO_GPU_SYMBOL_NONE, or whatever no symbol id can be) and
+ * every row at or past sequence_count gets 0 in ALL columns: an id never leaves its column's tuple space.  Where out_rows_dev is
+ * not NULL every one of its row_words words is written:
+ *     bit r = r < sequence_count && filter bit r (filter_dev NULL: every row) && every listed symbol of r is in complete_symbols
+ * (bit s of the mask: symbol s counts as complete; a byte of 32 or more is in the mask only where the mask is all ones), so the
+ * bits at or past sequence_count are 0 whatever the filter holds there, and with complete_symbols all ones the word is the filter
+ * masked to real rows.  One launch on `stream` (a thread per row, a wave's ballot is the word; no atomics), returns without
+ * waiting.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL symbol buffer, column array or column,
+ * n_symbols == 0 or above 32, n_positions == 0 or above the maximum, row_words == 0 or sequence_count > row_words * 64. */
+#define SILO_GPU_MAX_HAPLOTYPE_POSITIONS 12
+#define SILO_GPU_HAPLOTYPE_POSITIONS_PER_COLUMN 6 /* 16^6 = 2^24, 25^6 < 2^28: an id column is a uint32 */
+int silo_gpu_position_symbols(
+   const silo_gpu_store* store, uint32_t seqstore_id, const uint32_t* positions /* host, 0-based */, uint32_t n_positions,
+   uint8_t* out_symbols_dev /* [n_positions][row_words * 64] */, uint32_t* out_unresolved_dev /* 1 word */, void* stream
+);
+int silo_gpu_haplotype_ids(
+   const uint8_t* symbols_dev, uint32_t n_positions, uint32_t row_words, uint32_t sequence_count, uint32_t n_symbols,
+   uint32_t complete_symbols /* bit s: symbol s counts as complete */, const uint64_t* filter_dev /* NULL = all rows */,
+   uint32_t* const* out_ids_dev /* ceil(n_positions / 6) columns of row_words * 64 */, uint64_t* out_rows_dev /* row_words words, or NULL */,
+   void* stream
+);
+
 /* ---- K11: the rows of the whole store nearest to a query (NearestNeighbours) --------------------------
  * silo_gpu_query_distances compares one query — query_chars, `positions` characters in HOST memory — with EVERY row of a sequence
  * store, read off the store's own layout (identity / code planes with escape keys, one-hot rows with a derived symbol, runs of the

@@ -843,6 +843,8 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"Consensus", parseConsensus<Nucleotide>},
    {"AminoAcidConsensus", parseConsensus<AminoAcid>},
    {"NearestNeighbours", parseNearestNeighbours},
+   {"Haplotypes", parseHaplotypes<Nucleotide>},
+   {"AminoAcidHaplotypes", parseHaplotypes<AminoAcid>},
 };
 
 }  // namespace

@@ -722,6 +722,43 @@ class Aggregated : public Action {
    [[nodiscard]] bool countsOnly() const override { return group_by_fields.empty(); }
 };
 
+/// Haplotypes / AminoAcidHaplotypes: which combinations of symbols occur together at up to MAX_POSITIONS listed positions of one
+/// sequence store among the rows of the filter, and how often — Aggregated's group-by with sequence positions as columns.  Per
+/// partition the symbol of every row at the listed positions (K16, silo_gpu_position_symbols), packed six positions to a uint32
+/// id column (silo_gpu_haplotype_ids) behind the dictionary ids of the groupByFields, counted and merged over partitions by the
+/// helper Aggregated uses (metadata_actions.cpp).  The symbols are the store's full alphabet: the missing symbol and ambiguity
+/// codes are haplotype characters like any other, unless excludeIncomplete leaves out the rows that hold one at a listed position.
+/// One row per occurring tuple: the groupByFields, haplotype (the characters in request order), count, proportion (count over the
+/// sum of all counts of the response before limit and offset).  No counterpart in the reference.
+template <typename SymbolType>
+class Haplotypes : public Action {
+  public:
+   static constexpr uint32_t MAX_POSITIONS = SILO_GPU_MAX_HAPLOTYPE_POSITIONS;
+   static constexpr uint32_t POSITIONS_PER_COLUMN = SILO_GPU_HAPLOTYPE_POSITIONS_PER_COLUMN;
+   static constexpr uint32_t MAX_ID_COLUMNS = (MAX_POSITIONS + POSITIONS_PER_COLUMN - 1) / POSITIONS_PER_COLUMN;
+   static constexpr uint32_t MAX_FIELDS = SILO_GPU_MAX_GROUP_COLUMNS - MAX_ID_COLUMNS;
+   static std::string actionName() { return std::is_same_v<SymbolType, Nucleotide> ? "Haplotypes" : "AminoAcidHaplotypes"; }
+
+   Haplotypes(std::optional<std::string> sequence_name, std::vector<uint32_t> positions, std::vector<std::string> group_by_fields, bool exclude_incomplete)
+       : sequence_name(std::move(sequence_name)), positions(std::move(positions)), group_by_fields(std::move(group_by_fields)),
+         exclude_incomplete(exclude_incomplete) {}
+
+  private:
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   std::vector<uint32_t> positions;           // 1-based, distinct, in request order
+   std::vector<std::string> group_by_fields;
+   bool exclude_incomplete;
+
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+};
+/// The parser of Haplotypes / AminoAcidHaplotypes (metadata_actions.cpp).
+template <typename SymbolType>
+std::unique_ptr<Action> parseHaplotypes(const json::Value& json);
+/// Does a tuple space of these cardinalities (a column without values counts as 1) hold fewer than 2^64 - 1 tuples — the empty key
+/// of the hash table of silo_gpu_group_count_hashed?  Overflow-checked (metadata_actions.cpp).
+bool tupleSpaceFits(const std::vector<uint32_t>& cardinalities);
+
 /// details.cpp: the metadata of the selected rows.  The filter runs on the device; the rows are read from the host
 /// copies of the columns.
 class Details : public Action {

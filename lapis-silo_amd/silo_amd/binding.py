@@ -117,6 +117,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_distance_cross", "silo_gpu_nearest_columns",
     "silo_gpu_consensus_call",
     "silo_gpu_query_distances", "silo_gpu_nearest_rows", "silo_gpu_bitset_from_distances",
+    "silo_gpu_position_symbols", "silo_gpu_haplotype_ids",
 ]
 
 _lib = None
@@ -201,6 +202,9 @@ def load_library():
     lib.silo_gpu_query_distances.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_nearest_rows.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_bitset_from_distances.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_position_symbols.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_haplotype_ids.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp,
+                                           ctypes.POINTER(vp), vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -804,6 +808,50 @@ def consensus_call(alphabet_id, counts, reference_index, threshold, min_depth, f
             device_free(ptr)
 
 
+MAX_HAPLOTYPE_POSITIONS = 12          # SILO_GPU_MAX_HAPLOTYPE_POSITIONS: the positions of one silo_gpu_position_symbols / silo_gpu_haplotype_ids
+HAPLOTYPE_POSITIONS_PER_COLUMN = 6    # SILO_GPU_HAPLOTYPE_POSITIONS_PER_COLUMN: 16^6 = 2^24, 25^6 < 2^28: an id column is a uint32
+ALL_SYMBOLS_COMPLETE = 0xFFFFFFFF     # complete_symbols of silo_gpu_haplotype_ids: no row is left out
+
+
+def haplotype_ids(symbols, sequence_count, n_symbols, complete_symbols=ALL_SYMBOLS_COMPLETE, filter_words=None, want_rows=True, fill=None,
+                  guard_words=0, null=(), n_positions=None, row_words=None, stream=None):
+    """silo_gpu_haplotype_ids (K16) over a host byte matrix uint8 [n_positions][row_words * 64] as silo_gpu_position_symbols leaves
+    it; filter_words: uint64 [row_words], None = a null pointer (all rows).  Returns (ids uint32 [columns][row_words * 64 +
+    guard_words], rows uint64 [row_words + guard_words] or None, status).  Every output is filled with the byte `fill` before the
+    launch, so a test can see what is written and that nothing behind it is.  A status other than 0 is returned, not raised: the
+    refusals leave the outputs as they were.  null: which of "symbols", "ids", "column" (the last id column) the call gets as
+    NULL.  n_positions / row_words: what the call is told instead of the matrix's shape."""
+    lib = load_library()
+    symbols = np.ascontiguousarray(symbols, dtype=np.uint8)
+    k, rows = symbols.shape
+    words = rows // 64
+    n_columns = (k + HAPLOTYPE_POSITIONS_PER_COLUMN - 1) // HAPLOTYPE_POSITIONS_PER_COLUMN
+    column_words = rows + int(guard_words)
+    symbols_dev = device_malloc(symbols.nbytes)
+    columns = [device_malloc(column_words * 4, fill, stream) for _ in range(n_columns)]
+    rows_dev = device_malloc((words + int(guard_words)) * 8, fill, stream) if want_rows else None
+    filter_dev = None
+    try:
+        _check(lib.silo_gpu_memcpy_h2d(symbols_dev, _ptr(symbols), symbols.nbytes, stream))
+        if filter_words is not None:
+            filter_words = np.ascontiguousarray(filter_words, dtype=np.uint64)
+            filter_dev = device_malloc(filter_words.nbytes)
+            _check(lib.silo_gpu_memcpy_h2d(filter_dev, _ptr(filter_words), filter_words.nbytes, stream))
+        pointers = (ctypes.c_void_p * max(1, n_columns))(*[c.value for c in columns])
+        if "column" in null:
+            pointers[n_columns - 1] = None
+        status = lib.silo_gpu_haplotype_ids(
+            None if "symbols" in null else symbols_dev, k if n_positions is None else n_positions, words if row_words is None else row_words,
+            sequence_count, n_symbols, complete_symbols, filter_dev, None if "ids" in null else pointers, rows_dev, stream)
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        ids = np.stack([device_read(c, np.uint32, column_words, stream) for c in columns])
+        return ids, (device_read(rows_dev, np.uint64, words + int(guard_words), stream) if want_rows else None), status
+    finally:
+        for ptr in [symbols_dev, rows_dev, filter_dev, *columns]:
+            if ptr is not None:
+                device_free(ptr)
+
+
 MAX_NEAREST_ROWS = 1024              # SILO_GPU_MAX_NEAREST_ROWS
 NEAREST_ROWS_SCRATCH_BYTES = 32768   # SILO_GPU_NEAREST_ROWS_SCRATCH_BYTES
 QUERY_DISTANCE_COUNTER_PLANES = 12   # SILO_GPU_QUERY_DISTANCE_COUNTER_PLANES: a vertical counter of K11 is unpacked after 2^12 - 1 adds
@@ -1328,6 +1376,39 @@ class GpuStore:
                 self.free(scratch)
             if out_ptr is None and table is not None:
                 self.free(table)
+
+    def position_symbols(self, seqstore_id, positions, fill=None, guard_bytes=0, calls=1, null=(), n_positions=None, stream=None):
+        """silo_gpu_position_symbols (K16).  positions: 0-based, any order, repeats allowed.  Returns (symbols uint8
+        [len(positions) * row_words * 64 + guard_bytes], unresolved uint32 [1 + guard_bytes / 4], the status of the last of `calls`
+        calls).  Both outputs are filled with the byte `fill` before the first call, so a test can see that every byte is written,
+        that nothing behind them is, and that a second call gives the same bytes.  A status other than 0 is returned, not raised:
+        the refusals leave the outputs as they were.  null: which of "store", "positions", "symbols", "unresolved" the call gets
+        as NULL.  n_positions: what the call is told instead of len(positions)."""
+        positions = np.ascontiguousarray(positions, dtype=np.uint32)
+        symbol_bytes = len(positions) * self.row_words * 64 + int(guard_bytes)
+        unresolved_words = 1 + int(guard_bytes) // 4
+        symbols = self.malloc(max(8, symbol_bytes))
+        unresolved = self.malloc(unresolved_words * 4)
+        try:
+            if fill is not None:
+                self.memset(symbols, fill, max(8, symbol_bytes), stream)
+                self.memset(unresolved, fill, unresolved_words * 4, stream)
+            status = 0
+            for _ in range(calls):
+                status = self.lib.silo_gpu_position_symbols(
+                    None if "store" in null else self.handle, seqstore_id, None if "positions" in null else _ptr(positions),
+                    len(positions) if n_positions is None else n_positions, None if "symbols" in null else symbols,
+                    None if "unresolved" in null else unresolved, stream)
+            self.synchronize(stream)
+            return self.read(symbols, np.uint8, symbol_bytes, stream), self.read(unresolved, np.uint32, unresolved_words, stream), status
+        finally:
+            self.free(symbols)
+            self.free(unresolved)
+
+    def position_symbols_call(self, seqstore_id, positions, symbols_ptr, unresolved_ptr, stream=None):
+        """silo_gpu_position_symbols (K16) on the caller's device buffers, not waited for."""
+        positions = np.ascontiguousarray(positions, dtype=np.uint32)
+        _check(self.lib.silo_gpu_position_symbols(self.handle, seqstore_id, _ptr(positions), len(positions), symbols_ptr, unresolved_ptr, stream))
 
     # ---- metadata columns (K5 / K6) and FastaAligned ---------------------------------------------
     VALUE_TYPES = {np.dtype(np.int32): 0, np.dtype(np.uint32): 1, np.dtype(np.float64): 2}
