@@ -312,11 +312,49 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
    const auto endAt = [&](uint32_t j) { return ends[2u * j + 1u] - ends[2u * j]; };
    uint32_t without_symbol = 0;  // rows of the filter that have no valid symbol at p
    uint32_t in_end_run = 0;      // rows of the filter inside a leading or trailing run of the gap symbol at p
-   if (range.code_map != nullptr) {  // (uniform)
+   // What the thread needs of its own position besides the prefix sums depends on none of them: it is loaded here, ahead of the
+   // sweep, so that these latencies pass beside the sweep's and not one after another behind the barrier (a finish launch is
+   // 30 blocks: nothing else hides them).  Same guards as where the values are used.
+   const bool has_map = range.code_map != nullptr;  // (uniform)
+   const uint32_t filter_rows = has_map ? args.counters[q * SPARSE_COUNTER_STRIDE + 2] : 0u;  // |F|
+   uint32_t map_flags = 0, map_slot = 0, covered_here = 0;
+   if (p < n) {
+      if (has_map) {
+         const uint8_t* map = range.code_map + static_cast<size_t>(range.pos_begin + p) * CODE_MAP_STRIDE;
+         map_flags = map[0];
+         map_slot = map[IMPLICIT_SLOT];
+      }
+      covered_here = with_ends ? range.position_covered[range.pos_begin + p] : 0u;
+   }
+   // SELECT: the position's cells of the private table and the index of its reference symbol too.  The 22 cells of an amino-acid
+   // position held across the sweep cost a wave per SIMD (66 VGPRs against 50): there the cells are loaded where they are used.
+   constexpr bool CELLS_AHEAD = SELECT != 0 && SELECT <= 8;
+   uint32_t held[SELECT != 0 ? SELECT : 1] = {};
+   uint32_t reference = 0;
+   const auto loadCells = [&]() {
+      const uint32_t* __restrict__ cell = counts + static_cast<size_t>(p) * SELECT;
+#pragma unroll
+      for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
+         held[symbol] = cell[symbol];
+      }
+   };
+   if constexpr (SELECT != 0) {
+      if (p < n) {
+         if constexpr (CELLS_AHEAD) {
+            loadCells();
+         }
+         reference = args.sinks[q].reference_index[range.table_offset + p];
+      }
+   }
+   if (has_map) {  // (uniform)
       uint32_t before[2] = {0, 0};
       const uint4* __restrict__ diff16 = reinterpret_cast<const uint4*>(diff);
       const uint4* __restrict__ ends16 = reinterpret_cast<const uint4*>(ends);
-      const uint32_t own[2] = {p < n ? diffAt(p) : 0u, with_ends && p < n ? endAt(p) : 0u};  // (in flight beside the sweep's first loads)
+      uint32_t own[2] = {0u, 0u};
+      if (p < n) {  // (one guard for both, so that the two loads leave together and are waited for once)
+         own[0] = diffAt(p);
+         own[1] = with_ends ? endAt(p) : 0u;
+      }
       const uint32_t n16 = EVENTS ? first_position / 2u : first_position / 4u;  // (exact: first_position is a multiple of 1024)
       for (uint32_t base = 0; base < n16; base += DERIVED_THREADS * PREFIX_IN_FLIGHT) {  // (uniform)
          uint4 d[PREFIX_IN_FLIGHT];
@@ -352,13 +390,16 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
       if (!EVENTS && p < n) {
          without_symbol += ambiguous[p];
       }
-      in_end_run += args.counters[q * SPARSE_COUNTER_STRIDE + 2];
+      in_end_run += filter_rows;
    }
+   // (the bytes stay as loaded until here: left alone, the compiler tests them right behind their loads, which waits for each
+   // of them ahead of the sweep instead of beside it)
+   asm volatile("" : "+v"(map_flags), "+v"(map_slot), "+v"(covered_here));
    if constexpr (SELECT == 0) {
       if (p >= n) {
          return;
       }
-      if (!with_ends || range.position_covered[range.pos_begin + p] == 0) {  // only the covered positions take their gap rows from the end runs: everywhere else the row was read
+      if (covered_here == 0) {  // only the covered positions take their gap rows from the end runs: everywhere else the row was read
          in_end_run = 0;
       }
       uint32_t* __restrict__ out = range.caller_counts[q] + static_cast<size_t>(p) * n_scan;
@@ -371,42 +412,37 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
             out[symbol] += count;  // scans of one table are ordered on a stream: no atomic needed
          }
       }
-      if (range.code_map != nullptr) {
-         const uint8_t* map = range.code_map + static_cast<size_t>(range.pos_begin + p) * CODE_MAP_STRIDE;
-         if ((map[0] & LAYOUT_IMPLICIT) != 0) {
-            const uint32_t derived = args.counters[q * SPARSE_COUNTER_STRIDE + 2] - without_symbol - others;
-            if (derived != 0) {
-               out[map[IMPLICIT_SLOT]] += derived;
-            }
+      if ((map_flags & LAYOUT_IMPLICIT) != 0) {  // (0 without a code map)
+         const uint32_t derived = filter_rows - without_symbol - others;
+         if (derived != 0) {
+            out[map_slot] += derived;
          }
       }
    } else {
       const SelectSink& sink = args.sinks[q];
       uint32_t selected = 0;  // bit s: symbol s passes
       if (p < n) {
-         if (!with_ends || range.position_covered[range.pos_begin + p] == 0) {
+         if (covered_here == 0) {
             in_end_run = 0;
          }
-         const uint32_t* __restrict__ cell = counts + static_cast<size_t>(p) * SELECT;
+         if constexpr (!CELLS_AHEAD) {
+            loadCells();
+         }
          uint32_t count[SELECT];
          uint32_t others = 0;
 #pragma unroll
          for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
-            count[symbol] = cell[symbol] + (symbol == range.end_symbol ? in_end_run : 0u);
+            count[symbol] = held[symbol] + (symbol == range.end_symbol ? in_end_run : 0u);
             others += count[symbol];
          }
          uint32_t covered = others;  // the sum of the position's final cells (uint32 wrap-around as in K4)
-         if (range.code_map != nullptr) {
-            const uint8_t* map = range.code_map + static_cast<size_t>(range.pos_begin + p) * CODE_MAP_STRIDE;
-            if ((map[0] & LAYOUT_IMPLICIT) != 0) {
-               const uint32_t derived = args.counters[q * SPARSE_COUNTER_STRIDE + 2] - without_symbol - others;
-               const uint32_t slot = map[IMPLICIT_SLOT];
+         if ((map_flags & LAYOUT_IMPLICIT) != 0) {  // (0 without a code map)
+            const uint32_t derived = filter_rows - without_symbol - others;
 #pragma unroll
-               for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
-                  count[symbol] += symbol == slot ? derived : 0u;
-               }
-               covered += derived;
+            for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
+               count[symbol] += symbol == map_slot ? derived : 0u;
             }
+            covered += derived;
          }
          uint32_t* __restrict__ out = range.caller_counts[q] + static_cast<size_t>(p) * SELECT;
 #pragma unroll
@@ -418,7 +454,6 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
          if (covered != 0) {
             const uint32_t threshold_count =
                sink.min_proportion == 0 ? 0u : static_cast<uint32_t>(ceil(static_cast<double>(covered) * sink.min_proportion) - 1);
-            const uint32_t reference = sink.reference_index[position];
 #pragma unroll
             for (uint32_t symbol = 0; symbol < SELECT; ++symbol) {
                if (symbol != reference && count[symbol] > threshold_count) {
@@ -439,8 +474,16 @@ __global__ __launch_bounds__(DERIVED_THREADS) void k_finish_scan(const DerivedAr
             }
          }
       }
-      __threadfence_system();  // this thread's rows are in host memory ...
-      __syncthreads();         // ... and so are those of the whole block, before its ticket is taken
+      // Only a thread that stored a row has anything to make visible to the host, so only it pays for a system-scope fence:
+      //   - a row's stores are fenced by their writer, before that writer reaches the barrier;
+      //   - thread 0 takes the block's ticket after the barrier, so after every fence of the block;
+      //   - the holder of the last ticket has seen every other block's ticket, each taken after that block's fences, and
+      //     publishes the header with a system-scope release.
+      // The host reads rows only after it has read the header.  A block without a selected row takes its ticket with no fence at all.
+      if (selected != 0) {
+         __threadfence_system();
+      }
+      __syncthreads();
       if (threadIdx.x == 0) {
          if (atomicAdd(&sink.cursor_and_ticket[1], 1u) == sink.total_blocks - 1) {  // the last block of the scan's finish launches for this filter
             const uint32_t n_selected = atomicExch(&sink.cursor_and_ticket[0], 0u);

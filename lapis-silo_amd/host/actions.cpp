@@ -8,6 +8,7 @@
 #include <string_view>
 #include <tuple>
 
+#include "mutation_rows_json.h"
 #include "query_engine.h"
 
 namespace silo::query_engine::actions {
@@ -606,13 +607,6 @@ std::vector<typename Mutations<SymbolType>::SelectedRow> Mutations<SymbolType>::
 }
 
 template <typename SymbolType>
-std::string Mutations<SymbolType>::mutationName(const SelectedRow& row) const {  // "<reference symbol><1-based position><symbol>", mutations.cpp:213-216
-   const char from = SymbolType::symbolToChar(row.sequence_store->reference_sequence.at(row.position));
-   const char to = SymbolType::symbolToChar(SymbolType::VALID_MUTATION_SYMBOLS.at(row.symbol_index));
-   return from + std::to_string(row.position + 1) + to;
-}
-
-template <typename SymbolType>
 QueryResult Mutations<SymbolType>::collect(const Database& database, PendingScans& scans) const {
    std::vector<QueryResultEntry> result_rows;
    const std::vector<SelectedRow> selected = collectSelected(database, scans);
@@ -632,78 +626,95 @@ QueryResult Mutations<SymbolType>::finish(const Database& database, Action::Pend
 }
 
 template <typename SymbolType>
+std::pair<const silo_gpu_mutation_row*, size_t> Mutations<SymbolType>::deliveredRows(
+   const Database& database, PendingScans& scans, std::vector<silo_gpu_mutation_row>& from_table
+) const {
+   // what collectSelected waits for, left as it arrives: rows at their position in the query's table, in no particular order
+   if (!scans.fetch && !scans.row_slot) {
+      return {nullptr, 0};
+   }
+   const uint32_t* table = nullptr;
+   const silo_gpu_mutation_row* rows = nullptr;
+   uint32_t n_selected = 0;
+   if (scans.row_slot) {
+      std::tie(rows, n_selected) = scans.row_slot.wait();
+   } else {
+      table = static_cast<const uint32_t*>(scans.fetch.wait());
+   }
+   Trace::mark("counts_on_host");
+   if (scans.check_fetch) {
+      checkSameQuery(database, static_cast<const uint32_t*>(scans.check_fetch.wait()), scans.fingerprint);
+   }
+   HostFetch whole_table;
+   if (table == nullptr && n_selected > scans.row_capacity) {  // more rows than the list holds: take the whole table after all
+      whole_table = HostFetch(scans.device_table.get(), scans.table_bytes, queryStream());
+      table = static_cast<const uint32_t*>(whole_table.wait());
+   }
+   if (table == nullptr) {
+      return {rows, n_selected};
+   }
+   // the row selection of mutations.cpp:184-232 on the host (as in collectSelected), every requested store once
+   const MutationTableLayout& layout = database.getMutationTableLayout<SymbolType>();
+   constexpr uint32_t n_symbols = SymbolType::VALID_MUTATION_SYMBOLS.size();
+   for (auto name = scans.sequence_names.begin(); name != scans.sequence_names.end(); ++name) {
+      if (std::find(scans.sequence_names.begin(), name, *name) != name) {
+         continue;
+      }
+      const auto& reference = database.getSequenceStores<SymbolType>().at(*name).reference_sequence;
+      const uint32_t offset = layout.position_offset.at(*name);
+      for (size_t position = 0; position < reference.size(); ++position) {
+         const uint32_t* cell = table + (offset + position) * n_symbols;
+         uint32_t covered = 0;
+         for (size_t k = 0; k < n_symbols; ++k) {
+            covered += cell[k];
+         }
+         if (covered == 0) {
+            continue;
+         }
+         const uint32_t must_exceed = min_proportion == 0 ? 0 : static_cast<uint32_t>(std::ceil(static_cast<double>(covered) * min_proportion) - 1);
+         for (size_t k = 0; k < n_symbols; ++k) {
+            if (SymbolType::VALID_MUTATION_SYMBOLS[k] != reference[position] && cell[k] > must_exceed) {
+               from_table.push_back({offset + static_cast<uint32_t>(position), static_cast<uint32_t>(k), cell[k], covered});
+            }
+         }
+      }
+   }
+   return {from_table.data(), from_table.size()};
+}
+
+template <typename SymbolType>
 std::string Mutations<SymbolType>::finishJson(const Database& database, Action::Pending& pending) const {
-   // The bytes toJsonText(finish(...)) would give, written from the selected rows themselves.  Ordering: the comparator, the
-   // index array and the std:: algorithms of Action::applySort over the same values (a field of a row is a string, an
-   // int32 or a double there too), so ties fall the same way.
-   const std::vector<SelectedRow> selected = collectSelected(database, dynamic_cast<PendingScans&>(pending));
-   const size_t n_rows = selected.size();
-   std::vector<uint32_t> order(n_rows);
-   for (size_t row = 0; row < n_rows; ++row) {
-      order[row] = static_cast<uint32_t>(row);
+   // The bytes toJsonText(finish(...)) would give, written from the delivered rows themselves by mutation_rows_json.h: no
+   // entry, no string and no second copy of a row is made on the way.
+   namespace text = mutation_rows;
+   auto& scans = dynamic_cast<PendingScans&>(pending);
+   std::vector<silo_gpu_mutation_row> from_table;
+   const auto [rows, n_rows] = deliveredRows(database, scans, from_table);
+   const MutationTableLayout& layout = database.getMutationTableLayout<SymbolType>();
+   std::vector<text::StoreText> stores;
+   stores.reserve(scans.sequence_names.size());
+   for (const auto& sequence_name : scans.sequence_names) {
+      const SequenceStore<SymbolType>& store = database.getSequenceStores<SymbolType>().at(sequence_name);
+      stores.push_back(
+         {layout.position_offset.at(sequence_name), static_cast<uint32_t>(store.reference_characters.size()), store.reference_characters.data(),
+          store.sequence_name_fragment}
+      );
    }
-   std::vector<std::string> names;  // only where a row's name is needed before the rows are written: ordered by "mutation"
-   const size_t first = std::min<size_t>(offset.value_or(0), n_rows);
-   const size_t count = limit.has_value() ? std::min<size_t>(*limit, n_rows - first) : n_rows - first;
-   if (!order_by_fields.empty() && offset.value_or(0) < n_rows) {
-      enum class Key { MUTATION, PROPORTION, COUNT };
-      std::vector<std::pair<Key, bool>> keys;
-      for (const OrderByField& field : order_by_fields) {
-         keys.emplace_back(field.name == MUTATION_FIELD_NAME ? Key::MUTATION : (field.name == PROPORTION_FIELD_NAME ? Key::PROPORTION : Key::COUNT), field.ascending);
-         if (keys.back().first == Key::MUTATION && names.empty()) {
-            names.reserve(n_rows);
-            for (const SelectedRow& row : selected) {
-               names.push_back(mutationName(row));
-            }
-         }
+   static const std::string symbol_chars = [] {
+      std::string chars;
+      for (const auto symbol : SymbolType::VALID_MUTATION_SYMBOLS) {
+         chars.push_back(SymbolType::symbolToChar(symbol));
       }
-      const auto proportion = [&](uint32_t row) { return static_cast<double>(selected[row].count) / static_cast<double>(selected[row].total); };
-      const auto before = [&](uint32_t left, uint32_t right) {
-         for (const auto& [key, ascending] : keys) {
-            if (key == Key::MUTATION) {
-               if (!(names[left] == names[right])) {
-                  return (names[left] < names[right]) == ascending;
-               }
-            } else if (key == Key::PROPORTION) {
-               const double a = proportion(left), b = proportion(right);
-               if (!(a == b)) {
-                  return (a < b) == ascending;
-               }
-            } else {
-               const auto a = static_cast<int32_t>(selected[left].count), b = static_cast<int32_t>(selected[right].count);
-               if (!(a == b)) {
-                  return (a < b) == ascending;
-               }
-            }
-         }
-         return false;
-      };
-      const size_t window_end = limit.has_value() ? std::min<size_t>(n_rows, static_cast<size_t>(*limit) + offset.value_or(0)) : n_rows;
-      if (window_end < n_rows) {
-         std::partial_sort(order.begin(), order.begin() + static_cast<std::ptrdiff_t>(window_end), order.end(), before);
-      } else {
-         std::sort(order.begin(), order.end(), before);
-      }
+      return chars;
+   }();
+   std::vector<text::OrderBy> order_by;
+   for (const OrderByField& field : order_by_fields) {
+      order_by.push_back(
+         {field.name == MUTATION_FIELD_NAME ? text::OrderKey::MUTATION : (field.name == PROPORTION_FIELD_NAME ? text::OrderKey::PROPORTION : text::OrderKey::COUNT),
+          field.ascending}
+      );
    }
-   std::string out;
-   out.reserve(32 + count * 112);
-   out += "{\"queryResult\":[";
-   char digits[16];
-   for (size_t k = 0; k < count; ++k) {
-      const uint32_t index = order[first + k];
-      const SelectedRow& row = selected[index];
-      // keys in the order of the reference's std::map: count < mutation < proportion < sequenceName
-      out += k == 0 ? "{\"count\":" : ",{\"count\":";
-      out.append(digits, std::to_chars(digits, digits + sizeof(digits), static_cast<int32_t>(row.count)).ptr);
-      out += ",\"mutation\":";
-      json::Value::appendString(out, names.empty() ? mutationName(row) : names[index]);
-      out += ",\"proportion\":";
-      json::Value::appendDouble(out, static_cast<double>(row.count) / static_cast<double>(row.total));
-      out += ",\"sequenceName\":";
-      json::Value::appendString(out, *row.sequence_name);
-      out.push_back('}');
-   }
-   out += "]}";
+   std::string out = text::mutationRowsJson(rows, n_rows, stores, symbol_chars, order_by, limit, offset);
    Trace::mark("rows_built");
    return out;
 }

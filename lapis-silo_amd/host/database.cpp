@@ -5,6 +5,7 @@
 #include <chrono>
 #include <sstream>
 
+#include "mutation_rows_json.h"
 #include "query_engine.h"
 
 namespace silo {
@@ -509,7 +510,7 @@ uint32_t Database::ownerOfPosition(size_t position, size_t length) const {
 void Database::setReferenceGenomes(const json::Value& reference_genomes) {  // reference_genomes.cpp
    nuc_sequences.clear();
    aa_sequences.clear();
-   const auto read = [](const json::Value& list, auto& target, auto char_to_symbol, const char* what) {
+   const auto read = [](const json::Value& list, auto& target, auto char_to_symbol, auto symbol_to_char, const char* what) {
       for (const auto& entry : list.items()) {
          const std::string& name = entry.at("name").as_string();
          const std::string& sequence = entry.at("sequence").as_string();
@@ -522,10 +523,15 @@ void Database::setReferenceGenomes(const json::Value& reference_genomes) {  // r
             }
             store.reference_sequence.push_back(*symbol);
          }
+         store.reference_characters.clear();
+         for (const auto symbol : store.reference_sequence) {
+            store.reference_characters.push_back(symbol_to_char(symbol));
+         }
+         store.sequence_name_fragment = query_engine::actions::mutation_rows::sequenceNameFragment(name);
       }
    };
-   read(reference_genomes.at("nucleotideSequences"), nuc_sequences, Nucleotide::charToSymbol, "nucleotide");
-   read(reference_genomes.at("genes"), aa_sequences, AminoAcid::charToSymbol, "amino acid");
+   read(reference_genomes.at("nucleotideSequences"), nuc_sequences, Nucleotide::charToSymbol, Nucleotide::symbolToChar, "nucleotide");
+   read(reference_genomes.at("genes"), aa_sequences, AminoAcid::charToSymbol, AminoAcid::symbolToChar, "amino acid");
 }
 
 DatabasePartition& Database::addPartition(uint32_t sequence_count) {

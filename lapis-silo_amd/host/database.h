@@ -209,6 +209,10 @@ template <typename SymbolType>
 class SequenceStore {
   public:
    std::vector<typename SymbolType::Symbol> reference_sequence;
+   /// For the response text of a Mutations query (mutation_rows_json.h), made once with the store: the reference symbols as
+   /// characters, and the end of every row of the store, ,"sequenceName":"<escaped name>"}
+   std::string reference_characters;
+   std::string sequence_name_fragment;
 };
 
 /// Layout of the count table of a Mutations query: the stores of one alphabet back to back in name order,

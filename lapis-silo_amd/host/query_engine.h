@@ -996,7 +996,11 @@ class Mutations : public Action {
    /// The selected rows in the reference's output order: stores in request order, positions ascending, symbols in
    /// VALID_MUTATION_SYMBOLS order (mutations.cpp:190-229, 259-268).
    [[nodiscard]] std::vector<SelectedRow> collectSelected(const Database& database, PendingScans& scans) const;
-   [[nodiscard]] std::string mutationName(const SelectedRow& row) const;
+   /// The selected rows as they arrive, for finishJson: position in the query's table, no particular order.  They stay in the
+   /// row slot; only where the whole table had to be read (no row slot, or more rows than it holds) are they made in `from_table`.
+   [[nodiscard]] std::pair<const silo_gpu_mutation_row*, size_t> deliveredRows(
+      const Database& database, PendingScans& scans, std::vector<silo_gpu_mutation_row>& from_table
+   ) const;
 
   public:
    [[nodiscard]] std::unique_ptr<Action::Pending> begin(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
