@@ -446,7 +446,7 @@ std::unique_ptr<Action::Pending> Mutations<SymbolType>::begin(const Database& da
    // selection on the device and one transfer; finish() only waits for that transfer.
    const bool sharded = database.shard_world > 1 && database.all_reduce != nullptr;
    const MutationTableLayout& layout = database.getMutationTableLayout<SymbolType>();
-   constexpr uint32_t n_symbols = SymbolType::VALID_MUTATION_SYMBOLS.size();
+   static constexpr uint32_t n_symbols = SymbolType::VALID_MUTATION_SYMBOLS.size();  // (static: the lambdas below read it uncaptured)
    const size_t n_counts = static_cast<size_t>(layout.total_positions) * n_symbols;
    if (database.partitions.empty() || n_counts == 0 || pending->sequence_names.empty() || (bitmaps_to_evaluate.empty() && !sharded)) {
       return pending;  // nothing selected (and no other rank to contribute): no rows
@@ -480,7 +480,7 @@ std::unique_ptr<Action::Pending> Mutations<SymbolType>::begin(const Database& da
    if (ScanBatcher::active() == nullptr) {
       own_batcher.emplace();
    }
-   try {
+   waitIfThrown([&] {
    for (const auto& sequence_name : pending->sequence_names) {
       if (std::find(scanned.begin(), scanned.end(), sequence_name) != scanned.end()) {
          continue;
@@ -526,11 +526,7 @@ std::unique_ptr<Action::Pending> Mutations<SymbolType>::begin(const Database& da
    if (own_batcher) {
       own_batcher->flush();
    }
-   } catch (...) {
-      // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
-      (void)silo_gpu_stream_synchronize(queryStream());
-      throw;
-   }
+   });
    return pending;
 }
 
@@ -819,6 +815,30 @@ std::vector<std::string> parseRequiredSequenceNames(const json::Value& json, con
 }
 
 }  // namespace
+
+std::optional<std::string> optionalStringField(const json::Value& json, std::string_view field, const std::string& action_name) {
+   if (!json.contains(field)) {
+      return std::nullopt;
+   }
+   CHECK_SILO_QUERY(json[field].is_string(), action_name + " action: the field " + std::string(field) + ", if present, must be of type string")
+   return json[field].as_string();
+}
+
+std::optional<uint32_t> integerField(
+   const json::Value& json, std::string_view field, const std::string& action_name, bool required, int64_t minimum, int64_t maximum, const std::string& form
+) {
+   const std::string the_field = action_name + " action: the field " + std::string(field);
+   if (!json.contains(field)) {
+      CHECK_SILO_QUERY(!required, the_field + " is required")
+      return std::nullopt;
+   }
+   const json::Value& value = json[field];
+   CHECK_SILO_QUERY(
+      value.is_number_unsigned() && value.as_int64() >= minimum && value.as_int64() <= maximum,
+      the_field + (required ? " must be " : ", if present, must be ") + form
+   )
+   return value.as_uint32();
+}
 
 namespace {
 

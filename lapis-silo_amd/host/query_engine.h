@@ -682,21 +682,39 @@ std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json);
 std::unique_ptr<Action> parseCrossTabulation(const json::Value& json);
 template <typename SymbolType>
 std::unique_ptr<Action> parseConsensus(const json::Value& json);
-/// The parser of DistanceMatrix (metadata_actions.cpp).
+/// The parsers of the sequence-comparing actions (distance_actions.cpp).
 std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json);
-/// The parser of Clusters (metadata_actions.cpp).
 std::unique_ptr<Action> parseClusters(const json::Value& json);
-/// The parser of MinimumSpanningTree (metadata_actions.cpp).
 std::unique_ptr<Action> parseMinimumSpanningTree(const json::Value& json);
-/// The parser of NearestAmong (metadata_actions.cpp).
 std::unique_ptr<Action> parseNearestAmong(const json::Value& json);
-/// The parser of NearestNeighbours (metadata_actions.cpp).
 std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json);
+
+/// Two kinds of field that many action parsers read, with one wording of the complaint (actions.cpp).  An optional field of type
+/// string: none when absent; "<action_name> action: the field <field>, if present, must be of type string".
+std::optional<std::string> optionalStringField(const json::Value& json, std::string_view field, const std::string& action_name);
+/// An unsigned integer field whose value, read as int64, lies in [minimum, maximum]: none when absent and not `required`.
+/// "<action_name> action: the field <field>[, if present,] must be <form>"; a required field that is absent: "... is required".
+std::optional<uint32_t> integerField(
+   const json::Value& json, std::string_view field, const std::string& action_name, bool required, int64_t minimum, int64_t maximum, const std::string& form
+);
 
 /// Refuses a sharded database on behalf of an action whose counts are not all-reduced across ranks (table_actions.cpp).
 void requireUnsharded(const Database& database, const std::string& action_name);
+/// The metadata column `name` of a partition; a runtime_error if it was not loaded (metadata_actions.cpp).
+const storage::column::MetadataColumnPartition& columnOf(const DatabasePartition& partition, const std::string& name);
+/// The set bits of a filter, fetched from the device (metadata_actions.cpp).
+std::vector<uint32_t> selectedRows(const DatabasePartition& partition, const OperatorResult& filter);
 
-/// The aligned sequence that NearestNeighbours and WithinDistance compare every row with (metadata_actions.cpp).
+/// The rule that keeps a pooled device buffer from being handed to another query while a kernel of this one still uses it, for
+/// work enqueued on queryStream() that reads and writes DeviceBuffers declared BEFORE the call (so that they die after it).
+/// waitIfThrown runs `launches`; if they throw, launches of this query may be in flight on the stream: it lets them finish before
+/// the exception unwinds the buffers back into the pool.  On its own it serves work whose buffers outlive it anyway, or that ends
+/// in a synchronous copy.  launchAndWait also waits for the stream when `launches` return — a fetch was the last thing enqueued
+/// and has been waited for, but it says so: nothing of this query runs any more when its buffers go back (table_actions.cpp).
+void waitIfThrown(const std::function<void()>& launches);
+void launchAndWait(const std::function<void()>& launches);
+
+/// The aligned sequence that NearestNeighbours and WithinDistance compare every row with (distance_actions.cpp).
 struct QuerySequence {
    std::string characters;             // one per position of the sequence
    size_t own_partition = SIZE_MAX;    // where the row named by a primary key lives; a literal sequence has none
@@ -807,7 +825,7 @@ class FastaAligned : public Action {
    explicit FastaAligned(std::vector<std::string>&& sequence_names) : sequence_names(std::move(sequence_names)) {}
 };
 
-/// DistanceMatrix (metadata_actions.cpp): per unordered pair of the selected sequences the positions of one aligned sequence where
+/// DistanceMatrix (distance_actions.cpp): per unordered pair of the selected sequences the positions of one aligned sequence where
 /// both hold a valid mutation symbol (comparedPositions) and where those two differ (distance) — the SNP distance matrix a
 /// client would otherwise compute from a FastaAligned response.  The sequences are numbered in partition order, then by
 /// ascending row id; one row per pair i < j, row-major; with maxDistance only the pairs at most that far apart.  The rows
@@ -826,7 +844,7 @@ class DistanceMatrix : public Action {
        : sequence_name(std::move(sequence_name)), max_distance(max_distance) {}
 };
 
-/// Clusters (metadata_actions.cpp): the single-linkage clusters of the selected sequences — numbered as DistanceMatrix numbers them —
+/// Clusters (distance_actions.cpp): the single-linkage clusters of the selected sequences — numbered as DistanceMatrix numbers them —
 /// at a bound on DistanceMatrix's distance on one aligned sequence: two sequences are linked iff their distance is <= maxDistance
 /// and they compare at >= minComparedPositions positions, and a cluster is a connected component of the links.  One row per
 /// sequence: its key, the key of the lowest-numbered member of its cluster, the cluster's size; minClusterSize drops the rows of
@@ -849,7 +867,7 @@ class Clusters : public Action {
          min_cluster_size(min_cluster_size) {}
 };
 
-/// MinimumSpanningTree (metadata_actions.cpp): the minimum spanning forest of the selected sequences — numbered as DistanceMatrix
+/// MinimumSpanningTree (distance_actions.cpp): the minimum spanning forest of the selected sequences — numbered as DistanceMatrix
 /// numbers them — over the graph whose edges are the pairs i < j with distance <= maxDistance (absent: no bound) and >=
 /// minComparedPositions positions compared, ordered by the key distance * 2^26 + i * 2^13 + j.  The order is strict, so the forest is
 /// unique; cut at any d it leaves the clusters of Clusters at d.  One row per edge of the forest: the two keys, the distance, the
@@ -869,7 +887,7 @@ class MinimumSpanningTree : public Action {
        : sequence_name(std::move(sequence_name)), max_distance(max_distance), min_compared_positions(min_compared_positions) {}
 };
 
-/// NearestAmong (metadata_actions.cpp): for every sequence the filter selects (a subject) its `neighbours` closest sequences among
+/// NearestAmong (distance_actions.cpp): for every sequence the filter selects (a subject) its `neighbours` closest sequences among
 /// those `among` selects (the candidates; absent: the query's own filter), by DistanceMatrix's distance on one aligned sequence.
 /// Each side is numbered on its own as DistanceMatrix numbers a selection.  A candidate is eligible for a subject when it is another
 /// database row, >= minComparedPositions positions are compared and the distance is <= maxDistance (absent: no bound); a subject
@@ -903,7 +921,7 @@ class NearestAmong : public Action {
          min_compared_positions(min_compared_positions) {}
 };
 
-/// NearestNeighbours (metadata_actions.cpp): the `neighbours` rows of the WHOLE database closest to one query sequence — a row named
+/// NearestNeighbours (distance_actions.cpp): the `neighbours` rows of the WHOLE database closest to one query sequence — a row named
 /// by its primary key (then left out of its own list) or a literal aligned string — by DistanceMatrix's distance on one aligned
 /// sequence, among the rows the filter selects and, with maxDistance, at most that far away.  Per partition one
 /// silo_gpu_query_distances (every row's distance and compared positions read off the store's layout, K11) and one

@@ -13,11 +13,29 @@
 
 namespace silo::query_engine::actions {
 
-// ---- what the three actions share (requireUnsharded: with DistanceMatrix too) ----------------------------
+// ---- what the three actions share (requireUnsharded and the two stream guards: with every action that launches on its own) ----
 void requireUnsharded(const Database& database, const std::string& action_name) {
    CHECK_SILO_QUERY(
       database.shard_world <= 1, action_name + " is not supported on a sharded database yet: its counts are not all-reduced across ranks"
    )
+}
+
+void waitIfThrown(const std::function<void()>& launches) {
+   try {
+      launches();
+   } catch (...) {
+      // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
+      (void)silo_gpu_stream_synchronize(queryStream());
+      throw;
+   }
+}
+
+void launchAndWait(const std::function<void()>& launches) {
+   waitIfThrown([&] {
+      launches();
+      // a copy was the last thing enqueued, but say it: nothing of this query runs any more when its buffers go back
+      checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
+   });
 }
 
 namespace {
@@ -112,7 +130,7 @@ std::vector<uint32_t> countTable(
    checkGpu(silo_gpu_memset_async(device_table.get(), 0, words * sizeof(uint32_t), queryStream()), "silo_gpu_memset_async");
    LiveSet live;  // kept until the table has landed: the launches read it
    HostFetch fetch;
-   try {
+   waitIfThrown([&] {
       for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
          const DatabasePartition& partition = database.partitions[partition_id];
          const OperatorResult& filter = bitmap_filter[partition_id];
@@ -126,11 +144,7 @@ std::vector<uint32_t> countTable(
       fetch = HostFetch(device_table.get(), words * sizeof(uint32_t), queryStream());
       const auto* host = static_cast<const uint32_t*>(fetch.wait());
       table.assign(host, host + words);
-   } catch (...) {
-      // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
-      (void)silo_gpu_stream_synchronize(queryStream());
-      throw;
-   }
+   });
    return table;
 }
 
@@ -527,7 +541,7 @@ QueryResult Consensus<SymbolType>::execute(const Database& database, std::vector
       DeviceBuffer device_result;      // the summaries, then the characters: the one thing fetched
       DeviceBuffer device_reference;   // only where the database keeps no reference index on the device
       LiveSet live;                    // the groups' bitsets of one partition at a time
-      try {
+      launchAndWait([&] {
          if (on_device) {
             DevicePool& pool = database.partitions.front().pool;
             device_table = pool.acquire(n_groups * table_words * sizeof(uint32_t));
@@ -608,13 +622,7 @@ QueryResult Consensus<SymbolType>::execute(const Database& database, std::vector
             std::memcpy(summary.data(), host, summary.size() * sizeof(uint32_t));
             characters.assign(host + summary.size() * sizeof(uint32_t), characters.size());
          }
-         // the copy was the last thing enqueued, but say it: nothing of this query runs any more when its buffers go back
-         checkGpu(silo_gpu_stream_synchronize(queryStream()), "silo_gpu_stream_synchronize");
-      } catch (...) {
-         // launches of this query may be in flight on the stream: let them finish before its buffers return to the pool
-         (void)silo_gpu_stream_synchronize(queryStream());
-         throw;
-      }
+      });
    }
 
    // what came off the device is checked before it becomes a row: every character one the rule can give, the three kinds of
@@ -867,11 +875,7 @@ template <typename SymbolType>
 std::unique_ptr<Action> parseConsensus(const json::Value& json) {
    using ConsensusAction = Consensus<SymbolType>;
    const std::string action_name = ConsensusAction::actionName();
-   std::optional<std::string> sequence_name;
-   if (json.contains("sequenceName")) {
-      CHECK_SILO_QUERY(json["sequenceName"].is_string(), action_name + " action: the field sequenceName, if present, must be of type string")
-      sequence_name = json["sequenceName"].as_string();
-   }
+   std::optional<std::string> sequence_name = optionalStringField(json, "sequenceName", action_name);
    CHECK_SILO_QUERY(
       (std::is_same_v<SymbolType, Nucleotide>) || sequence_name.has_value(), action_name + " action must contain the field sequenceName of type string (a gene)"
    )
@@ -912,14 +916,8 @@ std::unique_ptr<Action> parseConsensus(const json::Value& json) {
       )
       threshold = json["threshold"].as_double();
    }
-   uint32_t min_depth = ConsensusAction::DEFAULT_MIN_DEPTH;
-   if (json.contains("minDepth")) {
-      CHECK_SILO_QUERY(
-         json["minDepth"].is_number_unsigned() && json["minDepth"].as_int64() >= 1 && json["minDepth"].as_int64() <= UINT32_MAX,
-         action_name + " action: the field minDepth, if present, must be an integer from 1 to " + std::to_string(UINT32_MAX)
-      )
-      min_depth = json["minDepth"].as_uint32();
-   }
+   const uint32_t min_depth = integerField(json, "minDepth", action_name, false, 1, UINT32_MAX, "an integer from 1 to " + std::to_string(UINT32_MAX))
+                                 .value_or(ConsensusAction::DEFAULT_MIN_DEPTH);
    return std::make_unique<ConsensusAction>(std::move(sequence_name), std::move(groups), threshold, min_depth);
 }
 
