@@ -813,6 +813,35 @@ int silo_gpu_haplotype_ids(
    void* stream
 );
 
+/* ---- K17: the comparison of count tables (MutationsComparison / AminoAcidMutationsComparison) -----------
+ * Takes no store.  counts_dev and reference_index_dev are as for silo_gpu_consensus_call: 2 <= n_tables <=
+ * SILO_GPU_MAX_COMPARISON_TABLES tables back to back, n_positions x n_symbols words each (n_symbols = 5 / 22), 4-byte aligned; the
+ * reference's symbol index per position, 0xFF for none.  With c[t][p][s] a cell and cov[t][p] = sum_s c[t][p][s] (no wrap is
+ * defined):
+ *     table t PASSES (p, s)   iff cov[t][p] > 0 and c[t][p][s] > bound, bound = 0 if min_proportion == 0, else
+ *                             (uint32_t)(ceil((double)cov[t][p] * min_proportion) - 1): the arithmetic of silo_gpu_mutations_select
+ *     difference(p, s)        = the highest minus the lowest of (double)c[t][p][s] / (double)cov[t][p] (IEEE division) over the
+ *                             tables with cov[t][p] > 0; 0.0 where fewer than two tables are covered
+ *     (p, s) is SELECTED      iff s != reference_index_dev[p], some table passes it and difference(p, s) >= min_difference
+ * WRITES out_dev, 4 + capacity * 2 + capacity * n_tables * 2 words:
+ *     4 header words          word 0 = the number of selected cells, which may exceed `capacity`; words 1 .. 3 = 0
+ *     capacity records        {uint32 position, uint32 symbol}: the selected cells that found a slot, in no particular order
+ *     capacity * n_tables cells   for record slot i and table t, {count, coverage} = {c[t][p][s], cov[t][p]} at word
+ *                             4 + capacity * 2 + (i * n_tables + t) * 2
+ * Past `capacity` only the counter advances, as in silo_gpu_mutations_select; slots at or past min(word 0, capacity) are not
+ * written.  capacity == 0 is legal: the count alone.  The entry clears the header itself, on `stream`, and the threads add
+ * integers to word 0, so two calls give the same bytes once the records are put in order; the caller clears nothing.  One kernel
+ * launch (a block of SILO_GPU_COMPARE_THREADS threads per as many positions, a thread per position, every table's slab of the
+ * block staged through LDS; no scratch memory), returns without waiting.  n_positions == 0: success, only the header cleared.
+ * Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for an alphabet other than the two, a NULL pointer, n_tables below 2 or
+ * above the limit, or min_proportion or min_difference outside [0, 1] or NaN. */
+#define SILO_GPU_MAX_COMPARISON_TABLES 64
+#define SILO_GPU_COMPARE_THREADS 256
+int silo_gpu_mutations_compare(
+   int alphabet, const uint32_t* counts_dev, uint32_t n_tables, uint32_t n_positions, const uint8_t* reference_index_dev, double min_proportion,
+   double min_difference, uint32_t capacity, uint32_t* out_dev, void* stream
+);
+
 /* ---- K11: the rows of the whole store nearest to a query (NearestNeighbours) --------------------------
  * silo_gpu_query_distances compares one query — query_chars, `positions` characters in HOST memory — with EVERY row of a sequence
  * store, read off the store's own layout (identity / code planes with escape keys, one-hot rows with a derived symbol, runs of the

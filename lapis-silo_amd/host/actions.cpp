@@ -1,5 +1,6 @@
 // actions.cpp — Action base (ordering / limit / offset), Aggregated (count), Mutations<SymbolType> and parseAction.  The actions
-// that answer from a small count table (MutationsOverTime, QueriesOverTime, CrossTabulation, Consensus) are in table_actions.cpp.
+// that answer from a small count table (MutationsOverTime, QueriesOverTime, CrossTabulation, Consensus, MutationsComparison) are in
+// table_actions.cpp.
 // Reference: src/silo/query_engine/actions/{action,aggregated,mutations}.cpp.
 #include <algorithm>
 #include <charconv>
@@ -873,6 +874,8 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"NearestAmong", parseNearestAmong},
    {"Consensus", parseConsensus<Nucleotide>},
    {"AminoAcidConsensus", parseConsensus<AminoAcid>},
+   {"MutationsComparison", parseMutationsComparison<Nucleotide>},
+   {"AminoAcidMutationsComparison", parseMutationsComparison<AminoAcid>},
    {"NearestNeighbours", parseNearestNeighbours},
    {"Haplotypes", parseHaplotypes<Nucleotide>},
    {"AminoAcidHaplotypes", parseHaplotypes<AminoAcid>},

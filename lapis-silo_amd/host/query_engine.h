@@ -682,6 +682,8 @@ std::unique_ptr<Action> parseQueriesOverTime(const json::Value& json);
 std::unique_ptr<Action> parseCrossTabulation(const json::Value& json);
 template <typename SymbolType>
 std::unique_ptr<Action> parseConsensus(const json::Value& json);
+template <typename SymbolType>
+std::unique_ptr<Action> parseMutationsComparison(const json::Value& json);
 /// The parsers of the sequence-comparing actions (distance_actions.cpp).
 std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json);
 std::unique_ptr<Action> parseClusters(const json::Value& json);
@@ -1175,6 +1177,46 @@ class Consensus : public Action {
    std::vector<Group> groups;
    double threshold;
    uint32_t min_depth;
+
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+};
+
+/// MutationsComparison / AminoAcidMutationsComparison: how often each of 2 .. MAX_GROUPS named groups — the query's filter AND the
+/// group's own expression, per partition, as Consensus resolves them — carries each mutation of one sequence store that any of them
+/// carries.  With c a cell of a group's Mutations table and cov the sum of the cells of its position: a group passes (position,
+/// symbol) iff cov > 0 and c > the bound of Mutations' row selection at min_proportion; difference = the highest minus the lowest
+/// c / cov over the groups with cov > 0 (0.0 with fewer than two); a mutation is selected iff the symbol is not the reference's, some
+/// group passes it and difference >= min_difference.  One row per selected mutation and group, in the order position, symbol, group
+/// of the request: mutation, sequenceName, position (1-based), group, count, coverage, proportion (null where coverage is 0),
+/// difference (the same on the rows of a mutation).  Per partition the exact Mutations scan of all groups' bitsets into one table per
+/// group, as for Consensus; one comparison (K17, silo_gpu_mutations_compare) with room for FIRST_CAPACITY records, a second one with
+/// exactly as much room as the first one's counter asks for where that is more; the header and the records with their cells are
+/// fetched: the tables never leave the device.  Every record is checked against the rule before it becomes rows.  No counterpart in
+/// the reference.
+template <typename SymbolType>
+class MutationsComparison : public Action {
+  public:
+   struct Group {
+      std::string name;
+      std::unique_ptr<filter_expressions::Expression> filter;
+   };
+   static constexpr uint32_t MIN_GROUPS = 2;
+   static constexpr uint32_t MAX_GROUPS = SILO_GPU_MAX_COMPARISON_TABLES;
+   static constexpr double DEFAULT_MIN_PROPORTION = 0.05;
+   static constexpr double DEFAULT_MIN_DIFFERENCE = 0;
+   static constexpr uint32_t FIRST_CAPACITY = 1024;  // records of the first comparison: a response above it costs a second launch
+   static_assert(MAX_GROUPS <= MAX_LIVE_FILTERS);    // the bitsets of every group of a partition are alive at a time
+   static std::string actionName() { return std::is_same_v<SymbolType, Nucleotide> ? "MutationsComparison" : "AminoAcidMutationsComparison"; }
+
+   MutationsComparison(std::optional<std::string> sequence_name, std::vector<Group> groups, double min_proportion, double min_difference)
+       : sequence_name(std::move(sequence_name)), groups(std::move(groups)), min_proportion(min_proportion), min_difference(min_difference) {}
+
+  private:
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   std::vector<Group> groups;
+   double min_proportion;
+   double min_difference;
 
    void validateOrderByFields(const Database& database) const override;
    [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;

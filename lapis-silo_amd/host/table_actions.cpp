@@ -1,9 +1,11 @@
 // table_actions.cpp — the actions that answer from one small table of counts filled on the device: MutationsOverTime<SymbolType>
-// (K7), QueriesOverTime (K8) and CrossTabulation (K9), which fetch the table, and Consensus<SymbolType> (K15), which fetches what
-// a last kernel makes of it, with their parsers.  Each differs in the kernel call of a partition and in the rows it makes of the
-// table; what stands around that — the refusals, the date column, the table's life on the device, the evaluation of labelled
-// sub-expressions and what has to stay alive while launches run — is here once.
+// (K7), QueriesOverTime (K8) and CrossTabulation (K9), which fetch the table, and Consensus<SymbolType> (K15) and
+// MutationsComparison<SymbolType> (K17), which fetch what a last kernel makes of the tables of their groups, with their parsers.
+// Each differs in the kernel call of a partition and in the rows it makes of the table; what stands around that — the refusals, the
+// date column, the table's life on the device, the evaluation of labelled sub-expressions, the tables of named groups and what has
+// to stay alive while launches run — is here once.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <functional>
 #include <set>
@@ -502,6 +504,104 @@ GroupRows evaluateWithinBase(
    return {cardinality, live.keep(std::move(result))};
 }
 
+/// A group of Consensus / MutationsComparison: what messages call it and its expression (nullptr: the query's filter alone).
+struct GroupFilter {
+   std::string name;
+   const filter_expressions::Expression* filter;
+};
+
+/// The exact Mutations tables of the groups of a request, on the device, with what the launches into them read.  Declared before the
+/// launchAndWait that fills and reads it: nothing in it returns to the pool before the stream has been waited for.
+struct GroupTables {
+   std::vector<uint32_t> group_rows;          // the rows of every group, over all partitions
+   DeviceBuffer tables;                       // a table per group, back to back: it never leaves the device.  None: nothing to scan
+   const uint8_t* reference_index = nullptr;  // the reference's symbol index of every position, on the device
+   DeviceBuffer own_reference;                // only where the database keeps no reference index on the device
+   LiveSet live;                              // the groups' bitsets of one partition at a time
+};
+
+/// Fills `out` for the sequence store `name` (inside a launchAndWait): the pooled tables cleared once; per partition whose base
+/// filter selects a row, every group's rows within the base (evaluateWithinBase), the store's cached totals added for a group that is
+/// every row of the partition (a NULL filter: no pass over the planes) and ONE exact silo_gpu_mutations_scan_batch for the others;
+/// then the reference index.  Where the database has no partition or the sequence no position, only the groups' rows are counted.
+template <typename SymbolType>
+void fillGroupTables(
+   const Database& database, const std::vector<OperatorResult>& bitmap_filter, const std::string& name, const std::vector<GroupFilter>& groups,
+   const std::string& action_name, GroupTables& out
+) {
+   const auto& reference = database.getSequenceStores<SymbolType>().at(name).reference_sequence;
+   constexpr uint32_t n_symbols = SymbolType::VALID_MUTATION_SYMBOLS.size();
+   const auto positions = static_cast<uint32_t>(reference.size());
+   const auto n_groups = static_cast<uint32_t>(groups.size());
+   const size_t table_words = static_cast<size_t>(positions) * n_symbols;  // of one group
+   const bool on_device = !database.partitions.empty() && positions != 0;
+   out.group_rows.assign(n_groups, 0);
+   if (on_device) {
+      out.tables = database.partitions.front().pool.acquire(n_groups * table_words * sizeof(uint32_t));
+      checkGpu(silo_gpu_memset_async(out.tables.get(), 0, n_groups * table_words * sizeof(uint32_t), queryStream()), "silo_gpu_memset_async");
+   }
+   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+      const DatabasePartition& partition = database.partitions[partition_id];
+      const OperatorResult& filter = bitmap_filter[partition_id];
+      const uint32_t base_selected = partition.sequence_count == 0 ? 0 : filter.cardinality();
+      if (base_selected == 0) {
+         continue;
+      }
+      // a filter that selects every row is passed as NULL (no all-ones bitset is made for it)
+      const uint64_t* base_bits = base_selected == partition.sequence_count ? nullptr : filter.bitset();
+      out.live.waitAndRelease();  // the scans of the partition before may still read its groups' bitsets
+      const SequenceStorePartition<SymbolType>& store = partition.getSequenceStores<SymbolType>().at(name);
+      std::vector<const uint64_t*> scan_filters;  // the groups that select some rows of the partition, not all
+      std::vector<uint32_t*> scan_tables;
+      for (uint32_t g = 0; g < n_groups; ++g) {
+         const std::string owner = action_name + " action: the field filterExpression of the group '" + groups[g].name + "'";
+         const GroupRows rows = evaluateWithinBase(database, partition, groups[g].filter, base_selected, base_bits, out.live, owner);
+         out.group_rows[g] += rows.cardinality;
+         if (rows.cardinality == 0 || !on_device) {  // empty here: its table stays as it is
+            continue;
+         }
+         uint32_t* table = out.tables.as<uint32_t>() + g * table_words;
+         if (rows.bits == nullptr) {  // every row: the store's cached totals are added, no pass over the planes
+            checkGpu(silo_gpu_mutations_scan(store.store, store.seqstore_id, nullptr, 0, positions, table, queryStream()), "silo_gpu_mutations_scan");
+            out.live.launched();
+         } else {
+            scan_filters.push_back(rows.bits);
+            scan_tables.push_back(table);
+         }
+      }
+      if (!scan_filters.empty()) {
+         // the EXACT scan (never a min_proportion variant: a pruned group would land on the derived symbol), every plane row
+         // read once per SILO_GPU_MAX_SCAN_BATCH groups; it accumulates, so partitions sum as they do for Mutations
+         checkGpu(
+            silo_gpu_mutations_scan_batch(
+               store.store, store.seqstore_id, scan_filters.data(), static_cast<uint32_t>(scan_filters.size()), 0, positions, scan_tables.data(),
+               queryStream()
+            ),
+            "silo_gpu_mutations_scan_batch"
+         );
+         out.live.launched();
+      }
+   }
+   if (on_device) {
+      const MutationTableLayout& layout = database.getMutationTableLayout<SymbolType>();
+      if (layout.reference_index_device != nullptr) {
+         out.reference_index = layout.reference_index_device.get() + layout.position_offset.at(name);
+      } else {
+         std::vector<uint8_t> index(positions, 0xFF);
+         for (uint32_t p = 0; p < positions; ++p) {
+            for (size_t s = 0; s < n_symbols; ++s) {
+               if (SymbolType::VALID_MUTATION_SYMBOLS[s] == reference[p]) {
+                  index[p] = static_cast<uint8_t>(s);
+               }
+            }
+         }
+         out.own_reference = database.partitions.front().pool.acquire(positions);
+         checkGpu(silo_gpu_memcpy_h2d(out.own_reference.get(), index.data(), positions, queryStream()), "silo_gpu_memcpy_h2d");
+         out.reference_index = out.own_reference.as<uint8_t>();
+      }
+   }
+}
+
 }  // namespace
 
 template <typename SymbolType>
@@ -519,111 +619,44 @@ QueryResult Consensus<SymbolType>::execute(const Database& database, std::vector
       found != database.getSequenceStores<SymbolType>().end(),
       "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + name + "'"
    )
-   const auto& reference = found->second.reference_sequence;
-   constexpr uint32_t n_symbols = SymbolType::VALID_MUTATION_SYMBOLS.size();
    constexpr uint32_t summary_words = 4;  // ambiguous, low coverage, deleted, differences
-   const auto positions = static_cast<uint32_t>(reference.size());
+   const auto positions = static_cast<uint32_t>(found->second.reference_sequence.size());
    const auto n_groups = static_cast<uint32_t>(groups.size());
    const char missing = SymbolType::symbolToChar(SymbolType::SYMBOL_MISSING);
-   const size_t table_words = static_cast<size_t>(positions) * n_symbols;  // of one group
 
-   std::vector<uint32_t> group_rows(n_groups, 0);  // over all partitions
    // what a group nobody scanned gets: the missing symbol everywhere, every position low coverage
    std::vector<uint32_t> summary(static_cast<size_t>(n_groups) * summary_words, 0);
    std::string characters(static_cast<size_t>(n_groups) * positions, missing);
    for (uint32_t g = 0; g < n_groups; ++g) {
       summary[g * summary_words + 1] = positions;
    }
-   {
-      // nothing in here returns to the pool before the stream has been waited for: the launches read it
-      const bool on_device = !database.partitions.empty() && positions != 0;
-      DeviceBuffer device_table;       // n_groups tables back to back: it never leaves the device
-      DeviceBuffer device_result;      // the summaries, then the characters: the one thing fetched
-      DeviceBuffer device_reference;   // only where the database keeps no reference index on the device
-      LiveSet live;                    // the groups' bitsets of one partition at a time
-      launchAndWait([&] {
-         if (on_device) {
-            DevicePool& pool = database.partitions.front().pool;
-            device_table = pool.acquire(n_groups * table_words * sizeof(uint32_t));
-            device_result = pool.acquire(summary.size() * sizeof(uint32_t) + characters.size());
-            checkGpu(silo_gpu_memset_async(device_table.get(), 0, n_groups * table_words * sizeof(uint32_t), queryStream()), "silo_gpu_memset_async");
-         }
-         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-            const DatabasePartition& partition = database.partitions[partition_id];
-            const OperatorResult& filter = bitmap_filter[partition_id];
-            const uint32_t base_selected = partition.sequence_count == 0 ? 0 : filter.cardinality();
-            if (base_selected == 0) {
-               continue;
-            }
-            // a filter that selects every row is passed as NULL (no all-ones bitset is made for it)
-            const uint64_t* base_bits = base_selected == partition.sequence_count ? nullptr : filter.bitset();
-            live.waitAndRelease();  // the scans of the partition before may still read its groups' bitsets
-            const SequenceStorePartition<SymbolType>& store = partition.getSequenceStores<SymbolType>().at(name);
-            std::vector<const uint64_t*> scan_filters;  // the groups that select some rows of the partition, not all
-            std::vector<uint32_t*> scan_tables;
-            for (uint32_t g = 0; g < n_groups; ++g) {
-               const std::string owner = action_name + " action: the field filterExpression of the group '" + groups[g].name.value_or("") + "'";
-               const GroupRows rows = evaluateWithinBase(database, partition, groups[g].filter.get(), base_selected, base_bits, live, owner);
-               group_rows[g] += rows.cardinality;
-               if (rows.cardinality == 0 || !on_device) {  // empty here: its table stays as it is
-                  continue;
-               }
-               uint32_t* table = device_table.as<uint32_t>() + g * table_words;
-               if (rows.bits == nullptr) {  // every row: the store's cached totals are added, no pass over the planes
-                  checkGpu(silo_gpu_mutations_scan(store.store, store.seqstore_id, nullptr, 0, positions, table, queryStream()), "silo_gpu_mutations_scan");
-                  live.launched();
-               } else {
-                  scan_filters.push_back(rows.bits);
-                  scan_tables.push_back(table);
-               }
-            }
-            if (!scan_filters.empty()) {
-               // the EXACT scan (never a min_proportion variant: a pruned group would land on the derived symbol), every plane row
-               // read once per SILO_GPU_MAX_SCAN_BATCH groups; it accumulates, so partitions sum as they do for Mutations
-               checkGpu(
-                  silo_gpu_mutations_scan_batch(
-                     store.store, store.seqstore_id, scan_filters.data(), static_cast<uint32_t>(scan_filters.size()), 0, positions, scan_tables.data(),
-                     queryStream()
-                  ),
-                  "silo_gpu_mutations_scan_batch"
-               );
-               live.launched();
-            }
-         }
-         if (on_device) {
-            const MutationTableLayout& layout = database.getMutationTableLayout<SymbolType>();
-            const uint8_t* reference_index = nullptr;
-            if (layout.reference_index_device != nullptr) {
-               reference_index = layout.reference_index_device.get() + layout.position_offset.at(name);
-            } else {
-               std::vector<uint8_t> index(positions, 0xFF);
-               for (uint32_t p = 0; p < positions; ++p) {
-                  for (size_t s = 0; s < n_symbols; ++s) {
-                     if (SymbolType::VALID_MUTATION_SYMBOLS[s] == reference[p]) {
-                        index[p] = static_cast<uint8_t>(s);
-                     }
-                  }
-               }
-               device_reference = database.partitions.front().pool.acquire(positions);
-               checkGpu(silo_gpu_memcpy_h2d(device_reference.get(), index.data(), positions, queryStream()), "silo_gpu_memcpy_h2d");
-               reference_index = device_reference.as<uint8_t>();
-            }
-            auto* device_summary = device_result.as<uint32_t>();
-            char* device_characters = device_result.as<char>() + summary.size() * sizeof(uint32_t);
-            checkGpu(
-               silo_gpu_consensus_call(
-                  SymbolType::ABI_ALPHABET, device_table.as<uint32_t>(), n_groups, positions, reference_index, threshold, min_depth, device_characters,
-                  device_summary, queryStream()
-               ),
-               "silo_gpu_consensus_call"
-            );
-            HostFetch fetch(device_result.get(), summary.size() * sizeof(uint32_t) + characters.size(), queryStream());
-            const auto* host = static_cast<const char*>(fetch.wait());
-            std::memcpy(summary.data(), host, summary.size() * sizeof(uint32_t));
-            characters.assign(host + summary.size() * sizeof(uint32_t), characters.size());
-         }
-      });
+   std::vector<GroupFilter> group_filters;
+   for (const Group& group : groups) {
+      group_filters.push_back({group.name.value_or(""), group.filter.get()});
    }
+   // nothing in here returns to the pool before the stream has been waited for: the launches read it
+   GroupTables tables;
+   DeviceBuffer device_result;  // the summaries, then the characters: the one thing fetched
+   launchAndWait([&] {
+      fillGroupTables<SymbolType>(database, bitmap_filter, name, group_filters, action_name, tables);
+      if (tables.tables) {
+         device_result = database.partitions.front().pool.acquire(summary.size() * sizeof(uint32_t) + characters.size());
+         auto* device_summary = device_result.as<uint32_t>();
+         char* device_characters = device_result.as<char>() + summary.size() * sizeof(uint32_t);
+         checkGpu(
+            silo_gpu_consensus_call(
+               SymbolType::ABI_ALPHABET, tables.tables.as<uint32_t>(), n_groups, positions, tables.reference_index, threshold, min_depth,
+               device_characters, device_summary, queryStream()
+            ),
+            "silo_gpu_consensus_call"
+         );
+         HostFetch fetch(device_result.get(), summary.size() * sizeof(uint32_t) + characters.size(), queryStream());
+         const auto* host = static_cast<const char*>(fetch.wait());
+         std::memcpy(summary.data(), host, summary.size() * sizeof(uint32_t));
+         characters.assign(host + summary.size() * sizeof(uint32_t), characters.size());
+      }
+   });
+   const std::vector<uint32_t>& group_rows = tables.group_rows;
 
    // what came off the device is checked before it becomes a row: every character one the rule can give, the three kinds of
    // position disjoint
@@ -654,6 +687,159 @@ QueryResult Consensus<SymbolType>::execute(const Database& database, std::vector
 
 template class Consensus<Nucleotide>;
 template class Consensus<AminoAcid>;
+
+// ---- MutationsComparison -----------------------------------------------------------------------------------
+// The mutations that up to 64 named groups under the query's filter carry, with every group's count and coverage, from the exact
+// Mutations scan of the groups and the comparison on the device (K17), with its parser.  No counterpart in the reference.
+namespace {
+
+/// K4's bound (k_mutations_select, Mutations' own row selection): a count passes a coverage above 0 iff it is above this.
+uint32_t mustExceed(uint32_t coverage, double min_proportion) {
+   return min_proportion == 0 ? 0 : static_cast<uint32_t>(std::ceil(static_cast<double>(coverage) * min_proportion) - 1);
+}
+
+}  // namespace
+
+template <typename SymbolType>
+void MutationsComparison<SymbolType>::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"mutation", "position", "group", "count", "coverage", "proportion", "difference"});
+}
+
+template <typename SymbolType>
+QueryResult MutationsComparison<SymbolType>::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string action_name = actionName();
+   requireUnsharded(database, action_name);
+   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+   const auto found = database.getSequenceStores<SymbolType>().find(name);
+   CHECK_SILO_QUERY(
+      found != database.getSequenceStores<SymbolType>().end(),
+      "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + name + "'"
+   )
+   const auto& reference = found->second.reference_sequence;
+   constexpr uint32_t n_symbols = SymbolType::VALID_MUTATION_SYMBOLS.size();
+   constexpr size_t header_words = 4;
+   const auto positions = static_cast<uint32_t>(reference.size());
+   const auto n_groups = static_cast<uint32_t>(groups.size());
+   const size_t record_words = 2 + static_cast<size_t>(n_groups) * 2;  // {position, symbol}, and {count, coverage} of every group
+
+   std::vector<GroupFilter> group_filters;
+   for (const Group& group : groups) {
+      group_filters.push_back({group.name, group.filter.get()});
+   }
+   uint32_t n_records = 0;
+   std::vector<uint32_t> records;  // n_records x {position, symbol}, then n_records x n_groups x {count, coverage}: as they came
+   {
+      // nothing in here returns to the pool before the stream has been waited for: the launches read and write it
+      GroupTables tables;
+      DeviceBuffer device_out[2];  // of the first comparison and, where its capacity was too low, of the second
+      launchAndWait([&] {
+         fillGroupTables<SymbolType>(database, bitmap_filter, name, group_filters, action_name, tables);
+         if (!tables.tables) {
+            return;
+         }
+         uint32_t capacity = FIRST_CAPACITY;
+         for (size_t call = 0; call < 2; ++call) {
+            DeviceBuffer& out = device_out[call];
+            out = database.partitions.front().pool.acquire((header_words + capacity * record_words) * sizeof(uint32_t));
+            checkGpu(
+               silo_gpu_mutations_compare(
+                  SymbolType::ABI_ALPHABET, tables.tables.as<uint32_t>(), n_groups, positions, tables.reference_index, min_proportion, min_difference,
+                  capacity, out.as<uint32_t>(), queryStream()
+               ),
+               "silo_gpu_mutations_compare"
+            );
+            const HostFetch header(out.get(), header_words * sizeof(uint32_t), queryStream());
+            const uint32_t selected = *static_cast<const uint32_t*>(header.wait());
+            if (selected > capacity) {
+               if (call == 1) {  // the tables have not changed: the second count is the first
+                  throw std::runtime_error(action_name + ": the device selected " + std::to_string(selected) + " cells where it had selected " + std::to_string(capacity));
+               }
+               capacity = selected;  // exactly as many: the count is deterministic
+               continue;
+            }
+            n_records = selected;
+            if (selected != 0) {
+               // one copy from the first record to the last cell in use (the record slots nobody took lie between them)
+               const size_t words = static_cast<size_t>(capacity) * 2 + static_cast<size_t>(selected) * n_groups * 2;
+               const HostFetch fetch(out.as<uint32_t>() + header_words, words * sizeof(uint32_t), queryStream());
+               const auto* host = static_cast<const uint32_t*>(fetch.wait());
+               records.assign(host, host + static_cast<size_t>(selected) * 2);
+               records.insert(records.end(), host + static_cast<size_t>(capacity) * 2, host + words);
+            }
+            break;
+         }
+      });
+   }
+
+   // what came off the device is checked before it becomes rows: every record a cell of the table that is not the reference's, once,
+   // with counts that a coverage can hold, and selected by the rule as the host computes it
+   const auto broken = [&](const std::string& what) { return std::runtime_error(action_name + ": the device delivered " + what); };
+   const uint32_t* cells = records.data() + static_cast<size_t>(n_records) * 2;
+   std::vector<uint32_t> order(n_records);
+   for (uint32_t r = 0; r < n_records; ++r) {
+      order[r] = r;
+      if (records[r * 2] >= positions || records[r * 2 + 1] >= n_symbols) {
+         throw broken("a record outside the table");
+      }
+   }
+   const auto key = [&](uint32_t r) { return static_cast<uint64_t>(records[r * 2]) * n_symbols + records[r * 2 + 1]; };
+   std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
+   QueryResult results;
+   results.query_result.reserve(static_cast<size_t>(n_records) * n_groups);
+   for (uint32_t k = 0; k < n_records; ++k) {
+      const uint32_t r = order[k];
+      const uint32_t position = records[r * 2];
+      const uint32_t symbol = records[r * 2 + 1];
+      const uint32_t* of_groups = cells + static_cast<size_t>(r) * n_groups * 2;
+      if (k != 0 && key(order[k - 1]) == key(r)) {
+         throw broken("a record twice");
+      }
+      if (SymbolType::VALID_MUTATION_SYMBOLS[symbol] == reference[position]) {
+         throw broken("the reference's symbol as a mutation");
+      }
+      bool passes = false;
+      uint32_t covered = 0;
+      double highest = 0;
+      double lowest = 1;
+      for (uint32_t g = 0; g < n_groups; ++g) {
+         const uint32_t count = of_groups[g * 2];
+         const uint32_t coverage = of_groups[g * 2 + 1];
+         if (count > coverage) {
+            throw broken("a count above its coverage");
+         }
+         if (coverage != 0) {
+            const double proportion = static_cast<double>(count) / static_cast<double>(coverage);
+            ++covered;
+            passes = passes || count > mustExceed(coverage, min_proportion);
+            highest = std::max(highest, proportion);
+            lowest = std::min(lowest, proportion);
+         }
+      }
+      const double difference = covered >= 2 ? highest - lowest : 0.0;
+      if (!passes || !(difference >= min_difference)) {
+         throw broken("a record that the rule does not select");
+      }
+      const std::string mutation =
+         SymbolType::symbolToChar(reference[position]) + std::to_string(position + 1) + SymbolType::symbolToChar(SymbolType::VALID_MUTATION_SYMBOLS[symbol]);
+      for (uint32_t g = 0; g < n_groups; ++g) {
+         const uint32_t count = of_groups[g * 2];
+         const uint32_t coverage = of_groups[g * 2 + 1];
+         QueryResultEntry& entry = results.query_result.emplace_back();
+         entry.fields.emplace("mutation", mutation);
+         entry.fields.emplace("sequenceName", name);
+         entry.fields.emplace("position", static_cast<int32_t>(position + 1));
+         entry.fields.emplace("group", groups[g].name);
+         entry.fields.emplace("count", static_cast<int32_t>(count));
+         entry.fields.emplace("coverage", static_cast<int32_t>(coverage));
+         entry.fields.emplace("proportion", coverage != 0 ? JsonValue{static_cast<double>(count) / static_cast<double>(coverage)} : JsonValue{std::nullopt});
+         entry.fields.emplace("difference", difference);
+      }
+   }
+   return results;
+}
+
+template class MutationsComparison<Nucleotide>;
+template class MutationsComparison<AminoAcid>;
 
 // ---- JSON -> the three actions ---------------------------------------------------------------------------
 namespace {
@@ -777,6 +963,32 @@ struct DistinctFilters {
    }
 };
 
+/// An entry of the groups field of Consensus and MutationsComparison, as the messages show it.
+const std::string GROUP_ENTRY_FORM = "{\"name\": string, \"filterExpression\": filter expression}";
+
+/// The entries of a groups field (`list`, an array) in request order: objects with a string name that no entry before had and a
+/// filterExpression, whose own complaint comes behind the field and the group.
+std::vector<std::pair<std::string, std::unique_ptr<filter_expressions::Expression>>> parseGroupEntries(const json::Value& list, const std::string& action_name) {
+   std::vector<std::pair<std::string, std::unique_ptr<filter_expressions::Expression>>> groups;
+   std::set<std::string> names;
+   for (const auto& element : list.items()) {
+      CHECK_SILO_QUERY(element.is_object(), action_name + " action: every entry of groups must be an object " + GROUP_ENTRY_FORM)
+      CHECK_SILO_QUERY(
+         element.contains("name") && element["name"].is_string(), action_name + " action: every entry of groups must contain the field name of type string"
+      )
+      const std::string group_name = element["name"].as_string();
+      CHECK_SILO_QUERY(names.insert(group_name).second, action_name + " action: the name '" + group_name + "' occurs more than once in groups")
+      const std::string owner = action_name + " action: the field filterExpression of the group '" + group_name + "'";
+      CHECK_SILO_QUERY(element.contains("filterExpression") && element["filterExpression"].is_object(), owner + " must be of type object (a filter expression)")
+      try {
+         groups.emplace_back(group_name, filter_expressions::parseExpression(element["filterExpression"]));
+      } catch (const QueryParseException& error) {
+         throw QueryParseException(owner + " is not a valid filter expression: " + error.what());
+      }
+   }
+   return groups;
+}
+
 }  // namespace
 
 template <typename SymbolType>
@@ -879,31 +1091,17 @@ std::unique_ptr<Action> parseConsensus(const json::Value& json) {
    CHECK_SILO_QUERY(
       (std::is_same_v<SymbolType, Nucleotide>) || sequence_name.has_value(), action_name + " action must contain the field sequenceName of type string (a gene)"
    )
-   const std::string entry_form = "{\"name\": string, \"filterExpression\": filter expression}";
    std::vector<typename ConsensusAction::Group> groups;
    if (json.contains("groups")) {
-      CHECK_SILO_QUERY(json["groups"].is_array(), action_name + " action: the field groups, if present, must be an array of objects " + entry_form)
+      CHECK_SILO_QUERY(json["groups"].is_array(), action_name + " action: the field groups, if present, must be an array of objects " + GROUP_ENTRY_FORM)
       const size_t n_groups = json["groups"].items().size();
       CHECK_SILO_QUERY(
          n_groups <= ConsensusAction::MAX_GROUPS,
          action_name + " action: the field groups holds " + std::to_string(n_groups) + " groups, more than the limit of " + std::to_string(ConsensusAction::MAX_GROUPS)
       )
       CHECK_SILO_QUERY(n_groups >= 1, action_name + " action: the field groups, if present, must hold at least one group")
-      std::set<std::string> names;
-      for (const auto& element : json["groups"].items()) {
-         CHECK_SILO_QUERY(element.is_object(), action_name + " action: every entry of groups must be an object " + entry_form)
-         CHECK_SILO_QUERY(
-            element.contains("name") && element["name"].is_string(), action_name + " action: every entry of groups must contain the field name of type string"
-         )
-         const std::string group_name = element["name"].as_string();
-         CHECK_SILO_QUERY(names.insert(group_name).second, action_name + " action: the name '" + group_name + "' occurs more than once in groups")
-         const std::string owner = action_name + " action: the field filterExpression of the group '" + group_name + "'";
-         CHECK_SILO_QUERY(element.contains("filterExpression") && element["filterExpression"].is_object(), owner + " must be of type object (a filter expression)")
-         try {
-            groups.push_back({group_name, filter_expressions::parseExpression(element["filterExpression"])});
-         } catch (const QueryParseException& error) {
-            throw QueryParseException(owner + " is not a valid filter expression: " + error.what());
-         }
+      for (auto& [group_name, filter] : parseGroupEntries(json["groups"], action_name)) {
+         groups.push_back({std::move(group_name), std::move(filter)});
       }
    } else {
       groups.push_back({std::nullopt, nullptr});  // the query's filter alone
@@ -923,5 +1121,52 @@ std::unique_ptr<Action> parseConsensus(const json::Value& json) {
 
 template std::unique_ptr<Action> parseConsensus<Nucleotide>(const json::Value& json);
 template std::unique_ptr<Action> parseConsensus<AminoAcid>(const json::Value& json);
+
+template <typename SymbolType>
+std::unique_ptr<Action> parseMutationsComparison(const json::Value& json) {
+   using Comparison = MutationsComparison<SymbolType>;
+   const std::string action_name = Comparison::actionName();
+   std::optional<std::string> sequence_name = optionalStringField(json, "sequenceName", action_name);
+   CHECK_SILO_QUERY(
+      (std::is_same_v<SymbolType, Nucleotide>) || sequence_name.has_value(), action_name + " action must contain the field sequenceName of type string (a gene)"
+   )
+   CHECK_SILO_QUERY(
+      json.contains("groups") && json["groups"].is_array(), action_name + " action must contain the field groups: an array of objects " + GROUP_ENTRY_FORM
+   )
+   const size_t n_groups = json["groups"].items().size();
+   CHECK_SILO_QUERY(
+      n_groups <= Comparison::MAX_GROUPS,
+      action_name + " action: the field groups holds " + std::to_string(n_groups) + " groups, more than the limit of " + std::to_string(Comparison::MAX_GROUPS)
+   )
+   CHECK_SILO_QUERY(
+      n_groups >= Comparison::MIN_GROUPS,
+      action_name + " action: the field groups holds " + std::to_string(n_groups) + " groups, fewer than the " + std::to_string(Comparison::MIN_GROUPS) +
+         " a comparison needs"
+   )
+   std::vector<typename Comparison::Group> groups;
+   for (auto& [group_name, filter] : parseGroupEntries(json["groups"], action_name)) {
+      groups.push_back({std::move(group_name), std::move(filter)});
+   }
+   double min_proportion = Comparison::DEFAULT_MIN_PROPORTION;
+   if (json.contains("minProportion")) {
+      CHECK_SILO_QUERY(
+         json["minProportion"].is_number(), action_name + " action: the field minProportion, if present, must be of type number with limits [0.0, 1.0]"
+      )
+      min_proportion = json["minProportion"].as_double();
+      CHECK_SILO_QUERY(min_proportion >= 0 && min_proportion <= 1, "Invalid proportion: minProportion must be in interval [0.0, 1.0]")
+   }
+   double min_difference = Comparison::DEFAULT_MIN_DIFFERENCE;
+   if (json.contains("minDifference")) {
+      CHECK_SILO_QUERY(
+         json["minDifference"].is_number() && json["minDifference"].as_double() >= 0 && json["minDifference"].as_double() <= 1,
+         action_name + " action: the field minDifference, if present, must be a number in [0, 1]"
+      )
+      min_difference = json["minDifference"].as_double();
+   }
+   return std::make_unique<Comparison>(std::move(sequence_name), std::move(groups), min_proportion, min_difference);
+}
+
+template std::unique_ptr<Action> parseMutationsComparison<Nucleotide>(const json::Value& json);
+template std::unique_ptr<Action> parseMutationsComparison<AminoAcid>(const json::Value& json);
 
 }  // namespace silo::query_engine::actions

@@ -118,6 +118,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_consensus_call",
     "silo_gpu_query_distances", "silo_gpu_nearest_rows", "silo_gpu_bitset_from_distances",
     "silo_gpu_position_symbols", "silo_gpu_haplotype_ids",
+    "silo_gpu_mutations_compare",
 ]
 
 _lib = None
@@ -205,6 +206,8 @@ def load_library():
     lib.silo_gpu_position_symbols.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_haplotype_ids.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp,
                                            ctypes.POINTER(vp), vp, vp]
+    lib.silo_gpu_mutations_compare.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_double, ctypes.c_double,
+                                               ctypes.c_uint32, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -808,7 +811,46 @@ def consensus_call(alphabet_id, counts, reference_index, threshold, min_depth, f
             device_free(ptr)
 
 
-MAX_HAPLOTYPE_POSITIONS = 12          # SILO_GPU_MAX_HAPLOTYPE_POSITIONS: the positions of one silo_gpu_position_symbols / silo_gpu_haplotype_ids
+MAX_COMPARISON_TABLES = 64     # SILO_GPU_MAX_COMPARISON_TABLES: the count tables (groups) of one silo_gpu_mutations_compare
+COMPARE_THREADS = 256          # SILO_GPU_COMPARE_THREADS: the positions that a block of K17 owns
+COMPARE_HEADER_WORDS = 4       # word 0: the selected cells; the others 0
+
+
+def mutations_compare(alphabet_id, counts, reference_index, min_proportion, min_difference, capacity, fill=None, guard_bytes=0, calls=1, null=(),
+                      n_tables=None, stream=None):
+    """silo_gpu_mutations_compare (K17) over host counts uint32 [n_tables][n_positions][n_symbols] and reference_index uint8
+    [n_positions]: (out uint32 [4 + capacity * 2 + capacity * n_tables * 2 + guard_bytes / 4], the status of the last call).  The
+    output is filled with the byte `fill` before the first of `calls` launches, so a test can see what is written, that nothing
+    behind it is, and that a second call adds nothing.  A status other than 0 is returned, not raised: the refusals leave the output
+    as it was.  null: which of "counts", "reference", "out" the call gets as NULL.  n_tables: what the call is told instead of the
+    number of tables there are (fewer, or a number the call refuses)."""
+    lib = load_library()
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    tables, n_positions = counts.shape[:2]
+    told = tables if n_tables is None else int(n_tables)
+    reference_index = np.ascontiguousarray(reference_index, dtype=np.uint8)
+    words = COMPARE_HEADER_WORDS + int(capacity) * 2 + int(capacity) * tables * 2 + int(guard_bytes) // 4
+    counts_dev = device_malloc(counts.nbytes)
+    reference_dev = device_malloc(reference_index.nbytes)
+    out = device_malloc(words * 4, fill, stream)
+    try:
+        if counts.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(counts_dev, _ptr(counts), counts.nbytes, stream))
+        if reference_index.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(reference_dev, _ptr(reference_index), reference_index.nbytes, stream))
+        status = 0
+        for _ in range(calls):
+            status = lib.silo_gpu_mutations_compare(
+                _abi_alphabet(alphabet_id), None if "counts" in null else counts_dev, told, n_positions, None if "reference" in null else reference_dev,
+                min_proportion, min_difference, capacity, None if "out" in null else out, stream)
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(out, np.uint32, words, stream), status
+    finally:
+        for ptr in (counts_dev, reference_dev, out):
+            device_free(ptr)
+
+
+MAX_HAPLOTYPE_POSITIONS = 12         # SILO_GPU_MAX_HAPLOTYPE_POSITIONS: the positions of one silo_gpu_position_symbols / silo_gpu_haplotype_ids
 HAPLOTYPE_POSITIONS_PER_COLUMN = 6    # SILO_GPU_HAPLOTYPE_POSITIONS_PER_COLUMN: 16^6 = 2^24, 25^6 < 2^28: an id column is a uint32
 ALL_SYMBOLS_COMPLETE = 0xFFFFFFFF     # complete_symbols of silo_gpu_haplotype_ids: no row is left out
 
