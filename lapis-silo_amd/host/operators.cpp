@@ -2,6 +2,7 @@
 // Reference: src/silo/query_engine/operators/*.cpp, src/silo/query_engine/operator_result.cpp.
 #include <algorithm>
 #include <bit>
+#include <deque>
 #include <mutex>
 #include <shared_mutex>
 
@@ -51,6 +52,12 @@ uint32_t readCount(const DeviceBuffer& counter) {
 bool isLeafOperand(uint32_t operand) {
    return operand >= SILO_GPU_LEAF_OPERAND;
 }
+
+/// allocRun() found no free run of slots.  ProgramBuilder::lowerChild takes the child it was lowering out of the program
+/// again and evaluates it on its own; anywhere else this is a bug of the size estimates.
+struct SlotsExhausted : QueryCompilationException {
+   SlotsExhausted() : QueryCompilationException("Internal error: the filter program ran out of device slots") {}
+};
 
 }  // namespace
 
@@ -166,7 +173,7 @@ uint32_t ProgramBuilder::allocRun(uint32_t count) {
          return first;
       }
    }
-   throw QueryCompilationException("Compilation Error: filter expression needs more than " + std::to_string(SILO_GPU_MAX_SLOTS) + " device slots");
+   throw SlotsExhausted();
 }
 
 uint32_t ProgramBuilder::allocSlot() {
@@ -203,10 +210,8 @@ uint32_t ProgramBuilder::sparseLeaf(uint32_t seqstore_id, uint32_t position, uin
 }
 
 uint32_t ProgramBuilder::leafRun(const std::vector<const uint64_t*>& columns) {
-   if (leaves.size() + columns.size() > SILO_GPU_MAX_LEAVES) {
-      throw QueryCompilationException(
-         "Compilation Error: filter expression reads more than " + std::to_string(SILO_GPU_MAX_LEAVES) + " stored columns in one device program"
-      );
+   if (leaves.size() + columns.size() > SILO_GPU_MAX_LEAVES) {  // the callers cut their runs to what is left
+      throw QueryCompilationException("Internal error: a run of stored columns does not fit the leaves of the filter program");
    }
    const auto first = static_cast<uint32_t>(leaves.size());
    leaves.insert(leaves.end(), columns.begin(), columns.end());  // consecutive, not de-duplicated
@@ -281,20 +286,117 @@ uint64_t* ProgramBuilder::temporaryBitset() {
    return pointer;
 }
 
+bool ProgramBuilder::fits(const operators::Cost& cost) const {
+   return code.size() / 2 + cost.instructions + 8 <= SILO_GPU_MAX_INSTRUCTIONS && leaves.size() + cost.leaves + 1 <= SILO_GPU_MAX_LEAVES &&
+          static_cast<uint32_t>(std::popcount(used_slots)) + cost.slots + 1 <= SILO_GPU_MAX_SLOTS;
+}
+
+bool ProgramBuilder::hasRoom(uint32_t more_leaves, uint32_t more_instructions) const {
+   return leaves.size() + more_leaves <= SILO_GPU_MAX_LEAVES && code.size() / 2 + more_instructions + 1 <= SILO_GPU_MAX_INSTRUCTIONS;
+}
+
+size_t ProgramBuilder::leafRoom() const {
+   return SILO_GPU_MAX_LEAVES - leaves.size();
+}
+
 uint32_t ProgramBuilder::lowerChild(const operators::Operator& child) {
-   const operators::Cost cost = child.cost();
-   const size_t instructions_after = code.size() / 2 + cost.instructions + 8;
-   const size_t leaves_after = leaves.size() + cost.leaves + 1;
-   const bool fits = instructions_after <= SILO_GPU_MAX_INSTRUCTIONS && leaves_after <= SILO_GPU_MAX_LEAVES;
-   const bool child_alone_fits = cost.instructions + 8 <= SILO_GPU_MAX_INSTRUCTIONS && cost.leaves + 1 <= SILO_GPU_MAX_LEAVES;
-   if (fits || !child_alone_fits) {
-      // too big even alone: descend — its own children are materialised one level down
-      return child.lower(*this);
+   return lowerChild(child, child.cost());
+}
+
+uint32_t ProgramBuilder::lowerChild(const operators::Operator& child, const operators::Cost& cost) {
+   if (fits(cost)) {
+      const size_t code_size = code.size();
+      const size_t leaf_count = leaves.size();
+      const uint32_t slots = used_slots;
+      const uint32_t water = high_water;
+      try {
+         return child.lower(*this);
+      } catch (const SlotsExhausted&) {
+         // Cost::slots counts live slots; first-fit runs can leave holes between them.  Take back what the child emitted and
+         // give it a program of its own.  The child is lowered a second time there: launches that its first lowering queued
+         // (metadata comparisons, leaves fetched from other ranks) are issued again, their buffers stay with this builder.
+         code.resize(code_size);
+         leaves.resize(leaf_count);
+         used_slots = slots;
+         high_water = water;
+      }
    }
+   // a program of its own, whose root cuts itself into as many programs as it needs
    OperatorResult result = child.evaluate();
    const uint32_t operand = SILO_GPU_LEAF_OPERAND + leaf(result.bitset());
    materialized_children.push_back(std::move(result));
    return operand;
+}
+
+void ProgramBuilder::restart() {
+   code.clear();
+   leaves.clear();
+   used_slots = 0;
+   high_water = 0;
+}
+
+uint32_t ProgramBuilder::flush(uint32_t operand) {
+   if (operand == NO_OPERAND) {
+      throw QueryCompilationException("Internal error: a filter program is full before it holds a value");
+   }
+   uint64_t* partial = temporaryBitset();
+   run(operand, partial, nullptr, queryStream());  // waits for the launch: the code and leaf arrays are written again at once
+   restart();
+   return SILO_GPU_LEAF_OPERAND + leaf(partial);
+}
+
+std::vector<const uint64_t*> ProgramBuilder::flushPlanes(uint32_t first, uint32_t planes) {
+   std::vector<const uint64_t*> partial;
+   const size_t code_size = code.size();
+   for (uint32_t plane = 0; plane < planes; ++plane) {
+      uint64_t* bitset = temporaryBitset();
+      run(first + plane, bitset, nullptr, queryStream());
+      code.resize(code_size);  // without the MOV of this plane
+      partial.push_back(bitset);
+   }
+   restart();
+   return partial;
+}
+
+void ProgramBuilder::combine(uint32_t& acc, uint32_t op, uint32_t operand) {
+   if (acc == NO_OPERAND) {
+      acc = operand;
+      return;
+   }
+   const uint32_t dst = isLeafOperand(acc) ? (isLeafOperand(operand) ? allocSlot() : operand) : acc;
+   emit(op, dst, acc, operand);
+   if (dst != operand) {
+      freeSlot(operand);
+   }
+   acc = dst;
+}
+
+void ProgramBuilder::foldColumns(uint32_t& acc, uint32_t fold_n, uint32_t op, const std::vector<const uint64_t*>& columns, bool may_flush) {
+   for (size_t done = 0; done < columns.size();) {
+      size_t take = columns.size() - done;
+      if (may_flush) {
+         if (!hasRoom(take >= 2 ? 2 : 1, 2)) {
+            acc = flush(acc);
+         }
+         take = std::min(take, leafRoom());
+      }
+      if (take == 1) {
+         combine(acc, op, SILO_GPU_LEAF_OPERAND + leaf(columns[done]));
+      } else {
+         const uint32_t folded = allocSlot();
+         emit(fold_n, folded, 0, 0, leafRun({columns.begin() + static_cast<ptrdiff_t>(done), columns.begin() + static_cast<ptrdiff_t>(done + take)}));
+         combine(acc, op, folded);
+      }
+      done += take;
+   }
+}
+
+uint32_t ProgramBuilder::lowerChildBeside(uint32_t& acc, const operators::Operator& child, bool may_flush) {
+   const operators::Cost cost = child.cost();
+   if (may_flush && acc != NO_OPERAND && !code.empty() && !fits(cost)) {
+      acc = flush(acc);
+   }
+   return lowerChild(child, cost);
 }
 
 silo_gpu_bitprog ProgramBuilder::finishProgram(uint32_t result_slot) {
@@ -302,8 +404,8 @@ silo_gpu_bitprog ProgramBuilder::finishProgram(uint32_t result_slot) {
       emit(SILO_GPU_OP_MOV, 0, result_slot);
       high_water = std::max(high_water, 1u);
    }
-   if (code.size() / 2 > SILO_GPU_MAX_INSTRUCTIONS || leaves.size() > SILO_GPU_MAX_LEAVES) {
-      throw QueryCompilationException("Compilation Error: filter expression does not fit one device program");
+   if (code.size() / 2 > SILO_GPU_MAX_INSTRUCTIONS || leaves.size() > SILO_GPU_MAX_LEAVES) {  // every lowering keeps to what is left
+      throw QueryCompilationException("Internal error: a filter program outgrew the device limits");
    }
    silo_gpu_bitprog program{};
    program.n_instructions = static_cast<uint32_t>(code.size() / 2);
@@ -370,21 +472,50 @@ OperatorVector copyAll(const OperatorVector& source) {
    return out;
 }
 
-Cost sumCost(const OperatorVector& a, const OperatorVector* b = nullptr) {
+/// Instructions and leaves of the children of an n-ary node (one combining instruction per child, two per negated one), and the
+/// slots of a fold of them: the accumulator, once two leaf operands or a composite child have made it a slot, beside the child
+/// that is being lowered.  (Threshold keeps a counter instead and takes `widest_child`.)
+struct FoldCost {
    Cost total;
-   for (const auto& child : a) {
-      const Cost c = child->cost();
-      total.instructions += c.instructions + 1;
-      total.leaves += c.leaves;
-   }
-   if (b != nullptr) {
-      for (const auto& child : *b) {
+   uint32_t widest_child = 0;
+};
+
+FoldCost sumCost(const OperatorVector& a, const OperatorVector* b = nullptr) {
+   FoldCost out;
+   bool accumulator = false;  // whether the fold's value sits in a slot by now
+   // One pass over the children of one sign.  Their leaf operands are taken as if they all came first (never too few slots):
+   // `leaf_fold` of them put the accumulator into a slot, which costs `leaf_slots` beside it.
+   const auto add = [&](const OperatorVector& children, uint32_t combining, uint32_t leaf_fold, uint32_t leaf_slots) {
+      uint32_t leaf_operands = 0;
+      uint32_t first = 0;  // the slots of the first child whose value arrives in a slot, and of the widest after it
+      uint32_t later = 0;
+      for (const auto& child : children) {
          const Cost c = child->cost();
-         total.instructions += c.instructions + 2;
-         total.leaves += c.leaves;
+         out.total.instructions += c.instructions + combining;
+         out.total.leaves += c.leaves;
+         out.widest_child = std::max(out.widest_child, c.slots);
+         if (c.slots == 0) {
+            ++leaf_operands;
+         } else if (first == 0) {
+            first = c.slots;
+         } else {
+            later = std::max(later, c.slots);
+         }
       }
+      if (leaf_operands >= leaf_fold) {
+         out.total.slots = std::max(out.total.slots, (accumulator ? 1u : 0u) + leaf_slots);
+         accumulator = true;
+      }
+      if (first != 0) {
+         out.total.slots = std::max({out.total.slots, (accumulator ? 1u : 0u) + first, later == 0 ? 0u : 1u + later});
+         accumulator = true;
+      }
+   };
+   add(a, 1, 2, 1);  // two leaf operands fold into one slot
+   if (b != nullptr) {
+      add(*b, 2, 1, 1);  // the OR_N of the negated columns, or the slot that ANDNOT of two leaf operands needs
    }
-   return total;
+   return out;
 }
 
 }  // namespace
@@ -457,11 +588,13 @@ std::unique_ptr<Operator> Selection::negate() const {  // selection.cpp:125-130
 }
 
 Cost Selection::cost() const {
-   Cost total{static_cast<uint32_t>(predicates.size()) + 1, static_cast<uint32_t>(predicates.size())};
+   const uint32_t accumulator = predicates.size() >= 2 ? 1 : 0;
+   Cost total{static_cast<uint32_t>(predicates.size()) + 1, static_cast<uint32_t>(predicates.size()), std::max(accumulator, predicates.empty() ? 1u : 0u)};
    if (child != nullptr) {
       const Cost child_cost = child->cost();
       total.instructions += child_cost.instructions;
       total.leaves += child_cost.leaves;
+      total.slots = accumulator + std::max(child_cost.slots, 1u);
    }
    return total;
 }
@@ -470,6 +603,7 @@ uint32_t Selection::lower(ProgramBuilder& builder) const {
    // The reference probes every predicate row by row (selection.cpp:88-108).  Here each predicate is one pass of
    // k_bitset_from_compare over its column (4-8 bytes per row, on the query's stream, ahead of the fused program),
    // and the program ANDs the resulting bitsets like any other stored columns.
+   const bool may_flush = builder.empty();
    std::vector<const uint64_t*> columns;
    for (const Predicate& predicate : predicates) {
       uint64_t* bitset = builder.temporaryBitset();
@@ -482,32 +616,15 @@ uint32_t Selection::lower(ProgramBuilder& builder) const {
       );
       columns.push_back(bitset);
    }
-   uint32_t acc = 0;
-   bool have = false;
-   if (columns.size() >= 2) {
-      acc = builder.allocSlot();
-      builder.emit(SILO_GPU_OP_AND_N, acc, 0, 0, builder.leafRun(columns));
-      have = true;
-   } else if (columns.size() == 1) {
-      acc = SILO_GPU_LEAF_OPERAND + builder.leaf(columns[0]);
-      have = true;
-   }
+   uint32_t acc = ProgramBuilder::NO_OPERAND;
+   builder.foldColumns(acc, SILO_GPU_OP_AND_N, SILO_GPU_OP_AND, columns, may_flush);
    if (child != nullptr) {
-      const uint32_t child_operand = builder.lowerChild(*child);
-      if (!have) {
-         return child_operand;
-      }
-      const uint32_t dst = isLeafOperand(acc) ? (isLeafOperand(child_operand) ? builder.allocSlot() : child_operand) : acc;
-      builder.emit(SILO_GPU_OP_AND, dst, acc, child_operand);
-      if (dst != child_operand && !isLeafOperand(child_operand)) {
-         builder.freeSlot(child_operand);
-      }
-      return dst;
+      const uint32_t operand = builder.lowerChildBeside(acc, *child, may_flush);
+      builder.combine(acc, SILO_GPU_OP_AND, operand);
    }
-   if (!have) {  // no predicate at all: every row
-      const uint32_t slot = builder.allocSlot();
-      builder.emit(SILO_GPU_OP_ONES, slot);
-      return slot;
+   if (acc == ProgramBuilder::NO_OPERAND) {  // no predicate at all: every row
+      acc = builder.allocSlot();
+      builder.emit(SILO_GPU_OP_ONES, acc);
    }
    return acc;
 }
@@ -599,6 +716,7 @@ uint32_t Complement::lower(ProgramBuilder& builder) const {  // flip(0,row_count
 Cost Complement::cost() const {
    Cost c = child->cost();
    c.instructions += 1;
+   c.slots = std::max(c.slots, 1u);
    return c;
 }
 
@@ -634,46 +752,26 @@ uint32_t Intersection::lower(ProgramBuilder& builder) const {
    // The reference orders children by cardinality to keep roaring intermediates small
    // (intersection.cpp:94-108); a dense word-parallel AND has no such sensitivity.  Children that are
    // stored columns are folded by ONE n-ary instruction (streamed 8 loads at a time).
+   // A node too wide for one program (only the root of a program is) is folded in pieces: see ProgramBuilder::flush.
+   const bool may_flush = builder.empty();
    const ProgramBuilder::Split positive = builder.split(children);
    const ProgramBuilder::Split negative = builder.split(negated_children);
-   constexpr uint32_t NONE = ~0u;
-   uint32_t acc = NONE;
-   const auto combine = [&](uint32_t op, uint32_t tmp) {
-      if (acc == NONE) {
-         acc = tmp;
-         return;
-      }
-      const uint32_t dst = isLeafOperand(acc) ? (isLeafOperand(tmp) ? builder.allocSlot() : tmp) : acc;
-      builder.emit(op, dst, acc, tmp);
-      if (dst != tmp) {
-         builder.freeSlot(tmp);
-      }
-      acc = dst;
-   };
-   if (positive.columns.size() >= 2) {
-      acc = builder.allocSlot();
-      builder.emit(SILO_GPU_OP_AND_N, acc, 0, 0, builder.leafRun(positive.columns));
-   } else if (positive.columns.size() == 1) {
-      acc = SILO_GPU_LEAF_OPERAND + builder.leaf(positive.columns[0]);
-   }
+   uint32_t acc = ProgramBuilder::NO_OPERAND;
+   builder.foldColumns(acc, SILO_GPU_OP_AND_N, SILO_GPU_OP_AND, positive.columns, may_flush);
    for (const Operator* child : positive.composite) {
-      combine(SILO_GPU_OP_AND, builder.lowerChild(*child));
+      const uint32_t operand = builder.lowerChildBeside(acc, *child, may_flush);
+      builder.combine(acc, SILO_GPU_OP_AND, operand);
    }
-   // children is never empty (constructor), so acc is set here
-   if (negative.columns.size() >= 2) {
-      const uint32_t tmp = builder.allocSlot();
-      builder.emit(SILO_GPU_OP_OR_N, tmp, 0, 0, builder.leafRun(negative.columns));
-      combine(SILO_GPU_OP_ANDNOT, tmp);
-   } else if (negative.columns.size() == 1) {
-      combine(SILO_GPU_OP_ANDNOT, SILO_GPU_LEAF_OPERAND + builder.leaf(negative.columns[0]));
-   }
+   // children is never empty (constructor), so acc is set here; acc &~ (a | b) = (acc &~ a) &~ b lets the negated runs be cut too
+   builder.foldColumns(acc, SILO_GPU_OP_OR_N, SILO_GPU_OP_ANDNOT, negative.columns, may_flush);
    for (const Operator* child : negative.composite) {
-      combine(SILO_GPU_OP_ANDNOT, builder.lowerChild(*child));
+      const uint32_t operand = builder.lowerChildBeside(acc, *child, may_flush);
+      builder.combine(acc, SILO_GPU_OP_ANDNOT, operand);
    }
    return acc;
 }
 Cost Intersection::cost() const {
-   return sumCost(children, &negated_children);
+   return sumCost(children, &negated_children).total;
 }
 
 // ---- Union (union.cpp) --------------------------------------------------------------------------
@@ -699,32 +797,19 @@ uint32_t Union::lower(ProgramBuilder& builder) const {
       builder.emit(SILO_GPU_OP_ZERO, slot);
       return slot;
    }
+   const bool may_flush = builder.empty();
    const ProgramBuilder::Split parts = builder.split(children);
-   constexpr uint32_t NONE = ~0u;
-   uint32_t acc = NONE;
-   if (parts.columns.size() >= 2) {  // roaring fastunion (union.cpp:44) -> one streamed n-ary OR
-      acc = builder.allocSlot();
-      builder.emit(SILO_GPU_OP_OR_N, acc, 0, 0, builder.leafRun(parts.columns));
-   } else if (parts.columns.size() == 1) {
-      acc = SILO_GPU_LEAF_OPERAND + builder.leaf(parts.columns[0]);
-   }
+   uint32_t acc = ProgramBuilder::NO_OPERAND;
+   // roaring fastunion (union.cpp:44) -> one streamed n-ary OR (several, with a flush between them, beyond the leaves of a program)
+   builder.foldColumns(acc, SILO_GPU_OP_OR_N, SILO_GPU_OP_OR, parts.columns, may_flush);
    for (const Operator* child : parts.composite) {
-      const uint32_t tmp = builder.lowerChild(*child);
-      if (acc == NONE) {
-         acc = tmp;
-         continue;
-      }
-      const uint32_t dst = isLeafOperand(acc) ? (isLeafOperand(tmp) ? builder.allocSlot() : tmp) : acc;
-      builder.emit(SILO_GPU_OP_OR, dst, acc, tmp);
-      if (dst != tmp) {
-         builder.freeSlot(tmp);
-      }
-      acc = dst;
+      const uint32_t operand = builder.lowerChildBeside(acc, *child, may_flush);
+      builder.combine(acc, SILO_GPU_OP_OR, operand);
    }
    return acc;
 }
 Cost Union::cost() const {
-   Cost c = sumCost(children);
+   Cost c = sumCost(children).total;
    c.instructions += 1;
    return c;
 }
@@ -767,12 +852,15 @@ uint32_t Threshold::lower(ProgramBuilder& builder) const {
    // ceil(log2(k+1)) slots, one ripple-carry add per child, one comparison with n at the end.
    const uint32_t k = static_cast<uint32_t>(non_negated_children.size() + negated_children.size());
    const uint32_t bits = static_cast<uint32_t>(std::bit_width(k));
+   const ProgramBuilder::Split positive = builder.split(non_negated_children);
+   const ProgramBuilder::Split negative = builder.split(negated_children);
+   if (builder.empty() && !builder.fits(cost())) {  // the root of a program, and possibly too wide for one
+      return lowerInPieces(builder, positive, negative, bits);
+   }
    const uint32_t counter = builder.allocRun(bits);
    for (uint32_t bit = 0; bit < bits; ++bit) {
       builder.emit(SILO_GPU_OP_ZERO, counter + bit);
    }
-   const ProgramBuilder::Split positive = builder.split(non_negated_children);
-   const ProgramBuilder::Split negative = builder.split(negated_children);
    if (!positive.columns.empty()) {
       builder.emit(SILO_GPU_OP_CNT_ADD_N, counter, 0, bits, builder.leafRun(positive.columns));
    }
@@ -796,9 +884,98 @@ uint32_t Threshold::lower(ProgramBuilder& builder) const {
    builder.freeRun(counter, bits);
    return result;
 }
+
+uint32_t Threshold::lowerInPieces(
+   ProgramBuilder& builder, const ProgramBuilder::Split& positive, const ProgramBuilder::Split& negative, uint32_t bits
+) const {
+   // The counter lives in slots and a program hands out one slot.  So a program that is full is run once per plane of its partial
+   // count (ProgramBuilder::flushPlanes), and plane j comes back as a term of weight 1 << j, which CNT_ADD adds into the next
+   // program's counter from bit j up.  The terms are taken in the order of lower(), planes last: a node that does fit one
+   // program gets the program of lower().  Every program takes more terms than the planes it returns, so this ends.  A composite
+   // child that fits no program is evaluated on its own by lowerChild; when terms were taken before it, the program is cut in
+   // front of it first (it might have fitted the next one), which costs a round of plane launches per such child.
+   struct Term {
+      const uint64_t* column;     // a stored column, or a plane of a partial count
+      const Operator* composite;  // or a sub-tree
+      bool negated;
+      uint32_t shift;
+   };
+   std::deque<Term> terms;
+   for (const uint64_t* column : positive.columns) {
+      terms.push_back({column, nullptr, false, 0});
+   }
+   for (const uint64_t* column : negative.columns) {
+      terms.push_back({column, nullptr, true, 0});
+   }
+   for (const Operator* child : positive.composite) {
+      terms.push_back({nullptr, child, false, 0});
+   }
+   for (const Operator* child : negative.composite) {
+      terms.push_back({nullptr, child, true, 0});
+   }
+   const size_t first_plane = terms.size();  // the terms before it are the children
+   size_t taken = 0;
+   while (true) {
+      const uint32_t counter = builder.allocRun(bits);
+      for (uint32_t bit = 0; bit < bits; ++bit) {
+         builder.emit(SILO_GPU_OP_ZERO, counter + bit);
+      }
+      uint64_t largest = 0;  // the largest count this program can reach
+      bool full = false;
+      while (taken < terms.size() && !full) {
+         const Term term = terms[taken];
+         if (term.composite != nullptr) {
+            const Cost cost = term.composite->cost();
+            if (largest > 0 && !builder.fits(cost)) {
+               full = true;
+               continue;
+            }
+            uint32_t operand = builder.lowerChild(*term.composite, cost);
+            if (term.negated) {
+               const uint32_t tmp = isLeafOperand(operand) ? builder.allocSlot() : operand;
+               builder.emit(SILO_GPU_OP_NOT, tmp, operand);
+               operand = tmp;
+            }
+            builder.emit(SILO_GPU_OP_CNT_ADD, counter, operand, bits);
+            builder.freeSlot(operand);
+            largest += 1;
+            ++taken;
+         } else if (!builder.hasRoom(1, 2)) {
+            full = true;
+         } else if (taken >= first_plane) {
+            builder.emit(SILO_GPU_OP_CNT_ADD, counter + term.shift, SILO_GPU_LEAF_OPERAND + builder.leaf(term.column), bits - term.shift);
+            largest += uint64_t{1} << term.shift;
+            ++taken;
+         } else {  // the run of columns of this sign, or as much of it as fits
+            std::vector<const uint64_t*> columns;
+            while (taken < first_plane && columns.size() < builder.leafRoom() && terms[taken].composite == nullptr && terms[taken].negated == term.negated) {
+               columns.push_back(terms[taken++].column);
+            }
+            builder.emit(term.negated ? SILO_GPU_OP_CNT_ADD_NOT_N : SILO_GPU_OP_CNT_ADD_N, counter, 0, bits, builder.leafRun(columns));
+            largest += columns.size();
+         }
+      }
+      if (taken == terms.size()) {
+         const uint32_t result = builder.allocSlot();
+         builder.emit(match_exactly ? SILO_GPU_OP_CNT_EQ : SILO_GPU_OP_CNT_GE, result, counter, bits, number_of_matchers);
+         builder.freeRun(counter, bits);
+         return result;
+      }
+      // no count exceeds k < 1 << bits, so `bits` planes hold any partial count
+      const uint32_t planes = std::min(bits, static_cast<uint32_t>(std::bit_width(largest)));
+      const std::vector<const uint64_t*> partial = builder.flushPlanes(counter, planes);
+      for (uint32_t plane = 0; plane < planes; ++plane) {
+         terms.push_back({partial[plane], nullptr, false, plane});
+      }
+   }
+}
 Cost Threshold::cost() const {
-   Cost c = sumCost(non_negated_children, &negated_children);
-   c.instructions += 8;
+   // what lower() emits: the ZEROs of the counter, an n-ary add per sign, the comparison; the counter beside the widest child
+   const uint32_t bits = static_cast<uint32_t>(std::bit_width(non_negated_children.size() + negated_children.size()));
+   const FoldCost children = sumCost(non_negated_children, &negated_children);
+   Cost c = children.total;
+   c.instructions += bits + 3;
+   c.slots = bits + std::max(children.widest_child, 1u);
    return c;
 }
 

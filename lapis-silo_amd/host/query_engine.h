@@ -68,6 +68,7 @@ struct RowSpace {
 
 namespace operators {
 class Operator;
+struct Cost;
 }
 
 /// Result of Operator::evaluate.  The reference holds a (borrowed or owned) roaring bitmap; here the
@@ -131,9 +132,38 @@ class ProgramBuilder {
       std::vector<const operators::Operator*> composite;
    };
    Split split(const std::vector<std::unique_ptr<operators::Operator>>& children);
-   /// Lowers `child` into this program, or — when it would not fit the instruction / leaf budget —
-   /// evaluates it with its own launch and loads the result as a leaf.
+   /// Lowers `child` into this program, or — when it would not fit the instruction / leaf / slot budget that is left —
+   /// evaluates it with launches of its own and loads the result as a leaf.
    uint32_t lowerChild(const operators::Operator& child);
+   uint32_t lowerChild(const operators::Operator& child, const operators::Cost& cost);  // with child.cost() at hand
+
+   // An expression that needs more than one device program is evaluated in pieces.  Only the node that was lowered into an
+   // EMPTY builder (the root of a program, or the only child of such a node) may cut: nothing but its own accumulator is live
+   // then.  Every other node was let into the program by lowerChild because its whole cost fitted, so it never needs to.
+   /// Nothing lowered so far: the node that begins now may flush().
+   [[nodiscard]] bool empty() const { return code.empty() && leaves.empty() && used_slots == 0; }
+   /// Whether a sub-tree of this cost fits what is left of the program (with room for the parent to combine it).
+   [[nodiscard]] bool fits(const operators::Cost& cost) const;
+   /// Room for `leaves` more leaves and `instructions` more instructions (besides the final MOV)?
+   [[nodiscard]] bool hasRoom(uint32_t leaves, uint32_t instructions) const;
+   /// The leaves that are left.
+   [[nodiscard]] size_t leafRoom() const;
+   /// Runs the program so far with `operand` as its result into a temporary bitset, starts a fresh program and returns
+   /// that bitset as its first leaf operand.  Only for the node that began in an empty() builder.
+   uint32_t flush(uint32_t operand);
+   /// flush() for `planes` results of one program (the planes of a Threshold's counter, slots first .. first+planes-1): one
+   /// launch per plane.  Starts a fresh program; the bitsets are NOT leaves of it yet.
+   std::vector<const uint64_t*> flushPlanes(uint32_t first, uint32_t planes);
+   /// acc = acc `op` operand, in place where one of the two is a slot (acc == NO_OPERAND: acc = operand).
+   static constexpr uint32_t NO_OPERAND = ~0u;
+   void combine(uint32_t& acc, uint32_t op, uint32_t operand);
+   /// acc = acc `op` fold_n(columns): one n-ary instruction where the run fits the program; in a builder that `may_flush`, runs
+   /// of what fits with a flush() between them (both folds are associative, and so is ANDNOT of an OR-run).
+   void foldColumns(uint32_t& acc, uint32_t fold_n, uint32_t op, const std::vector<const uint64_t*>& columns, bool may_flush);
+   /// lowerChild for a composite child of an n-ary node whose value so far is `acc`: when the child does not fit what is left,
+   /// but more would be left after a flush() of the accumulator, it flushes first.  (A child that fits no program is then
+   /// evaluated on its own by lowerChild.)
+   uint32_t lowerChildBeside(uint32_t& acc, const operators::Operator& child, bool may_flush);
 
    /// Launches the program (result expected in `result_slot`).
    void run(uint32_t result_slot, uint64_t* out_bitset, uint64_t* out_count, void* stream);
@@ -150,6 +180,7 @@ class ProgramBuilder {
    const RowSpace rows;
 
   private:
+   void restart();  // a fresh program; buffers and materialised children stay with the builder
    std::vector<uint32_t> code;
    std::vector<const uint64_t*> leaves;
    std::vector<DeviceBuffer> temporaries;
@@ -166,9 +197,12 @@ enum Type {
    EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION
 };
 
+/// What lowering a sub-tree into a program takes at most.  `slots`: the slots that are live at once while it is lowered, its
+/// result included; 0 says that the result is a leaf operand.
 struct Cost {
    uint32_t instructions = 0;
    uint32_t leaves = 0;
+   uint32_t slots = 0;
 };
 
 class Operator {
@@ -203,7 +237,7 @@ class Empty : public Operator {
    std::unique_ptr<Operator> copy() const override;
    std::unique_ptr<Operator> negate() const override;
    uint32_t lower(ProgramBuilder& builder) const override;
-   Cost cost() const override { return {1, 0}; }
+   Cost cost() const override { return {1, 0, 1}; }
 };
 
 class Full : public Operator {
@@ -214,7 +248,7 @@ class Full : public Operator {
    std::unique_ptr<Operator> copy() const override;
    std::unique_ptr<Operator> negate() const override;
    uint32_t lower(ProgramBuilder& builder) const override;
-   Cost cost() const override { return {1, 0}; }
+   Cost cost() const override { return {1, 0, 1}; }
 };
 
 /// index_scan.cpp: borrows a stored bitmap; here a dense plane pointer in HBM, or a sparse symbol.
@@ -256,7 +290,7 @@ class BitmapSelection : public Operator {
    std::unique_ptr<Operator> negate() const override;
    uint32_t lower(ProgramBuilder& builder) const override;
    const uint64_t* storedColumn(ProgramBuilder& builder) const override;
-   Cost cost() const override { return {2, 1}; }
+   Cost cost() const override { return {2, 1, comparator == CONTAINS ? 0u : 1u}; }
 
    const uint64_t* missing_plane;
    Comparator comparator;
@@ -391,6 +425,10 @@ class Threshold : public Operator {
    OperatorVector negated_children;
    uint32_t number_of_matchers;
    bool match_exactly;
+
+  private:
+   /// lower() for the root of a program whose children may not fit it: as many programs as they need.
+   uint32_t lowerInPieces(ProgramBuilder& builder, const ProgramBuilder::Split& positive, const ProgramBuilder::Split& negative, uint32_t bits) const;
 };
 
 }  // namespace operators

@@ -131,6 +131,47 @@ def test_count_slot_evaluator_with_16_leaf_loads_in_flight(built, n):
         lib.silo_gpu_tune(TUNE_EVAL_LEAF_BATCH, previous)
 
 
+@pytest.mark.parametrize("n", [777, 8193, 65_537])
+def test_batch_evaluator_slot_classes_in_shuffled_order(built, n):
+    """silo_gpu_filter_eval_batch sorts its programs into launches of <= 8, <= 16 and <= 32 slots: the programs of A (1, 2, 4, 6, 12,
+    16, 17 and 32 slots, the 19-leaf runs), some without an output bitset.  First a batch of 3, one program of each class with the
+    widest first, then one of 40 in a shuffled order, so that the thread's scratch regrows.  Every count equals numpy and
+    silo_gpu_filter_eval; every bitset that was asked for equals both, with zero padding."""
+    rng = np.random.default_rng(2000 + n)
+    masks = _eval_masks(rng, n)
+    with _plain_store(n) as store:
+        leaves = _upload_masks(store, masks)
+        known = _count_slot_programs(masks)
+        assert {n_slots for _, n_slots, _ in known} >= {1, 2, 4, 6, 12, 16, 17, 32}
+        singles = [_eval(store, code, leaves, n_slots) for code, n_slots, _ in known]  # silo_gpu_filter_eval: (words, count)
+        for index, ((words, count), (_, _, want)) in enumerate(zip(singles, known)):
+            assert count == int(want.sum()), index
+        outs = [store.bitset_alloc() for _ in range(40)]
+        by_slots = {n_slots: index for index, (_, n_slots, _) in enumerate(known)}
+        for size in (3, 40):
+            if size == 3:  # one program of each slot class, the widest first
+                order = [by_slots[32], by_slots[1], by_slots[16]]
+            else:
+                order = [int(i) % len(known) for i in rng.permutation(size)]
+                assert set(order) == set(range(len(known)))  # every program, every slot class
+            with_bitset = [k % 3 != 1 for k in range(size)]
+            for out in outs[:size]:  # all ones: every word the kernel owes is seen
+                store.memset(out, 0xFF, store.row_words * 8)
+            counts = store.filter_eval_batch([(known[i][0], leaves, known[i][1]) for i in order],
+                                             [outs[k] if with_bitset[k] else None for k in range(size)])
+            for k, index in enumerate(order):
+                want = known[index][2]
+                assert counts[k] == int(want.sum()) == singles[index][1], (size, k, index)
+                if with_bitset[k]:
+                    words = store.bitset_download(outs[k])
+                    bits = dense.unpack_bits(words, store.row_words * 64)
+                    assert np.array_equal(bits[:n], want), (size, k, index)
+                    assert not bits[n:].any(), (size, k, index)
+                    assert np.array_equal(words, singles[index][0]), (size, k, index)
+        for out in outs:
+            store.free(out)
+
+
 def _reuse_programs(b):
     """(code, n_slots, expected(masks)) — fat (<= 16 slots: 8 waves per block) and thin (> 16: 4 waves, twice the parts) programs
     that select everything, nothing and something.  Seven of them, so that over the launches every program meets both stores
