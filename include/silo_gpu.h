@@ -842,6 +842,58 @@ int silo_gpu_mutations_compare(
    double min_difference, uint32_t capacity, uint32_t* out_dev, void* stream
 );
 
+/* ---- K18: each row's differences from the reference (MutationsPerSequence / AminoAcidMutationsPerSequence) ----
+ * Takes no store (like K10 and K17): it starts from the characters that silo_gpu_reconstruct_sequences writes for every store
+ * layout, chars_dev[r * positions + p], rows back to back without padding (so a row starts at any byte alignment), and the
+ * reference as characters, reference_dev[p].  With "valid" as in K10 (nucleotide "-ACGT", amino acid "-ACDEFGHIKLMNPQRSTVWY*") and
+ * the missing symbol 'N' / 'X', the CLASS of the cell (r, p) with c = chars_dev[r * positions + p] is
+ *     MISSING       c is the missing symbol, whatever the reference holds at p
+ *     AMBIGUOUS     c is any other byte that is not valid: ambiguity codes, lower case, 0x00, 0xFF
+ *     SAME          c is valid and equals reference_dev[p]
+ *     DELETION      c is valid, differs from reference_dev[p] and is '-'
+ *     SUBSTITUTION  c is valid, differs from reference_dev[p] and is not '-' (a reference byte that is not valid differs from
+ *                   every valid c)
+ * and the cell EMITS exactly one record word (p << 9) | (close << 8) | byte iff
+ *     its class is SUBSTITUTION or AMBIGUOUS                                                      byte = c, close = 0
+ *     its class is DELETION or MISSING and p == 0 or the class of (r, p - 1) differs: a run start  byte = c, close = 0
+ *     its class is SAME, p > 0 and the class of (r, p - 1) is DELETION or MISSING: a run's close   byte = 0, close = 1
+ * A run that is followed by a substitution, an ambiguous cell or a run of the other kind has no close: the next record's position
+ * ends it; a run that reaches the end of the row is ended by `positions`.  The left neighbour is always a cell of the SAME row:
+ * the last cell of row r - 1, which lies directly in front of (r, 0) in memory, is never looked at.
+ * WRITES
+ *     offsets_dev[0 .. n_rows]     offsets_dev[0] = 0, offsets_dev[r + 1] = the words of rows 0 .. r; offsets_dev[n_rows] may
+ *                                  exceed `capacity`
+ *     stats_dev[r * 4 + 0 .. 3]    the substitution, deleted, missing and ambiguous CELLS (not runs) of row r
+ *     records_dev[i]               for i < min(offsets_dev[n_rows], capacity): word i of the ONE list of all rows' words, ordered by
+ *                                  row, then by ascending position — with a short capacity an exact prefix; nothing at or past
+ *                                  min(total, capacity) is touched.  capacity == 0 is legal (records_dev may then be NULL): the
+ *                                  counts alone.
+ * Every word of offsets_dev and stats_dev is written and nothing is accumulated into memory the caller would have to clear: a
+ * second call gives the same bytes everywhere.  scratch_dev: SILO_GPU_DIFFERENCES_SCRATCH_BYTES(n_rows, positions) bytes, 4-byte
+ * aligned like the three outputs — per (row, chunk) the words and the four cell counts; a chunk is the cells of a row in
+ * SILO_GPU_DIFFERENCE_CHUNK bytes of memory counted from the 16-byte boundary at or below the row's first byte, so every chunk is
+ * read with aligned 16-byte loads and a row has at most SILO_GPU_DIFFERENCE_CHUNKS(positions) of them.
+ * Four launches on `stream`, no waiting, no atomics, no floating point: a count pass over (chunk, row) blocks (a thread per 16
+ * bytes; the class left of a thread's first cell comes from the lane before, for a wave's first lane from one extra byte of the
+ * same row); a wave per row that sums the row's chunks and turns their counts into starts within the row; one block that turns
+ * the rows' totals into offsets_dev; a write pass that recomputes the flags and places each word at its chunk's start plus its
+ * rank, every index checked against `capacity` (not launched for capacity == 0).  n_rows == 0 or positions == 0: success, the
+ * offsets and stats written as 0, nothing launched.  Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for an alphabet
+ * other than the two, a NULL pointer (records_dev only where capacity != 0), a pointer that is not 4-byte aligned, n_rows >
+ * SILO_GPU_MAX_DIFFERENCE_ROWS, positions > SILO_GPU_MAX_DIFFERENCE_POSITIONS or n_rows * positions >= 2^32. */
+#define SILO_GPU_MAX_DIFFERENCE_ROWS 10000
+#define SILO_GPU_MAX_DIFFERENCE_POSITIONS (1u << 23)
+#define SILO_GPU_DIFFERENCE_STATS 4
+#define SILO_GPU_DIFFERENCE_CHUNK 4096 /* bytes of a row per block: 256 threads x 16 bytes */
+#define SILO_GPU_DIFFERENCE_CHUNKS(positions) (((positions) + 15u + SILO_GPU_DIFFERENCE_CHUNK - 1u) / SILO_GPU_DIFFERENCE_CHUNK)
+#define SILO_GPU_DIFFERENCES_SCRATCH_BYTES(n_rows, positions) \
+   ((size_t)(n_rows) * SILO_GPU_DIFFERENCE_CHUNKS(positions) * (1u + SILO_GPU_DIFFERENCE_STATS) * sizeof(uint32_t))
+int silo_gpu_sequence_differences(
+   int alphabet, const char* chars_dev /* [n_rows][positions] */, uint32_t n_rows, uint32_t positions, const char* reference_dev /* [positions] */,
+   uint32_t capacity, uint32_t* offsets_dev /* n_rows + 1 */, uint32_t* stats_dev /* n_rows * 4 */,
+   uint32_t* records_dev /* capacity words; may be NULL iff capacity == 0 */, void* scratch_dev, void* stream
+);
+
 /* ---- K11: the rows of the whole store nearest to a query (NearestNeighbours) --------------------------
  * silo_gpu_query_distances compares one query — query_chars, `positions` characters in HOST memory — with EVERY row of a sequence
  * store, read off the store's own layout (identity / code planes with escape keys, one-hot rows with a derived symbol, runs of the

@@ -879,6 +879,8 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"NearestNeighbours", parseNearestNeighbours},
    {"Haplotypes", parseHaplotypes<Nucleotide>},
    {"AminoAcidHaplotypes", parseHaplotypes<AminoAcid>},
+   {"MutationsPerSequence", parseMutationsPerSequence<Nucleotide>},
+   {"AminoAcidMutationsPerSequence", parseMutationsPerSequence<AminoAcid>},
 };
 
 }  // namespace

@@ -865,6 +865,35 @@ class FastaAligned : public Action {
    explicit FastaAligned(std::vector<std::string>&& sequence_names) : sequence_names(std::move(sequence_names)) {}
 };
 
+/// MutationsPerSequence / AminoAcidMutationsPerSequence (metadata_actions.cpp): what each selected sequence carries against the
+/// reference of ONE sequence store — its substitutions, its deletions and the stretches where it holds the missing symbol as maximal
+/// runs, its ambiguous positions — the diff a client would otherwise make of a FastaAligned response, row by row; the row-wise dual
+/// of Mutations.  The sequences are numbered in partition order, then by ascending row id, as FastaAligned returns them.  The rows
+/// of every partition are gathered (silo_gpu_reconstruct_sequences) into their slice of ONE pooled [n x positions] buffer, the
+/// reference is uploaded once, and ONE silo_gpu_sequence_differences (K18) runs over all n rows with room for FIRST_WORDS_PER_ROW x n
+/// record words; where the total asks for more, a second one with exactly that many runs on the characters still on the device.
+/// The host re-checks every fetched row before it becomes text.  One row per sequence: the primary key, sequenceName,
+/// substitutions ("C241T,A23403G"), deletions and missing ("11288-11296,21991": 1-based, inclusive), ambiguous ("C1059Y") — lists
+/// joined by commas, "" when empty — and substitutionCount, deletedPositions, missingPositions, ambiguousPositions.  Insertions
+/// are not part of it.  No counterpart in the reference.
+template <typename SymbolType>
+class MutationsPerSequence : public Action {
+  public:
+   static constexpr uint32_t SEQUENCE_LIMIT = SILO_GPU_MAX_DIFFERENCE_ROWS;
+   static constexpr uint32_t FIRST_WORDS_PER_ROW = 32;
+   static std::string actionName() { return std::is_same_v<SymbolType, Nucleotide> ? "MutationsPerSequence" : "AminoAcidMutationsPerSequence"; }
+
+   explicit MutationsPerSequence(std::optional<std::string> sequence_name) : sequence_name(std::move(sequence_name)) {}
+
+  private:
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+};
+/// The parser of MutationsPerSequence / AminoAcidMutationsPerSequence (metadata_actions.cpp).
+template <typename SymbolType>
+std::unique_ptr<Action> parseMutationsPerSequence(const json::Value& json);
+
 /// DistanceMatrix (distance_actions.cpp): per unordered pair of the selected sequences the positions of one aligned sequence where
 /// both hold a valid mutation symbol (comparedPositions) and where those two differ (distance) — the SNP distance matrix a
 /// client would otherwise compute from a FastaAligned response.  The sequences are numbered in partition order, then by

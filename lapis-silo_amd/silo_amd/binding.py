@@ -119,6 +119,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_query_distances", "silo_gpu_nearest_rows", "silo_gpu_bitset_from_distances",
     "silo_gpu_position_symbols", "silo_gpu_haplotype_ids",
     "silo_gpu_mutations_compare",
+    "silo_gpu_sequence_differences",
 ]
 
 _lib = None
@@ -208,6 +209,7 @@ def load_library():
                                            ctypes.POINTER(vp), vp, vp]
     lib.silo_gpu_mutations_compare.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_double, ctypes.c_double,
                                                ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_sequence_differences.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -847,6 +849,64 @@ def mutations_compare(alphabet_id, counts, reference_index, min_proportion, min_
         return device_read(out, np.uint32, words, stream), status
     finally:
         for ptr in (counts_dev, reference_dev, out):
+            device_free(ptr)
+
+
+MAX_DIFFERENCE_ROWS = 10000            # SILO_GPU_MAX_DIFFERENCE_ROWS: the rows of one silo_gpu_sequence_differences
+MAX_DIFFERENCE_POSITIONS = 1 << 23     # SILO_GPU_MAX_DIFFERENCE_POSITIONS: a position lies above the 9 low bits of a record word
+DIFFERENCE_STATS = 4                   # SILO_GPU_DIFFERENCE_STATS: substitution, deleted, missing, ambiguous cells of a row
+DIFFERENCE_CHUNK = 4096                # SILO_GPU_DIFFERENCE_CHUNK: bytes of a row per block of K18, 256 threads x 16 bytes
+
+
+def difference_chunks(positions):
+    """SILO_GPU_DIFFERENCE_CHUNKS: the most chunks a row can have (it starts up to 15 bytes past a 16-byte boundary)."""
+    return (positions + 15 + DIFFERENCE_CHUNK - 1) // DIFFERENCE_CHUNK
+
+
+def differences_scratch_bytes(n_rows, positions):
+    """SILO_GPU_DIFFERENCES_SCRATCH_BYTES: per (row, chunk) the words and the four cell counts."""
+    return n_rows * difference_chunks(positions) * (1 + DIFFERENCE_STATS) * 4
+
+
+def sequence_differences(alphabet_id, chars, reference, capacity, fill=None, guard_bytes=0, calls=1, null=(), n_rows=None, positions=None,
+                         chars_offset=0, stream=None):
+    """silo_gpu_sequence_differences (K18) over host chars uint8 [n][P] and reference uint8 [P]: (offsets uint32 [n + 1 + guard],
+    stats uint32 [n * 4 + guard], records uint32 [capacity + guard], the status of the last call), guard = guard_bytes / 4 words
+    behind each.  The three outputs are filled with the byte `fill` before the first of `calls` launches, so a test can see what
+    is written, that nothing behind it is, and that a second call gives the same bytes.  A status other than 0 is returned, not
+    raised: the refusals leave the outputs as they were.  null: which of "chars", "reference", "offsets", "stats", "records",
+    "scratch" the call gets as NULL.  n_rows / positions: what the call is told instead of the matrix's shape (a shape it
+    refuses).  chars_offset: the bytes the first row starts past a 256-byte boundary."""
+    lib = load_library()
+    chars = np.ascontiguousarray(chars, dtype=np.uint8)
+    rows, width = chars.shape
+    reference = np.ascontiguousarray(reference, dtype=np.uint8)
+    guard = int(guard_bytes) // 4
+    offset_words, stat_words, record_words = rows + 1 + guard, rows * DIFFERENCE_STATS + guard, int(capacity) + guard
+    chars_dev = device_malloc(chars.size + int(chars_offset))
+    reference_dev = device_malloc(reference.size)
+    offsets = device_malloc(offset_words * 4, fill, stream)
+    stats = device_malloc(stat_words * 4, fill, stream)
+    records = device_malloc(record_words * 4, fill, stream)
+    scratch = device_malloc(differences_scratch_bytes(rows, width))
+    try:
+        chars_at = ctypes.c_void_p(chars_dev.value + int(chars_offset))
+        if chars.size:
+            _check(lib.silo_gpu_memcpy_h2d(chars_at, _ptr(chars), chars.size, stream))
+        if reference.size:
+            _check(lib.silo_gpu_memcpy_h2d(reference_dev, _ptr(reference), reference.size, stream))
+        status = 0
+        for _ in range(calls):
+            status = lib.silo_gpu_sequence_differences(
+                _abi_alphabet(alphabet_id), None if "chars" in null else chars_at, rows if n_rows is None else int(n_rows),
+                width if positions is None else int(positions), None if "reference" in null else reference_dev, int(capacity),
+                None if "offsets" in null else offsets, None if "stats" in null else stats, None if "records" in null else records,
+                None if "scratch" in null else scratch, stream)
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return (device_read(offsets, np.uint32, offset_words, stream), device_read(stats, np.uint32, stat_words, stream),
+                device_read(records, np.uint32, record_words, stream), status)
+    finally:
+        for ptr in (chars_dev, reference_dev, offsets, stats, records, scratch):
             device_free(ptr)
 
 
