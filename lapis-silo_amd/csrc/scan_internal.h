@@ -163,7 +163,7 @@ struct DerivedPlan {
    // range, seqstore null where it has none) and none of the passes of the runs and the sparse keys runs
    bool events = false;
    std::vector<ScanRange> gap_ranges;
-   // Which ranges count the end runs of the gap symbol instead of reading its covered rows (SeqStoreHost::Layout::d_ends_sliced):
+   // Which ranges count the end runs of the gap symbol instead of reading its covered rows (SeqStoreHost::Layout::ends):
    // decided ONCE per scan and range (usesEndRuns), whatever the proportions, the partitions or the entry — the counts are exact.
    // The row kernel and the gather kernel leave the covered rows out, the escape pass counts the end events into end_ranges (counts =
    // the range's ends tables; seqstore null where the range reads its rows) and the residual keys into the private tables,

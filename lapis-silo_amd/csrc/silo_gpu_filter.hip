@@ -617,7 +617,7 @@ int silo_gpu_store_sparse_plane(const silo_gpu_store* store, uint32_t seqstore_i
          const uint32_t key_begin = seqstore.layout.escape_first[position];
          const uint32_t key_end = seqstore.layout.escape_first[position + 1];
          if (key_end > key_begin) {
-            k_clear_keys<<<(key_end - key_begin + 255) / 256, 256, 0, hip_stream>>>(seqstore.layout.d_escapes, key_begin, key_end, dst_dev);
+            k_clear_keys<<<(key_end - key_begin + 255) / 256, 256, 0, hip_stream>>>(seqstore.layout.d_escapes.get(), key_begin, key_end, dst_dev);
          }
          if (seqstore.dev.n_missing_runs > 0) {
             k_runs_clear_plane<<<(seqstore.dev.n_missing_runs + 255) / 256, 256, 0, hip_stream>>>(
@@ -639,7 +639,7 @@ int silo_gpu_store_sparse_plane(const silo_gpu_store* store, uint32_t seqstore_i
          const uint32_t begin = seqstore.layout.escape_first_symbol[counter];
          const uint32_t end = seqstore.layout.escape_first_symbol[counter + 1];
          if (end > begin) {
-            k_scatter_sparse<<<(end - begin + 255) / 256, 256, 0, hip_stream>>>(seqstore.layout.d_escapes, begin, end, dst_dev);
+            k_scatter_sparse<<<(end - begin + 255) / 256, 256, 0, hip_stream>>>(seqstore.layout.d_escapes.get(), begin, end, dst_dev);
             HIP_TRY(hipGetLastError());
          }
       }

@@ -58,24 +58,24 @@ void cutIntoPieces(const std::vector<ScanRange>& ranges, uint32_t q_count, std::
             return;
          }
          ScanPiece piece{};
-         const bool encoded = seqstore.layout.built && seqstore.layout.d_row_of != nullptr;
+         const bool encoded = seqstore.layout.built && seqstore.layout.d_row_of.get() != nullptr;
          const size_t first_row = encoded ? seqstore.layout.row_of[begin] : static_cast<size_t>(begin) * dev.n_bits;
          piece.planes = dev.planes + first_row * dev.row_words;
          piece.n_positions = end - begin;
          if (one_hot) {
-            piece.code_map = reinterpret_cast<const uint8_t*>(seqstore.layout.d_row_target + first_row);
+            piece.code_map = reinterpret_cast<const uint8_t*>(seqstore.layout.d_row_target.get() + first_row);
             piece.n_positions = seqstore.layout.row_of[end] - seqstore.layout.row_of[begin];
             piece.target_base = begin * dev.n_scan;
-            if (seqstore.layout.d_row_heaviest != nullptr && seqstore.layout.d_row_without != nullptr) {
-               piece.row_heaviest = seqstore.layout.d_row_heaviest + first_row;
-               piece.row_without = seqstore.layout.d_row_without + first_row;
+            if (seqstore.layout.d_row_heaviest.get() != nullptr && seqstore.layout.d_row_without.get() != nullptr) {
+               piece.row_heaviest = seqstore.layout.d_row_heaviest.get() + first_row;
+               piece.row_without = seqstore.layout.d_row_without.get() + first_row;
             }
-            piece.row_covered = covered ? seqstore.layout.d_row_covered + first_row : nullptr;
+            piece.row_covered = covered ? seqstore.layout.d_row_covered.get() + first_row : nullptr;
             if (piece.n_positions == 0) {
                return;  // positions whose only stored symbol is derived: no rows
             }
          } else if (!identity) {
-            piece.code_map = seqstore.layout.d_code_map + static_cast<size_t>(begin) * CODE_MAP_STRIDE;
+            piece.code_map = seqstore.layout.d_code_map.get() + static_cast<size_t>(begin) * CODE_MAP_STRIDE;
          }
          for (uint32_t q = 0; q < q_count; ++q) {
             piece.counts[q] = range.counts[q] + static_cast<size_t>(begin - range.pos_begin) * dev.n_scan;
@@ -291,7 +291,7 @@ int forkSidePasses(
    bool any_escapes = false;
    for (const ScanRange& range : ranges) {
       const SeqStoreHost::Layout& layout = range.seqstore->layout;
-      any_escapes = any_escapes || (layout.built && layout.d_escapes != nullptr && layout.escape_first[range.pos_end] != layout.escape_first[range.pos_begin]);
+      any_escapes = any_escapes || (layout.built && layout.d_escapes.get() != nullptr && layout.escape_first[range.pos_end] != layout.escape_first[range.pos_begin]);
    }
    if (!any_escapes && derived == nullptr) {
       return SILO_GPU_OK;
@@ -717,7 +717,7 @@ int silo_gpu_store_scan_prunable_granules(
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_store_scan_prunable_granules: bad arguments");
    }
    const SeqStoreHost::Layout& layout = store->seqstores[seqstore_id].layout;
-   *out_total = layout.packed_keys / ESCAPE_GRANULE_KEYS;
+   *out_total = layout.escapes_sliced.packed_keys / ESCAPE_GRANULE_KEYS;
    *out_skippable = 0;
    for (size_t g = 0; g < layout.granule_heaviest.size(); ++g) {  // (empty where the store has no bounds)
       *out_skippable += granulePrunable(cardinality, layout.granule_without[g], layout.granule_heaviest[g], min_proportion) ? 1 : 0;

@@ -36,7 +36,7 @@ namespace {
 //      (k_scan_missing_runs: +1 where a selected row's run starts, -1 where it ends, summed along the positions afterwards)
 //      and those with an ambiguity code (k_count_sparse_keys),
 //   3. k_finish_scan: derived count = |filter| - (2.) - sum of (1.) at the position; private tables -> the caller's.
-// Where the store has its gap events (SeqStoreHost::Layout::d_gaps_sliced), 2. is part of the escape pass instead: the events
+// Where the store has its gap events (SeqStoreHost::Layout::gaps), 2. is part of the escape pass instead: the events
 // are one more range of k_scan_escapes_sliced, counted into gaps[n][2], and k_finish_scan<true> sums starts less ends.
 // The filter's cardinality comes from the prepare step (k_compact_filter, counter [2]).
 // ------------------------------------------------------------------------------------------------
@@ -504,7 +504,7 @@ uint32_t runBlocksPerSlice(const DerivedArgs& launch, uint32_t q_count) {
 /// (SILO_GPU_TUNE_END_RUNS, read once per scan) allows it, and every run of one-hot rows of the range fits the row kernel's list of live rows.
 bool usesEndRuns(const ScanRange& range, int knob) {
    const SeqStoreHost::Layout& layout = range.seqstore->layout;
-   if (layout.d_ends_sliced == nullptr || layout.d_row_covered == nullptr || knob < 0) {
+   if (layout.ends.d_keys.get() == nullptr || layout.d_row_covered.get() == nullptr || knob < 0) {
       return false;
    }
    for (const SeqStoreHost::Run& run : layout.runs) {
@@ -573,7 +573,7 @@ void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& rang
       // diff[n + 1] and ambiguous[n]; gaps / diff and ends begin at a multiple of 16 bytes (the sweep of k_finish_scan)
       const bool end_runs = plan.events && seqstore.layout.has_implicit && usesEndRuns(range, end_knob);
       plan.end_runs[r] = end_runs ? 1 : 0;
-      entry.position_covered = end_runs ? seqstore.layout.d_position_covered : nullptr;
+      entry.position_covered = end_runs ? seqstore.layout.d_position_covered.get() : nullptr;
       entry.end_symbol = seqstore.layout.end_symbol;
       const auto rounded = [](size_t words) { return (words + 3) / 4 * 4; };
       const size_t gaps_offset = rounded(static_cast<size_t>(n) * seqstore.dev.n_scan);
@@ -585,10 +585,10 @@ void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& rang
       offset += static_cast<size_t>(entry.stride) * q_count;
       if (seqstore.layout.has_implicit) {
          plan.run_counts[r / DERIVED_MAX_RANGES][launch.n_ranges - 1] = seqstore.dev.n_missing_runs;
-         entry.code_map = seqstore.layout.d_code_map;
+         entry.code_map = seqstore.layout.d_code_map.get();
          entry.run_keys = seqstore.dev.missing_run_keys;
          entry.run_ends = seqstore.dev.missing_run_ends;
-         entry.run_slice_first = seqstore.layout.d_run_slice_first;
+         entry.run_slice_first = seqstore.layout.d_run_slice_first.get();
          launch.n_run_slices = seqstore.layout.n_run_slices;
          entry.sparse_keys = seqstore.d_sparse;
          const auto lo = std::lower_bound(seqstore.sparse_sorted.begin(), seqstore.sparse_sorted.end(), static_cast<uint64_t>(range.pos_begin) << 37);

@@ -82,7 +82,7 @@ struct EscapeSliceArgs {
    const uint32_t* counters;
    double min_proportion[SILO_GPU_MAX_SCAN_BATCH];
    struct Range {
-      const uint32_t* keys;          // the packed slice-major keys of the store (SeqStoreHost::Layout::d_escapes_sliced or d_gaps_sliced)
+      const uint32_t* keys;          // the packed slice-major keys of the store (a SliceMajorKeys of SeqStoreHost::Layout: escapes_sliced, gaps, ends or residual)
       const uint32_t* granule_base;  // counter of every granule's first key
       const uint32_t* slice_first;   // [n_slices][positions + 1], in the packed numbering
       const uint32_t* heaviest;      // per granule (SeqStoreHost::Layout::d_granule_heaviest), or nullptr: every granule is counted
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
    flushChunk();
 }
 
-/// The few keys of a store that do not fit the packed form (SeqStoreHost::Layout::d_escapes_overflow: counter << 32 | sequence),
+/// The few keys of a store that do not fit the packed form (SliceMajorKeys::d_overflow of SeqStoreHost::Layout::escapes_sliced: counter << 32 | sequence),
 /// for the positions [pos_begin, pos_end): one global filter lookup and one atomic each; grid.y = filter.
 __global__ __launch_bounds__(256) void k_scan_escapes_overflow(
    const uint64_t* __restrict__ keys, uint32_t n_keys, const ScanBatchArgs batch, uint32_t pos_begin, uint32_t pos_end
@@ -601,9 +601,9 @@ int scanEscapes(
       return SILO_GPU_OK;
    };
    // one entry of a launch: the packed keys (or gap events) of a store over [key_from, pos_end) of its positions
-   const auto addSliced = [&](const ScanRange& range, uint32_t n_slices, const uint32_t* keys, const uint32_t* granule_base, const uint32_t* slice_first,
-                              const std::vector<uint32_t>& host_slice_first, uint32_t out_symbols, uint32_t key_from, const uint32_t* heaviest = nullptr,
+   const auto addSliced = [&](const ScanRange& range, const SliceMajorKeys& stream, uint32_t out_symbols, uint32_t key_from, const uint32_t* heaviest = nullptr,
                               const uint32_t* without = nullptr) -> int {
+      const uint32_t n_slices = stream.n_slices;
       if (n_sliced == ESCAPE_MAX_RANGES || (n_sliced != 0 && sliced.n_slices != n_slices)) {
          if (const int rc = launchSliced(); rc != SILO_GPU_OK) {
             return rc;
@@ -612,9 +612,9 @@ int scanEscapes(
       sliced.row_words = range.seqstore->dev.row_words;
       sliced.n_slices = n_slices;
       EscapeSliceArgs::Range& entry = sliced.ranges[n_sliced];
-      entry.keys = keys;
-      entry.granule_base = granule_base;
-      entry.slice_first = slice_first;
+      entry.keys = stream.d_keys.get();
+      entry.granule_base = stream.d_granule_base.get();
+      entry.slice_first = stream.d_slice_first.get();
       entry.heaviest = heaviest;
       entry.without = without;
       entry.positions = range.seqstore->dev.positions;
@@ -625,7 +625,7 @@ int scanEscapes(
       std::copy_n(range.counts, q_count, entry.counts);
       const size_t stride = static_cast<size_t>(entry.positions) + 1;
       for (uint32_t slice = 0; slice < n_slices; ++slice) {
-         const uint32_t n = host_slice_first[slice * stride + range.pos_end] - host_slice_first[slice * stride + key_from];
+         const uint32_t n = stream.slice_first[slice * stride + range.pos_end] - stream.slice_first[slice * stride + key_from];
          total_keys += n;
          most_keys[n_sliced] = std::max(most_keys[n_sliced], n + ESCAPE_GRANULE_KEYS - 1u);  // (blocks start at a granule boundary)
       }
@@ -635,30 +635,26 @@ int scanEscapes(
    // the gap events of a range's store, behind its keys: from its first position on where the range begins later (see EscapeSliceArgs)
    const auto addGaps = [&](size_t r) -> int {
       const SeqStoreHost::Layout& layout = ranges[r].seqstore->layout;
-      if (gaps == nullptr || (*gaps)[r].seqstore == nullptr || layout.d_gaps_sliced == nullptr) {
+      if (gaps == nullptr || (*gaps)[r].seqstore == nullptr || layout.gaps.d_keys.get() == nullptr) {
          return SILO_GPU_OK;
       }
-      return addSliced((*gaps)[r], layout.gap_slices, layout.d_gaps_sliced, layout.d_gap_granule_base, layout.d_gap_slice_first, layout.gap_slice_first, 2, 0);
+      return addSliced((*gaps)[r], layout.gaps, 2, 0);
    };
    // the end events of a range that counts the end runs of the gap symbol — from position 0 on, clamped like the gap events: a
    // leading run that ended before the range's first position has ended there — and the residual keys of its covered rows
    const auto addEnds = [&](size_t r) -> int {
       const SeqStoreHost::Layout& layout = ranges[r].seqstore->layout;
-      if (ends == nullptr || (*ends)[r].seqstore == nullptr || layout.d_ends_sliced == nullptr) {
+      if (ends == nullptr || (*ends)[r].seqstore == nullptr || layout.ends.d_keys.get() == nullptr) {
          return SILO_GPU_OK;
       }
-      if (const int rc = addSliced((*ends)[r], layout.end_slices, layout.d_ends_sliced, layout.d_end_granule_base, layout.d_end_slice_first, layout.end_slice_first, 2, 0);
-          rc != SILO_GPU_OK) {
+      if (const int rc = addSliced((*ends)[r], layout.ends, 2, 0); rc != SILO_GPU_OK) {
          return rc;
       }
       end_entries = true;
-      if (layout.d_residual_sliced == nullptr) {
+      if (layout.residual.d_keys.get() == nullptr) {
          return SILO_GPU_OK;
       }
-      const int rc = addSliced(
-         ranges[r], layout.end_slices, layout.d_residual_sliced, layout.d_residual_granule_base, layout.d_residual_slice_first, layout.residual_slice_first,
-         ranges[r].seqstore->dev.n_scan, ranges[r].pos_begin
-      );
+      const int rc = addSliced(ranges[r], layout.residual, ranges[r].seqstore->dev.n_scan, ranges[r].pos_begin);
       end_entries = true;
       return rc;
    };
@@ -671,25 +667,26 @@ int scanEscapes(
       if (only_ends) {
          continue;
       }
-      const uint32_t begin = layout.built && layout.d_escapes != nullptr ? layout.escape_first[range.pos_begin] : 0;
-      const uint32_t count = layout.built && layout.d_escapes != nullptr ? layout.escape_first[range.pos_end] - begin : 0;
+      const uint32_t begin = layout.built && layout.d_escapes.get() != nullptr ? layout.escape_first[range.pos_begin] : 0;
+      const uint32_t count = layout.built && layout.d_escapes.get() != nullptr ? layout.escape_first[range.pos_end] - begin : 0;
       if (count == 0) {
          if (const int rc = addGaps(r); rc != SILO_GPU_OK) {
             return rc;
          }
          continue;
       }
-      if (layout.d_escapes_sliced != nullptr && g_tune_side_stream.load() != 3) {  // the slice-major keys, a slice of the filter in LDS
-         if (layout.n_overflow != 0) {  // the few keys that do not fit the packed form: a small launch of their own
-            k_scan_escapes_overflow<<<dim3((layout.n_overflow + 255) / 256, q_count), 256, 0, hip_stream>>>(
-               layout.d_escapes_overflow, layout.n_overflow, keyBatch(range, filters, q_count), range.pos_begin, range.pos_end
+      const SliceMajorKeys& keys = layout.escapes_sliced;
+      if (keys.d_keys.get() != nullptr && g_tune_side_stream.load() != 3) {  // the slice-major keys, a slice of the filter in LDS
+         if (keys.n_overflow != 0) {  // the few keys that do not fit the packed form: a small launch of their own
+            k_scan_escapes_overflow<<<dim3((keys.n_overflow + 255) / 256, q_count), 256, 0, hip_stream>>>(
+               keys.d_overflow.get(), keys.n_overflow, keyBatch(range, filters, q_count), range.pos_begin, range.pos_end
             );
             HIP_TRY(hipGetLastError());
          }
-         const bool bounds = prune && layout.d_granule_heaviest != nullptr && layout.d_granule_without != nullptr;
+         const bool bounds = prune && layout.d_granule_heaviest.get() != nullptr && layout.d_granule_without.get() != nullptr;
          if (const int rc = addSliced(
-                range, layout.n_slices, layout.d_escapes_sliced, layout.d_granule_base, layout.d_slice_first, layout.slice_first, range.seqstore->dev.n_scan,
-                range.pos_begin, bounds ? layout.d_granule_heaviest : nullptr, bounds ? layout.d_granule_without : nullptr
+                range, keys, range.seqstore->dev.n_scan, range.pos_begin, bounds ? layout.d_granule_heaviest.get() : nullptr,
+                bounds ? layout.d_granule_without.get() : nullptr
              );
              rc != SILO_GPU_OK) {
             return rc;
@@ -704,7 +701,7 @@ int scanEscapes(
       }
       const uint32_t keys_per_block = 256 * ESCAPE_KEYS_PER_THREAD;
       k_scan_escapes<<<dim3((count + keys_per_block - 1) / keys_per_block, q_count), 256, 0, hip_stream>>>(
-         layout.d_escapes + begin, count, keyBatch(range, filters, q_count), range.pos_begin
+         layout.d_escapes.get() + begin, count, keyBatch(range, filters, q_count), range.pos_begin
       );
       HIP_TRY(hipGetLastError());
    }

@@ -1,7 +1,9 @@
 // store_internal.h — what the translation units of libsilo_gpu.so share about a store (not part of the C ABI): the device-side
 // description of a sequence store, its host-side state, the store itself, the wave-level helpers and a few constants.
 //   silo_gpu_runtime.hip   errors, tuning knobs, memory / stream / event wrappers, the stream-read probe
-//   silo_gpu_store.hip     store lifetime, the build kernels (transpose, generator), finalize: runs of the missing symbol, layout
+//   silo_gpu_store.hip     store lifetime and the order of the build and finalize stages; the stages, one file each:
+//                          silo_gpu_store_build.hip (rows coming in: transpose, generator), silo_gpu_store_layout.hip (the adaptive
+//                          planes), silo_gpu_store_streams.hip (what finalize derives for the scan: runs, slice-major streams, bounds)
 //   silo_gpu_scan.hip      K1 the Mutations scan over ranges; its passes, one file each behind scan_internal.h:
 //                          silo_gpu_scan_planes.hip (plane rows), silo_gpu_scan_keys.hip (escape keys), silo_gpu_scan_derived.hip (derived symbols)
 //   silo_gpu_select.hip    K4 row selection, row slots
@@ -57,17 +59,57 @@ inline int fail(int code, const std::string& message) {
    return silo_gpu_internal_fail(code, message);
 }
 
-#define HIP_TRY(expr)                                                                          \
-   do {                                                                                        \
-      hipError_t err_ = (expr);                                                                \
-      if (err_ != hipSuccess) {                                                                \
-         (void)hipGetLastError(); /* clear the sticky error so later launch checks start clean */ \
-         return fail(                                                                          \
-            err_ == hipErrorOutOfMemory ? SILO_GPU_ERR_OUT_OF_MEMORY : SILO_GPU_ERR_HIP,       \
-            std::string(#expr) + ": " + hipGetErrorString(err_)                                \
-         );                                                                                    \
-      }                                                                                        \
-   } while (0)
+#define HIP_TRY(expr) SILO_HIP_TRY(expr)
+
+/// A failed HIP call as the library's error: `what`, then HIP's own words (the sticky error is cleared, as HIP_TRY does).
+inline int failHip(const std::string& what, hipError_t status) {
+   (void)hipGetLastError();
+   return fail(status == hipErrorOutOfMemory ? SILO_GPU_ERR_OUT_OF_MEMORY : SILO_GPU_ERR_HIP, what + ": " + hipGetErrorString(status));
+}
+
+/// The owner of one device allocation: alloc() is hipMalloc, and hipFree comes when the owner goes, is reset or is assigned to.
+/// Move-only.  Kernels and SeqStoreDev take get().
+template <typename T>
+class DeviceArray {
+  public:
+   DeviceArray() = default;
+   DeviceArray(DeviceArray&& other) noexcept : ptr_(other.release()) {}
+   DeviceArray& operator=(DeviceArray&& other) noexcept {
+      if (this != &other) {
+         reset();
+         ptr_ = other.release();
+      }
+      return *this;
+   }
+   DeviceArray(const DeviceArray&) = delete;
+   DeviceArray& operator=(const DeviceArray&) = delete;
+   ~DeviceArray() { reset(); }
+   /// Room for `count` elements; what the owner held before is freed first.
+   hipError_t alloc(size_t count) {
+      reset();
+      const hipError_t status = hipMalloc(&ptr_, count * sizeof(T));
+      if (status != hipSuccess) {
+         ptr_ = nullptr;
+      }
+      return status;
+   }
+   T* get() const { return ptr_; }
+   /// Hands the allocation over: the caller frees it.
+   T* release() {
+      T* ptr = ptr_;
+      ptr_ = nullptr;
+      return ptr;
+   }
+   void reset() {
+      if (ptr_ != nullptr) {
+         (void)hipFree(ptr_);
+         ptr_ = nullptr;
+      }
+   }
+
+  private:
+   T* ptr_ = nullptr;
+};
 
 constexpr uint32_t ROW_ALIGN_WORDS = 32;  // 256-byte rows
 
@@ -246,11 +288,30 @@ __device__ __forceinline__ uint32_t codeOfRow(const PositionLayout& layout, uint
    return code;
 }
 
+/// A list of 8-byte keys position << 37 | symbol << 32 | sequence in the form the scan's escape pass streams
+/// (k_scan_escapes_sliced; packSliceMajor makes it).  SLICE-major: slice = sequence >> ESCAPE_SLICE_SHIFT, (position, symbol,
+/// sequence) order within a slice, a slice of the filter in LDS.  PACKED, 4 bytes per key: row within the slice (17 bits) |
+/// counter relative to the key's granule << 17, where a granule is ESCAPE_GRANULE_KEYS consecutive keys of one slice (a slice's
+/// keys are padded to whole granules with 0xFFFFFFFF) and d_granule_base[g] = the counter (position * n_scan + symbol) of the
+/// granule's first key.  A key whose relative counter does not fit (a stretch of positions almost without keys) goes, 8 bytes
+/// wide, to the overflow list instead — or, for a stream packed with a span, the granule ends early and nothing overflows.
+/// A stream that was never packed is empty: null arrays, n_slices = 0.
+struct SliceMajorKeys {
+   DeviceArray<uint32_t> d_keys;
+   DeviceArray<uint32_t> d_granule_base;  // [packed_keys / ESCAPE_GRANULE_KEYS]
+   DeviceArray<uint64_t> d_overflow;      // counter << 32 | sequence; null where n_overflow = 0
+   uint32_t n_overflow = 0;
+   uint64_t packed_keys = 0;              // slots of d_keys (keys + padding)
+   uint32_t n_slices = 0;
+   DeviceArray<uint32_t> d_slice_first;   // [n_slices][P + 1] first key of a position within a slice, in the packed numbering
+   std::vector<uint32_t> slice_first;     // host copy
+};
+
 struct SeqStoreHost {
    SeqStoreDev dev{};
    uint32_t alphabet = 0;
    std::vector<uint8_t> reference;
-   uint8_t* d_reference = nullptr;
+   DeviceArray<uint8_t> d_reference;
    // sparse symbols: key = position << 37 | symbol << 32 | sequence id
    uint64_t* d_sparse = nullptr;
    uint32_t sparse_capacity = 0;
@@ -268,12 +329,13 @@ struct SeqStoreHost {
    uint32_t* d_totals = nullptr;
    bool totals_ready = false;
    // the runs of the missing symbol (PLANE_RUNS), owned
-   uint64_t* d_missing_run_keys = nullptr;
-   uint32_t* d_missing_run_ends = nullptr;
-   // a two-pass build between its passes / during the second (silo_gpu_store_build_pass): the layout in the making
+   DeviceArray<uint64_t> d_missing_run_keys;
+   DeviceArray<uint32_t> d_missing_run_ends;
+   // a two-pass build between its passes / during the second (silo_gpu_store_build_pass): the layout in the making, freed with
+   // the pointer where the build is never finalized
    struct LayoutWork;
    std::shared_ptr<LayoutWork> work;
-   unsigned long long* d_run_count = nullptr;  // runs of the missing symbol counted / written while the store is built in two passes
+   DeviceArray<unsigned long long> d_run_count;  // runs of the missing symbol counted / written while the store is built in two passes
    // The adaptive code planes of the finalized store (see SeqStoreDev and buildLayout).
    struct Run {  // consecutive positions of one layout: a scan launch takes runs of ONE layout
       uint32_t begin;
@@ -284,27 +346,16 @@ struct SeqStoreHost {
    };
    struct Layout {
       bool built = false;
-      uint64_t* planes = nullptr;       // owned; nullptr when the store keeps its build-time planes (dev.planes == dev.scan)
-      uint32_t* d_row_of = nullptr;
-      uint32_t* d_row_target = nullptr;  // [rows] one-hot rows: position * n_scan + scan symbol of the row (else 0xFFFFFFFF)
-      uint8_t* d_code_map = nullptr;
-      uint64_t* d_escapes = nullptr;
-      uint32_t* d_escape_first = nullptr;
-      // the same keys once more, SLICE-major: slice = sequence >> slice_shift, (position, symbol, sequence) order within a
-      // slice — what the scan's escape pass streams, a slice of the filter in LDS (k_scan_escapes_sliced)
-      // PACKED, 4 bytes per key: row within the slice (17 bits) | counter relative to the key's granule << 17, where a granule is
-      // ESCAPE_GRANULE_KEYS consecutive keys of one slice (a slice's keys are padded to whole granules with 0xFFFFFFFF) and
-      // granule_base[g] = the counter (position * n_scan + symbol) of the granule's first key.  A key whose relative counter does
-      // not fit 15 bits (a stretch of positions almost without keys) goes, 8 bytes wide, to the overflow list instead.
-      uint32_t* d_escapes_sliced = nullptr;
-      uint32_t* d_granule_base = nullptr;          // [packed keys / ESCAPE_GRANULE_KEYS]
-      uint64_t* d_escapes_overflow = nullptr;      // counter << 32 | sequence
-      uint32_t n_overflow = 0;
-      uint64_t packed_keys = 0;                    // slots of d_escapes_sliced (keys + padding)
+      DeviceArray<uint64_t> planes;        // null when the store keeps its build-time planes (dev.planes == dev.scan)
+      DeviceArray<uint32_t> d_row_of;
+      DeviceArray<uint32_t> d_row_target;  // [rows] one-hot rows: position * n_scan + scan symbol of the row (else 0xFFFFFFFF)
+      DeviceArray<uint8_t> d_code_map;
+      DeviceArray<uint64_t> d_escapes;
+      DeviceArray<uint32_t> d_escape_first;
+      // the same keys once more, slice-major and packed (SliceMajorKeys): what the scan's escape pass streams; the only one of
+      // the four streams with an overflow list.  Empty (n_slices = 0) where the store has no keys or more than ESCAPE_MAX_SLICES slices.
+      SliceMajorKeys escapes_sliced;
       uint32_t slice_shift = 0;
-      uint32_t n_slices = 0;
-      uint32_t* d_slice_first = nullptr;          // [n_slices][P + 1] first key of a position within a slice
-      std::vector<uint32_t> slice_first;          // host copy
       std::vector<uint32_t> row_of;               // [P + 1]
       std::vector<uint8_t> code_map;              // [P][CODE_MAP_STRIDE]
       std::vector<uint32_t> escape_first;         // [P + 1]
@@ -314,28 +365,23 @@ struct SeqStoreHost {
       // positions whose most numerous symbol is derived (LAYOUT_IMPLICIT): a scan then counts the rows of the filter without a
       // valid symbol per position — the runs of the missing symbol by slices of 2^17 sequences (run_slice_first), the sparse keys
       bool has_implicit = false;
-      uint32_t* d_run_slice_first = nullptr;  // [n_run_slices + 1] first run of a slice of sequences
+      DeviceArray<uint32_t> d_run_slice_first;  // [n_run_slices + 1] first run of a slice of sequences
       uint32_t n_run_slices = 0;
-      // the same rows without a valid symbol as GAP EVENTS, slice-major and packed like d_escapes_sliced: every run of the
+      // the same rows without a valid symbol as GAP EVENTS, slice-major and packed like escapes_sliced: every run of the
       // missing symbol [start, end) and every sparse key (ambiguity code) at p as [p, p + 1) gives the keys
       // start << 37 | 0 << 32 | sequence and end << 37 | 1 << 32 | sequence (counter = position * 2 + kind; an end at P is left
       // out).  Granules end early where the next event lies more than GAP_MAX_SPAN positions past their first: no overflow.
-      // nullptr where the store has no derived symbol or more than ESCAPE_MAX_SLICES slices (the scan then takes the runs and
+      // Empty where the store has no derived symbol or more than ESCAPE_MAX_SLICES slices (the scan then takes the runs and
       // the sparse keys by themselves: k_scan_missing_runs, k_count_sparse_keys).
       bool gap_stream = false;  // built (empty where the store has neither runs nor sparse keys)
-      uint32_t* d_gaps_sliced = nullptr;
-      uint32_t* d_gap_granule_base = nullptr;
-      uint32_t* d_gap_slice_first = nullptr;  // [gap_slices][P + 1]
-      uint32_t gap_slices = 0;
-      std::vector<uint32_t> gap_slice_first;  // host copy
-      uint64_t gap_packed = 0;                // slots of d_gaps_sliced
-      // two bounds per granule of d_escapes_sliced, for a scan that may leave out the keys no Mutations row can come from
+      SliceMajorKeys gaps;
+      // two bounds per granule of escapes_sliced, for a scan that may leave out the keys no Mutations row can come from
       // (silo_gpu_mutations_scan_ranges_min_proportion; buildPruneBounds).  heaviest: the most keys the whole store has of a
       // (position, symbol) with a key in the granule — UINT32_MAX where one of its keys lies at a position that derives no
       // symbol or derives another one than the reference's.  without: the most rows without a valid symbol (inside a run of
       // the missing symbol, ambiguity codes) at a position of the granule.  Built only beside the gap events.
-      uint32_t* d_granule_heaviest = nullptr;
-      uint32_t* d_granule_without = nullptr;
+      DeviceArray<uint32_t> d_granule_heaviest;
+      DeviceArray<uint32_t> d_granule_without;
       std::vector<uint32_t> granule_heaviest;  // host copies
       std::vector<uint32_t> granule_without;
       // the same two bounds per plane row, in the order of d_row_target, for the rows of one-hot positions (buildRowBounds): a
@@ -343,35 +389,28 @@ struct SeqStoreHost {
       // (position, symbol) — UINT32_MAX for a row of a position that derives no symbol or another one than the reference's or
       // whose derived symbol does not hold the majority of its valid rows, for a row without a symbol and for the rows of code planes — and its without the rows of the store without a valid symbol
       // at that very position.  Built beside the gap events; nullptr where the store has none (the scan stays exact).
-      uint32_t* d_row_heaviest = nullptr;
-      uint32_t* d_row_without = nullptr;
+      DeviceArray<uint32_t> d_row_heaviest;
+      DeviceArray<uint32_t> d_row_without;
       std::vector<uint32_t> row_heaviest;  // host copies
       std::vector<uint32_t> row_without;
       // the END RUNS of the gap symbol ('-': a sequence that has not begun yet, or has already ended), for the Mutations scan
       // alone (buildEndRuns; every other reader keeps reading the rows).  Per sequence lead = the length of its maximal prefix
       // of gap cells and trail_start >= lead = the first cell of its maximal suffix of them (P: none).  As events, packed like
-      // d_gaps_sliced (counter = position * 2 + kind): kind 0 at lead (every row, also lead = 0; an event at P is left out),
+      // gaps (counter = position * 2 + kind): kind 0 at lead (every row, also lead = 0; an event at P is left out),
       // kind 1 at trail_start (none at P).  The selected rows inside an end run at p: |F| - sum_{q<=p} kind 0 + sum_{q<=p} kind 1.
       // A one-hot row of the gap symbol is COVERED — not read by the scan — where its position is LAYOUT_IMPLICIT, derives
       // another symbol, and the row's bits outside every end run (interior deletions, gap cells cut off from their run by an N)
       // cost less as keys than the row (silo_gpu_layout::endRunCovers); those bits are the residual keys, packed like
-      // d_escapes_sliced but in a stream of their own (the other readers would count them on top of the row).
-      // Built only beside the gap events and while finalize still has the build-time planes; nullptr / empty otherwise.
-      uint32_t* d_end_lead = nullptr;   // [sequences] between the walk of the build-time planes and buildEndRuns only
-      uint32_t* d_end_trail = nullptr;
-      uint32_t* d_ends_sliced = nullptr;
-      uint32_t* d_end_granule_base = nullptr;
-      uint32_t* d_end_slice_first = nullptr;  // [end_slices][P + 1]
-      uint32_t end_slices = 0;
-      std::vector<uint32_t> end_slice_first;
+      // escapes_sliced but in a stream of their own (the other readers would count them on top of the row).
+      // Built only beside the gap events and while finalize still has the build-time planes; null / empty otherwise.
+      DeviceArray<uint32_t> d_end_lead;   // [sequences] between the walk of the build-time planes and buildEndRuns only
+      DeviceArray<uint32_t> d_end_trail;
+      SliceMajorKeys ends;
       uint64_t end_events = 0;                // events at a position < P
-      uint32_t* d_residual_sliced = nullptr;
-      uint32_t* d_residual_granule_base = nullptr;
-      uint32_t* d_residual_slice_first = nullptr;
-      std::vector<uint32_t> residual_slice_first;
+      SliceMajorKeys residual;                // as many slices as `ends`; empty where no covered row has a bit outside the end runs
       uint64_t residual_keys = 0;
-      uint8_t* d_row_covered = nullptr;       // [rows] in the order of d_row_target
-      uint8_t* d_position_covered = nullptr;  // [P]
+      DeviceArray<uint8_t> d_row_covered;       // [rows] in the order of d_row_target
+      DeviceArray<uint8_t> d_position_covered;  // [P]
       std::vector<uint8_t> row_covered;       // host copies
       std::vector<uint8_t> position_covered;
       uint64_t covered_rows = 0;
@@ -388,27 +427,15 @@ struct SeqStoreHost::LayoutWork {
    uint64_t total_rows = 0, total_escapes = 0;
    size_t plane_bytes = 0, escape_bytes = 0;
    bool has_implicit = false;
-   uint8_t* d_code_map = nullptr;
-   uint32_t* d_cursor = nullptr;
-   uint32_t* d_first = nullptr;
-   uint32_t* d_row_of = nullptr;
-   uint32_t* d_row_target = nullptr;
-   uint32_t* d_escape_first = nullptr;
-   uint64_t* d_planes = nullptr;
-   uint64_t* d_escapes = nullptr;
-   void discard() {
-      (void)hipFree(d_row_target);
-      (void)hipFree(d_code_map);
-      (void)hipFree(d_cursor);
-      (void)hipFree(d_first);
-      (void)hipFree(d_row_of);
-      (void)hipFree(d_escape_first);
-      (void)hipFree(d_planes);
-      (void)hipFree(d_escapes);
-      *this = LayoutWork{};
-   }
+   DeviceArray<uint8_t> d_code_map;
+   DeviceArray<uint32_t> d_cursor;
+   DeviceArray<uint32_t> d_first;
+   DeviceArray<uint32_t> d_row_of;
+   DeviceArray<uint32_t> d_row_target;
+   DeviceArray<uint32_t> d_escape_first;
+   DeviceArray<uint64_t> d_planes;
+   DeviceArray<uint64_t> d_escapes;
 };
-
 
 }  // namespace silo_gpu_detail
 
@@ -547,9 +574,31 @@ int scanRanges(
    const double* min_proportion = nullptr, const ScanSelect* select = nullptr
 );
 
+/// The slices of 2^ESCAPE_SLICE_SHIFT sequences a store of `sequence_count` rows has.
+inline uint32_t sliceCount(uint32_t sequence_count) {
+   return (sequence_count + (1u << ESCAPE_SLICE_SHIFT) - 1) >> ESCAPE_SLICE_SHIFT;
+}
+
 // host helpers of the store (silo_gpu_store.hip)
 int ensureDevice(int device);
 int growSparse(SeqStoreHost& seqstore, uint32_t needed);
 int ensureBuildPlanes(silo_gpu_store* store, SeqStoreHost& seqstore);
+int downloadTotals(const SeqStoreHost& seqstore, std::vector<uint32_t>& totals);  // seqstore.d_totals, [positions][n_scan]
+
+// the stages of finalize, in the order finalizeSeqStore (silo_gpu_store.hip) runs them
+// silo_gpu_store_layout.hip
+bool reencodes(const silo_gpu_store* store, const SeqStoreDev& dev);
+int planLayout(const silo_gpu_store* store, SeqStoreHost& seqstore, SeqStoreHost::LayoutWork& work, bool zero_planes, bool allow_implicit, bool* fits);
+int buildLayout(silo_gpu_store* store, SeqStoreHost& seqstore);
+// silo_gpu_store_streams.hip
+int compactMissingPlane(silo_gpu_store* store, SeqStoreHost& seqstore);
+int packSliceMajor(uint64_t* d_sorted, uint64_t n_keys, uint32_t n_scan, uint32_t positions, uint32_t n_slices, uint32_t max_span, SliceMajorKeys& out);
+int rowsWithoutSymbol(const SeqStoreHost& seqstore, std::vector<uint32_t>& without);
+int walkEndRuns(silo_gpu_store* store, SeqStoreHost& seqstore, bool has_implicit);  // called by buildLayout, while the build-time planes are there
+int buildRunSliceIndex(silo_gpu_store* store, SeqStoreHost& seqstore);
+int buildGapEvents(silo_gpu_store* store, SeqStoreHost& seqstore);
+int buildPruneBounds(silo_gpu_store* store, SeqStoreHost& seqstore);
+int buildRowBounds(silo_gpu_store* store, SeqStoreHost& seqstore);
+int buildEndRuns(silo_gpu_store* store, SeqStoreHost& seqstore);
 
 }  // namespace silo_gpu_detail
