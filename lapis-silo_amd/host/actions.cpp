@@ -426,11 +426,10 @@ std::unique_ptr<Action::Pending> Mutations<SymbolType>::begin(const Database& da
    validateOrderByFields(database);
    auto pending = std::make_unique<PendingScans>();
    for (const auto& sequence_name : sequence_names) {
-      CHECK_SILO_QUERY(
-         database.getSequenceStores<SymbolType>().count(sequence_name) != 0,
-         "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + sequence_name + "'"
-      )
-      pending->sequence_names.emplace_back(sequence_name);
+      pending->sequence_names.emplace_back(
+         sequenceStoreOf<SymbolType>(database, sequence_name, "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: ")
+            .name
+      );
    }
    if (sequence_names.empty()) {
       for (const auto& [sequence_name, _] : database.getSequenceStores<SymbolType>()) {

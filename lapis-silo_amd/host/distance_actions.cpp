@@ -8,7 +8,8 @@
 //   NearestAmong          two selections: per row of the one its nearest rows of the other (K14)
 //   NearestNeighbours     the rows of the whole database closest to one query sequence (K11); resolveQuerySequence, which
 //                         WithinDistance shares with it
-// The first four gather and pack the rows they compare in the same way: that is here once, as PackedSelection.
+// The first four gather and pack the rows they compare in the same way: that is here once, as PackedSelection, over the walk that
+// every action on the selected rows' sequences shares (SelectedSequences, sequence_actions.cpp).
 #include <algorithm>
 #include <cstring>
 #include <tuple>
@@ -22,121 +23,60 @@ namespace {
 
 using storage::column::MetadataColumnPartition;
 
-/// A sequence by name, as the five actions take it: none is the default nucleotide sequence.
-struct ComparedSequence {
-   std::string name;
-   bool is_amino_acid;
-   int alphabet;
-   uint32_t positions;
-   size_t row_plane_words;  // of one row in the plane buffer of silo_gpu_distance_pack
-
-   [[nodiscard]] uint32_t seqstoreOf(const DatabasePartition& partition) const {
-      return is_amino_acid ? partition.aa_sequences.at(name).seqstore_id : partition.nuc_sequences.at(name).seqstore_id;
-   }
-};
-
-ComparedSequence comparedSequence(const Database& database, const std::optional<std::string>& sequence_name) {
-   ComparedSequence sequence;
-   sequence.name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
-   sequence.is_amino_acid = database.nuc_sequences.count(sequence.name) == 0;
-   CHECK_SILO_QUERY(
-      !sequence.is_amino_acid || database.aa_sequences.count(sequence.name) != 0,
-      "Database does not contain a sequence with name: '" + sequence.name + "'"
-   )
-   sequence.alphabet = sequence.is_amino_acid ? SILO_GPU_ALPHABET_AMINO_ACID : SILO_GPU_ALPHABET_NUCLEOTIDE;
-   sequence.positions = static_cast<uint32_t>(
-      sequence.is_amino_acid ? database.aa_sequences.at(sequence.name).reference_sequence.size()
-                             : database.nuc_sequences.at(sequence.name).reference_sequence.size()
-   );
-   sequence.row_plane_words = static_cast<size_t>(SILO_GPU_DISTANCE_PLANES(sequence.alphabet)) * SILO_GPU_DISTANCE_WORDS(sequence.positions);
-   return sequence;
-}
-
-/// The rows the filters select, over all partitions that hold rows.
-size_t selectedCount(const Database& database, const std::vector<OperatorResult>& bitmap_filter) {
-   size_t total_count = 0;
-   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-      total_count += database.partitions[partition_id].sequence_count == 0 ? 0 : bitmap_filter[partition_id].cardinality();
-   }
-   return total_count;
-}
-
 const std::string NON_NEGATIVE_INTEGER = "a non-negative integer";  // how the parsers word what maxDistance and minComparedPositions must be
 
 constexpr uint32_t PACK_BATCH_ROWS = SILO_GPU_MAX_DISTANCE_ROWS;  // what one silo_gpu_distance_pack takes
 
 /// The character buffer that a PackedSelection of up to n rows gathers into (pool of the first partition).
-DeviceBuffer gatherBuffer(const Database& database, const ComparedSequence& sequence, uint32_t n) {
+DeviceBuffer gatherBuffer(const Database& database, const AlignedSequence& sequence, uint32_t n) {
    return database.partitions.front().pool.acquire(std::max<size_t>(1, static_cast<size_t>(std::min(n, PACK_BATCH_ROWS)) * sequence.positions));
 }
 
-/// The n rows the filters select, numbered in partition order, then by ascending row id, as bit planes over positions on the
-/// device.  The constructor reconstructs them in batches of PACK_BATCH_ROWS into device_chars (gatherBuffer) and packs every batch
-/// into its rows of the ONE plane buffer (n * row_plane_words words, pool of the first partition), all enqueued on queryStream().
-/// Every batch — and every selection that is given the same device_chars — gathers into the SAME characters: they are in order
-/// on the stream, so a gather starts after the pack before it has read them.  The object owns what those launches read and write
-/// (the planes; per partition its row ids, from that partition's pool): like device_chars it must outlive the wait for the stream,
-/// so it is declared before the launchAndWait whose launches read planes().  A sequence without positions: only the keys are
-/// collected, nothing is launched.  `what`: who asks, for the messages.
-class PackedSelection {
+/// A sequence by name, as the five actions take it: none is the default nucleotide sequence.
+AlignedSequence comparedSequence(const Database& database, const std::optional<std::string>& sequence_name) {
+   return alignedSequence(database, sequence_name, "Database does not contain a sequence with name: ");
+}
+
+/// The n rows the filters select, numbered as SelectedSequences numbers them, as bit planes over positions on the device.  The
+/// constructor reconstructs them in batches of PACK_BATCH_ROWS into device_chars (gatherBuffer) and packs every batch into its rows
+/// of the ONE plane buffer (n * row_plane_words words, pool of the first partition), all enqueued on queryStream().  Every batch —
+/// and every selection that is given the same device_chars — gathers into the SAME characters: they are in order on the stream, so
+/// a gather starts after the pack before it has read them.  The object owns what those launches read and write (the planes; per
+/// partition its row ids, from that partition's pool): like device_chars it must outlive the wait for the stream, so it is declared
+/// before the launchAndWait whose launches read planes().  A sequence without positions: only the keys are collected, nothing is
+/// launched.  `what`: who asks, for the messages.
+class PackedSelection : private SelectedSequences {
   public:
-   using PartitionRow = std::pair<uint32_t, uint32_t>;
-   std::vector<JsonValue> keys;          // the primary keys of sequence 0 .. n - 1
-   std::vector<PartitionRow> numbering;  // if `numbered`: their (partition, row id), ascending
+   using SelectedSequences::keys;
+   using SelectedSequences::numbering;
 
    PackedSelection(
-      const Database& database, const std::vector<OperatorResult>& bitmap_filter, const ComparedSequence& sequence, uint32_t n, const DeviceBuffer& device_chars,
+      const Database& database, const std::vector<OperatorResult>& bitmap_filter, const AlignedSequence& sequence, uint32_t n, const DeviceBuffer& device_chars,
       const std::string& what, bool numbered = false
    ) {
+      // of one row in the plane buffer of silo_gpu_distance_pack
+      const size_t row_plane_words = static_cast<size_t>(SILO_GPU_DISTANCE_PLANES(sequence.alphabet)) * SILO_GPU_DISTANCE_WORDS(sequence.positions);
+      const Step pack_batches = [&](const DatabasePartition& partition, const uint32_t* device_rows, uint32_t n_rows, size_t first_sequence) {
+         for (uint32_t begin = 0; begin < n_rows; begin += PACK_BATCH_ROWS) {
+            const uint32_t batch_rows = std::min(PACK_BATCH_ROWS, n_rows - begin);
+            checkGpu(
+               silo_gpu_reconstruct_sequences(
+                  partition.store, sequence.seqstoreOf(partition), device_rows + begin, batch_rows, device_chars.as<char>(), queryStream()
+               ),
+               "silo_gpu_reconstruct_sequences"
+            );
+            checkGpu(
+               silo_gpu_distance_pack(
+                  sequence.alphabet, device_chars.as<char>(), batch_rows, sequence.positions,
+                  device_planes.as<uint64_t>() + (first_sequence + begin) * row_plane_words, queryStream()
+               ),
+               "silo_gpu_distance_pack"
+            );
+         }
+      };
       waitIfThrown([&] {  // (a constructor that throws destroys its members: not while a launch reads them)
-         device_planes = database.partitions.front().pool.acquire(std::max<size_t>(8, n * sequence.row_plane_words * sizeof(uint64_t)));
-         const std::string& primary_key_column = database.database_config.primary_key;
-         keys.reserve(n);
-         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-            const DatabasePartition& partition = database.partitions[partition_id];
-            if (partition.sequence_count == 0) {
-               continue;
-            }
-            const std::vector<uint32_t> rows = selectedRows(partition, bitmap_filter[partition_id]);
-            if (rows.empty()) {
-               continue;
-            }
-            const size_t first_sequence = keys.size();
-            const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
-            for (const uint32_t row : rows) {
-               keys.push_back(primary_key.jsonOfRow(row));
-               if (numbered) {
-                  numbering.emplace_back(static_cast<uint32_t>(partition_id), row);
-               }
-            }
-            if (keys.size() > n) {
-               throw std::runtime_error(what + ": a filter selects more rows than its cardinality says");
-            }
-            if (sequence.positions == 0) {
-               continue;
-            }
-            auto* device_rows = row_ids.emplace_back(partition.pool.acquire(rows.size() * sizeof(uint32_t))).as<uint32_t>();
-            checkGpu(silo_gpu_memcpy_h2d(device_rows, rows.data(), rows.size() * sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
-            for (size_t begin = 0; begin < rows.size(); begin += PACK_BATCH_ROWS) {
-               const auto batch_rows = static_cast<uint32_t>(std::min<size_t>(PACK_BATCH_ROWS, rows.size() - begin));
-               checkGpu(
-                  silo_gpu_reconstruct_sequences(
-                     partition.store, sequence.seqstoreOf(partition), device_rows + begin, batch_rows, device_chars.as<char>(), queryStream()
-                  ),
-                  "silo_gpu_reconstruct_sequences"
-               );
-               checkGpu(
-                  silo_gpu_distance_pack(
-                     sequence.alphabet, device_chars.as<char>(), batch_rows, sequence.positions,
-                     device_planes.as<uint64_t>() + (first_sequence + begin) * sequence.row_plane_words, queryStream()
-                  ),
-                  "silo_gpu_distance_pack"
-               );
-            }
-         }
-         if (keys.size() != n) {
-            throw std::runtime_error(what + ": a filter selects fewer rows than its cardinality says");
-         }
+         device_planes = database.partitions.front().pool.acquire(std::max<size_t>(8, n * row_plane_words * sizeof(uint64_t)));
+         gather(database, bitmap_filter, n, what, numbered, sequence.positions == 0 ? Step{} : pack_batches);
       });
    }
 
@@ -144,7 +84,6 @@ class PackedSelection {
 
   private:
    DeviceBuffer device_planes;
-   std::vector<DeviceBuffer> row_ids;  // per partition with selected rows
 };
 
 }  // namespace
@@ -156,7 +95,7 @@ void DistanceMatrix::validateOrderByFields(const Database& /*database*/) const {
 }
 
 QueryResult DistanceMatrix::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
-   const ComparedSequence sequence = comparedSequence(database, sequence_name);
+   const AlignedSequence sequence = comparedSequence(database, sequence_name);
    const size_t total_count = selectedCount(database, bitmap_filter);
    CHECK_SILO_QUERY(total_count <= SEQUENCE_LIMIT, "DistanceMatrix action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences")
    requireUnsharded(database, "DistanceMatrix");
@@ -223,7 +162,7 @@ void Clusters::validateOrderByFields(const Database& /*database*/) const {
 }
 
 QueryResult Clusters::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
-   const ComparedSequence sequence = comparedSequence(database, sequence_name);
+   const AlignedSequence sequence = comparedSequence(database, sequence_name);
    const size_t total_count = selectedCount(database, bitmap_filter);
    CHECK_SILO_QUERY(total_count <= SEQUENCE_LIMIT, "Clusters action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences")
    requireUnsharded(database, "Clusters");
@@ -305,7 +244,7 @@ void MinimumSpanningTree::validateOrderByFields(const Database& /*database*/) co
 }
 
 QueryResult MinimumSpanningTree::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
-   const ComparedSequence sequence = comparedSequence(database, sequence_name);
+   const AlignedSequence sequence = comparedSequence(database, sequence_name);
    const size_t total_count = selectedCount(database, bitmap_filter);
    CHECK_SILO_QUERY(
       total_count <= SEQUENCE_LIMIT, "MinimumSpanningTree action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences"
@@ -418,7 +357,7 @@ void NearestAmong::validateOrderByFields(const Database& /*database*/) const {
 }
 
 QueryResult NearestAmong::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
-   const ComparedSequence sequence = comparedSequence(database, sequence_name);
+   const AlignedSequence sequence = comparedSequence(database, sequence_name);
    requireUnsharded(database, "NearestAmong");
    // the candidates: `among`, compiled and evaluated per partition as the top-level filter is; absent, the query's own filter
    std::vector<OperatorResult> among_filter;
@@ -580,15 +519,15 @@ std::optional<uint32_t> rowOfKey(const MetadataColumnPartition& column, const js
 }  // namespace
 
 QuerySequence resolveQuerySequence(
-   const Database& database, const std::string& name, bool is_amino_acid, const std::optional<json::Value>& primary_key,
-   const std::optional<std::string>& sequence, const std::string& what
+   const Database& database, const AlignedSequence& compared, const std::optional<json::Value>& primary_key, const std::optional<std::string>& sequence,
+   const std::string& what
 ) {
-   const size_t positions = is_amino_acid ? database.aa_sequences.at(name).reference_sequence.size() : database.nuc_sequences.at(name).reference_sequence.size();
+   const size_t positions = compared.positions;
    QuerySequence query;
    if (sequence.has_value()) {
       CHECK_SILO_QUERY(
-         sequence->size() == positions, what + ": the field sequence has " + std::to_string(sequence->size()) + " characters, the sequence '" + name +
-                                           "' has " + std::to_string(positions)
+         sequence->size() == positions, what + ": the field sequence has " + std::to_string(sequence->size()) + " characters, the sequence '" +
+                                           compared.name + "' has " + std::to_string(positions)
       )
       query.characters = *sequence;
       return query;
@@ -608,14 +547,13 @@ QuerySequence resolveQuerySequence(
    query.characters.resize(positions);
    if (positions != 0) {
       const DatabasePartition& partition = database.partitions[query.own_partition];
-      const uint32_t seqstore_id = is_amino_acid ? partition.aa_sequences.at(name).seqstore_id : partition.nuc_sequences.at(name).seqstore_id;
       // the two buffers return to the pool when the gather has been waited for: the copy to the host is synchronous
       const DeviceBuffer device_row = partition.pool.acquire(sizeof(uint32_t));
       const DeviceBuffer device_chars = partition.pool.acquire(positions);
       waitIfThrown([&] {
          checkGpu(silo_gpu_memcpy_h2d(device_row.get(), &query.own_row, sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
          checkGpu(
-            silo_gpu_reconstruct_sequences(partition.store, seqstore_id, device_row.as<uint32_t>(), 1, device_chars.as<char>(), queryStream()),
+            silo_gpu_reconstruct_sequences(partition.store, compared.seqstoreOf(partition), device_row.as<uint32_t>(), 1, device_chars.as<char>(), queryStream()),
             "silo_gpu_reconstruct_sequences"
          );
          checkGpu(silo_gpu_memcpy_d2h(query.characters.data(), device_chars.get(), positions, queryStream()), "silo_gpu_memcpy_d2h");
@@ -629,7 +567,7 @@ void NearestNeighbours::validateOrderByFields(const Database& /*database*/) cons
 }
 
 QueryResult NearestNeighbours::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
-   const ComparedSequence compared = comparedSequence(database, sequence_name);
+   const AlignedSequence compared = comparedSequence(database, sequence_name);
    requireUnsharded(database, "NearestNeighbours");
    const std::string& primary_key_column = database.database_config.primary_key;
 
@@ -645,8 +583,7 @@ QueryResult NearestNeighbours::execute(const Database& database, std::vector<Ope
       std::vector<DeviceBuffer> live;  // per partition: the table, two scratches, the list
       launchAndWait([&] {
          // the query's characters: the literal string, or the row of that key gathered from its partition (and left out there)
-         const QuerySequence resolved =
-            resolveQuerySequence(database, compared.name, compared.is_amino_acid, primary_key, sequence, "NearestNeighbours action");
+         const QuerySequence resolved = resolveQuerySequence(database, compared, primary_key, sequence, "NearestNeighbours action");
          const std::string& query = resolved.characters;
          const size_t own_partition = resolved.own_partition;
          const uint32_t own_row = resolved.own_row;

@@ -864,19 +864,15 @@ std::string WithinDistance::toString(const Database& /*database*/) const {
 std::unique_ptr<Operator> WithinDistance::compile(const Database& database, const DatabasePartition& database_partition, AmbiguityMode /*mode*/) const {
    // distance and compared are exact numbers of the stored symbols: there is no upper or lower bound of them to take
    const RowSpace rows = rowsOf(database_partition);
-   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
-   const bool is_amino_acid = database.nuc_sequences.count(name) == 0;
-   CHECK_SILO_QUERY(
-      !is_amino_acid || database.aa_sequences.count(name) != 0,
-      "WithinDistance: the field sequenceName: Database does not contain a sequence with name: '" + name + "'"
-   )
+   const actions::AlignedSequence compared =
+      actions::alignedSequence(database, sequence_name, "WithinDistance: the field sequenceName: Database does not contain a sequence with name: ");
    CHECK_SILO_QUERY(
       database.shard_world <= 1, "WithinDistance is not supported on a sharded database yet: the table of distances of a position shard is partial, "
                                  "and the row of a primary key may live on another rank"
    )
    // resolved for every partition compiled (the parsed expression is kept by query text, whatever the database holds): a lookup in the
    // host copy of the key column and a gather of one row per partition of the database
-   const actions::QuerySequence query = actions::resolveQuerySequence(database, name, is_amino_acid, primary_key, sequence, "WithinDistance");
+   const actions::QuerySequence query = actions::resolveQuerySequence(database, compared, primary_key, sequence, "WithinDistance");
    if (database_partition.sequence_count == 0) {
       return std::make_unique<operators::Empty>(rows);
    }
@@ -886,8 +882,7 @@ std::unique_ptr<Operator> WithinDistance::compile(const Database& database, cons
       }
       return std::make_unique<operators::Empty>(rows);
    }
-   const uint32_t seqstore_id = is_amino_acid ? database_partition.aa_sequences.at(name).seqstore_id : database_partition.nuc_sequences.at(name).seqstore_id;
-   return std::make_unique<operators::DistanceSelection>(seqstore_id, query.characters, max_distance, min_compared_positions, rows);
+   return std::make_unique<operators::DistanceSelection>(compared.seqstoreOf(database_partition), query.characters, max_distance, min_compared_positions, rows);
 }
 
 namespace {

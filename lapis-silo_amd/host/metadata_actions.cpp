@@ -3,11 +3,8 @@
 //   Haplotypes                      (not in the reference) the same group-by with the symbols at listed sequence positions as
 //                                   further columns (K16)
 //   Details                         src/silo/query_engine/actions/details.cpp
-//   Fasta                           src/silo/query_engine/actions/fasta.cpp
-//   FastaAligned                    src/silo/query_engine/actions/fasta_aligned.cpp
 //   Insertions                      src/silo/query_engine/actions/insertions.cpp
-//   MutationsPerSequence            (not in the reference) FastaAligned's rows as each row's differences from the reference (K18)
-// and what the sequence-comparing actions (distance_actions.cpp) read of metadata with them: columnOf, selectedRows.
+// and what the actions that return or compare sequences (sequence_actions.cpp, distance_actions.cpp) read of metadata: columnOf.
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -28,42 +25,16 @@ const MetadataColumnPartition& columnOf(const DatabasePartition& partition, cons
    return found->second;
 }
 
-/// The set bits of a filter, fetched from the device.
-std::vector<uint32_t> selectedRows(const DatabasePartition& partition, const OperatorResult& filter) {
-   std::vector<uint32_t> rows;
-   const uint32_t cardinality = filter.cardinality();
-   if (cardinality == 0) {
-      return rows;
-   }
-   rows.reserve(cardinality);
-   std::vector<uint64_t> words(partition.rowWords());
-   checkGpu(silo_gpu_memcpy_d2h(words.data(), filter.bitset(), words.size() * sizeof(uint64_t), queryStream()), "silo_gpu_memcpy_d2h");
-   for (size_t word = 0; word < words.size(); ++word) {
-      uint64_t bits = words[word];
-      while (bits != 0) {
-         rows.push_back(static_cast<uint32_t>(word * 64 + static_cast<uint32_t>(__builtin_ctzll(bits))));
-         bits &= bits - 1;
-      }
-   }
-   return rows;
-}
-
 namespace {
 
 /// Under position-range sharding every rank holds every row (and every metadata column), so row-wise actions simply
 /// run on each rank.  A sequence-id shard is one DatabasePartition of the reference (query_engine.cpp:40-49): an action
-/// whose rows are rows of the database (Details, Fasta, FastaAligned) answers for ITS rows and the front end concatenates
+/// whose rows are rows of the database (Details; Fasta and FastaAligned, sequence_actions.cpp) answers for ITS rows and the front end concatenates
 /// the shards' responses — no collective; ordering, offset and limit then hold per shard.  An action
 /// that merges rows across partitions (Aggregated with groupByFields, Insertions) would need a gather that is not built.
 void requireRowsMergedLocally(const Database& database, const char* what) {
    if (database.shard_world > 1 && !database.shard_by_position) {
       throw std::runtime_error(std::string(what) + " is not supported on a database sharded by sequence id");
-   }
-}
-/// Needs every position of a sequence on this device: not on a position-range shard.
-void requireAllPositionsLocal(const Database& database, const char* what) {
-   if (database.shard_world > 1 && database.shard_by_position) {
-      throw std::runtime_error(std::string(what) + " is not supported on a database sharded by position range");
    }
 }
 
@@ -284,13 +255,10 @@ template <typename SymbolType>
 QueryResult Haplotypes<SymbolType>::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
    const std::string action_name = actionName();
    requireUnsharded(database, action_name);
-   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
-   const auto found = database.getSequenceStores<SymbolType>().find(name);
-   CHECK_SILO_QUERY(
-      found != database.getSequenceStores<SymbolType>().end(),
-      action_name + " action: the database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + name + "'"
-   )
-   const size_t length = found->second.reference_sequence.size();
+   const auto [name, store] = sequenceStoreOf<SymbolType>(
+      database, sequence_name, action_name + " action: the database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: "
+   );
+   const size_t length = store.reference_sequence.size();
    const auto n_positions = static_cast<uint32_t>(positions.size());
    std::vector<uint32_t> listed;  // 0-based
    for (const uint32_t position : positions) {
@@ -627,63 +595,6 @@ QueryResult Details::executeAndOrder(const Database& database, std::vector<Opera
    return results_in_format;
 }
 
-// ---- Fasta (fasta.cpp) ---------------------------------------------------------------------------------------
-void Fasta::validateOrderByFields(const Database& database) const {  // :42-57
-   const std::string& primary_key_field = database.database_config.primary_key;
-   for (const OrderByField& field : order_by_fields) {
-      std::string joined;
-      for (size_t i = 0; i < sequence_names.size(); ++i) {
-         joined += (i == 0 ? "" : ",") + sequence_names[i];
-      }
-      CHECK_SILO_QUERY(
-         field.name == primary_key_field || std::find(sequence_names.begin(), sequence_names.end(), field.name) != sequence_names.end(),
-         "The only fields returned by the Fasta action are " + joined + " and " + primary_key_field
-      )
-   }
-}
-
-QueryResult Fasta::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {  // :214-245
-   for (const std::string& sequence_name : sequence_names) {
-      // every nucleotide sequence has an unaligned store (database.cpp:664-673)
-      CHECK_SILO_QUERY(
-         database.nuc_sequences.count(sequence_name) != 0, "Database does not contain an unaligned sequence with name: '" + sequence_name + "'"
-      )
-   }
-   const std::string& primary_key_column = database.database_config.primary_key;
-   size_t total_count = 0;
-   for (const auto& filter : bitmap_filter) {
-      total_count += filter.cardinality();
-   }
-   CHECK_SILO_QUERY(total_count <= SEQUENCE_LIMIT, "Fasta action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences")
-   QueryResult results;
-   results.query_result.reserve(total_count);
-   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-      const DatabasePartition& partition = database.partitions[partition_id];
-      const std::vector<uint32_t> rows = selectedRows(partition, bitmap_filter[partition_id]);
-      if (rows.empty()) {
-         continue;
-      }
-      const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
-      for (const uint32_t row : rows) {
-         QueryResultEntry& entry = results.query_result.emplace_back();
-         JsonValue key = primary_key.jsonOfRow(row);
-         if (!key.has_value()) {
-            throw std::runtime_error("Detected primary_key in column '" + primary_key_column + "' that is null.");
-         }
-         entry.fields.emplace(primary_key_column, std::move(key));
-         for (const std::string& sequence_name : sequence_names) {
-            const auto found = partition.unaligned_nuc_sequences.find(sequence_name);
-            if (found != partition.unaligned_nuc_sequences.end() && row < found->second.size() && found->second[row].has_value()) {
-               entry.fields.emplace(sequence_name, *found->second[row]);
-            } else {
-               entry.fields.emplace(sequence_name, std::nullopt);
-            }
-         }
-      }
-   }
-   return results;
-}
-
 // ---- Insertions / AminoAcidInsertions (insertions.cpp) ---------------------------------------------------
 template <typename SymbolType>
 void InsertionAggregation<SymbolType>::validateOrderByFields(const Database& /*database*/) const {  // :41-59
@@ -785,372 +696,5 @@ QueryResult InsertionAggregation<SymbolType>::execute(const Database& database, 
 
 template class InsertionAggregation<Nucleotide>;
 template class InsertionAggregation<AminoAcid>;
-
-// ---- FastaAligned ----------------------------------------------------------------------------------------
-void FastaAligned::validateOrderByFields(const Database& database) const {  // fasta_aligned.cpp:28-42
-   const std::string& primary_key_field = database.database_config.primary_key;
-   for (const OrderByField& field : order_by_fields) {
-      std::string joined;
-      for (size_t i = 0; i < sequence_names.size(); ++i) {
-         joined += (i == 0 ? "" : ",") + sequence_names[i];
-      }
-      CHECK_SILO_QUERY(
-         field.name == primary_key_field || std::find(sequence_names.begin(), sequence_names.end(), field.name) != sequence_names.end(),
-         "The only fields returned by the FastaAligned action are " + joined + " and " + primary_key_field
-      )
-   }
-}
-
-QueryResult FastaAligned::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {  // fasta_aligned.cpp:85-136
-   struct Requested {
-      std::string name;
-      bool is_amino_acid;
-   };
-   std::vector<Requested> requested;  // nucleotide sequences first, then genes (:89-103); the row is a map anyway
-   for (const std::string& sequence_name : sequence_names) {
-      CHECK_SILO_QUERY(
-         database.nuc_sequences.count(sequence_name) != 0 || database.aa_sequences.count(sequence_name) != 0,
-         "Database does not contain a sequence with name: '" + sequence_name + "'"
-      )
-      requested.push_back({sequence_name, database.nuc_sequences.count(sequence_name) == 0});
-   }
-   size_t total_count = 0;
-   for (const auto& filter : bitmap_filter) {
-      total_count += filter.cardinality();
-   }
-   CHECK_SILO_QUERY(total_count < 10001, "FastaAligned action currently limited to 10000 sequences")
-   requireAllPositionsLocal(database, "FastaAligned");
-
-   const std::string& primary_key_column = database.database_config.primary_key;
-   QueryResult results;
-   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-      const DatabasePartition& partition = database.partitions[partition_id];
-      const std::vector<uint32_t> rows = selectedRows(partition, bitmap_filter[partition_id]);
-      if (rows.empty()) {
-         continue;
-      }
-      const size_t first_entry = results.query_result.size();
-      const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
-      for (const uint32_t row : rows) {
-         results.query_result.emplace_back().fields.emplace(primary_key_column, primary_key.jsonOfRow(row));
-      }
-      // reconstructSequence (:44-83) for all selected rows of a store at once: one gather over the planes
-      DeviceBuffer device_rows = partition.pool.acquire(rows.size() * sizeof(uint32_t));
-      checkGpu(silo_gpu_memcpy_h2d(device_rows.get(), rows.data(), rows.size() * sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
-      for (const Requested& sequence : requested) {
-         uint32_t seqstore_id = 0;
-         size_t length = 0;
-         if (sequence.is_amino_acid) {
-            const auto& store = partition.aa_sequences.at(sequence.name);
-            seqstore_id = store.seqstore_id;
-            length = store.reference_sequence.size();
-         } else {
-            const auto& store = partition.nuc_sequences.at(sequence.name);
-            seqstore_id = store.seqstore_id;
-            length = store.reference_sequence.size();
-         }
-         std::vector<char> chars(rows.size() * length);
-         if (!chars.empty()) {
-            DeviceBuffer device_chars = partition.pool.acquire(chars.size());
-            checkGpu(
-               silo_gpu_reconstruct_sequences(
-                  partition.store, seqstore_id, static_cast<const uint32_t*>(device_rows.get()), static_cast<uint32_t>(rows.size()),
-                  static_cast<char*>(device_chars.get()), queryStream()
-               ),
-               "silo_gpu_reconstruct_sequences"
-            );
-            checkGpu(silo_gpu_memcpy_d2h(chars.data(), device_chars.get(), chars.size(), queryStream()), "silo_gpu_memcpy_d2h");
-         }
-         for (size_t index = 0; index < rows.size(); ++index) {
-            results.query_result[first_entry + index].fields.emplace(sequence.name, std::string(chars.data() + index * length, length));
-         }
-      }
-   }
-   return results;
-}
-
-// ---- MutationsPerSequence / AminoAcidMutationsPerSequence -------------------------------------------------
-// Each selected sequence's differences from the reference, from the rows FastaAligned would return, on the device (K18).  No
-// counterpart in the reference.
-namespace {
-
-/// The class of a cell as silo_gpu_sequence_differences defines it (include/silo_gpu.h), on the host's reference.
-enum class CellClass : uint8_t { SAME, SUBSTITUTION, DELETION, MISSING, AMBIGUOUS };
-
-template <typename SymbolType>
-CellClass classOfCell(uint8_t byte, char reference) {
-   const auto character = static_cast<char>(byte);
-   if (character == SymbolType::symbolToChar(SymbolType::SYMBOL_MISSING)) {
-      return CellClass::MISSING;
-   }
-   bool valid = false;
-   for (const auto symbol : SymbolType::VALID_MUTATION_SYMBOLS) {
-      valid = valid || SymbolType::symbolToChar(symbol) == character;
-   }
-   if (!valid) {
-      return CellClass::AMBIGUOUS;
-   }
-   if (character == reference) {
-      return CellClass::SAME;
-   }
-   return character == '-' ? CellClass::DELETION : CellClass::SUBSTITUTION;
-}
-
-/// What one row's record words say, as the response's four lists and four counts.
-struct RowDifferences {
-   std::string lists[SILO_GPU_DIFFERENCE_STATS];   // substitutions, deletions, missing, ambiguous
-   uint32_t cells[SILO_GPU_DIFFERENCE_STATS] = {};  // the cells behind each
-};
-
-/// Reads the words [begin, end) of one row and checks them on the way: positions strictly ascending and inside the sequence, a
-/// close only directly after a run start, every byte a symbol of the alphabet whose class against `reference` is the one its record
-/// kind needs, no run start that continues a run of its own class.  A run ends where the next record stands, or with the sequence.
-/// An empty string: the row is sound.
-template <typename SymbolType>
-std::string readRowDifferences(const uint32_t* begin, const uint32_t* end, const std::string& reference, RowDifferences& row) {
-   const auto positions = static_cast<uint32_t>(reference.size());
-   const auto append = [](std::string& list, const std::string& item) {
-      list += list.empty() ? "" : ",";
-      list += item;
-   };
-   bool run_open = false;          // a run of deletions or of the missing symbol has started and not ended
-   bool previous_is_start = false;  // ... with the record just before this one
-   uint32_t run_list = 0;
-   uint32_t run_first = 0;
-   const auto endRun = [&](uint32_t past) {
-      if (run_open) {
-         append(row.lists[run_list], past - run_first == 1 ? std::to_string(run_first + 1) : std::to_string(run_first + 1) + "-" + std::to_string(past));
-         row.cells[run_list] += past - run_first;
-         run_open = false;
-      }
-   };
-   uint32_t next_position = 0;  // what a record's position is at least
-   for (const uint32_t* word = begin; word != end; ++word) {
-      const uint32_t position = *word >> 9u;
-      const bool close = ((*word >> 8u) & 1u) != 0;
-      const auto byte = static_cast<uint8_t>(*word & 0xFFu);
-      if (position < next_position || position >= positions) {
-         return "a record whose position " + std::to_string(position) + " is not above the one before it or not inside the sequence";
-      }
-      next_position = position + 1;
-      if (close) {
-         if (!previous_is_start || byte != 0) {
-            return "a close at position " + std::to_string(position) + " that does not follow a run start";
-         }
-         endRun(position);
-         previous_is_start = false;
-         continue;
-      }
-      if (!SymbolType::charToSymbol(static_cast<char>(byte)).has_value()) {
-         return "a record at position " + std::to_string(position) + " whose byte " + std::to_string(byte) + " is no symbol of the alphabet";
-      }
-      const CellClass cell_class = classOfCell<SymbolType>(byte, reference[position]);
-      if (cell_class == CellClass::SAME) {
-         return "a record at position " + std::to_string(position) + " that holds the reference's symbol";
-      }
-      const uint32_t list = cell_class == CellClass::SUBSTITUTION ? 0u : cell_class == CellClass::DELETION ? 1u : cell_class == CellClass::MISSING ? 2u : 3u;
-      const bool is_start = list == 1u || list == 2u;
-      if (is_start && run_open && run_list == list) {
-         return "a run start at position " + std::to_string(position) + " inside a run of its own kind";
-      }
-      endRun(position);
-      previous_is_start = is_start;
-      if (is_start) {
-         run_open = true;
-         run_list = list;
-         run_first = position;
-      } else {
-         append(row.lists[list], std::string(1, reference[position]) + std::to_string(position + 1) + std::string(1, static_cast<char>(byte)));
-         ++row.cells[list];
-      }
-   }
-   endRun(positions);
-   return "";
-}
-
-}  // namespace
-
-template <typename SymbolType>
-void MutationsPerSequence<SymbolType>::validateOrderByFields(const Database& database) const {
-   checkOrderByFields({database.database_config.primary_key, "substitutionCount", "deletedPositions", "missingPositions", "ambiguousPositions"});
-}
-
-template <typename SymbolType>
-QueryResult MutationsPerSequence<SymbolType>::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
-   const std::string action_name = actionName();
-   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
-   const auto found = database.getSequenceStores<SymbolType>().find(name);
-   CHECK_SILO_QUERY(found != database.getSequenceStores<SymbolType>().end(), "Database does not contain a sequence with name: '" + name + "'")
-   size_t total_count = 0;
-   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-      total_count += database.partitions[partition_id].sequence_count == 0 ? 0 : bitmap_filter[partition_id].cardinality();
-   }
-   CHECK_SILO_QUERY(total_count <= SEQUENCE_LIMIT, action_name + " action currently limited to " + std::to_string(SEQUENCE_LIMIT) + " sequences")
-   requireUnsharded(database, action_name);
-   std::string reference;  // as characters, what the device compares with and what the host re-checks against
-   for (const auto symbol : found->second.reference_sequence) {
-      reference += SymbolType::symbolToChar(symbol);
-   }
-   CHECK_SILO_QUERY(
-      reference.size() <= SILO_GPU_MAX_DIFFERENCE_POSITIONS && total_count * reference.size() < (uint64_t{1} << 32u),
-      action_name + " action: the sequence '" + name + "' has more than " + std::to_string(SILO_GPU_MAX_DIFFERENCE_POSITIONS) +
-         " positions, or the selected sequences hold 2^32 characters or more"
-   )
-   const auto n = static_cast<uint32_t>(total_count);
-   const auto positions = static_cast<uint32_t>(reference.size());
-   constexpr size_t STATS = SILO_GPU_DIFFERENCE_STATS;
-   const size_t head_words = n + 1u + n * STATS;  // the offsets, then the stats: fetched together
-
-   std::vector<JsonValue> keys;          // of sequence 0 .. n - 1: partition order, then ascending row id
-   std::vector<uint32_t> heads(head_words, 0u);  // (no selection or a sequence without positions: nothing launched, no word, no cell)
-   std::vector<uint32_t> records;
-   keys.reserve(n);
-   {
-      // nothing in here returns to the pool before the stream has been waited for: the launches read and write it
-      const bool launches = n != 0 && positions != 0;
-      DevicePool& pool = database.partitions.front().pool;
-      DeviceBuffer device_chars, device_reference, device_heads, device_scratch;
-      DeviceBuffer device_records[2];       // of the first call and, where its capacity was too low, of the second
-      std::vector<DeviceBuffer> device_rows;  // per partition with selected rows, from its pool
-      launchAndWait([&] {
-         if (launches) {
-            device_chars = pool.acquire(static_cast<size_t>(n) * positions);
-            device_reference = pool.acquire(positions);
-            device_heads = pool.acquire(head_words * sizeof(uint32_t));
-            device_scratch = pool.acquire(std::max<size_t>(sizeof(uint32_t), SILO_GPU_DIFFERENCES_SCRATCH_BYTES(n, positions)));
-            checkGpu(silo_gpu_memcpy_h2d(device_reference.get(), reference.data(), positions, queryStream()), "silo_gpu_memcpy_h2d");
-         }
-         const std::string& primary_key_column = database.database_config.primary_key;
-         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
-            const DatabasePartition& partition = database.partitions[partition_id];
-            if (partition.sequence_count == 0) {
-               continue;
-            }
-            const std::vector<uint32_t> rows = selectedRows(partition, bitmap_filter[partition_id]);
-            if (rows.empty()) {
-               continue;
-            }
-            const size_t first_sequence = keys.size();
-            if (first_sequence + rows.size() > n) {
-               throw std::runtime_error(action_name + ": a filter selects more rows than its cardinality says");
-            }
-            const MetadataColumnPartition& primary_key = columnOf(partition, primary_key_column);
-            for (const uint32_t row : rows) {
-               keys.push_back(primary_key.jsonOfRow(row));
-            }
-            if (!launches) {
-               continue;
-            }
-            // reconstructSequence for the partition's rows at once, into their slice of the one buffer
-            auto* rows_on_device = device_rows.emplace_back(partition.pool.acquire(rows.size() * sizeof(uint32_t))).template as<uint32_t>();
-            checkGpu(silo_gpu_memcpy_h2d(rows_on_device, rows.data(), rows.size() * sizeof(uint32_t), queryStream()), "silo_gpu_memcpy_h2d");
-            checkGpu(
-               silo_gpu_reconstruct_sequences(
-                  partition.store, partition.template getSequenceStores<SymbolType>().at(name).seqstore_id, rows_on_device, static_cast<uint32_t>(rows.size()),
-                  device_chars.template as<char>() + first_sequence * positions, queryStream()
-               ),
-               "silo_gpu_reconstruct_sequences"
-            );
-         }
-         if (keys.size() != n) {
-            throw std::runtime_error(action_name + ": a filter selects fewer rows than its cardinality says");
-         }
-         if (!launches) {
-            return;
-         }
-         // rows of all partitions at once: one list, one pair of fetches
-         uint32_t capacity = FIRST_WORDS_PER_ROW * n;
-         for (size_t call = 0; call < 2; ++call) {
-            DeviceBuffer& device_list = device_records[call];
-            device_list = pool.acquire(static_cast<size_t>(capacity) * sizeof(uint32_t));
-            checkGpu(
-               silo_gpu_sequence_differences(
-                  SymbolType::ABI_ALPHABET, device_chars.template as<char>(), n, positions, device_reference.template as<char>(), capacity,
-                  device_heads.template as<uint32_t>(), device_heads.template as<uint32_t>() + n + 1u, device_list.template as<uint32_t>(),
-                  device_scratch.get(), queryStream()
-               ),
-               "silo_gpu_sequence_differences"
-            );
-            const HostFetch head_fetch(device_heads.get(), head_words * sizeof(uint32_t), queryStream());
-            const auto* host_heads = static_cast<const uint32_t*>(head_fetch.wait());
-            const uint32_t total = host_heads[n];
-            if (total > capacity) {
-               if (call == 1) {  // the characters have not changed: the second total is the first
-                  throw std::runtime_error(action_name + ": the device counted " + std::to_string(total) + " words where it had counted " + std::to_string(capacity));
-               }
-               capacity = total;  // exactly as many: the count is deterministic
-               continue;
-            }
-            if (call == 1 && total != capacity) {
-               throw std::runtime_error(action_name + ": the device counted " + std::to_string(total) + " words where it had counted " + std::to_string(capacity));
-            }
-            heads.assign(host_heads, host_heads + head_words);
-            if (total != 0) {
-               const HostFetch list_fetch(device_list.get(), static_cast<size_t>(total) * sizeof(uint32_t), queryStream());
-               const auto* host_list = static_cast<const uint32_t*>(list_fetch.wait());
-               records.assign(host_list, host_list + total);
-            }
-            break;
-         }
-      });
-   }
-   Trace::mark("differences_on_host");
-
-   // what came off the device is checked before it becomes rows: the offsets monotone and ending with the list, every row's words
-   // sound (readRowDifferences), the cells they stand for equal to the row's four counts
-   const auto broken = [&](const std::string& what) { return std::runtime_error(action_name + ": the device delivered " + what); };
-   const uint32_t* offsets = heads.data();
-   const uint32_t* stats = heads.data() + n + 1u;
-   if (offsets[0] != 0 || offsets[n] != records.size()) {
-      throw broken("offsets that do not span the list");
-   }
-   for (uint32_t r = 0; r < n; ++r) {
-      if (offsets[r] > offsets[r + 1u]) {
-         throw broken("offsets that decrease");
-      }
-   }
-   static const char* const LIST_FIELDS[STATS] = {"substitutions", "deletions", "missing", "ambiguous"};
-   static const char* const COUNT_FIELDS[STATS] = {"substitutionCount", "deletedPositions", "missingPositions", "ambiguousPositions"};
-   const std::string& primary_key_column = database.database_config.primary_key;
-   QueryResult results;
-   results.query_result.reserve(n);
-   for (uint32_t r = 0; r < n; ++r) {
-      RowDifferences row;
-      const std::string complaint = readRowDifferences<SymbolType>(records.data() + offsets[r], records.data() + offsets[r + 1u], reference, row);
-      if (!complaint.empty()) {
-         throw broken("for sequence " + std::to_string(r) + " " + complaint);
-      }
-      QueryResultEntry& entry = results.query_result.emplace_back();
-      entry.fields.emplace(primary_key_column, std::move(keys[r]));
-      entry.fields.emplace("sequenceName", name);
-      for (size_t k = 0; k < STATS; ++k) {
-         if (row.cells[k] != stats[r * STATS + k]) {
-            throw broken(
-               "for sequence " + std::to_string(r) + " records of " + std::to_string(row.cells[k]) + " cells in " + LIST_FIELDS[k] + " and a count of " +
-               std::to_string(stats[r * STATS + k])
-            );
-         }
-         entry.fields.emplace(LIST_FIELDS[k], std::move(row.lists[k]));
-         entry.fields.emplace(COUNT_FIELDS[k], static_cast<int32_t>(row.cells[k]));
-      }
-   }
-   return results;
-}
-
-template class MutationsPerSequence<Nucleotide>;
-template class MutationsPerSequence<AminoAcid>;
-
-template <typename SymbolType>
-std::unique_ptr<Action> parseMutationsPerSequence(const json::Value& json) {
-   const std::string action_name = MutationsPerSequence<SymbolType>::actionName();
-   std::optional<std::string> sequence_name = optionalStringField(json, "sequenceName", action_name);
-   CHECK_SILO_QUERY(
-      (std::is_same_v<SymbolType, Nucleotide>) || sequence_name.has_value(), action_name + " action must contain the field sequenceName of type string (a gene)"
-   )
-   return std::make_unique<MutationsPerSequence<SymbolType>>(std::move(sequence_name));
-}
-
-template std::unique_ptr<Action> parseMutationsPerSequence<Nucleotide>(const json::Value& json);
-template std::unique_ptr<Action> parseMutationsPerSequence<AminoAcid>(const json::Value& json);
 
 }  // namespace silo::query_engine::actions

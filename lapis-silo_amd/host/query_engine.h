@@ -742,8 +742,59 @@ std::optional<uint32_t> integerField(
 void requireUnsharded(const Database& database, const std::string& action_name);
 /// The metadata column `name` of a partition; a runtime_error if it was not loaded (metadata_actions.cpp).
 const storage::column::MetadataColumnPartition& columnOf(const DatabasePartition& partition, const std::string& name);
-/// The set bits of a filter, fetched from the device (metadata_actions.cpp).
+/// The set bits of a filter, fetched from the device (sequence_actions.cpp).
 std::vector<uint32_t> selectedRows(const DatabasePartition& partition, const OperatorResult& filter);
+/// The rows the filters select, over all partitions that hold rows (sequence_actions.cpp).
+size_t selectedCount(const Database& database, const std::vector<OperatorResult>& bitmap_filter);
+
+/// A sequence store of one alphabet by name, as the templated actions take it: none is the default nucleotide sequence.
+template <typename SymbolType>
+struct NamedSequenceStore {
+   std::string name;
+   const SequenceStore<SymbolType>& store;
+};
+/// `complaint`: the caller's wording of the refusal up to the name, which follows it in single quotes.
+template <typename SymbolType>
+NamedSequenceStore<SymbolType> sequenceStoreOf(const Database& database, const std::optional<std::string>& sequence_name, const std::string& complaint) {
+   std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
+   const auto found = database.getSequenceStores<SymbolType>().find(name);
+   CHECK_SILO_QUERY(found != database.getSequenceStores<SymbolType>().end(), complaint + "'" + name + "'")
+   return {std::move(name), found->second};
+}
+
+/// An aligned sequence of either alphabet by name, as the actions and filters that read characters take it: a nucleotide sequence
+/// if there is one of that name, otherwise a gene; none is the default nucleotide sequence (sequence_actions.cpp).
+struct AlignedSequence {
+   std::string name;
+   bool is_amino_acid;
+   int alphabet;  // SILO_GPU_ALPHABET_*
+   uint32_t positions;
+   [[nodiscard]] uint32_t seqstoreOf(const DatabasePartition& partition) const;
+};
+/// `complaint` as for sequenceStoreOf.
+AlignedSequence alignedSequence(const Database& database, const std::optional<std::string>& sequence_name, const std::string& complaint);
+
+/// The walk that every action over the selected rows' sequences begins with (FastaAligned, MutationsPerSequence, and through
+/// PackedSelection the distance actions): the rows the filters select, numbered in partition order, then by ascending row id.
+/// gather() takes every partition that holds rows and selected rows in turn: it collects the primary keys (a null key as it is),
+/// uploads the row ids into a buffer of that partition's pool and hands them to `step`, which enqueues the gather
+/// (silo_gpu_reconstruct_sequences) on queryStream().  The object owns the row-id buffers, which those launches read: it is declared
+/// BEFORE the waitIfThrown / launchAndWait that gather() is called under, so that it outlives the wait for the stream.
+class SelectedSequences {
+  public:
+   using PartitionRow = std::pair<uint32_t, uint32_t>;
+   /// (the partition, its selected row ids on the device, how many, the number of the first of them)
+   using Step = std::function<void(const DatabasePartition& partition, const uint32_t* device_rows, uint32_t n_rows, size_t first_sequence)>;
+   std::vector<JsonValue> keys;          // the primary keys of sequence 0 .. n - 1
+   std::vector<PartitionRow> numbering;  // if `numbered`: their (partition, row id), ascending
+
+   /// n: selectedCount of the filters; a filter that selects more or fewer rows is a runtime_error ("<what>: a filter selects ...").
+   /// No `step`: only the keys are collected, nothing is uploaded or launched.
+   void gather(const Database& database, const std::vector<OperatorResult>& bitmap_filter, size_t n, const std::string& what, bool numbered, const Step& step);
+
+  private:
+   std::vector<DeviceBuffer> row_ids;  // per partition with selected rows
+};
 
 /// The rule that keeps a pooled device buffer from being handed to another query while a kernel of this one still uses it, for
 /// work enqueued on queryStream() that reads and writes DeviceBuffers declared BEFORE the call (so that they die after it).
@@ -760,12 +811,12 @@ struct QuerySequence {
    size_t own_partition = SIZE_MAX;    // where the row named by a primary key lives; a literal sequence has none
    uint32_t own_row = UINT32_MAX;
 };
-/// The literal `sequence` (which must have the length of the sequence `name`), or the row whose primary key is `primary_key`:
+/// The literal `sequence` (which must have the length of `compared`), or the row whose primary key is `primary_key`:
 /// looked up in the host copies of the key column of every partition and gathered from its store (silo_gpu_reconstruct_sequences,
 /// n = 1) on the calling thread's queryStream(), which is waited for.  `what` opens every message ("NearestNeighbours action").
 QuerySequence resolveQuerySequence(
-   const Database& database, const std::string& name, bool is_amino_acid, const std::optional<json::Value>& primary_key,
-   const std::optional<std::string>& sequence, const std::string& what
+   const Database& database, const AlignedSequence& compared, const std::optional<json::Value>& primary_key, const std::optional<std::string>& sequence,
+   const std::string& what
 );
 
 class Aggregated : public Action {
@@ -830,7 +881,7 @@ class Details : public Action {
    [[nodiscard]] QueryResult finish(const Database& database, Pending& pending) const override;
 };
 
-/// fasta.cpp: primary key + the unaligned nucleotide sequences of the selected rows (host data only).
+/// fasta.cpp: primary key + the unaligned nucleotide sequences of the selected rows (host data only; sequence_actions.cpp).
 class Fasta : public Action {
    std::vector<std::string> sequence_names;
    void validateOrderByFields(const Database& database) const override;
@@ -855,7 +906,7 @@ class InsertionAggregation : public Action {
 };
 
 /// fasta_aligned.cpp: primary key + the aligned sequences of the selected rows, gathered from the planes on the
-/// device (k_reconstruct_sequences).
+/// device (k_reconstruct_sequences; sequence_actions.cpp).
 class FastaAligned : public Action {
    std::vector<std::string> sequence_names;
    void validateOrderByFields(const Database& database) const override;
@@ -865,7 +916,7 @@ class FastaAligned : public Action {
    explicit FastaAligned(std::vector<std::string>&& sequence_names) : sequence_names(std::move(sequence_names)) {}
 };
 
-/// MutationsPerSequence / AminoAcidMutationsPerSequence (metadata_actions.cpp): what each selected sequence carries against the
+/// MutationsPerSequence / AminoAcidMutationsPerSequence (sequence_actions.cpp): what each selected sequence carries against the
 /// reference of ONE sequence store — its substitutions, its deletions and the stretches where it holds the missing symbol as maximal
 /// runs, its ambiguous positions — the diff a client would otherwise make of a FastaAligned response, row by row; the row-wise dual
 /// of Mutations.  The sequences are numbered in partition order, then by ascending row id, as FastaAligned returns them.  The rows
@@ -890,7 +941,7 @@ class MutationsPerSequence : public Action {
    void validateOrderByFields(const Database& database) const override;
    [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
 };
-/// The parser of MutationsPerSequence / AminoAcidMutationsPerSequence (metadata_actions.cpp).
+/// The parser of MutationsPerSequence / AminoAcidMutationsPerSequence (sequence_actions.cpp).
 template <typename SymbolType>
 std::unique_ptr<Action> parseMutationsPerSequence(const json::Value& json);
 

@@ -192,13 +192,10 @@ QueryResult MutationsOverTime<SymbolType>::execute(const Database& database, std
    std::vector<Resolved> resolved;
    resolved.reserve(mutations.size());
    for (const Mutation& mutation : mutations) {
-      const std::string name = mutation.sequence_name.value_or(database.database_config.default_nucleotide_sequence);
-      const auto found = database.getSequenceStores<SymbolType>().find(name);
-      CHECK_SILO_QUERY(
-         found != database.getSequenceStores<SymbolType>().end(),
-         "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + name + "'"
-      )
-      const auto& reference = found->second.reference_sequence;
+      const auto [name, store] = sequenceStoreOf<SymbolType>(
+         database, mutation.sequence_name, "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: "
+      );
+      const auto& reference = store.reference_sequence;
       CHECK_SILO_QUERY(
          mutation.position >= 1 && mutation.position <= reference.size(),
          "The position " + std::to_string(mutation.position) + " of a mutation of " + action_name + " is outside the sequence '" + name + "' (1 to " +
@@ -212,7 +209,7 @@ QueryResult MutationsOverTime<SymbolType>::execute(const Database& database, std
                SymbolType::symbolToChar(reference_symbol) + "' at position " + std::to_string(mutation.position) + " of '" + name + "')"
          )
       }
-      resolved.push_back({name, &found->second, mutation.position - 1});
+      resolved.push_back({name, &store, mutation.position - 1});
    }
 
    // the table: one block of rows per sequence store touched, the store's mutations in request order within it
@@ -613,14 +610,11 @@ template <typename SymbolType>
 QueryResult Consensus<SymbolType>::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
    const std::string action_name = actionName();
    requireUnsharded(database, action_name);
-   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
-   const auto found = database.getSequenceStores<SymbolType>().find(name);
-   CHECK_SILO_QUERY(
-      found != database.getSequenceStores<SymbolType>().end(),
-      "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + name + "'"
-   )
+   const auto [name, store] = sequenceStoreOf<SymbolType>(
+      database, sequence_name, "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: "
+   );
    constexpr uint32_t summary_words = 4;  // ambiguous, low coverage, deleted, differences
-   const auto positions = static_cast<uint32_t>(found->second.reference_sequence.size());
+   const auto positions = static_cast<uint32_t>(store.reference_sequence.size());
    const auto n_groups = static_cast<uint32_t>(groups.size());
    const char missing = SymbolType::symbolToChar(SymbolType::SYMBOL_MISSING);
 
@@ -709,13 +703,10 @@ template <typename SymbolType>
 QueryResult MutationsComparison<SymbolType>::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
    const std::string action_name = actionName();
    requireUnsharded(database, action_name);
-   const std::string name = sequence_name.value_or(database.database_config.default_nucleotide_sequence);
-   const auto found = database.getSequenceStores<SymbolType>().find(name);
-   CHECK_SILO_QUERY(
-      found != database.getSequenceStores<SymbolType>().end(),
-      "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: '" + name + "'"
-   )
-   const auto& reference = found->second.reference_sequence;
+   const auto [name, store] = sequenceStoreOf<SymbolType>(
+      database, sequence_name, "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: "
+   );
+   const auto& reference = store.reference_sequence;
    constexpr uint32_t n_symbols = SymbolType::VALID_MUTATION_SYMBOLS.size();
    constexpr size_t header_words = 4;
    const auto positions = static_cast<uint32_t>(reference.size());

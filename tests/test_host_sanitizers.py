@@ -16,7 +16,7 @@ def test_query_parsing_is_clean_under_asan_and_ubsan(built, tmp_path):
     if shutil.which("g++") is None:
         pytest.skip("no g++")
     sources = [os.path.join(HOST, name) for name in ("actions.cpp", "database.cpp", "filter_expressions.cpp", "operators.cpp", "query_engine.cpp",
-                                                      "metadata_columns.cpp", "metadata_actions.cpp", "table_actions.cpp", "distance_actions.cpp")]
+                                                      "metadata_columns.cpp", "metadata_actions.cpp", "table_actions.cpp", "distance_actions.cpp", "sequence_actions.cpp")]
     driver = str(tmp_path / "sanitizer_driver")
     build = subprocess.run(
         ["g++", "-O1", "-g", "-std=c++20", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
