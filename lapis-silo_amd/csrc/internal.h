@@ -29,3 +29,51 @@ int silo_gpu_internal_sort_pairs(uint64_t* keys_dev, uint32_t* values_dev, size_
          );                                                                                                 \
       }                                                                                                     \
    } while (0)
+
+namespace silo_gpu_detail {
+
+/// The owner of one device allocation: alloc() is hipMalloc, and hipFree comes when the owner goes, is reset or is assigned to.
+/// Move-only.  Kernels and SeqStoreDev take get().
+template <typename T>
+class DeviceArray {
+  public:
+   DeviceArray() = default;
+   DeviceArray(DeviceArray&& other) noexcept : ptr_(other.release()) {}
+   DeviceArray& operator=(DeviceArray&& other) noexcept {
+      if (this != &other) {
+         reset();
+         ptr_ = other.release();
+      }
+      return *this;
+   }
+   DeviceArray(const DeviceArray&) = delete;
+   DeviceArray& operator=(const DeviceArray&) = delete;
+   ~DeviceArray() { reset(); }
+   /// Room for `count` elements; what the owner held before is freed first.
+   hipError_t alloc(size_t count) {
+      reset();
+      const hipError_t status = hipMalloc(&ptr_, count * sizeof(T));
+      if (status != hipSuccess) {
+         ptr_ = nullptr;
+      }
+      return status;
+   }
+   T* get() const { return ptr_; }
+   /// Hands the allocation over: the caller frees it.
+   T* release() {
+      T* ptr = ptr_;
+      ptr_ = nullptr;
+      return ptr;
+   }
+   void reset() {
+      if (ptr_ != nullptr) {
+         (void)hipFree(ptr_);
+         ptr_ = nullptr;
+      }
+   }
+
+  private:
+   T* ptr_ = nullptr;
+};
+
+}  // namespace silo_gpu_detail

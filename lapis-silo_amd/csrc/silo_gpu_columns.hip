@@ -10,6 +10,8 @@
 
 #include "internal.h"
 
+using silo_gpu_detail::DeviceArray;
+
 namespace {
 
 template <typename T>
@@ -379,52 +381,35 @@ int silo_gpu_group_count_hashed(
       capacity *= 2;
    }
    auto hip_stream = static_cast<hipStream_t>(stream);
-   unsigned long long* table_keys = nullptr;
-   uint32_t* table_counts = nullptr;
-   unsigned long long* keys = nullptr;
-   uint32_t* counts = nullptr;
-   uint32_t* n_out = nullptr;
-   const auto release = [&](bool keep_outputs) {
-      (void)hipFree(table_keys);
-      (void)hipFree(table_counts);
-      (void)hipFree(n_out);
-      if (!keep_outputs) {
-         (void)hipFree(keys);
-         (void)hipFree(counts);
-      }
-   };
-   hipError_t err = hipMalloc(&table_keys, capacity * sizeof(unsigned long long));
-   if (err == hipSuccess) err = hipMalloc(&table_counts, capacity * sizeof(uint32_t));
-   if (err == hipSuccess) err = hipMalloc(&keys, static_cast<size_t>(rows_bound) * sizeof(unsigned long long));
-   if (err == hipSuccess) err = hipMalloc(&counts, static_cast<size_t>(rows_bound) * sizeof(uint32_t));
-   if (err == hipSuccess) err = hipMalloc(&n_out, 2 * sizeof(uint32_t));  // [0] groups, [1] overflow flag
-   if (err == hipSuccess) err = hipMemsetAsync(table_keys, 0xFF, capacity * sizeof(unsigned long long), hip_stream);
-   if (err == hipSuccess) err = hipMemsetAsync(table_counts, 0, capacity * sizeof(uint32_t), hip_stream);
-   if (err == hipSuccess) err = hipMemsetAsync(n_out, 0, 2 * sizeof(uint32_t), hip_stream);
+   DeviceArray<unsigned long long> table_keys, keys;
+   DeviceArray<uint32_t> table_counts, counts, n_out;
+   hipError_t err = table_keys.alloc(capacity);
+   if (err == hipSuccess) err = table_counts.alloc(capacity);
+   if (err == hipSuccess) err = keys.alloc(rows_bound);
+   if (err == hipSuccess) err = counts.alloc(rows_bound);
+   if (err == hipSuccess) err = n_out.alloc(2);  // [0] groups, [1] overflow flag
+   if (err == hipSuccess) err = hipMemsetAsync(table_keys.get(), 0xFF, capacity * sizeof(unsigned long long), hip_stream);
+   if (err == hipSuccess) err = hipMemsetAsync(table_counts.get(), 0, capacity * sizeof(uint32_t), hip_stream);
+   if (err == hipSuccess) err = hipMemsetAsync(n_out.get(), 0, 2 * sizeof(uint32_t), hip_stream);
    if (err == hipSuccess) {
       k_group_hash_insert<<<(n_rows + 255) / 256, 256, 0, hip_stream>>>(
-         filter_dev, n_rows, args, table_keys, table_counts, static_cast<uint32_t>(capacity - 1), n_out + 1
+         filter_dev, n_rows, args, table_keys.get(), table_counts.get(), static_cast<uint32_t>(capacity - 1), n_out.get() + 1
       );
       k_group_hash_compact<<<static_cast<uint32_t>((capacity + 255) / 256), 256, 0, hip_stream>>>(
-         table_keys, table_counts, static_cast<uint32_t>(capacity), keys, counts, rows_bound, n_out
+         table_keys.get(), table_counts.get(), static_cast<uint32_t>(capacity), keys.get(), counts.get(), rows_bound, n_out.get()
       );
       err = hipGetLastError();
    }
    uint32_t result[2] = {0, 0};
-   if (err == hipSuccess) err = hipMemcpyAsync(result, n_out, sizeof(result), hipMemcpyDeviceToHost, hip_stream);
+   if (err == hipSuccess) err = hipMemcpyAsync(result, n_out.get(), sizeof(result), hipMemcpyDeviceToHost, hip_stream);
    if (err == hipSuccess) err = hipStreamSynchronize(hip_stream);
-   if (err != hipSuccess) {
-      release(false);
-      SILO_HIP_TRY(err);
-   }
+   SILO_HIP_TRY(err);
    const uint32_t n_groups = result[0];
    if (result[1] != 0 || n_groups > rows_bound) {
-      release(false);
       return silo_gpu_internal_fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_group_count_hashed: more selected rows than max_rows");
    }
-   release(true);
-   *out_keys_dev = reinterpret_cast<uint64_t*>(keys);
-   *out_counts_dev = counts;
+   *out_keys_dev = reinterpret_cast<uint64_t*>(keys.release());  // the caller frees the two results
+   *out_counts_dev = counts.release();
    *out_n_groups = n_groups;
    return SILO_GPU_OK;
 }
@@ -441,14 +426,13 @@ int silo_gpu_bitset_from_pairs(
    if (n_pairs == 0) {
       return SILO_GPU_OK;
    }
-   uint8_t* d_membership = nullptr;
-   SILO_HIP_TRY(hipMalloc(&d_membership, n_ids));
-   hipError_t err = hipMemcpyAsync(d_membership, membership_by_id, n_ids, hipMemcpyHostToDevice, hip_stream);
+   DeviceArray<uint8_t> d_membership;
+   SILO_HIP_TRY(d_membership.alloc(n_ids));
+   hipError_t err = hipMemcpyAsync(d_membership.get(), membership_by_id, n_ids, hipMemcpyHostToDevice, hip_stream);
    if (err == hipSuccess) {
-      k_bitset_from_pairs<<<(n_pairs + 255) / 256, 256, 0, hip_stream>>>(rows_dev, ids_dev, n_pairs, d_membership, dst_dev);
-      err = hipStreamSynchronize(hip_stream);  // the membership table is freed below
+      k_bitset_from_pairs<<<(n_pairs + 255) / 256, 256, 0, hip_stream>>>(rows_dev, ids_dev, n_pairs, d_membership.get(), dst_dev);
+      err = hipStreamSynchronize(hip_stream);  // the membership table is freed when this function returns
    }
-   (void)hipFree(d_membership);
    if (err != hipSuccess) {
       (void)hipGetLastError();
       return silo_gpu_internal_fail(SILO_GPU_ERR_HIP, std::string("k_bitset_from_pairs: ") + hipGetErrorString(err));

@@ -176,10 +176,10 @@ int silo_gpu_filters_cross(
       return SILO_GPU_OK;
    }
    for (uint32_t i = 0; i < R; ++i) {
-      tables[i] = reinterpret_cast<uint64_t>(row_filters_dev[i] != nullptr ? row_filters_dev[i] : store->d_ones);
+      tables[i] = reinterpret_cast<uint64_t>(row_filters_dev[i] != nullptr ? row_filters_dev[i] : store->d_ones.get());
    }
    for (uint32_t j = 0; j < C; ++j) {
-      tables[R + j] = reinterpret_cast<uint64_t>(col_filters_dev[j] != nullptr ? col_filters_dev[j] : store->d_ones);
+      tables[R + j] = reinterpret_cast<uint64_t>(col_filters_dev[j] != nullptr ? col_filters_dev[j] : store->d_ones.get());
    }
    if (tables.size() * sizeof(uint64_t) > SILO_GPU_FILTERS_CROSS_SCRATCH_BYTES(n_rows, n_cols)) {
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_filters_cross: scratch layout exceeds its documented size");  // (cannot happen)

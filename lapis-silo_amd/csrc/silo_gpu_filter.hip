@@ -1,6 +1,5 @@
 // silo_gpu_filter.hip — K2 k_popcount, K3 k_filter_eval, K3b k_filter_eval_batch (the fused operator tree of
-// operators/{index_scan,complement,intersection,union,threshold,full,empty,bitmap_selection}.cpp), count slots, row bitsets
-// from metadata, the plane of a single symbol at a position (filter leaves) and FastaAligned.
+// operators/{index_scan,complement,intersection,union,threshold,full,empty,bitmap_selection}.cpp) and the count slots.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -279,401 +278,9 @@ __global__ __launch_bounds__(EVAL_BATCH_THREADS) void k_filter_eval_batch(
    }
 }
 
-
-__global__ __launch_bounds__(256) void k_bitset_from_lineages(
-   const uint16_t* __restrict__ lineage, const uint8_t* __restrict__ membership, uint32_t sequence_count,
-   uint32_t row_words, uint64_t* __restrict__ out
-) {
-   const uint32_t lane = threadIdx.x & 63u;
-   const uint32_t word = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-   if (word >= row_words) {
-      return;
-   }
-   const uint64_t sequence = static_cast<uint64_t>(word) * 64u + lane;
-   const bool member = sequence < sequence_count && membership[lineage[sequence]] != 0;
-   const uint64_t mask = __ballot(member);
-   if (lane == 0) {
-      out[word] = mask;
-   }
-}
-
-__global__ __launch_bounds__(256) void k_bitset_from_value_ids(
-   const uint32_t* __restrict__ value_ids, const uint8_t* __restrict__ membership, uint32_t n_values,
-   uint32_t sequence_count, uint32_t row_words, uint64_t* __restrict__ out
-) {
-   const uint32_t lane = threadIdx.x & 63u;
-   const uint32_t word = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-   if (word >= row_words) {
-      return;
-   }
-   const uint64_t sequence = static_cast<uint64_t>(word) * 64u + lane;
-   bool member = false;
-   if (sequence < sequence_count) {
-      const uint32_t value = value_ids[sequence];
-      member = value < n_values && membership[value] != 0;
-   }
-   const uint64_t mask = __ballot(member);
-   if (lane == 0) {
-      out[word] = mask;
-   }
-}
-
-/// The plane of the missing symbol at one position out of its runs: one thread per run (`out` zeroed beforehand).
-__global__ __launch_bounds__(256) void k_runs_to_plane(
-   const uint64_t* __restrict__ run_keys, const uint32_t* __restrict__ run_ends, uint32_t n_runs, uint32_t position, uint64_t* __restrict__ out
-) {
-   const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x;
-   if (run >= n_runs) {
-      return;
-   }
-   const uint64_t key = run_keys[run];
-   if (static_cast<uint32_t>(key) <= position && position < run_ends[run]) {
-      const uint32_t sequence = static_cast<uint32_t>(key >> 32);
-      atomicOr(reinterpret_cast<unsigned long long*>(out + (sequence >> 6)), 1ull << (sequence & 63u));
-   }
-}
-
-/// Does `sequence` have the missing symbol at `position`?  The last run that starts at or before the cell decides.
-__device__ __forceinline__ bool missingInRuns(const SeqStoreDev& store, uint32_t sequence, uint32_t position) {
-   const uint64_t cell = (static_cast<uint64_t>(sequence) << 32) | position;
-   uint32_t lo = 0, hi = store.n_missing_runs;
-   while (lo < hi) {  // first run whose (sequence, start) is beyond the cell
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (store.missing_run_keys[mid] <= cell) {
-         lo = mid + 1;
-      } else {
-         hi = mid;
-      }
-   }
-   if (lo == 0) {
-      return false;
-   }
-   const uint64_t key = store.missing_run_keys[lo - 1];
-   return static_cast<uint32_t>(key >> 32) == sequence && position < store.missing_run_ends[lo - 1];
-}
-
-// FastaAligned: one thread per (requested row, position) looks the row's bit up in every dense plane of the
-// position; a cell no dense plane claims holds a sparsely stored symbol (IUPAC code) and is found by binary search
-// for position << 37 | symbol << 32 | sequence in the sorted sparse keys.  A gather (one 8-byte word per plane),
-// sized for the <= 10 000 rows the action allows.
-__global__ __launch_bounds__(256) void k_reconstruct_sequences(
-   const SeqStoreDev store, const uint64_t* __restrict__ sparse_keys, uint32_t n_sparse, const uint32_t* __restrict__ row_ids,
-   const char* __restrict__ symbol_chars, char* __restrict__ out
-) {
-   const uint32_t position = blockIdx.x * blockDim.x + threadIdx.x;
-   if (position >= store.positions) {
-      return;
-   }
-   const uint32_t sequence = row_ids[blockIdx.y];
-   const uint32_t word = sequence >> 6;
-   const uint32_t bit = sequence & 63u;
-   uint32_t found = 0xFFu;
-   // the row's code in the position's planes, and the valid mutation symbol that code stands for there (0 = none coded)
-   const PositionLayout layout = layoutOf(store, position);
-   const uint32_t code = codeOfRow(layout, store.row_words, word, bit);
-   const uint32_t coded_index = code == 0 ? 0xFFu : (layout.identity ? code - 1u : layout.map[code]);
-   for (uint32_t symbol = 0; symbol < store.n_symbols; ++symbol) {
-      if (store.kind[symbol] == PLANE_SCAN) {
-         if (store.index[symbol] == coded_index) {
-            found = symbol;
-         }
-         continue;
-      }
-      if (store.kind[symbol] == PLANE_RUNS) {
-         if (missingInRuns(store, sequence, position)) {
-            found = symbol;
-         }
-         continue;
-      }
-      const uint64_t* plane = planePtr(store, position, symbol);
-      if (plane != nullptr && ((plane[word] >> bit) & 1u) != 0) {
-         found = symbol;
-      }
-   }
-   const auto listed = [&](const uint64_t* keys, uint32_t lo, uint32_t hi, uint64_t key) {  // binary search in keys[lo, hi)
-      const uint32_t end = hi;
-      while (lo < hi) {
-         const uint32_t mid = lo + (hi - lo) / 2;
-         if (keys[mid] < key) {
-            lo = mid + 1;
-         } else {
-            hi = mid;
-         }
-      }
-      return lo < end && keys[lo] == key;
-   };
-   if (found == 0xFFu && store.escapes != nullptr) {  // a valid symbol that has no code at this position: an escape key
-      const uint32_t first = store.escape_first[position];
-      const uint32_t last = store.escape_first[position + 1];
-      for (uint32_t symbol = 0; symbol < store.n_symbols && found == 0xFFu && first < last; ++symbol) {
-         if (store.kind[symbol] == PLANE_SCAN &&
-             listed(store.escapes, first, last, (static_cast<uint64_t>(position) << 37) | (static_cast<uint64_t>(store.index[symbol]) << 32) | sequence)) {
-            found = symbol;
-         }
-      }
-   }
-   if (found == 0xFFu) {
-      for (uint32_t symbol = 0; symbol < store.n_symbols && found == 0xFFu; ++symbol) {
-         if (store.kind[symbol] == PLANE_SPARSE &&
-             listed(sparse_keys, 0, n_sparse, (static_cast<uint64_t>(position) << 37) | (static_cast<uint64_t>(symbol) << 32) | sequence)) {
-            found = symbol;
-         }
-      }
-   }
-   if (found == 0xFFu && layout.implicit) {  // no other symbol claims the cell: the position's derived symbol
-      for (uint32_t symbol = 0; symbol < store.n_symbols; ++symbol) {
-         if (store.kind[symbol] == PLANE_SCAN && store.index[symbol] == layout.map[IMPLICIT_SLOT]) {
-            found = symbol;
-         }
-      }
-   }
-   out[static_cast<size_t>(blockIdx.y) * store.positions + position] = found == 0xFFu ? '?' : symbol_chars[found];
-}
-
-// One-hot plane of a valid mutation symbol out of the position's code planes (2, 3 or n_bits reads per word); a symbol
-// that has no code at the position yields zeros (its rows are escape keys: the caller scatters them on top).
-__global__ __launch_bounds__(256) void k_decode_plane(
-   const SeqStoreDev store, uint32_t position, uint32_t symbol, const uint64_t* __restrict__ valid_words, uint64_t* __restrict__ out
-) {
-   const uint32_t word = blockIdx.x * blockDim.x + threadIdx.x;
-   if (word < store.row_words) {
-      const PositionLayout layout = layoutOf(store, position);
-      const uint32_t code = codeOfSymbol(layout, store.index[symbol]);
-      if (code == CODE_IMPLICIT) {  // the derived symbol: every row no stored row claims (the caller clears the keys, the runs, the sparse symbols)
-         uint64_t others = 0;
-         for (uint32_t row = 0; row < layout.bits; ++row) {
-            others |= layout.rows[static_cast<size_t>(row) * store.row_words + word];
-         }
-         out[word] = ~others & valid_words[word];
-         return;
-      }
-      out[word] = code == CODE_ESCAPED ? 0ull : decodeCodeWord(layout, store.row_words, code, word);
-   }
-}
-
-/// Clears the rows of keys[begin, end) (sequence in the low 32 bits) in `out`.
-__global__ void k_clear_keys(const uint64_t* __restrict__ keys, uint32_t begin, uint32_t end, uint64_t* out) {
-   const uint32_t k = begin + blockIdx.x * blockDim.x + threadIdx.x;
-   if (k < end) {
-      const uint32_t sequence = static_cast<uint32_t>(keys[k] & 0xFFFFFFFFull);
-      atomicAnd(reinterpret_cast<unsigned long long*>(out + (sequence >> 6)), ~(1ull << (sequence & 63u)));
-   }
-}
-
-/// Clears the rows whose run of the missing symbol covers `position` in `out`.
-__global__ __launch_bounds__(256) void k_runs_clear_plane(
-   const uint64_t* __restrict__ run_keys, const uint32_t* __restrict__ run_ends, uint32_t n_runs, uint32_t position, uint64_t* __restrict__ out
-) {
-   const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x;
-   if (run >= n_runs) {
-      return;
-   }
-   const uint64_t key = run_keys[run];
-   if (static_cast<uint32_t>(key) <= position && position < run_ends[run]) {
-      const uint32_t sequence = static_cast<uint32_t>(key >> 32);
-      atomicAnd(reinterpret_cast<unsigned long long*>(out + (sequence >> 6)), ~(1ull << (sequence & 63u)));
-   }
-}
-
-__global__ void k_scatter_sparse(const uint64_t* __restrict__ keys, uint32_t begin, uint32_t end, uint64_t* out) {
-   const uint32_t k = begin + blockIdx.x * blockDim.x + threadIdx.x;
-   if (k < end) {
-      const uint32_t sequence = static_cast<uint32_t>(keys[k] & 0xFFFFFFFFull);
-      atomicOr(reinterpret_cast<unsigned long long*>(out + (sequence >> 6)), 1ull << (sequence & 63u));
-   }
-}
-
-
 }  // namespace
 
 extern "C" {
-
-int silo_gpu_bitset_alloc(const silo_gpu_store* store, uint64_t** out_dev) {
-   if (store == nullptr || out_dev == nullptr) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_bitset_alloc: bad arguments");
-   }
-   HIP_TRY(hipSetDevice(store->device));
-   const size_t bytes = static_cast<size_t>(store->row_words) * sizeof(uint64_t);
-   HIP_TRY(hipMalloc(out_dev, bytes));
-   HIP_TRY(hipMemset(*out_dev, 0, bytes));
-   HIP_TRY(hipStreamSynchronize(nullptr));  // the fill is enqueued on the null stream; the caller's stream would not wait for it
-   return SILO_GPU_OK;
-}
-
-int silo_gpu_bitset_upload(const silo_gpu_store* store, uint64_t* dst_dev, const uint64_t* src_host, size_t n_words, void* stream) {
-   if (store == nullptr || dst_dev == nullptr || src_host == nullptr || n_words > store->row_words) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_bitset_upload: bad arguments");
-   }
-   auto hip_stream = static_cast<hipStream_t>(stream);
-   HIP_TRY(hipMemsetAsync(dst_dev, 0, static_cast<size_t>(store->row_words) * sizeof(uint64_t), hip_stream));
-   HIP_TRY(hipMemcpyAsync(dst_dev, src_host, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, hip_stream));
-   HIP_TRY(hipStreamSynchronize(hip_stream));
-   return SILO_GPU_OK;
-}
-
-int silo_gpu_bitset_download(const silo_gpu_store* store, uint64_t* dst_host, const uint64_t* src_dev, size_t n_words, void* stream) {
-   if (store == nullptr || dst_host == nullptr || src_dev == nullptr || n_words > store->row_words) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_bitset_download: bad arguments");
-   }
-   auto hip_stream = static_cast<hipStream_t>(stream);
-   HIP_TRY(hipMemcpyAsync(dst_host, src_dev, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, hip_stream));
-   HIP_TRY(hipStreamSynchronize(hip_stream));
-   return SILO_GPU_OK;
-}
-
-int silo_gpu_bitset_from_lineages(const silo_gpu_store* store, uint64_t* dst_dev, const uint8_t* membership_by_lineage, uint32_t n_lineages, void* stream) {
-   if (store == nullptr || dst_dev == nullptr || membership_by_lineage == nullptr) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_bitset_from_lineages: bad arguments");
-   }
-   if (store->d_lineage == nullptr || n_lineages != store->n_lineages) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "store holds no synthetic lineage assignment of that size");
-   }
-   auto hip_stream = static_cast<hipStream_t>(stream);
-   uint8_t* d_membership = nullptr;
-   HIP_TRY(hipMalloc(&d_membership, n_lineages));
-   hipError_t err = hipMemcpyAsync(d_membership, membership_by_lineage, n_lineages, hipMemcpyHostToDevice, hip_stream);
-   if (err == hipSuccess) {
-      const uint32_t threads = store->row_words * 64u;
-      k_bitset_from_lineages<<<(threads + 255) / 256, 256, 0, hip_stream>>>(
-         store->d_lineage, d_membership, store->sequence_count, store->row_words, dst_dev
-      );
-      err = hipStreamSynchronize(hip_stream);
-   }
-   (void)hipFree(d_membership);
-   if (err != hipSuccess) {
-      return fail(SILO_GPU_ERR_HIP, std::string("k_bitset_from_lineages: ") + hipGetErrorString(err));
-   }
-   return SILO_GPU_OK;
-}
-
-int silo_gpu_upload_u32(const uint32_t* src_host, size_t n, uint32_t** out_dev) {
-   if (out_dev == nullptr || (src_host == nullptr && n > 0)) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_upload_u32: bad arguments");
-   }
-   uint32_t* ptr = nullptr;
-   HIP_TRY(hipMalloc(&ptr, std::max<size_t>(n, 1) * sizeof(uint32_t)));
-   hipError_t err = hipMemcpy(ptr, src_host, n * sizeof(uint32_t), hipMemcpyHostToDevice);
-   if (err != hipSuccess) {
-      (void)hipFree(ptr);
-      return fail(SILO_GPU_ERR_HIP, std::string("silo_gpu_upload_u32: ") + hipGetErrorString(err));
-   }
-   *out_dev = ptr;
-   return SILO_GPU_OK;
-}
-
-int silo_gpu_bitset_from_value_ids(const silo_gpu_store* store, uint64_t* dst_dev, const uint32_t* value_ids_dev, const uint8_t* membership_by_value, uint32_t n_values, void* stream) {
-   if (store == nullptr || dst_dev == nullptr || value_ids_dev == nullptr || membership_by_value == nullptr || n_values == 0) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_bitset_from_value_ids: bad arguments");
-   }
-   auto hip_stream = static_cast<hipStream_t>(stream);
-   uint8_t* d_membership = nullptr;
-   HIP_TRY(hipMalloc(&d_membership, n_values));
-   hipError_t err = hipMemcpyAsync(d_membership, membership_by_value, n_values, hipMemcpyHostToDevice, hip_stream);
-   if (err == hipSuccess) {
-      const uint32_t threads = store->row_words * 64u;
-      k_bitset_from_value_ids<<<(threads + 255) / 256, 256, 0, hip_stream>>>(
-         value_ids_dev, d_membership, n_values, store->sequence_count, store->row_words, dst_dev
-      );
-      err = hipStreamSynchronize(hip_stream);
-   }
-   (void)hipFree(d_membership);
-   if (err != hipSuccess) {
-      return fail(SILO_GPU_ERR_HIP, std::string("k_bitset_from_value_ids: ") + hipGetErrorString(err));
-   }
-   return SILO_GPU_OK;
-}
-
-const uint64_t* silo_gpu_store_plane(const silo_gpu_store* store, uint32_t seqstore_id, uint32_t position, uint32_t symbol) {
-   if (store == nullptr || seqstore_id >= store->seqstores.size()) {
-      return nullptr;
-   }
-   const SeqStoreDev& dev = store->seqstores[seqstore_id].dev;
-   if (position >= dev.positions || symbol >= dev.n_symbols) {
-      return nullptr;
-   }
-   return planePtr(dev, position, symbol);
-}
-
-int silo_gpu_store_sparse_plane(const silo_gpu_store* store, uint32_t seqstore_id, uint32_t position, uint32_t symbol, uint64_t* dst_dev, void* stream) {
-   if (store == nullptr || seqstore_id >= store->seqstores.size() || dst_dev == nullptr) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_store_sparse_plane: bad arguments");
-   }
-   const SeqStoreHost& seqstore = store->seqstores[seqstore_id];
-   if (position >= seqstore.dev.positions || symbol >= seqstore.dev.n_symbols) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "position or symbol out of range");
-   }
-   if (!seqstore.finalized) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "store not finalized");
-   }
-   HIP_TRY(hipSetDevice(store->device));
-   auto hip_stream = static_cast<hipStream_t>(stream);
-   if (seqstore.dev.kind[symbol] == PLANE_SCAN) {  // a valid mutation symbol: decode its one-hot plane from the position's code planes
-      k_decode_plane<<<(store->row_words + 255) / 256, 256, 0, hip_stream>>>(seqstore.dev, position, symbol, store->d_ones, dst_dev);
-      HIP_TRY(hipGetLastError());
-      const uint8_t* map = seqstore.layout.code_map.empty() ? nullptr : seqstore.layout.code_map.data() + static_cast<size_t>(position) * CODE_MAP_STRIDE;
-      if (map != nullptr && (map[0] & LAYOUT_IMPLICIT) != 0 && map[IMPLICIT_SLOT] == seqstore.dev.index[symbol]) {
-         // the position's derived symbol: "no other symbol and not missing" (the reference rebuilds its deleted bitmap the same way,
-         // nucleotide_symbol_equals.cpp:158-180) — the kernel took the stored rows away; now the keys, the runs, the ambiguity codes
-         const uint32_t key_begin = seqstore.layout.escape_first[position];
-         const uint32_t key_end = seqstore.layout.escape_first[position + 1];
-         if (key_end > key_begin) {
-            k_clear_keys<<<(key_end - key_begin + 255) / 256, 256, 0, hip_stream>>>(seqstore.layout.d_escapes.get(), key_begin, key_end, dst_dev);
-         }
-         if (seqstore.dev.n_missing_runs > 0) {
-            k_runs_clear_plane<<<(seqstore.dev.n_missing_runs + 255) / 256, 256, 0, hip_stream>>>(
-               seqstore.dev.missing_run_keys, seqstore.dev.missing_run_ends, seqstore.dev.n_missing_runs, position, dst_dev
-            );
-         }
-         const auto lo = std::lower_bound(seqstore.sparse_sorted.begin(), seqstore.sparse_sorted.end(), static_cast<uint64_t>(position) << 37);
-         const auto hi = std::lower_bound(lo, seqstore.sparse_sorted.end(), (static_cast<uint64_t>(position) + 1) << 37);
-         if (hi > lo) {
-            const uint32_t begin = static_cast<uint32_t>(lo - seqstore.sparse_sorted.begin());
-            const uint32_t end = static_cast<uint32_t>(hi - seqstore.sparse_sorted.begin());
-            k_clear_keys<<<(end - begin + 255) / 256, 256, 0, hip_stream>>>(seqstore.d_sparse, begin, end, dst_dev);
-         }
-         HIP_TRY(hipGetLastError());
-         return SILO_GPU_OK;
-      }
-      if (!seqstore.layout.escape_first_symbol.empty()) {  // rows of the symbol that are listed as escape keys (it has no code here)
-         const size_t counter = static_cast<size_t>(position) * seqstore.dev.n_scan + seqstore.dev.index[symbol];
-         const uint32_t begin = seqstore.layout.escape_first_symbol[counter];
-         const uint32_t end = seqstore.layout.escape_first_symbol[counter + 1];
-         if (end > begin) {
-            k_scatter_sparse<<<(end - begin + 255) / 256, 256, 0, hip_stream>>>(seqstore.layout.d_escapes.get(), begin, end, dst_dev);
-            HIP_TRY(hipGetLastError());
-         }
-      }
-      return SILO_GPU_OK;
-   }
-   if (seqstore.dev.kind[symbol] == PLANE_RUNS) {  // the missing symbol: its runs that cover the position
-      HIP_TRY(hipMemsetAsync(dst_dev, 0, static_cast<size_t>(store->row_words) * sizeof(uint64_t), hip_stream));
-      const uint32_t n_runs = seqstore.dev.n_missing_runs;
-      if (n_runs > 0) {
-         k_runs_to_plane<<<(n_runs + 255) / 256, 256, 0, hip_stream>>>(seqstore.dev.missing_run_keys, seqstore.dev.missing_run_ends, n_runs, position, dst_dev);
-         HIP_TRY(hipGetLastError());
-      }
-      return SILO_GPU_OK;
-   }
-   if (seqstore.dev.kind[symbol] == PLANE_EXTRA) {  // already a plane: copy it
-      HIP_TRY(hipMemcpyAsync(
-         dst_dev, planePtr(seqstore.dev, position, symbol), static_cast<size_t>(store->row_words) * sizeof(uint64_t), hipMemcpyDeviceToDevice,
-         hip_stream
-      ));
-      return SILO_GPU_OK;
-   }
-   HIP_TRY(hipMemsetAsync(dst_dev, 0, static_cast<size_t>(store->row_words) * sizeof(uint64_t), hip_stream));
-   const uint64_t key_begin = (static_cast<uint64_t>(position) << 37) | (static_cast<uint64_t>(symbol) << 32);
-   const uint64_t key_end = key_begin + (1ull << 32);
-   const auto lo = std::lower_bound(seqstore.sparse_sorted.begin(), seqstore.sparse_sorted.end(), key_begin);
-   const auto hi = std::lower_bound(lo, seqstore.sparse_sorted.end(), key_end);
-   const uint32_t begin = static_cast<uint32_t>(lo - seqstore.sparse_sorted.begin());
-   const uint32_t end = static_cast<uint32_t>(hi - seqstore.sparse_sorted.begin());
-   if (end > begin) {
-      k_scatter_sparse<<<(end - begin + 255) / 256, 256, 0, hip_stream>>>(seqstore.d_sparse, begin, end, dst_dev);
-      HIP_TRY(hipGetLastError());
-   }
-   return SILO_GPU_OK;
-}
 
 struct silo_gpu_count_slot {
    unsigned long long* host_parts = nullptr;      // page-locked, COUNT_MAX_PARTS words: epoch << 32 | the block's count
@@ -915,7 +522,7 @@ namespace {
 /// after the HIP runtime has shut down).
 struct EvalBatchScratch {
    uint8_t* host_table = nullptr;
-   uint8_t* device_table = nullptr;
+   uint8_t* device_table = nullptr;  // raw on purpose: an owner would free it at thread exit
    size_t table_capacity = 0;
    uint32_t* host_counts = nullptr;
    size_t counts_capacity = 0;  // programs
@@ -1052,46 +659,5 @@ int silo_gpu_popcount(const silo_gpu_store* store, const uint64_t* bitset_dev, u
    HIP_TRY(hipGetLastError());
    return SILO_GPU_OK;
 }
-
-
-int silo_gpu_reconstruct_sequences(
-   const silo_gpu_store* store, uint32_t seqstore_id, const uint32_t* row_ids_dev, uint32_t n_rows, char* out_chars_dev, void* stream
-) {
-   if (store == nullptr || seqstore_id >= store->seqstores.size() || row_ids_dev == nullptr || out_chars_dev == nullptr) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_reconstruct_sequences: bad arguments");
-   }
-   if (n_rows > 65535) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_reconstruct_sequences: at most 65535 rows per call");
-   }
-   HIP_TRY(hipSetDevice(store->device));
-   auto* mutable_store = const_cast<silo_gpu_store*>(store);  // the symbol -> char table is created on first use
-   const SeqStoreHost& seqstore = store->seqstores[seqstore_id];
-   if (!seqstore.finalized) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_reconstruct_sequences: store is not finalized");
-   }
-   if (n_rows == 0 || seqstore.dev.positions == 0) {
-      return SILO_GPU_OK;
-   }
-   const uint32_t alphabet = seqstore.alphabet == SILO_GPU_ALPHABET_AMINO_ACID ? 1 : 0;
-   {
-      const std::lock_guard<std::mutex> lock(mutable_store->mutex);
-      if (mutable_store->d_symbol_chars[alphabet] == nullptr) {
-         // enum order of the reference's alphabets (nucleotide_symbols.h:15-34, aa_symbols.h:15-43)
-         const char* chars = alphabet == 0 ? "-ACGTRYSWKMBDHVN" : "-ACDEFGHIKLMNPQRSTVWYBZ*X";
-         char* device = nullptr;
-         HIP_TRY(hipMalloc(&device, SILO_GPU_MAX_SYMBOLS));
-         HIP_TRY(hipMemcpy(device, chars, strlen(chars), hipMemcpyHostToDevice));
-         mutable_store->d_symbol_chars[alphabet] = device;
-      }
-   }
-   const dim3 grid((seqstore.dev.positions + 255) / 256, n_rows);
-   k_reconstruct_sequences<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(
-      seqstore.dev, seqstore.d_sparse, static_cast<uint32_t>(seqstore.sparse_sorted.size()), row_ids_dev,
-      store->d_symbol_chars[alphabet], out_chars_dev
-   );
-   HIP_TRY(hipGetLastError());
-   return SILO_GPU_OK;
-}
-
 
 }  // extern "C"

@@ -536,7 +536,7 @@ int silo_gpu_mutations_grouped(
    args.h_sym = d_counters + G;
    args.h_stored = args.h_sym + static_cast<size_t>(M) * G;
    args.without_symbol = args.h_stored + static_cast<size_t>(M) * G;
-   args.sparse_keys = seqstore.d_sparse;
+   args.sparse_keys = seqstore.d_sparse.get();
    args.n_mutations = M;
    args.n_groups = G;
    args.n_derived = n_derived;

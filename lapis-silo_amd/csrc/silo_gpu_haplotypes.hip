@@ -348,7 +348,7 @@ int silo_gpu_position_symbols(
       k_symbols_missing_runs<<<blocksOf(dev.n_missing_runs), 256, 0, hip_stream>>>(args);
       HIP_TRY(hipGetLastError());
    }
-   if (seqstore.d_sparse != nullptr && !seqstore.sparse_sorted.empty()) {
+   if (seqstore.d_sparse.get() != nullptr && !seqstore.sparse_sorted.empty()) {
       const std::vector<uint64_t>& sorted = seqstore.sparse_sorted;  // the host copy of d_sparse, as silo_gpu_store_sparse_plane reads it
       KeyRanges ranges{};
       for (uint32_t i = 0; i < args.n_distinct; ++i) {
@@ -358,7 +358,7 @@ int silo_gpu_position_symbols(
          ranges.first[i + 1u] = ranges.first[i] + static_cast<uint32_t>(hi - lo);
       }
       if (const uint32_t keys = ranges.first[args.n_distinct]; keys != 0) {
-         k_symbols_sparse_keys<<<blocksOf(keys), 256, 0, hip_stream>>>(args, seqstore.d_sparse, ranges);
+         k_symbols_sparse_keys<<<blocksOf(keys), 256, 0, hip_stream>>>(args, seqstore.d_sparse.get(), ranges);
          HIP_TRY(hipGetLastError());
       }
    }

@@ -242,7 +242,7 @@ __global__ void k_scatter_missing(const SeqStoreDev store, const uint32_t* __res
 /// Expands one payload into store->d_import_row (zeroed first).
 int expandPayload(silo_gpu_store* store, const void* bytes, size_t n_bytes) {
    const size_t row_bytes = static_cast<size_t>(store->row_words) * sizeof(uint64_t);
-   HIP_TRY(hipMemsetAsync(store->d_import_row, 0, row_bytes, nullptr));
+   HIP_TRY(hipMemsetAsync(store->d_import_row.get(), 0, row_bytes, nullptr));
    std::vector<RoaringContainer> containers;
    if (const int rc = parseRoaringDirectory(static_cast<const uint8_t*>(bytes), n_bytes, containers); rc != SILO_GPU_OK) {
       return rc;
@@ -250,22 +250,20 @@ int expandPayload(silo_gpu_store* store, const void* bytes, size_t n_bytes) {
    if (containers.empty()) {
       return SILO_GPU_OK;
    }
-   uint8_t* d_payload = nullptr;
-   RoaringContainer* d_containers = nullptr;
-   HIP_TRY(hipMalloc(&d_payload, (n_bytes + 7) / 8 * 8));
-   hipError_t status = hipMalloc(&d_containers, containers.size() * sizeof(RoaringContainer));
+   DeviceArray<uint8_t> d_payload;
+   DeviceArray<RoaringContainer> d_containers;
+   HIP_TRY(d_payload.alloc((n_bytes + 7) / 8 * 8));
+   hipError_t status = d_containers.alloc(containers.size());
    if (status == hipSuccess) {
-      status = hipMemcpy(d_payload, bytes, n_bytes, hipMemcpyHostToDevice);  // ONE contiguous copy
+      status = hipMemcpy(d_payload.get(), bytes, n_bytes, hipMemcpyHostToDevice);  // ONE contiguous copy
    }
    if (status == hipSuccess) {
-      status = hipMemcpy(d_containers, containers.data(), containers.size() * sizeof(RoaringContainer), hipMemcpyHostToDevice);
+      status = hipMemcpy(d_containers.get(), containers.data(), containers.size() * sizeof(RoaringContainer), hipMemcpyHostToDevice);
    }
    if (status == hipSuccess) {
-      k_expand_roaring<<<static_cast<uint32_t>(containers.size()), 256>>>(d_payload, d_containers, store->d_import_row, store->row_words, store->sequence_count);
+      k_expand_roaring<<<static_cast<uint32_t>(containers.size()), 256>>>(d_payload.get(), d_containers.get(), store->d_import_row.get(), store->row_words, store->sequence_count);
       status = hipDeviceSynchronize();
    }
-   (void)hipFree(d_payload);
-   (void)hipFree(d_containers);
    HIP_TRY(status);
    return SILO_GPU_OK;
 }
@@ -332,18 +330,17 @@ int silo_gpu_store_import_missing_rows(
    if (pair_rows.empty()) {
       return SILO_GPU_OK;
    }
-   uint32_t* d_pairs = nullptr;
+   DeviceArray<uint32_t> d_pairs;
    const size_t n = pair_rows.size();
-   HIP_TRY(hipMalloc(&d_pairs, 2 * n * sizeof(uint32_t)));
-   hipError_t status = hipMemcpy(d_pairs, pair_positions.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
+   HIP_TRY(d_pairs.alloc(2 * n));
+   hipError_t status = hipMemcpy(d_pairs.get(), pair_positions.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
    if (status == hipSuccess) {
-      status = hipMemcpy(d_pairs + n, pair_rows.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
+      status = hipMemcpy(d_pairs.get() + n, pair_rows.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
    }
    if (status == hipSuccess) {
-      k_scatter_missing<<<static_cast<uint32_t>((n + 255) / 256), 256>>>(seqstore.dev, d_pairs, d_pairs + n, static_cast<uint32_t>(n));
+      k_scatter_missing<<<static_cast<uint32_t>((n + 255) / 256), 256>>>(seqstore.dev, d_pairs.get(), d_pairs.get() + n, static_cast<uint32_t>(n));
       status = hipDeviceSynchronize();
    }
-   (void)hipFree(d_pairs);
    HIP_TRY(status);
    return SILO_GPU_OK;
 }
@@ -389,14 +386,14 @@ int silo_gpu_store_import_position(
    seqstore.finalized = false;
    seqstore.totals_ready = false;
    const size_t row_bytes = static_cast<size_t>(store->row_words) * sizeof(uint64_t);
-   if (store->d_import_row == nullptr) {
-      HIP_TRY(hipMalloc(&store->d_import_row, row_bytes));
-      HIP_TRY(hipMalloc(&store->d_import_union, row_bytes));
+   if (store->d_import_row.get() == nullptr) {
+      HIP_TRY(store->d_import_row.alloc(store->row_words));
+      HIP_TRY(store->d_import_union.alloc(store->row_words));
    }
-   HIP_TRY(hipMemsetAsync(store->d_import_union, 0, row_bytes, nullptr));
+   HIP_TRY(hipMemsetAsync(store->d_import_union.get(), 0, row_bytes, nullptr));
    const uint32_t blocks = (store->row_words + 255) / 256;
    uint32_t count_before = 0;
-   HIP_TRY(hipMemcpy(&count_before, seqstore.d_sparse_count, sizeof(uint32_t), hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(&count_before, seqstore.d_sparse_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
    const auto merge = [&](uint32_t symbol) -> int {
       // a sparsely stored symbol appends one key per row: make room for every row of the store (an import is not a hot path)
       if (dev.kind[symbol] == PLANE_SPARSE) {
@@ -407,15 +404,15 @@ int silo_gpu_store_import_position(
       seqstore.imported_positions.resize(dev.positions, 0);
       seqstore.imported_positions[position] = 1;  // the first launch that writes the planes of the position: it has had its import
       k_merge_symbol_row<<<blocks, 256>>>(
-         seqstore.dev, position, symbol, store->d_import_row, store->d_import_union, seqstore.d_sparse, seqstore.d_sparse_count, seqstore.sparse_capacity,
-         store->d_error_flag
+         seqstore.dev, position, symbol, store->d_import_row.get(), store->d_import_union.get(), seqstore.d_sparse.get(), seqstore.d_sparse_count.get(), seqstore.sparse_capacity,
+         store->d_error_flag.get()
       );
       HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipMemcpy(&count_before, seqstore.d_sparse_count, sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&count_before, seqstore.d_sparse_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
       uint32_t overlap = 0;
-      HIP_TRY(hipMemcpy(&overlap, store->d_error_flag, sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&overlap, store->d_error_flag.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
       if (overlap != 0) {
-         HIP_TRY(hipMemset(store->d_error_flag, 0, sizeof(uint32_t)));
+         HIP_TRY(hipMemset(store->d_error_flag.get(), 0, sizeof(uint32_t)));
          return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_store_import_position: the bitmaps of the position overlap (a row with two symbols) — or the position was imported before");
       }
       return SILO_GPU_OK;
@@ -432,7 +429,7 @@ int silo_gpu_store_import_position(
          return rc;
       }
       if (symbol == flipped_symbol) {  // stored as its complement (position.cpp:70-100)
-         k_complement_rows<<<blocks, 256>>>(store->d_import_row, store->d_import_row, nullptr, store->row_words, store->sequence_count);
+         k_complement_rows<<<blocks, 256>>>(store->d_import_row.get(), store->d_import_row.get(), nullptr, store->row_words, store->sequence_count);
          HIP_TRY(hipGetLastError());
       }
       if (const int rc = merge(symbol); rc != SILO_GPU_OK) {
@@ -442,7 +439,7 @@ int silo_gpu_store_import_position(
    if (deleted_symbol != SILO_GPU_SYMBOL_NONE) {
       // the deleted symbol's rows: every row no other symbol claims and that is not missing here (position.cpp:102-127)
       const uint64_t* missing = dev.kind[dev.missing_symbol] == PLANE_EXTRA ? planePtr(dev, position, dev.missing_symbol) : nullptr;
-      k_complement_rows<<<blocks, 256>>>(store->d_import_row, store->d_import_union, missing, store->row_words, store->sequence_count);
+      k_complement_rows<<<blocks, 256>>>(store->d_import_row.get(), store->d_import_union.get(), missing, store->row_words, store->sequence_count);
       HIP_TRY(hipGetLastError());
       if (const int rc = merge(deleted_symbol); rc != SILO_GPU_OK) {
          return rc;

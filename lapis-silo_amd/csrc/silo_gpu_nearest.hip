@@ -537,8 +537,8 @@ int silo_gpu_query_distances(
    args.q_scan = base;
    args.pref_q = reinterpret_cast<const uint32_t*>(base + scan_bytes);
    args.pref_m = reinterpret_cast<const uint32_t*>(base + scan_bytes + prefix_bytes);
-   args.sparse_keys = seqstore.d_sparse;
-   args.n_sparse = seqstore.d_sparse != nullptr ? static_cast<uint32_t>(seqstore.sparse_sorted.size()) : 0u;
+   args.sparse_keys = seqstore.d_sparse.get();
+   args.n_sparse = seqstore.d_sparse.get() != nullptr ? static_cast<uint32_t>(seqstore.sparse_sorted.size()) : 0u;
    args.n_escapes = has_map && dev.escapes != nullptr && dev.escape_first != nullptr && !seqstore.layout.escape_first.empty()
                        ? seqstore.layout.escape_first.back()
                        : 0u;

@@ -98,7 +98,7 @@ int silo_gpu_malloc(size_t bytes, void** out_dev) {
    if (out_dev == nullptr) {
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_malloc: null out pointer");
    }
-   HIP_TRY(hipMalloc(out_dev, bytes));
+   HIP_TRY(hipMalloc(out_dev, bytes));  // raw on purpose: the caller owns it and returns it through silo_gpu_free
    return SILO_GPU_OK;
 }
 
@@ -256,31 +256,29 @@ int silo_gpu_stream_read_probe(uint64_t bytes, uint32_t reps, float* out_ms_per_
    if (out_ms_per_pass == nullptr || bytes < (1u << 20) || reps == 0) {
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_stream_read_probe: bad arguments");
    }
-   uint64_t* data = nullptr;
-   unsigned long long* sink = nullptr;
+   DeviceArray<uint64_t> data;
+   DeviceArray<unsigned long long> sink;
    hipEvent_t start = nullptr, stop = nullptr;
    bytes &= ~uint64_t{15};
-   hipError_t status = hipMalloc(&data, bytes);
-   status = status != hipSuccess ? status : hipMalloc(&sink, sizeof(unsigned long long));
-   status = status != hipSuccess ? status : hipMemset(data, 0x5A, bytes);
-   status = status != hipSuccess ? status : hipMemset(sink, 0, sizeof(unsigned long long));
+   hipError_t status = data.alloc(bytes / sizeof(uint64_t));
+   status = status != hipSuccess ? status : sink.alloc(1);
+   status = status != hipSuccess ? status : hipMemset(data.get(), 0x5A, bytes);
+   status = status != hipSuccess ? status : hipMemset(sink.get(), 0, sizeof(unsigned long long));
    status = status != hipSuccess ? status : hipEventCreate(&start);
    status = status != hipSuccess ? status : hipEventCreate(&stop);
    float ms = 0;
    if (status == hipSuccess) {
       const uint32_t blocks = 256u * 32u;  // many short blocks: a few rounds of 4-8 blocks of 256 threads per CU
-      k_stream_sum<<<blocks, 256>>>(data, bytes / 16, sink);  // warm-up
+      k_stream_sum<<<blocks, 256>>>(data.get(), bytes / 16, sink.get());  // warm-up
       status = hipEventRecord(start, nullptr);
       for (uint32_t rep = 0; rep < reps && status == hipSuccess; ++rep) {
-         k_stream_sum<<<blocks, 256>>>(data, bytes / 16, sink);
+         k_stream_sum<<<blocks, 256>>>(data.get(), bytes / 16, sink.get());
          status = hipGetLastError();
       }
       status = status != hipSuccess ? status : hipEventRecord(stop, nullptr);
       status = status != hipSuccess ? status : hipEventSynchronize(stop);
       status = status != hipSuccess ? status : hipEventElapsedTime(&ms, start, stop);
    }
-   (void)hipFree(data);
-   (void)hipFree(sink);
    if (start != nullptr) {
       (void)hipEventDestroy(start);
    }
@@ -296,16 +294,26 @@ int silo_gpu_upload_bytes(const void* src_host, size_t bytes, void** out_dev) {
    if (src_host == nullptr || out_dev == nullptr || bytes == 0) {
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_upload_bytes: bad arguments");
    }
-   void* dev = nullptr;
-   HIP_TRY(hipMalloc(&dev, bytes));
-   const hipError_t status = hipMemcpy(dev, src_host, bytes, hipMemcpyHostToDevice);
-   if (status != hipSuccess) {
-      (void)hipFree(dev);
-      HIP_TRY(status);
-   }
-   *out_dev = dev;
+   DeviceArray<uint8_t> dev;
+   HIP_TRY(dev.alloc(bytes));
+   const hipError_t status = hipMemcpy(dev.get(), src_host, bytes, hipMemcpyHostToDevice);
+   HIP_TRY(status);
+   *out_dev = dev.release();
    return SILO_GPU_OK;
 }
 
+int silo_gpu_upload_u32(const uint32_t* src_host, size_t n, uint32_t** out_dev) {
+   if (out_dev == nullptr || (src_host == nullptr && n > 0)) {
+      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_upload_u32: bad arguments");
+   }
+   DeviceArray<uint32_t> dev;
+   HIP_TRY(dev.alloc(std::max<size_t>(n, 1)));
+   hipError_t err = hipMemcpy(dev.get(), src_host, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+   if (err != hipSuccess) {
+      return fail(SILO_GPU_ERR_HIP, std::string("silo_gpu_upload_u32: ") + hipGetErrorString(err));
+   }
+   *out_dev = dev.release();
+   return SILO_GPU_OK;
+}
 
 }  // extern "C"

@@ -186,7 +186,7 @@ int acquireSparseScratch(int device, uint32_t capacity, size_t table_words, Spar
    block->device = device;
    block->capacity = capacity;
    block->table_words = std::max<size_t>(table_words, size_t{1} << 20);
-   void* memory = nullptr;
+   void* memory = nullptr;  // raw on purpose: the pool lives as long as the process and is never freed (the HIP runtime may be gone by then)
    // one allocation: the private tables, the index lists, then the two counter sets (zeroed here, by the scans from then on)
    const size_t counter_words = static_cast<size_t>(SILO_GPU_MAX_SCAN_BATCH) * SPARSE_COUNTER_STRIDE;
    const size_t bytes = (block->table_words + static_cast<size_t>(SILO_GPU_MAX_SCAN_BATCH) * capacity + 2 * counter_words) * sizeof(uint32_t);
@@ -539,7 +539,7 @@ static int scanRangesEntry(
                slot->epoch = 1;
             }
             select.sinks[q] = SelectSink{
-               sink.reference_index_dev, slot->d_cursor_and_ticket, reinterpret_cast<silo_gpu_mutation_row*>(static_cast<char*>(slot->host_dev) + 16),
+               sink.reference_index_dev, slot->d_cursor_and_ticket.get(), reinterpret_cast<silo_gpu_mutation_row*>(static_cast<char*>(slot->host_dev) + 16),
                static_cast<unsigned long long*>(slot->host_dev), min_proportion != nullptr ? min_proportion[first + q] : 0.0, slot->capacity, slot->epoch, 0};
          }
          if (!group.empty()) {
@@ -789,11 +789,11 @@ int silo_gpu_mutations_scan(
       {
          const std::lock_guard<std::mutex> lock(mutable_store->mutex);
          if (!seqstore.totals_ready) {
-            if (seqstore.d_totals == nullptr) {
-               HIP_TRY(hipMalloc(&seqstore.d_totals, n_totals * sizeof(uint32_t)));
+            if (seqstore.d_totals.get() == nullptr) {
+               HIP_TRY(seqstore.d_totals.alloc(n_totals));
             }
-            HIP_TRY(hipMemsetAsync(seqstore.d_totals, 0, n_totals * sizeof(uint32_t), hip_stream_early));
-            const int rc = silo_gpu_mutations_scan(store, seqstore_id, store->d_ones, 0, dev.positions, seqstore.d_totals, stream);
+            HIP_TRY(hipMemsetAsync(seqstore.d_totals.get(), 0, n_totals * sizeof(uint32_t), hip_stream_early));
+            const int rc = silo_gpu_mutations_scan(store, seqstore_id, store->d_ones.get(), 0, dev.positions, seqstore.d_totals.get(), stream);
             if (rc != SILO_GPU_OK) {
                return rc;
             }
@@ -803,7 +803,7 @@ int silo_gpu_mutations_scan(
       }
       const uint32_t n = (pos_end - pos_begin) * dev.n_scan;
       k_add_u32<<<(n + 255) / 256, 256, 0, hip_stream_early>>>(
-         counts_out_dev, seqstore.d_totals + static_cast<size_t>(pos_begin) * dev.n_scan, n
+         counts_out_dev, seqstore.d_totals.get() + static_cast<size_t>(pos_begin) * dev.n_scan, n
       );
       HIP_TRY(hipGetLastError());
       g_last_scan_kernel = "k_add_u32 (cached totals)";

@@ -590,7 +590,7 @@ void planDerived(const silo_gpu_store* store, const std::vector<ScanRange>& rang
          entry.run_ends = seqstore.dev.missing_run_ends;
          entry.run_slice_first = seqstore.layout.d_run_slice_first.get();
          launch.n_run_slices = seqstore.layout.n_run_slices;
-         entry.sparse_keys = seqstore.d_sparse;
+         entry.sparse_keys = seqstore.d_sparse.get();
          const auto lo = std::lower_bound(seqstore.sparse_sorted.begin(), seqstore.sparse_sorted.end(), static_cast<uint64_t>(range.pos_begin) << 37);
          const auto hi = std::lower_bound(lo, seqstore.sparse_sorted.end(), static_cast<uint64_t>(range.pos_end) << 37);
          entry.sparse_begin = static_cast<uint32_t>(lo - seqstore.sparse_sorted.begin());

@@ -142,8 +142,8 @@ int silo_gpu_row_slot_create(uint32_t row_capacity, silo_gpu_row_slot** out_slot
       return fail(SILO_GPU_ERR_OUT_OF_MEMORY, "out of host memory");
    }
    slot->capacity = row_capacity;
-   hipError_t err = hipMalloc(&slot->d_cursor_and_ticket, 2 * sizeof(uint32_t));
-   err = err != hipSuccess ? err : hipMemset(slot->d_cursor_and_ticket, 0, 2 * sizeof(uint32_t));
+   hipError_t err = slot->d_cursor_and_ticket.alloc(2);
+   err = err != hipSuccess ? err : hipMemset(slot->d_cursor_and_ticket.get(), 0, 2 * sizeof(uint32_t));
    err = err != hipSuccess ? err : hipStreamSynchronize(nullptr);  // (the fill is only enqueued; the launches come on other streams)
    err = err != hipSuccess ? err : hipHostMalloc(&slot->host, 16 + sizeof(silo_gpu_mutation_row) * static_cast<size_t>(row_capacity), hipHostMallocMapped | hipHostMallocCoherent);
    if (err == hipSuccess) {
@@ -160,11 +160,10 @@ int silo_gpu_row_slot_create(uint32_t row_capacity, silo_gpu_row_slot** out_slot
 
 void silo_gpu_row_slot_destroy(silo_gpu_row_slot* slot) {
    if (slot != nullptr) {
-      (void)hipFree(slot->d_cursor_and_ticket);
       if (slot->host != nullptr) {
          (void)hipHostFree(slot->host);
       }
-      delete slot;
+      delete slot;  // frees d_cursor_and_ticket
    }
 }
 
@@ -181,7 +180,7 @@ int silo_gpu_mutations_select_to_slot(
    }
    auto* header = static_cast<unsigned long long*>(slot->host_dev);
    k_mutations_select_to_host<<<(n_positions + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(
-      counts_dev, reference_index_dev, n_positions, n_symbols, min_proportion, slot->capacity, slot->d_cursor_and_ticket,
+      counts_dev, reference_index_dev, n_positions, n_symbols, min_proportion, slot->capacity, slot->d_cursor_and_ticket.get(),
       reinterpret_cast<silo_gpu_mutation_row*>(reinterpret_cast<char*>(slot->host_dev) + 16), header, slot->epoch
    );
    HIP_TRY(hipGetLastError());

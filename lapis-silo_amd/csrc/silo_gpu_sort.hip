@@ -8,6 +8,8 @@
 
 #include "internal.h"
 
+using silo_gpu_detail::DeviceArray;
+
 int silo_gpu_internal_sort_keys(uint64_t* keys_dev, size_t n) {
    return silo_gpu_internal_sort_keys_by_bits(keys_dev, n, 0, 64);
 }
@@ -16,22 +18,20 @@ int silo_gpu_internal_sort_keys_by_bits(uint64_t* keys_dev, size_t n, int begin_
    if (n < 2 || begin_bit >= end_bit) {
       return SILO_GPU_OK;
    }
-   uint64_t* sorted = nullptr;
-   void* scratch = nullptr;
+   DeviceArray<uint64_t> sorted;
+   DeviceArray<uint8_t> scratch;
    size_t scratch_bytes = 0;
-   SILO_HIP_TRY(hipMalloc(&sorted, n * sizeof(uint64_t)));
-   hipError_t status = hipcub::DeviceRadixSort::SortKeys(nullptr, scratch_bytes, keys_dev, sorted, n, begin_bit, end_bit, nullptr);
+   SILO_HIP_TRY(sorted.alloc(n));
+   hipError_t status = hipcub::DeviceRadixSort::SortKeys(nullptr, scratch_bytes, keys_dev, sorted.get(), n, begin_bit, end_bit, nullptr);
    if (status == hipSuccess) {
-      status = hipMalloc(&scratch, scratch_bytes);
+      status = scratch.alloc(scratch_bytes);
    }
    if (status == hipSuccess) {
-      status = hipcub::DeviceRadixSort::SortKeys(scratch, scratch_bytes, keys_dev, sorted, n, begin_bit, end_bit, nullptr);
+      status = hipcub::DeviceRadixSort::SortKeys(scratch.get(), scratch_bytes, keys_dev, sorted.get(), n, begin_bit, end_bit, nullptr);
    }
    if (status == hipSuccess) {
-      status = hipMemcpy(keys_dev, sorted, n * sizeof(uint64_t), hipMemcpyDeviceToDevice);
+      status = hipMemcpy(keys_dev, sorted.get(), n * sizeof(uint64_t), hipMemcpyDeviceToDevice);
    }
-   (void)hipFree(scratch);
-   (void)hipFree(sorted);
    SILO_HIP_TRY(status);
    return SILO_GPU_OK;
 }
@@ -40,32 +40,29 @@ int silo_gpu_internal_sort_pairs(uint64_t* keys_dev, uint32_t* values_dev, size_
    if (n < 2) {
       return SILO_GPU_OK;
    }
-   uint64_t* sorted_keys = nullptr;
-   uint32_t* sorted_values = nullptr;
-   void* scratch = nullptr;
+   DeviceArray<uint64_t> sorted_keys;
+   DeviceArray<uint32_t> sorted_values;
+   DeviceArray<uint8_t> scratch;
    size_t scratch_bytes = 0;
-   hipError_t status = hipMalloc(&sorted_keys, n * sizeof(uint64_t));
+   hipError_t status = sorted_keys.alloc(n);
    if (status == hipSuccess) {
-      status = hipMalloc(&sorted_values, n * sizeof(uint32_t));
+      status = sorted_values.alloc(n);
    }
    if (status == hipSuccess) {
-      status = hipcub::DeviceRadixSort::SortPairs(nullptr, scratch_bytes, keys_dev, sorted_keys, values_dev, sorted_values, n, 0, 64, nullptr);
+      status = hipcub::DeviceRadixSort::SortPairs(nullptr, scratch_bytes, keys_dev, sorted_keys.get(), values_dev, sorted_values.get(), n, 0, 64, nullptr);
    }
    if (status == hipSuccess) {
-      status = hipMalloc(&scratch, scratch_bytes);
+      status = scratch.alloc(scratch_bytes);
    }
    if (status == hipSuccess) {
-      status = hipcub::DeviceRadixSort::SortPairs(scratch, scratch_bytes, keys_dev, sorted_keys, values_dev, sorted_values, n, 0, 64, nullptr);
+      status = hipcub::DeviceRadixSort::SortPairs(scratch.get(), scratch_bytes, keys_dev, sorted_keys.get(), values_dev, sorted_values.get(), n, 0, 64, nullptr);
    }
    if (status == hipSuccess) {
-      status = hipMemcpy(keys_dev, sorted_keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice);
+      status = hipMemcpy(keys_dev, sorted_keys.get(), n * sizeof(uint64_t), hipMemcpyDeviceToDevice);
    }
    if (status == hipSuccess) {
-      status = hipMemcpy(values_dev, sorted_values, n * sizeof(uint32_t), hipMemcpyDeviceToDevice);
+      status = hipMemcpy(values_dev, sorted_values.get(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice);
    }
-   (void)hipFree(scratch);
-   (void)hipFree(sorted_keys);
-   (void)hipFree(sorted_values);
    SILO_HIP_TRY(status);
    return SILO_GPU_OK;
 }

@@ -60,11 +60,10 @@ int growSparse(SeqStoreHost& seqstore, uint32_t needed) {
    }
    DeviceArray<uint64_t> bigger;
    HIP_TRY(bigger.alloc(capacity));
-   if (seqstore.d_sparse != nullptr) {
-      HIP_TRY(hipMemcpy(bigger.get(), seqstore.d_sparse, static_cast<size_t>(seqstore.sparse_capacity) * sizeof(uint64_t), hipMemcpyDeviceToDevice));
-      HIP_TRY(hipFree(seqstore.d_sparse));
+   if (seqstore.d_sparse.get() != nullptr) {
+      HIP_TRY(hipMemcpy(bigger.get(), seqstore.d_sparse.get(), static_cast<size_t>(seqstore.sparse_capacity) * sizeof(uint64_t), hipMemcpyDeviceToDevice));
    }
-   seqstore.d_sparse = bigger.release();
+   seqstore.d_sparse = std::move(bigger);
    seqstore.sparse_capacity = capacity;
    return SILO_GPU_OK;
 }
@@ -84,11 +83,13 @@ int ensureBuildPlanes(silo_gpu_store* store, SeqStoreHost& seqstore) {
    const size_t scan_bytes = dev.build_mode == BUILD_ENCODE ? 0 : static_cast<size_t>(dev.positions) * dev.n_bits * dev.row_words * sizeof(uint64_t);
    const size_t extra_bytes = dev.runs_at_build != 0 ? 0 : static_cast<size_t>(dev.positions) * dev.n_extra * dev.row_words * sizeof(uint64_t);
    if (scan_bytes > 0) {
-      HIP_TRY(hipMalloc(&dev.scan, scan_bytes));
+      HIP_TRY(seqstore.d_scan.alloc(scan_bytes / sizeof(uint64_t)));
+      dev.scan = seqstore.d_scan.get();
       HIP_TRY(hipMemset(dev.scan, 0, scan_bytes));
    }
    if (extra_bytes > 0) {
-      HIP_TRY(hipMalloc(&dev.extra, extra_bytes));
+      HIP_TRY(seqstore.d_extra.alloc(extra_bytes / sizeof(uint64_t)));
+      dev.extra = seqstore.d_extra.get();
       HIP_TRY(hipMemset(dev.extra, 0, extra_bytes));
    }
    dev.planes = dev.scan;
@@ -99,7 +100,7 @@ int ensureBuildPlanes(silo_gpu_store* store, SeqStoreHost& seqstore) {
 /// The unfiltered totals of a sequence store (seqstore.d_totals), on the host.
 int downloadTotals(const SeqStoreHost& seqstore, std::vector<uint32_t>& totals) {
    totals.resize(static_cast<size_t>(seqstore.dev.positions) * seqstore.dev.n_scan);
-   HIP_TRY(hipMemcpy(totals.data(), seqstore.d_totals, totals.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(totals.data(), seqstore.d_totals.get(), totals.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
    return SILO_GPU_OK;
 }
 
@@ -190,26 +191,26 @@ int silo_gpu_store_create(const silo_gpu_store_desc* desc, silo_gpu_store** out)
          err = hipMemcpy(seqstore.d_reference.get(), in.reference, in.positions, hipMemcpyHostToDevice);
       }
       if (err == hipSuccess) {
-         err = hipMalloc(&seqstore.d_sparse_count, sizeof(uint32_t));
+         err = seqstore.d_sparse_count.alloc(1);
       }
       if (err == hipSuccess) {
-         err = hipMemset(seqstore.d_sparse_count, 0, sizeof(uint32_t));
+         err = hipMemset(seqstore.d_sparse_count.get(), 0, sizeof(uint32_t));
       }
       if (err != hipSuccess) {
          return cleanup(failHip("allocating planes", err));
       }
    }
-   hipError_t err = hipMalloc(&store->d_ones, static_cast<size_t>(row_words) * sizeof(uint64_t));
+   hipError_t err = store->d_ones.alloc(row_words);
    if (err == hipSuccess) {
-      err = hipMalloc(&store->d_error_flag, sizeof(uint32_t));
+      err = store->d_error_flag.alloc(1);
    }
    if (err == hipSuccess) {
-      err = hipMemset(store->d_error_flag, 0, sizeof(uint32_t));
+      err = hipMemset(store->d_error_flag.get(), 0, sizeof(uint32_t));
    }
    if (err != hipSuccess) {
       return cleanup(fail(SILO_GPU_ERR_HIP, std::string("allocating store: ") + hipGetErrorString(err)));
    }
-   k_fill_ones<<<(row_words + 255) / 256, 256>>>(store->d_ones, row_words, store->sequence_count);
+   k_fill_ones<<<(row_words + 255) / 256, 256>>>(store->d_ones.get(), row_words, store->sequence_count);
    err = hipDeviceSynchronize();
    if (err != hipSuccess) {
       return cleanup(fail(SILO_GPU_ERR_HIP, std::string("k_fill_ones: ") + hipGetErrorString(err)));
@@ -223,25 +224,7 @@ void silo_gpu_store_destroy(silo_gpu_store* store) {
       return;
    }
    (void)hipSetDevice(store->device);
-   for (SeqStoreHost& seqstore : store->seqstores) {
-      (void)hipFree(seqstore.dev.scan);
-      (void)hipFree(seqstore.dev.extra);
-      (void)hipFree(seqstore.d_sparse);
-      (void)hipFree(seqstore.d_sparse_count);
-      (void)hipFree(seqstore.d_totals);
-   }
-   (void)hipFree(store->d_ones);
-   (void)hipFree(store->d_lineage);
-   (void)hipFree(store->d_error_flag);
-   (void)hipFree(store->d_stage);
-   (void)hipFree(store->d_stage_null);
-   (void)hipFree(store->d_import_row);
-   (void)hipFree(store->d_import_union);
-   (void)hipFree(store->d_char_table[0]);
-   (void)hipFree(store->d_char_table[1]);
-   (void)hipFree(store->d_symbol_chars[0]);
-   (void)hipFree(store->d_symbol_chars[1]);
-   delete store;  // frees what the sequence stores own through DeviceArray members, an unfinished two-pass build (SeqStoreHost::work) included
+   delete store;  // frees what the store and its sequence stores own through DeviceArray members, an unfinished two-pass build (SeqStoreHost::work) included
 }
 
 int silo_gpu_store_set_options(silo_gpu_store* store, const silo_gpu_store_options* options) {
@@ -290,17 +273,17 @@ int finalizeSeqStore(silo_gpu_store* store, SeqStoreHost& seqstore) {
       return rc;
    }
    uint32_t count = 0;
-   HIP_TRY(hipMemcpy(&count, seqstore.d_sparse_count, sizeof(uint32_t), hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(&count, seqstore.d_sparse_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
    count = std::min(count, seqstore.sparse_capacity);
    seqstore.sparse_sorted.resize(count);
    if (count > 0) {
-      HIP_TRY(hipMemcpy(seqstore.sparse_sorted.data(), seqstore.d_sparse, static_cast<size_t>(count) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(seqstore.sparse_sorted.data(), seqstore.d_sparse.get(), static_cast<size_t>(count) * sizeof(uint64_t), hipMemcpyDeviceToHost));
       std::sort(seqstore.sparse_sorted.begin(), seqstore.sparse_sorted.end());
       // a replayed batch may have appended duplicates
       seqstore.sparse_sorted.erase(std::unique(seqstore.sparse_sorted.begin(), seqstore.sparse_sorted.end()), seqstore.sparse_sorted.end());
       count = static_cast<uint32_t>(seqstore.sparse_sorted.size());
-      HIP_TRY(hipMemcpy(seqstore.d_sparse, seqstore.sparse_sorted.data(), static_cast<size_t>(count) * sizeof(uint64_t), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(seqstore.d_sparse_count, &count, sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(seqstore.d_sparse.get(), seqstore.sparse_sorted.data(), static_cast<size_t>(count) * sizeof(uint64_t), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(seqstore.d_sparse_count.get(), &count, sizeof(uint32_t), hipMemcpyHostToDevice));
    }
    seqstore.finalized = true;
    // the missing symbol first: its plane goes before the adaptive planes come (a lower peak), and only a store that keeps it as
@@ -343,13 +326,13 @@ int silo_gpu_store_build_pass(silo_gpu_store* store, uint32_t seqstore_id, int p
       if (dev.scan != nullptr || dev.extra != nullptr || dev.build_mode != BUILD_PLANES) {
          return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_store_build_pass: the counting pass has to come before any sequence of the store");
       }
-      if (seqstore.d_totals == nullptr) {
-         HIP_TRY(hipMalloc(&seqstore.d_totals, std::max<size_t>(n_counters, 1) * sizeof(uint32_t)));
+      if (seqstore.d_totals.get() == nullptr) {
+         HIP_TRY(seqstore.d_totals.alloc(std::max<size_t>(n_counters, 1)));
       }
-      HIP_TRY(hipMemset(seqstore.d_totals, 0, std::max<size_t>(n_counters, 1) * sizeof(uint32_t)));
+      HIP_TRY(hipMemset(seqstore.d_totals.get(), 0, std::max<size_t>(n_counters, 1) * sizeof(uint32_t)));
       HIP_TRY(hipStreamSynchronize(nullptr));
       seqstore.totals_ready = false;
-      dev.enc_counts = seqstore.d_totals;
+      dev.enc_counts = seqstore.d_totals.get();
       dev.build_mode = BUILD_COUNT;
       // the missing symbol, where it is the store's only extra plane, is counted (and then written) as runs right away
       dev.runs_at_build = dev.n_extra == 1 && dev.kind[dev.missing_symbol] == PLANE_EXTRA && dev.index[dev.missing_symbol] == 0 && missingRunsOption(store) >= 0 ? 1 : 0;
@@ -369,7 +352,7 @@ int silo_gpu_store_build_pass(silo_gpu_store* store, uint32_t seqstore_id, int p
    HIP_TRY(hipDeviceSynchronize());  // every count of the first pass has landed
    {  // the sparsely stored symbols the first pass counted (it stored none): room for all of them, the counter starts over
       uint32_t counted = 0;
-      HIP_TRY(hipMemcpy(&counted, seqstore.d_sparse_count, sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&counted, seqstore.d_sparse_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
       if (counted > 0xFFFF0000u) {
          return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "two-pass build: too many sparsely stored symbols");
       }
@@ -377,7 +360,7 @@ int silo_gpu_store_build_pass(silo_gpu_store* store, uint32_t seqstore_id, int p
          return rc;
       }
       const uint32_t zero = 0;
-      HIP_TRY(hipMemcpy(seqstore.d_sparse_count, &zero, sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(seqstore.d_sparse_count.get(), &zero, sizeof(uint32_t), hipMemcpyHostToDevice));
    }
    dev.build_mode = BUILD_PLANES;
    dev.enc_counts = nullptr;

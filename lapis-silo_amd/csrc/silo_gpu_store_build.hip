@@ -342,7 +342,7 @@ int launchAndReplay(SeqStoreHost& seqstore, uint32_t rewind_to, uint32_t reserve
       hipError_t err = hipDeviceSynchronize();
       uint32_t count_after = 0;
       if (err == hipSuccess) {
-         err = hipMemcpy(&count_after, seqstore.d_sparse_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
+         err = hipMemcpy(&count_after, seqstore.d_sparse_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost);
       }
       if (err != hipSuccess) {
          return fail(SILO_GPU_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(err));
@@ -353,7 +353,7 @@ int launchAndReplay(SeqStoreHost& seqstore, uint32_t rewind_to, uint32_t reserve
       if (build_mode == BUILD_ENCODE) {
          return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "two-pass build: the second pass brought more sparsely stored symbols than the first pass counted");
       }
-      err = hipMemcpy(seqstore.d_sparse_count, &rewind_to, sizeof(uint32_t), hipMemcpyHostToDevice);
+      err = hipMemcpy(seqstore.d_sparse_count.get(), &rewind_to, sizeof(uint32_t), hipMemcpyHostToDevice);
       if (err != hipSuccess) {
          return fail(SILO_GPU_ERR_HIP, std::string("rewinding sparse counter: ") + hipGetErrorString(err));
       }
@@ -397,29 +397,27 @@ int silo_gpu_store_append_sequences(
 
    const size_t stage_bytes = static_cast<size_t>(n_sequences) * pitch;
    if (stage_bytes > store->stage_capacity) {
-      (void)hipFree(store->d_stage);
-      store->d_stage = nullptr;
       store->stage_capacity = 0;
-      HIP_TRY(hipMalloc(&store->d_stage, stage_bytes));
+      HIP_TRY(store->d_stage.alloc(stage_bytes));
       store->stage_capacity = stage_bytes;
    }
    if (is_null != nullptr && n_sequences > store->stage_null_capacity) {
-      (void)hipFree(store->d_stage_null);
-      store->d_stage_null = nullptr;
       store->stage_null_capacity = 0;
-      HIP_TRY(hipMalloc(&store->d_stage_null, n_sequences));
+      HIP_TRY(store->d_stage_null.alloc(n_sequences));
       store->stage_null_capacity = n_sequences;
    }
-   uint8_t*& d_table_slot = store->d_char_table[seqstore.alphabet == SILO_GPU_ALPHABET_NUCLEOTIDE ? 0 : 1];
-   if (d_table_slot == nullptr) {
+   DeviceArray<uint8_t>& d_table_slot = store->d_char_table[seqstore.alphabet == SILO_GPU_ALPHABET_NUCLEOTIDE ? 0 : 1];
+   if (d_table_slot.get() == nullptr) {
       uint8_t table[256];
       fillCharTable(seqstore.alphabet, table);
-      HIP_TRY(hipMalloc(&d_table_slot, 256));
-      HIP_TRY(hipMemcpy(d_table_slot, table, 256, hipMemcpyHostToDevice));
+      DeviceArray<uint8_t> uploaded;
+      HIP_TRY(uploaded.alloc(256));
+      HIP_TRY(hipMemcpy(uploaded.get(), table, 256, hipMemcpyHostToDevice));
+      d_table_slot = std::move(uploaded);
    }
-   uint8_t* d_chars = store->d_stage;
-   uint8_t* d_null = is_null != nullptr ? store->d_stage_null : nullptr;
-   uint8_t* d_table = d_table_slot;
+   uint8_t* d_chars = store->d_stage.get();
+   uint8_t* d_null = is_null != nullptr ? store->d_stage_null.get() : nullptr;
+   uint8_t* d_table = d_table_slot.get();
    HIP_TRY(hipMemcpy(d_chars, chars, stage_bytes, hipMemcpyHostToDevice));
    if (is_null != nullptr) {
       HIP_TRY(hipMemcpy(d_null, is_null, n_sequences, hipMemcpyHostToDevice));
@@ -431,23 +429,23 @@ int silo_gpu_store_append_sequences(
    const dim3 grid((n_words + 3) / 4, (positions + TRANSPOSE_POSITIONS_PER_WAVE - 1) / TRANSPOSE_POSITIONS_PER_WAVE);
 
    uint32_t count_before = 0;
-   const hipError_t err = hipMemcpy(&count_before, seqstore.d_sparse_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
+   const hipError_t err = hipMemcpy(&count_before, seqstore.d_sparse_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost);
    if (err != hipSuccess) {
       return fail(SILO_GPU_ERR_HIP, std::string("reading sparse counter: ") + hipGetErrorString(err));
    }
    const int rc = launchAndReplay(seqstore, count_before, count_before + (1u << 16), 8, "k_transpose_sequences", [&](uint32_t sparse_capacity) {
       k_transpose_sequences<<<grid, 256>>>(
          seqstore.dev, d_chars, d_null, pitch, first_sequence, n_sequences, first_word, n_words, d_table,
-         seqstore.d_sparse, seqstore.d_sparse_count, sparse_capacity, store->d_error_flag
+         seqstore.d_sparse.get(), seqstore.d_sparse_count.get(), sparse_capacity, store->d_error_flag.get()
       );
    });
    if (rc != SILO_GPU_OK) {
       return rc;
    }
    uint32_t error_flag = 0;
-   HIP_TRY(hipMemcpy(&error_flag, store->d_error_flag, sizeof(uint32_t), hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(&error_flag, store->d_error_flag.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
    if (error_flag != 0) {
-      HIP_TRY(hipMemset(store->d_error_flag, 0, sizeof(uint32_t)));
+      HIP_TRY(hipMemset(store->d_error_flag.get(), 0, sizeof(uint32_t)));
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "Illegal character contained in sequence.");
    }
    return SILO_GPU_OK;
@@ -472,11 +470,11 @@ int silo_gpu_store_generate_synthetic(silo_gpu_store* store, uint32_t seqstore_i
    DeviceArray<uint32_t> d_u32[4];
    DeviceArray<uint8_t> d_lineage_symbol;
    hipError_t err = hipSuccess;
-   if (store->d_lineage == nullptr) {
-      err = hipMalloc(&store->d_lineage, static_cast<size_t>(n) * sizeof(uint16_t));
+   if (store->d_lineage.get() == nullptr) {
+      err = store->d_lineage.alloc(n);
    }
    if (err == hipSuccess) {
-      err = hipMemcpy(store->d_lineage, synth->lineage_of_sequence, static_cast<size_t>(n) * sizeof(uint16_t), hipMemcpyHostToDevice);
+      err = hipMemcpy(store->d_lineage.get(), synth->lineage_of_sequence, static_cast<size_t>(n) * sizeof(uint16_t), hipMemcpyHostToDevice);
       store->n_lineages = synth->n_lineages;
    }
    const uint32_t* host_u32[4] = {synth->lead_gap, synth->trail_gap, synth->missing_start, synth->missing_len};
@@ -501,7 +499,7 @@ int silo_gpu_store_generate_synthetic(silo_gpu_store* store, uint32_t seqstore_i
    args.seed = synth->seed;
    args.n_lineages = synth->n_lineages;
    args.sequence_count = n;
-   args.lineage = store->d_lineage;
+   args.lineage = store->d_lineage.get();
    args.lead_gap = d_u32[0].get();
    args.trail_gap = d_u32[1].get();
    args.missing_start = d_u32[2].get();
@@ -532,7 +530,7 @@ int silo_gpu_store_generate_synthetic(silo_gpu_store* store, uint32_t seqstore_i
    // expected sparse entries: cells * ambiguous_threshold / 2^24 (+ slack)
    const double expected = static_cast<double>(n) * positions * (static_cast<double>(synth->ambiguous_threshold) / 16777216.0);
    uint32_t zero = 0;
-   err = hipMemcpy(seqstore.d_sparse_count, &zero, sizeof(uint32_t), hipMemcpyHostToDevice);
+   err = hipMemcpy(seqstore.d_sparse_count.get(), &zero, sizeof(uint32_t), hipMemcpyHostToDevice);
    if (err != hipSuccess) {
       return fail(SILO_GPU_ERR_HIP, std::string("resetting sparse counter: ") + hipGetErrorString(err));
    }
@@ -541,7 +539,7 @@ int silo_gpu_store_generate_synthetic(silo_gpu_store* store, uint32_t seqstore_i
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "ambiguous_threshold too large for the sparse store");
    }
    return launchAndReplay(seqstore, 0u, static_cast<uint32_t>(wanted), 4, "k_generate_synthetic", [&](uint32_t sparse_capacity) {
-      k_generate_synthetic<<<grid, 256>>>(seqstore.dev, args, n_words, seqstore.d_sparse, seqstore.d_sparse_count, sparse_capacity);
+      k_generate_synthetic<<<grid, 256>>>(seqstore.dev, args, n_words, seqstore.d_sparse.get(), seqstore.d_sparse_count.get(), sparse_capacity);
    });
 }
 

@@ -142,7 +142,7 @@ int everyRowHasASymbol(const silo_gpu_store* store, const SeqStoreHost& seqstore
    const SeqStoreDev& dev = seqstore.dev;
    const uint32_t positions = dev.positions;
    *complete = false;
-   if (seqstore.d_totals == nullptr || !seqstore.totals_ready || dev.kind[dev.missing_symbol] != PLANE_RUNS) {
+   if (seqstore.d_totals.get() == nullptr || !seqstore.totals_ready || dev.kind[dev.missing_symbol] != PLANE_RUNS) {
       return SILO_GPU_OK;
    }
    std::vector<uint32_t> totals, without;
@@ -291,7 +291,7 @@ int finishLayout(silo_gpu_store* store, SeqStoreHost& seqstore, SeqStoreHost::La
    work.d_cursor.reset();
    if (dev.scan != nullptr) {  // the adaptive planes take over; the build-time planes go
       const size_t build_bytes = static_cast<size_t>(positions) * dev.n_bits * dev.row_words * sizeof(uint64_t);
-      (void)hipFree(dev.scan);
+      seqstore.d_scan.reset();
       dev.scan = nullptr;
       store->device_bytes -= build_bytes;
       std::vector<uint8_t>().swap(seqstore.imported_positions);
@@ -368,14 +368,14 @@ int buildLayout(silo_gpu_store* store, SeqStoreHost& seqstore) {
    }
    // the unfiltered totals decide the codes (and are what a full filter adds later on)
    const size_t n_counters = static_cast<size_t>(positions) * dev.n_scan;
-   if (seqstore.d_totals == nullptr) {
-      HIP_TRY(hipMalloc(&seqstore.d_totals, n_counters * sizeof(uint32_t)));
+   if (seqstore.d_totals.get() == nullptr) {
+      HIP_TRY(seqstore.d_totals.alloc(n_counters));
    }
    if (!seqstore.totals_ready) {
-      HIP_TRY(hipMemsetAsync(seqstore.d_totals, 0, n_counters * sizeof(uint32_t), nullptr));
+      HIP_TRY(hipMemsetAsync(seqstore.d_totals.get(), 0, n_counters * sizeof(uint32_t), nullptr));
       ScanRange all{&seqstore, 0, positions, {}};
-      all.counts[0] = seqstore.d_totals;
-      const uint64_t* ones = store->d_ones;
+      all.counts[0] = seqstore.d_totals.get();
+      const uint64_t* ones = store->d_ones.get();
       layout.runs.clear();  // scan the build-time planes
       const int rc = scanRanges(store, {all}, &ones, 1, nullptr);
       if (rc != SILO_GPU_OK) {

@@ -409,7 +409,7 @@ int compactMissingPlane(silo_gpu_store* store, SeqStoreHost& seqstore) {
       return rc;
    }
    d_count.reset();
-   (void)hipFree(dev.extra);  // before the adaptive planes are allocated: a lower peak
+   seqstore.d_extra.reset();  // before the adaptive planes are allocated: a lower peak
    dev.extra = nullptr;
    store->device_bytes -= plane_bytes;
    store->device_bytes += slots * (sizeof(uint64_t) + sizeof(uint32_t));
@@ -546,7 +546,7 @@ int buildGapEvents(silo_gpu_store* store, SeqStoreHost& seqstore) {
       HIP_TRY(d_events.alloc(n_events));
       const uint32_t n_intervals = static_cast<uint32_t>(n_events / 2u);
       k_gap_events<<<(n_intervals + 255) / 256, 256>>>(
-         dev.missing_run_keys, dev.missing_run_ends, dev.n_missing_runs, seqstore.d_sparse, static_cast<uint32_t>(n_sparse), dev.positions, d_events.get()
+         dev.missing_run_keys, dev.missing_run_ends, dev.n_missing_runs, seqstore.d_sparse.get(), static_cast<uint32_t>(n_sparse), dev.positions, d_events.get()
       );
       if (hipGetLastError() != hipSuccess) {
          return fail(SILO_GPU_ERR_HIP, "gap events: the launch failed");
@@ -658,7 +658,7 @@ int buildRowBounds(silo_gpu_store* store, SeqStoreHost& seqstore) {
    SeqStoreHost::Layout& layout = seqstore.layout;
    const SeqStoreDev& dev = seqstore.dev;
    if (!layout.built || !layout.has_implicit || !layout.gap_stream || layout.d_row_target.get() == nullptr || layout.d_row_heaviest.get() != nullptr ||
-       seqstore.d_totals == nullptr || !seqstore.totals_ready || layout.row_of.size() != static_cast<size_t>(dev.positions) + 1) {
+       seqstore.d_totals.get() == nullptr || !seqstore.totals_ready || layout.row_of.size() != static_cast<size_t>(dev.positions) + 1) {
       return SILO_GPU_OK;
    }
    const uint32_t positions = dev.positions;
@@ -756,7 +756,7 @@ int buildEndRuns(silo_gpu_store* store, SeqStoreHost& seqstore) {
    const uint32_t sequences = store->sequence_count;
    const uint32_t symbol = gapScanSymbol(dev);
    if (d_lead.get() == nullptr || !layout.built || !layout.has_implicit || !layout.gap_stream || layout.d_row_target.get() == nullptr || layout.planes.get() == nullptr ||
-       seqstore.d_totals == nullptr || !seqstore.totals_ready || layout.row_of.size() != static_cast<size_t>(positions) + 1 || layout.ends.d_keys.get() != nullptr) {
+       seqstore.d_totals.get() == nullptr || !seqstore.totals_ready || layout.row_of.size() != static_cast<size_t>(positions) + 1 || layout.ends.d_keys.get() != nullptr) {
       return SILO_GPU_OK;
    }
    const uint32_t n_slices = sliceCount(sequences);

@@ -7,7 +7,9 @@
 //   silo_gpu_scan.hip      K1 the Mutations scan over ranges; its passes, one file each behind scan_internal.h:
 //                          silo_gpu_scan_planes.hip (plane rows), silo_gpu_scan_keys.hip (escape keys), silo_gpu_scan_derived.hip (derived symbols)
 //   silo_gpu_select.hip    K4 row selection, row slots
-//   silo_gpu_filter.hip    K2 / K3 / K3b filter evaluation, count slots, bitsets, planes of single symbols, FastaAligned
+//   silo_gpu_filter.hip    K2 / K3 / K3b filter evaluation, count slots
+//   silo_gpu_bitsets.hip   row bitsets: allocation, transfers, membership tables of metadata filters
+//   silo_gpu_planes.hip    planes of single symbols decoded from the store (filter leaves), FastaAligned
 //   silo_gpu_import.hip    import of the reference's roaring payloads
 //   silo_gpu_columns.hip, silo_gpu_comm.hip, silo_gpu_sort.hip   metadata columns, RCCL, rocPRIM sorts
 #pragma once
@@ -48,7 +50,7 @@ extern std::atomic<int> g_tune_sparse_divisor;  // 0 = default (row_words / 16 f
 struct silo_gpu_row_slot {
    uint32_t capacity = 0;
    uint32_t epoch = 0;                       // of the last launch
-   uint32_t* d_cursor_and_ticket = nullptr;  // device: rows appended so far, blocks done so far
+   silo_gpu_detail::DeviceArray<uint32_t> d_cursor_and_ticket;  // device: rows appended so far, blocks done so far
    void* host = nullptr;                     // page-locked: header word (epoch << 32 | selected cells), then the rows from byte 16
    void* host_dev = nullptr;                 // its device address
 };
@@ -66,50 +68,6 @@ inline int failHip(const std::string& what, hipError_t status) {
    (void)hipGetLastError();
    return fail(status == hipErrorOutOfMemory ? SILO_GPU_ERR_OUT_OF_MEMORY : SILO_GPU_ERR_HIP, what + ": " + hipGetErrorString(status));
 }
-
-/// The owner of one device allocation: alloc() is hipMalloc, and hipFree comes when the owner goes, is reset or is assigned to.
-/// Move-only.  Kernels and SeqStoreDev take get().
-template <typename T>
-class DeviceArray {
-  public:
-   DeviceArray() = default;
-   DeviceArray(DeviceArray&& other) noexcept : ptr_(other.release()) {}
-   DeviceArray& operator=(DeviceArray&& other) noexcept {
-      if (this != &other) {
-         reset();
-         ptr_ = other.release();
-      }
-      return *this;
-   }
-   DeviceArray(const DeviceArray&) = delete;
-   DeviceArray& operator=(const DeviceArray&) = delete;
-   ~DeviceArray() { reset(); }
-   /// Room for `count` elements; what the owner held before is freed first.
-   hipError_t alloc(size_t count) {
-      reset();
-      const hipError_t status = hipMalloc(&ptr_, count * sizeof(T));
-      if (status != hipSuccess) {
-         ptr_ = nullptr;
-      }
-      return status;
-   }
-   T* get() const { return ptr_; }
-   /// Hands the allocation over: the caller frees it.
-   T* release() {
-      T* ptr = ptr_;
-      ptr_ = nullptr;
-      return ptr;
-   }
-   void reset() {
-      if (ptr_ != nullptr) {
-         (void)hipFree(ptr_);
-         ptr_ = nullptr;
-      }
-   }
-
-  private:
-   T* ptr_ = nullptr;
-};
 
 constexpr uint32_t ROW_ALIGN_WORDS = 32;  // 256-byte rows
 
@@ -313,9 +271,9 @@ struct SeqStoreHost {
    std::vector<uint8_t> reference;
    DeviceArray<uint8_t> d_reference;
    // sparse symbols: key = position << 37 | symbol << 32 | sequence id
-   uint64_t* d_sparse = nullptr;
+   DeviceArray<uint64_t> d_sparse;
    uint32_t sparse_capacity = 0;
-   uint32_t* d_sparse_count = nullptr;  // device counter
+   DeviceArray<uint32_t> d_sparse_count;  // device counter
    std::vector<uint64_t> sparse_sorted;  // host copy after finalize
    bool finalized = false;
    // rows that received a sequence (append / generate; an import counts none: its bitmaps may leave rows without a symbol).  Only
@@ -326,8 +284,11 @@ struct SeqStoreHost {
    std::vector<uint8_t> imported_positions;
    // counts of the unfiltered store, [positions][n_scan]: what the reference reads from stored
    // cardinalities for a full filter (mutations.cpp:98-136); computed by one scan on first use
-   uint32_t* d_totals = nullptr;
+   DeviceArray<uint32_t> d_totals;
    bool totals_ready = false;
+   // the build-time planes (dev.scan / dev.extra are the views kernels get), owned until finalize releases them
+   DeviceArray<uint64_t> d_scan;
+   DeviceArray<uint64_t> d_extra;
    // the runs of the missing symbol (PLANE_RUNS), owned
    DeviceArray<uint64_t> d_missing_run_keys;
    DeviceArray<uint32_t> d_missing_run_ends;
@@ -445,22 +406,22 @@ struct silo_gpu_store {
    uint32_t row_words = 0;
    uint64_t device_bytes = 0;
    std::vector<silo_gpu_detail::SeqStoreHost> seqstores;
-   uint64_t* d_ones = nullptr;       // the Full bitset
-   uint16_t* d_lineage = nullptr;    // synthetic stores only
+   silo_gpu_detail::DeviceArray<uint64_t> d_ones;     // the Full bitset
+   silo_gpu_detail::DeviceArray<uint16_t> d_lineage;  // synthetic stores only
    uint32_t n_lineages = 0;
-   uint32_t* d_error_flag = nullptr;
+   silo_gpu_detail::DeviceArray<uint32_t> d_error_flag;
    // staging of append_sequences, grown on demand and reused across batches
-   uint8_t* d_stage = nullptr;
+   silo_gpu_detail::DeviceArray<uint8_t> d_stage;
    size_t stage_capacity = 0;
-   uint8_t* d_stage_null = nullptr;
+   silo_gpu_detail::DeviceArray<uint8_t> d_stage_null;
    size_t stage_null_capacity = 0;
    // scratch of silo_gpu_store_import_position: the one-hot row being expanded and the union of the rows seen so far
-   uint64_t* d_import_row = nullptr;
-   uint64_t* d_import_union = nullptr;
+   silo_gpu_detail::DeviceArray<uint64_t> d_import_row;
+   silo_gpu_detail::DeviceArray<uint64_t> d_import_union;
    // how finalize lays the store out: this store's choice, or (SILO_GPU_OPTION_DEFAULT) the process-wide silo_gpu_tune knob
    silo_gpu_store_options options{SILO_GPU_OPTION_DEFAULT, SILO_GPU_OPTION_DEFAULT, SILO_GPU_OPTION_DEFAULT, SILO_GPU_OPTION_DEFAULT};
-   uint8_t* d_char_table[2] = {nullptr, nullptr};  // per alphabet, uploaded on first use
-   char* d_symbol_chars[2] = {nullptr, nullptr};   // symbol -> character, for FastaAligned
+   silo_gpu_detail::DeviceArray<uint8_t> d_char_table[2];  // per alphabet, uploaded on first use
+   silo_gpu_detail::DeviceArray<char> d_symbol_chars[2];   // symbol -> character, for FastaAligned
    std::mutex mutex;
 };
 
