@@ -942,6 +942,63 @@ int silo_gpu_bitset_from_distances(
    void* stream
 );
 
+/* ---- K19: a seeded random subset of a filter's rows (the filter expression Sample) -----------------------
+ * Row r of a partition whose first row has the number first_row in the database is the GLOBAL row first_row + r (< 2^32), and
+ *     key(seed, row) = fmix32(fmix32(row + k1) ^ k2)   with k1 / k2 = the low / high 32 bits of splitmix64(seed)
+ * (fmix32: MurmurHash3's finaliser; arithmetic mod 2^32, splitmix64 mod 2^64) — a bijection of uint32, so no two rows tie.
+ * silo_gpu_sample_key is that function on the host; the kernels compile the same code.  The entries take no store (like
+ * silo_gpu_nearest_rows and silo_gpu_bitset_from_distances).  A selection of the `size` smallest keys per group ("stratum") of rows,
+ * over any number of partitions, is a radix select in four rounds of 8 key bits, most significant first, all on the device:
+ *     silo_gpu_sample_begin, then for round = 0 .. 3 { silo_gpu_sample_count per partition; silo_gpu_sample_advance },
+ *     then silo_gpu_sample_select per partition.
+ * groups_dev: uint16 [row_words * 64], a row's group (< n_groups) or 0xFFFF (any value >= n_groups) for none; NULL = one group that
+ * holds every selected row.  A row COUNTS when its bit in filter_dev is set, it is < sequence_count (padding bits of a filter never
+ * select a row) and it has a group.
+ * state_dev: SILO_GPU_SAMPLE_STATE_BYTES(n_groups) bytes, 16-byte aligned, as uint32 words
+ *     [0] n_groups  [1] size  [2] k1  [3] k2
+ *     [4 + 4g + 0 .. 2]  per group g: the key prefix found so far, the rows still to take under that prefix, the take-all flag
+ *     [4 + 4 * n_groups + g * 256 + d]  the round's histogram
+ * silo_gpu_sample_groups WRITES groups_out_dev[r] for every r < row_words * 64: the date range (index into range_bounds, the ranges
+ *     and the rules for them exactly as for K7: both ends inclusive, 0 / 0xFFFFFFFF where unbounded, pairwise disjoint, NULL dates
+ *     in no range) of each counting row, 0xFFFF for every other row.  Uploads the sorted ranges and waits for the stream once, behind
+ *     its launch.
+ * silo_gpu_sample_begin WRITES the whole state: no prefix, `size` rows to take in every group, histogram 0.  1 <= n_groups <=
+ *     SILO_GPU_MAX_SAMPLE_GROUPS.
+ * silo_gpu_sample_count adds 1 to the histogram cell [group][digit] for every counting row whose group is not take-all and whose
+ *     key's top 8 * round bits equal the group's prefix; digit = the next 8 key bits.  ACCUMULATED, like K1, K7, K8 and K9: one call
+ *     per partition fills one table, which is what makes the selection global.  Integer adds only: the table does not depend on how
+ *     the blocks are scheduled.  Up to SILO_GPU_SAMPLE_LDS_GROUPS groups a block counts into a histogram in LDS and adds its
+ *     non-zero cells to the table; above, every row adds to the table directly.
+ * silo_gpu_sample_advance, per group that is not take-all: in round 0 a group whose histogram sums to <= size becomes take-all;
+ *     otherwise the first digit whose running sum reaches the rows still to take is appended to the prefix and the cells in front
+ *     of it are subtracted from the rows still to take.  Clears the histogram.  After round 3 the prefix is the largest selected
+ *     key of the group and exactly one row is still to take.
+ * silo_gpu_sample_select WRITES every one of the row_words words of out_bitset_dev and nothing behind them:
+ *     bit r = r counts && (take_all[group] || key(r) <= prefix[group]), and 0 for every r when size == 0.
+ * All launch on `stream` and return without waiting (silo_gpu_sample_groups: see above).  Each fails with
+ * SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL state, filter, date column, ranges or output, row_words == 0,
+ * sequence_count > row_words * 64, n_groups / n_ranges outside 1 .. 1 024, ranges K7 refuses, size > INT32_MAX, round > 3, or
+ * first_row + sequence_count > 2^32. */
+#define SILO_GPU_MAX_SAMPLE_GROUPS 1024
+#define SILO_GPU_SAMPLE_LDS_GROUPS 16 /* 16 x 256 cells of 4 bytes: 16 KiB of a block's LDS */
+#define SILO_GPU_SAMPLE_ROUNDS 4
+#define SILO_GPU_SAMPLE_STATE_BYTES(n_groups) (16u + (size_t)(n_groups) * (16u + 256u * 4u))
+uint32_t silo_gpu_sample_key(uint64_t seed, uint32_t global_row);
+int silo_gpu_sample_groups(
+   const uint64_t* filter_dev, const uint32_t* date_column_dev, const uint32_t* range_bounds, uint32_t n_ranges, uint32_t sequence_count,
+   uint32_t row_words, uint16_t* groups_out_dev, void* stream
+);
+int silo_gpu_sample_begin(void* state_dev, uint32_t n_groups, uint32_t size, uint64_t seed, void* stream);
+int silo_gpu_sample_count(
+   void* state_dev, const uint64_t* filter_dev, const uint16_t* groups_dev, uint32_t sequence_count, uint32_t row_words, uint32_t first_row,
+   uint32_t round, void* stream
+);
+int silo_gpu_sample_advance(void* state_dev, uint32_t round, void* stream);
+int silo_gpu_sample_select(
+   const void* state_dev, const uint64_t* filter_dev, const uint16_t* groups_dev, uint32_t sequence_count, uint32_t row_words,
+   uint32_t first_row, uint64_t* out_bitset_dev, void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

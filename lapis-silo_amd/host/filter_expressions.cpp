@@ -928,6 +928,120 @@ std::unique_ptr<Expression> parseWithinDistance(const json::Value& json) {
 
 }  // namespace
 
+// ---- Sample (no counterpart in the reference) -----------------------------------------------------------
+std::string Sample::toString(const Database& database) const {
+   const std::string strata = date_field.has_value() ? " of each of " + std::to_string(range_bounds.size() / 2) + " ranges of '" + *date_field + "'" : "";
+   return "Sample of " + std::to_string(size) + " rows" + strata + " with seed " + std::to_string(seed) + " of (" + child->toString(database) + ")";
+}
+
+std::unique_ptr<Operator> Sample::compile(const Database& database, const DatabasePartition& database_partition, AmbiguityMode mode) const {
+   const RowSpace rows = rowsOf(database_partition);
+   CHECK_SILO_QUERY(
+      database.shard_world <= 1, "Sample is not supported on a sharded database yet: the rows of a selection on the other ranks take part in "
+                                 "the choice, and a row's number in the database is not known to a rank"
+   )
+   if (date_field.has_value()) {
+      const std::optional<storage::ColumnMetadata> column = database.database_config.getMetadata(*date_field);
+      CHECK_SILO_QUERY(
+         column.has_value() && column->type == config::ColumnType::DATE,
+         "The field 'dateField' in a Sample expression ('" + *date_field + "') is not a date column"
+      )
+   }
+   // the child of every partition that has rows, with the number of its first row in the database: the choice is one over all of them
+   std::vector<operators::SampleSelection::Part> parts;
+   std::optional<uint32_t> own;
+   uint64_t first_row = 0;
+   for (const DatabasePartition& partition : database.partitions) {
+      if (first_row + partition.sequence_count >= (uint64_t{1} << 32)) {
+         throw QueryCompilationException("Sample numbers the rows of the database with 32 bits: it needs a database of fewer than 2^32 rows");
+      }
+      if (partition.sequence_count != 0) {
+         if (&partition == &database_partition) {
+            own = static_cast<uint32_t>(parts.size());
+         }
+         const uint32_t* dates = nullptr;
+         if (date_field.has_value()) {
+            const auto* date_column = partition.columns.find(*date_field, config::ColumnType::DATE);
+            CHECK_SILO_QUERY(date_column != nullptr, "The field 'dateField' in a Sample expression ('" + *date_field + "') is not a date column")
+            dates = static_cast<const uint32_t*>(date_column->deviceValues());
+         }
+         parts.push_back({child->compile(database, partition, mode), dates, static_cast<uint32_t>(first_row)});
+      }
+      first_row += partition.sequence_count;
+   }
+   if (!own.has_value() || size == 0 || (date_field.has_value() && range_bounds.empty())) {  // no rows here, or none to take anywhere
+      return std::make_unique<operators::Empty>(rows);
+   }
+   return std::make_unique<operators::SampleSelection>(std::move(parts), *own, size, seed, range_bounds, rows);
+}
+
+namespace {
+
+std::unique_ptr<Expression> parseSample(const json::Value& json) {
+   CHECK_SILO_QUERY(json.contains("child"), "The field 'child' is required in a Sample expression")
+   CHECK_SILO_QUERY(json["child"].is_object(), "The field 'child' in a Sample expression needs to be an object")
+   CHECK_SILO_QUERY(json.contains("size"), "The field 'size' is required in a Sample expression")
+   CHECK_SILO_QUERY(
+      json["size"].is_number_unsigned() && json["size"].as_int64() >= 0 && json["size"].as_int64() <= INT32_MAX,
+      "The field 'size' in a Sample expression needs to be a non-negative integer"
+   )
+   uint64_t seed = 0;
+   if (json.contains("seed")) {
+      CHECK_SILO_QUERY(
+         json["seed"].is_number_unsigned() && json["seed"].as_int64() >= 0,
+         "The field 'seed' in a Sample expression, if present, needs to be a non-negative integer"
+      )
+      seed = static_cast<uint64_t>(json["seed"].as_int64());
+   }
+   CHECK_SILO_QUERY(
+      json.contains("dateField") == json.contains("dateRanges"), "The fields 'dateField' and 'dateRanges' in a Sample expression need to be given together"
+   )
+   std::optional<std::string> date_field;
+   std::vector<uint32_t> range_bounds;  // (from, to) per range as K7 takes them: both inclusive, an open end as the least / greatest date
+   if (json.contains("dateField")) {
+      const std::string entry_form = "{\"dateFrom\": string or null, \"dateTo\": string or null}";
+      CHECK_SILO_QUERY(json["dateField"].is_string(), "The field 'dateField' in a Sample expression needs to be a string")
+      CHECK_SILO_QUERY(json["dateRanges"].is_array(), "The field 'dateRanges' in a Sample expression needs to be an array of objects " + entry_form)
+      date_field = json["dateField"].as_string();
+      for (const auto& element : json["dateRanges"].items()) {
+         CHECK_SILO_QUERY(element.is_object(), "The field 'dateRanges' in a Sample expression needs to be an array of objects " + entry_form)
+         CHECK_SILO_QUERY(
+            range_bounds.size() / 2 < SILO_GPU_MAX_DATE_RANGES, "A Sample expression takes at most " + std::to_string(SILO_GPU_MAX_DATE_RANGES) + " date ranges"
+         )
+         uint32_t from = 1, to = UINT32_MAX;
+         for (const char* field : {"dateFrom", "dateTo"}) {
+            if (!element.contains(field) || element[field].is_null()) {
+               continue;
+            }
+            CHECK_SILO_QUERY(
+               element[field].is_string(), std::string("The field '") + field + "' of a date range in a Sample expression needs to be a string or null"
+            )
+            const common::Date date = common::stringToDate(element[field].as_string());
+            CHECK_SILO_QUERY(
+               date != common::NULL_DATE,
+               std::string("The ") + field + " '" + element[field].as_string() + "' of a date range in a Sample expression is not a valid date (YYYY-MM-DD)"
+            )
+            (std::string_view(field) == "dateFrom" ? from : to) = date;
+         }
+         CHECK_SILO_QUERY(from <= to, "A date range in a Sample expression has dateFrom after dateTo: " + element.dump())
+         range_bounds.push_back(from);
+         range_bounds.push_back(to);
+      }
+      // pairwise disjoint (both ends inclusive): in order of their start, each must begin after the one before ends
+      std::vector<std::pair<uint32_t, uint32_t>> spans;
+      for (size_t k = 0; k < range_bounds.size(); k += 2) {
+         spans.emplace_back(range_bounds[k], range_bounds[k + 1]);
+      }
+      std::sort(spans.begin(), spans.end());
+      for (size_t k = 1; k < spans.size(); ++k) {
+         CHECK_SILO_QUERY(spans[k].first > spans[k - 1].second, "The date ranges in a Sample expression overlap; each row may fall in at most one")
+      }
+   }
+   return std::make_unique<Sample>(parseExpression(json["child"]), json["size"].as_uint32(), seed, std::move(date_field), std::move(range_bounds));
+}
+
+}  // namespace
+
 // ---- JSON -> Expression (the from_json functions) ------------------------------------------------------
 namespace {
 
@@ -1161,6 +1275,9 @@ std::unique_ptr<Expression> parseExpression(const json::Value& json) {  // expre
    }
    if (expression_type == "WithinDistance") {
       return parseWithinDistance(json);
+   }
+   if (expression_type == "Sample") {
+      return parseSample(json);
    }
    throw QueryParseException("Unknown object filter type '" + expression_type + "'");
 }

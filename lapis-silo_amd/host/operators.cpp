@@ -272,6 +272,12 @@ void* ProgramBuilder::temporaryBuffer(size_t bytes) {
    return pointer;
 }
 
+void ProgramBuilder::keep(OperatorResult result) {
+   materialized_children.push_back(std::move(result));
+   buffer_stream = queryStream();
+   has_buffers = true;
+}
+
 ProgramBuilder::~ProgramBuilder() {
    if (has_buffers) {
       (void)silo_gpu_stream_synchronize(buffer_stream);
@@ -670,6 +676,67 @@ uint32_t DistanceSelection::lower(ProgramBuilder& builder) const {
    checkGpu(
       silo_gpu_bitset_from_distances(table, partition.sequence_count, row_words, max_distance, min_compared, bitset, queryStream()),
       "silo_gpu_bitset_from_distances"
+   );
+   return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
+}
+
+// ---- SampleSelection (no counterpart in the reference) --------------------------------------------------
+std::string SampleSelection::toString() const {
+   return "SampleSelection[" + std::to_string(size) + " rows" + (range_bounds.empty() ? "" : " of each of " + std::to_string(range_bounds.size() / 2) + " date ranges") +
+          ", seed " + std::to_string(seed) + "](" + parts[own].child->toString() + ")";
+}
+std::unique_ptr<Operator> SampleSelection::copy() const {
+   std::vector<Part> copies;
+   for (const Part& part : parts) {
+      copies.push_back({part.child->copy(), part.dates, part.first_row});
+   }
+   return std::make_unique<SampleSelection>(std::move(copies), own, size, seed, range_bounds, rows);
+}
+std::unique_ptr<Operator> SampleSelection::negate() const {
+   return std::make_unique<Complement>(this->copy(), rows);
+}
+uint32_t SampleSelection::lower(ProgramBuilder& builder) const {
+   // every partition's rows of the child and, with date ranges, 2 bytes of group per row: they never leave the device.  The
+   // thresholds come from one histogram that all partitions add to, so the same request selects the same rows of the database
+   // however it is cut into partitions; every launch is on the query's stream, ahead of the fused program.
+   struct Evaluated {
+      const uint64_t* filter;
+      const uint16_t* groups;
+      uint32_t sequence_count, row_words, first_row;
+   };
+   const auto n_ranges = static_cast<uint32_t>(range_bounds.size() / 2);
+   void* state = builder.temporaryBuffer(SILO_GPU_SAMPLE_STATE_BYTES(std::max(n_ranges, 1u)));
+   std::vector<Evaluated> evaluated;
+   for (const Part& part : parts) {
+      const DatabasePartition& partition = *part.child->rows.partition;
+      OperatorResult result = part.child->evaluate();
+      Evaluated rows_of{result.bitset(), nullptr, partition.sequence_count, partition.rowWords(), part.first_row};
+      builder.keep(std::move(result));
+      if (n_ranges != 0) {
+         auto* groups = static_cast<uint16_t*>(builder.temporaryBuffer(static_cast<size_t>(rows_of.row_words) * 64u * sizeof(uint16_t)));
+         checkGpu(
+            silo_gpu_sample_groups(rows_of.filter, part.dates, range_bounds.data(), n_ranges, rows_of.sequence_count, rows_of.row_words, groups, queryStream()),
+            "silo_gpu_sample_groups"
+         );
+         rows_of.groups = groups;
+      }
+      evaluated.push_back(rows_of);
+   }
+   checkGpu(silo_gpu_sample_begin(state, std::max(n_ranges, 1u), size, seed, queryStream()), "silo_gpu_sample_begin");
+   for (uint32_t round = 0; round < SILO_GPU_SAMPLE_ROUNDS; ++round) {
+      for (const Evaluated& part : evaluated) {
+         checkGpu(
+            silo_gpu_sample_count(state, part.filter, part.groups, part.sequence_count, part.row_words, part.first_row, round, queryStream()),
+            "silo_gpu_sample_count"
+         );
+      }
+      checkGpu(silo_gpu_sample_advance(state, round, queryStream()), "silo_gpu_sample_advance");
+   }
+   const Evaluated& mine = evaluated[own];
+   uint64_t* bitset = builder.temporaryBitset();
+   checkGpu(
+      silo_gpu_sample_select(state, mine.filter, mine.groups, mine.sequence_count, mine.row_words, mine.first_row, bitset, queryStream()),
+      "silo_gpu_sample_select"
    );
    return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
 }

@@ -124,6 +124,9 @@ class ProgramBuilder {
    /// `bytes` of device memory from the partition's pool with the same lifetime, for a lowering whose launches on queryStream()
    /// need more than a bitset (DistanceSelection: the table of distances and its scratch).  queuedDeviceWork() holds for it too.
    void* temporaryBuffer(size_t bytes);
+   /// Keeps a result whose bitset launches of this lowering read (SampleSelection: the child's rows in the OTHER partitions) as long as
+   /// the builder's own buffers: it returns to its pool behind the same wait.
+   void keep(OperatorResult result);
    /// Appends `columns` as consecutive leaves; returns the imm of an n-ary instruction (first | count << 16).
    uint32_t leafRun(const std::vector<const uint64_t*>& columns);
    /// Children that are stored columns (foldable by one n-ary instruction) vs composite sub-trees.
@@ -194,7 +197,7 @@ class ProgramBuilder {
 namespace operators {
 
 enum Type {
-   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION
+   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION, SAMPLE_SELECTION
 };
 
 /// What lowering a sub-tree into a program takes at most.  `slots`: the slots that are live at once while it is lowered, its
@@ -411,6 +414,38 @@ class DistanceSelection : public Operator {
    uint32_t min_compared;
 };
 
+/// A seeded random subset of the rows a child selects (the filter expression Sample; no counterpart in the reference): the `size`
+/// rows with the smallest keys of a keyed permutation of the database's row numbers — of the whole selection, or of each date range.
+/// The selection is one over ALL partitions, so the operator of a partition holds the child of every partition: lower() evaluates
+/// each of them, finds every group's threshold with K19 (silo_gpu_sample_begin, four rounds of silo_gpu_sample_count per partition
+/// and silo_gpu_sample_advance) without a host round trip, and writes its own partition's bitset (silo_gpu_sample_select), all on
+/// the lowering thread's stream ahead of the fused program, which reads the bitset as a leaf.  The state, the group arrays and the
+/// children's results belong to the builder, like DistanceSelection's buffers: nothing returns to a pool before the stream has
+/// been waited for.
+class SampleSelection : public Operator {
+  public:
+   /// A partition of the database that has rows, in the database's order.
+   struct Part {
+      std::unique_ptr<Operator> child;
+      const uint32_t* dates = nullptr;  // the date column's values on the device; null without date ranges
+      uint32_t first_row = 0;           // the number of the partition's first row in the database
+   };
+   SampleSelection(std::vector<Part> parts, uint32_t own, uint32_t size, uint64_t seed, std::vector<uint32_t> range_bounds, RowSpace rows)
+       : Operator(rows), parts(std::move(parts)), own(own), size(size), seed(seed), range_bounds(std::move(range_bounds)) {}
+   Type type() const override { return SAMPLE_SELECTION; }
+   std::string toString() const override;
+   std::unique_ptr<Operator> copy() const override;
+   std::unique_ptr<Operator> negate() const override;
+   uint32_t lower(ProgramBuilder& builder) const override;
+   Cost cost() const override { return {1, 1}; }
+
+   std::vector<Part> parts;
+   uint32_t own;  // the part this operator answers for
+   uint32_t size;
+   uint64_t seed;
+   std::vector<uint32_t> range_bounds;  // (from, to) per date range as K7 takes them; empty: one group of all rows
+};
+
 class Threshold : public Operator {
   public:
    Threshold(OperatorVector&& non_negated_children, OperatorVector&& negated_children, uint32_t number_of_matchers, bool match_exactly, RowSpace rows);
@@ -597,6 +632,21 @@ struct WithinDistance : public Expression {
    std::optional<std::string> sequence;
    uint32_t max_distance;
    uint32_t min_compared_positions;
+};
+/// Sample (no counterpart in the reference): `size` rows of the child's selection over the WHOLE database, chosen by the order of
+/// key(seed, global row number) — or, with dateField and dateRanges, at most `size` rows of each date range (both ends inclusive, a
+/// NULL date in no range; rows of the child in no range are not selected).  The selection depends on the seed, the child's rows and
+/// their numbers in the database alone, not on how the rows are cut into partitions.  The child is compiled in the mode Sample is
+/// compiled in, for every partition: P partitions compile and evaluate it P times each (no state is kept between them).
+struct Sample : public Expression {
+   Sample(std::unique_ptr<Expression> child, uint32_t size, uint64_t seed, std::optional<std::string> date_field, std::vector<uint32_t> range_bounds)
+       : child(std::move(child)), size(size), seed(seed), date_field(std::move(date_field)), range_bounds(std::move(range_bounds)) {}
+   SILO_DECLARE_EXPRESSION_METHODS
+   std::unique_ptr<Expression> child;
+   uint32_t size;
+   uint64_t seed;
+   std::optional<std::string> date_field;  // with it: range_bounds, (from, to) per range as K7 takes them
+   std::vector<uint32_t> range_bounds;
 };
 struct DateBetween : public Expression {  // date_between.cpp
    DateBetween(std::string column, std::optional<common::Date> date_from, std::optional<common::Date> date_to)

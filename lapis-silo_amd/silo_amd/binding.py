@@ -120,6 +120,8 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_position_symbols", "silo_gpu_haplotype_ids",
     "silo_gpu_mutations_compare",
     "silo_gpu_sequence_differences",
+    "silo_gpu_sample_key", "silo_gpu_sample_groups", "silo_gpu_sample_begin", "silo_gpu_sample_count", "silo_gpu_sample_advance",
+    "silo_gpu_sample_select",
 ]
 
 _lib = None
@@ -210,6 +212,13 @@ def load_library():
     lib.silo_gpu_mutations_compare.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_double, ctypes.c_double,
                                                ctypes.c_uint32, vp, vp]
     lib.silo_gpu_sequence_differences.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, vp, vp]
+    lib.silo_gpu_sample_key.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+    lib.silo_gpu_sample_key.restype = ctypes.c_uint32
+    lib.silo_gpu_sample_groups.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_sample_begin.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, vp]
+    lib.silo_gpu_sample_count.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp]
+    lib.silo_gpu_sample_advance.argtypes = [vp, ctypes.c_uint32, vp]
+    lib.silo_gpu_sample_select.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -1025,6 +1034,95 @@ def bitset_from_distances(table, sequence_count, row_words, max_distance=NO_ROW,
     finally:
         device_free(table_dev)
         device_free(out)
+
+
+MAX_SAMPLE_GROUPS = 1024   # SILO_GPU_MAX_SAMPLE_GROUPS
+SAMPLE_LDS_GROUPS = 16     # SILO_GPU_SAMPLE_LDS_GROUPS: above, silo_gpu_sample_count adds to the table in global memory directly
+SAMPLE_ROUNDS = 4          # SILO_GPU_SAMPLE_ROUNDS
+NO_SAMPLE_GROUP = 0xFFFF   # a row of a group array that belongs to no group
+
+
+def sample_state_bytes(n_groups):
+    """SILO_GPU_SAMPLE_STATE_BYTES: the state of a selection over n_groups groups."""
+    return 16 + int(n_groups) * (16 + 256 * 4)
+
+
+def sample_key(seed, global_row):
+    """silo_gpu_sample_key: the key of a row of the database under a seed (host function; the kernels compile the same code)."""
+    return int(load_library().silo_gpu_sample_key(int(seed), int(global_row)))
+
+
+def sample_state(words, n_groups):
+    """The uint32 words of a K19 state as a dict: n_groups, size, k1, k2, and per group prefix, remaining, take_all (uint32
+    [n_groups] each) and histogram uint32 [n_groups][256]."""
+    words = np.asarray(words, dtype=np.uint32)
+    groups = words[4:4 + 4 * n_groups].reshape(n_groups, 4)
+    return {"n_groups": int(words[0]), "size": int(words[1]), "k1": int(words[2]), "k2": int(words[3]), "prefix": groups[:, 0].copy(),
+            "remaining": groups[:, 1].copy(), "take_all": groups[:, 2].copy(),
+            "histogram": words[4 + 4 * n_groups:4 + 4 * n_groups + 256 * n_groups].reshape(n_groups, 256).copy()}
+
+
+def _upload(array, stream=None):
+    """A device copy of a host array (free with device_free)."""
+    ptr = device_malloc(array.nbytes)
+    if array.nbytes:
+        _check(load_library().silo_gpu_memcpy_h2d(ptr, _ptr(array), array.nbytes, stream))
+    return ptr
+
+
+def sample_groups(filter_words, dates, range_bounds, sequence_count, row_words, fill=None, guard_rows=0, stream=None):
+    """silo_gpu_sample_groups (K19) over host arrays: filter_words uint64 [row_words], dates uint32 [>= sequence_count] (0 = NULL),
+    range_bounds uint32 [n_ranges][2] = from, to (both inclusive).  Returns uint16 [row_words * 64 + guard_rows]: each row's range,
+    0xFFFF for none, followed by `guard_rows` entries the call must not touch (they hold the byte `fill` repeated)."""
+    lib = load_library()
+    filter_words = np.ascontiguousarray(filter_words, dtype=np.uint64)
+    dates = np.ascontiguousarray(dates, dtype=np.uint32)
+    range_bounds = np.ascontiguousarray(range_bounds, dtype=np.uint32).reshape(-1, 2)
+    rows = int(row_words) * 64 + int(guard_rows)
+    filter_dev, dates_dev, out = _upload(filter_words, stream), _upload(dates, stream), device_malloc(rows * 2, fill, stream)
+    try:
+        _check(lib.silo_gpu_sample_groups(filter_dev, dates_dev, _ptr(range_bounds), len(range_bounds), sequence_count, row_words, out, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(out, np.uint16, rows, stream)
+    finally:
+        for ptr in (filter_dev, dates_dev, out):
+            device_free(ptr)
+
+
+def sample(partitions, size, seed=0, n_groups=1, fill=None, guard_words=0, stream=None):
+    """A whole K19 selection over host arrays: silo_gpu_sample_begin, four rounds of silo_gpu_sample_count per partition and
+    silo_gpu_sample_advance, silo_gpu_sample_select per partition.  partitions: a list of dicts {filter: uint64 [row_words], groups:
+    uint16 [row_words * 64] or None (one group of every selected row), sequence_count, row_words, first_row}.  Returns (outputs,
+    state): per partition the row_words words silo_gpu_sample_select writes followed by `guard_words` words behind them that it
+    must not touch (every output is filled with the byte `fill` before the launches), and the state after round 3 as sample_state
+    gives it."""
+    lib = load_library()
+    state = device_malloc(sample_state_bytes(n_groups), fill, stream)
+    device = []
+    try:
+        for part in partitions:
+            filter_words = np.ascontiguousarray(part["filter"], dtype=np.uint64)
+            groups = None if part.get("groups") is None else np.ascontiguousarray(part["groups"], dtype=np.uint16)
+            device.append({"filter": _upload(filter_words, stream), "groups": None if groups is None else _upload(groups, stream),
+                           "out": device_malloc((int(part["row_words"]) + int(guard_words)) * 8, fill, stream)})
+        _check(lib.silo_gpu_sample_begin(state, n_groups, size, seed, stream))
+        for sample_round in range(SAMPLE_ROUNDS):
+            for part, dev in zip(partitions, device):
+                _check(lib.silo_gpu_sample_count(state, dev["filter"], dev["groups"], part["sequence_count"], part["row_words"], part["first_row"],
+                                                 sample_round, stream))
+            _check(lib.silo_gpu_sample_advance(state, sample_round, stream))
+        for part, dev in zip(partitions, device):
+            _check(lib.silo_gpu_sample_select(state, dev["filter"], dev["groups"], part["sequence_count"], part["row_words"], part["first_row"],
+                                              dev["out"], stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        outputs = [device_read(dev["out"], np.uint64, int(part["row_words"]) + int(guard_words), stream) for part, dev in zip(partitions, device)]
+        return outputs, sample_state(device_read(state, np.uint32, sample_state_bytes(n_groups) // 4, stream), n_groups)
+    finally:
+        device_free(state)
+        for dev in device:
+            for ptr in dev.values():
+                if ptr is not None:
+                    device_free(ptr)
 
 
 class GpuStore:
