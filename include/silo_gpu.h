@@ -416,6 +416,12 @@ int silo_gpu_mutations_scan(
  * silo_gpu_store_scan_escapes: number of exception keys (0 without the index). */
 uint32_t silo_gpu_store_scan_planes(const silo_gpu_store* store, uint32_t seqstore_id);
 uint64_t silo_gpu_store_scan_escapes(const silo_gpu_store* store, uint32_t seqstore_id);
+/* The scan's escape pass reads the exception keys slice by slice of 2^17 sequences, packed to 4 bytes in granules of 4 096 keys:
+ * a key's counter (position x scan symbols + symbol) relative to its granule's first.  A key more than 6 000 counters past it —
+ * a stretch of positions with very few exceptions — is kept at 8 bytes in an overflow list that the scan counts in a launch of
+ * its own.  silo_gpu_store_scan_overflow_keys: the keys of that list (0 for a store that is not finalized or has no
+ * slice-major keys). */
+uint64_t silo_gpu_store_scan_overflow_keys(const silo_gpu_store* store, uint32_t seqstore_id);
 /* Plane rows (of Wp words each) the Mutations scan reads for positions [pos_begin, pos_end) of a sequence store: the
  * physical bytes of a scan are this x 8 Wp, plus the filter and 8 bytes per escape key. */
 uint64_t silo_gpu_store_scan_rows(const silo_gpu_store* store, uint32_t seqstore_id, uint32_t pos_begin, uint32_t pos_end);

@@ -764,6 +764,13 @@ uint64_t silo_gpu_store_scan_escapes(const silo_gpu_store* store, uint32_t seqst
    return store->seqstores[seqstore_id].layout.escape_first.back();
 }
 
+uint64_t silo_gpu_store_scan_overflow_keys(const silo_gpu_store* store, uint32_t seqstore_id) {
+   if (store == nullptr || seqstore_id >= store->seqstores.size() || !store->seqstores[seqstore_id].layout.built) {
+      return 0;
+   }
+   return store->seqstores[seqstore_id].layout.escapes_sliced.n_overflow;  // (0 in a store without slice-major keys)
+}
+
 
 int silo_gpu_mutations_scan(
    const silo_gpu_store* store, uint32_t seqstore_id, const uint64_t* filter_dev, uint32_t pos_begin, uint32_t pos_end,

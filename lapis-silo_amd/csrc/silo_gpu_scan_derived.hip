@@ -712,7 +712,16 @@ int finishDerived(DerivedPlan& plan, uint32_t q_count, hipStream_t hip_stream) {
       }
       if (launch.first_unit[launch.n_ranges] != 0) {
          const dim3 grid(launch.first_unit[launch.n_ranges], q_count);
-         if (plan.select && launch.ranges[0].n_scan == 5) {  // (a scan's ranges are of one alphabet)
+         const bool nucleotide = launch.ranges[0].n_scan == 5;  // (a scan's ranges are of one alphabet)
+         uint64_t table_bytes = 0;  // the private tables: every word read once
+         for (uint32_t k = 0; k < launch.n_ranges; ++k) {
+            table_bytes += static_cast<uint64_t>(launch.ranges[k].stride) * q_count * sizeof(uint32_t);
+         }
+         // (the instantiation is named in the timing log: whether a scan selected its rows here is not visible in its tables)
+         const char* const name = plan.select ? (nucleotide ? "k_finish_scan<true, 5>" : "k_finish_scan<true, 22>")
+                                              : (plan.events ? "k_finish_scan<true, 0>" : "k_finish_scan<false, 0>");
+         ScanLaunchTiming* timing = startLaunchTiming(name, 0, table_bytes, q_count, grid.x * grid.y, hip_stream);
+         if (plan.select && nucleotide) {
             k_finish_scan<true, 5><<<grid, DERIVED_THREADS, 0, hip_stream>>>(launch);
          } else if (plan.select) {
             k_finish_scan<true, 22><<<grid, DERIVED_THREADS, 0, hip_stream>>>(launch);
@@ -722,6 +731,7 @@ int finishDerived(DerivedPlan& plan, uint32_t q_count, hipStream_t hip_stream) {
             k_finish_scan<false, 0><<<grid, DERIVED_THREADS, 0, hip_stream>>>(launch);
          }
          HIP_TRY(hipGetLastError());
+         finishLaunchTiming(timing, hip_stream);
       }
    }
    return SILO_GPU_OK;

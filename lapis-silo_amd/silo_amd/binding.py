@@ -103,7 +103,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_bitset_upload", "silo_gpu_bitset_download", "silo_gpu_bitset_from_lineages", "silo_gpu_upload_u32",
     "silo_gpu_bitset_from_value_ids", "silo_gpu_free",
     "silo_gpu_malloc", "silo_gpu_memcpy_d2h", "silo_gpu_memcpy_h2d", "silo_gpu_stream_synchronize", "silo_gpu_stream_create", "silo_gpu_set_device", "silo_gpu_stream_destroy", "silo_gpu_store_plane",
-    "silo_gpu_store_sparse_plane", "silo_gpu_filter_eval", "silo_gpu_filter_eval_batch", "silo_gpu_popcount", "silo_gpu_mutations_scan", "silo_gpu_mutations_scan_batch", "silo_gpu_mutations_scan_ranges", "silo_gpu_mutations_grouped", "silo_gpu_store_scan_planes", "silo_gpu_store_scan_escapes", "silo_gpu_store_scan_rows", "silo_gpu_store_scan_runs", "silo_gpu_row_slot_create", "silo_gpu_row_slot_destroy", "silo_gpu_mutations_select_to_slot", "silo_gpu_row_slot_wait", "silo_gpu_store_scan_sparse_keys", "silo_gpu_store_finalize_seqstore", "silo_gpu_store_build_pass", "silo_gpu_store_build_mode", "silo_gpu_store_memory_info", "silo_gpu_store_import_position", "silo_gpu_store_import_missing_rows",
+    "silo_gpu_store_sparse_plane", "silo_gpu_filter_eval", "silo_gpu_filter_eval_batch", "silo_gpu_popcount", "silo_gpu_mutations_scan", "silo_gpu_mutations_scan_batch", "silo_gpu_mutations_scan_ranges", "silo_gpu_mutations_grouped", "silo_gpu_store_scan_planes", "silo_gpu_store_scan_escapes", "silo_gpu_store_scan_overflow_keys", "silo_gpu_store_scan_rows", "silo_gpu_store_scan_runs", "silo_gpu_row_slot_create", "silo_gpu_row_slot_destroy", "silo_gpu_mutations_select_to_slot", "silo_gpu_row_slot_wait", "silo_gpu_store_scan_sparse_keys", "silo_gpu_store_finalize_seqstore", "silo_gpu_store_build_pass", "silo_gpu_store_build_mode", "silo_gpu_store_memory_info", "silo_gpu_store_import_position", "silo_gpu_store_import_missing_rows",
     "silo_gpu_memset_async", "silo_gpu_event_create", "silo_gpu_event_record", "silo_gpu_event_elapsed_ms",
     "silo_gpu_event_destroy", "silo_gpu_event_synchronize", "silo_gpu_host_alloc", "silo_gpu_host_free", "silo_gpu_memcpy_d2h_async", "silo_gpu_mutations_select", "silo_gpu_upload_bytes", "silo_gpu_upload_column", "silo_gpu_bitset_from_compare", "silo_gpu_group_count", "silo_gpu_group_count_hashed", "silo_gpu_reconstruct_sequences", "silo_gpu_bitset_from_pairs", "silo_gpu_count_pairs", "silo_gpu_count_slot_create", "silo_gpu_count_slot_destroy", "silo_gpu_filter_eval_count", "silo_gpu_count_slot_wait", "silo_gpu_tune", "silo_gpu_last_scan_kernel", "silo_gpu_scan_timings", "silo_gpu_stream_read_probe", "silo_gpu_last_error",
     "silo_gpu_comm_unique_id", "silo_gpu_comm_create", "silo_gpu_comm_destroy", "silo_gpu_comm_rank", "silo_gpu_comm_world",
@@ -177,6 +177,8 @@ def load_library():
     lib.silo_gpu_store_scan_planes.restype = ctypes.c_uint32
     lib.silo_gpu_store_scan_escapes.argtypes = [vp, ctypes.c_uint32]
     lib.silo_gpu_store_scan_escapes.restype = ctypes.c_uint64
+    lib.silo_gpu_store_scan_overflow_keys.argtypes = [vp, ctypes.c_uint32]
+    lib.silo_gpu_store_scan_overflow_keys.restype = ctypes.c_uint64
     lib.silo_gpu_mutations_scan_ranges.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32, ctypes.POINTER(vp), vp]
     lib.silo_gpu_mutations_scan_ranges_min_proportion.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(vp), ctypes.c_uint32,
                                                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(vp), vp]
@@ -1390,6 +1392,11 @@ class GpuStore:
 
     def scan_escapes(self, seqstore_id):
         return self.lib.silo_gpu_store_scan_escapes(self.handle, seqstore_id)
+
+    def scan_overflow_keys(self, seqstore_id):
+        """Escape keys of the store that do not fit the packed form of their granule: a scan counts them in a launch of its own
+        (0 for a store that is not finalized or has no slice-major keys)."""
+        return int(self.lib.silo_gpu_store_scan_overflow_keys(self.handle, seqstore_id))
 
     def scan_prunable_granules(self, seqstore_id, cardinality, min_proportion):
         """(skippable, total) granules of the store's slice-major escape keys for one filter of `cardinality` rows."""
