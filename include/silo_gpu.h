@@ -1005,6 +1005,67 @@ int silo_gpu_sample_select(
    uint32_t first_row, uint64_t* out_bitset_dev, void* stream
 );
 
+/* ---- K20: one row per distinct aligned sequence (the filter expression DistinctSequences) -----------------
+ * sym(r, p) is the index of the symbol row r holds at position p in the alphabet's own order — what silo_gpu_reconstruct_sequences
+ * turns into a character — and 31 for a cell that nothing stored claims (its '?').  With splitmix64 as in K19, mod 2^64:
+ *     x = p * 32 + sym,   H0(p, sym) = splitmix64(x),   H1(p, sym) = splitmix64(x + 2^40)
+ *     hash(r) = (sum over p of H0(p, sym(r, p)), sum over p of H1(p, sym(r, p)))
+ * Rows with equal aligned sequences have equal hashes; rows with equal hashes are TREATED as equal (two given different rows
+ * collide with probability 2^-128 for a function drawn at random): the one probabilistic answer of this library.
+ * silo_gpu_row_hash_term is H0 (lane 0) / H1 (lane 1) on the host; the kernels compile the same code.
+ * silo_gpu_row_hashes WRITES out_dev[r] = hash(r) for every r < sequence_count and (0, 0) for every other r < row_words * 64, for a
+ *     finalized store in any layout: the plane pass writes each row's sums over what the planes say (code planes, one-hot rows,
+ *     extra planes; a cell they leave open counts as the position's derived symbol, or as 31 where none is derived) with plain
+ *     16-byte stores, then a thread per escape key, per run of the missing symbol and per sparse key adds the difference between its
+ *     symbol's term and the one the plane pass assumed (64-bit integer atomics: exact, whatever the schedule).  scratch_dev:
+ *     SILO_GPU_ROW_HASH_SCRATCH_BYTES(positions) bytes, 256-byte aligned, for two per-position tables built on the host; uploads
+ *     them and waits for the stream once, ahead of its launches.
+ * silo_gpu_store_row_hashes returns the store's own copy of that table: the first call per sequence store allocates 16 bytes x
+ *     row_words * 64 (from then on part of silo_gpu_store_device_bytes), runs silo_gpu_row_hashes on `stream` and waits; every
+ *     later call returns the same pointer without device work.  Thread-safe.  The table lives as long as the store.
+ * Both fail with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer, a seqstore_id out of range or a store that is
+ * not finalized.
+ *
+ * The selection takes no store.  A database is an array of PARTS ordered by first_row; row r of a part is the GLOBAL row
+ * first_row + r (< 2^32 - 1).  table_dev: SILO_GPU_DISTINCT_TABLE_BYTES(slots) bytes as uint32 — `slots` owners (a power of two; the
+ * global row that represents a class, 0xFFFFFFFF = empty) and one overflow counter behind them.
+ * silo_gpu_distinct_begin WRITES the whole table: every slot empty, the counter 0.
+ * silo_gpu_distinct_insert, once per part: every row of the part that counts — its bit in filter_dev set and r < sequence_count
+ *     (padding bits of a filter never select a row) — probes linearly from (lane 0 of its hash) & (slots - 1): an empty slot is
+ *     claimed with a compare-and-swap; a slot whose owner has the row's hash takes the smaller of the two global rows (atomic min);
+ *     any other slot is passed.  A slot, once claimed, only ever holds rows of one class, and a class only ever sits in one slot.
+ *     A row that has passed `slots` slots adds 1 to the overflow counter and gives up: with slots >= 2 x the rows inserted this
+ *     does not happen.  After the inserts of all parts a class's slot holds its smallest global row, whatever the schedule.
+ * silo_gpu_distinct_select WRITES every one of the part's row_words words of out_bitset_dev and nothing behind them:
+ *     bit r = r counts && the slot of r's class is owned by first_row + r   (a read-only probe).
+ * All launch on `stream`.  silo_gpu_distinct_begin returns without waiting; insert and select read parts_dev[part] back first (24
+ * bytes behind whatever `stream` holds: one wait ahead of the launch), which sizes the grid and is what they check.  Each fails with
+ * SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer, slots 0 or not a power of two, n_parts == 0, part >= n_parts,
+ * a part with a NULL hash table, row_words == 0, sequence_count > row_words * 64 or first_row + sequence_count >= 2^32 - 1. */
+#define SILO_GPU_ROW_HASH_NO_SYMBOL 31u
+#define SILO_GPU_ROW_HASH_SCRATCH_BYTES(positions) ((size_t)(positions) * 17u + 1024u)
+#define SILO_GPU_DISTINCT_EMPTY 0xFFFFFFFFu
+#define SILO_GPU_DISTINCT_TABLE_BYTES(slots) (((size_t)(slots) + 1u) * 4u)
+typedef struct silo_gpu_distinct_part {
+   const uint64_t* hashes_dev; /* [row_words * 64][2], as silo_gpu_row_hashes writes them */
+   uint32_t first_row;
+   uint32_t sequence_count;
+   uint32_t row_words;
+   uint32_t reserved;
+} silo_gpu_distinct_part;
+uint64_t silo_gpu_row_hash_term(uint32_t position, uint32_t symbol, uint32_t lane);
+int silo_gpu_row_hashes(const silo_gpu_store* store, uint32_t seqstore_id, uint64_t* out_dev, void* scratch_dev, void* stream);
+int silo_gpu_store_row_hashes(silo_gpu_store* store, uint32_t seqstore_id, const uint64_t** out_dev, void* stream);
+int silo_gpu_distinct_begin(void* table_dev, uint32_t slots, void* stream);
+int silo_gpu_distinct_insert(
+   void* table_dev, uint32_t slots, const silo_gpu_distinct_part* parts_dev, uint32_t n_parts, uint32_t part, const uint64_t* filter_dev,
+   void* stream
+);
+int silo_gpu_distinct_select(
+   const void* table_dev, uint32_t slots, const silo_gpu_distinct_part* parts_dev, uint32_t n_parts, uint32_t part,
+   const uint64_t* filter_dev, uint64_t* out_bitset_dev, void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

@@ -286,6 +286,10 @@ struct SeqStoreHost {
    // cardinalities for a full filter (mutations.cpp:98-136); computed by one scan on first use
    DeviceArray<uint32_t> d_totals;
    bool totals_ready = false;
+   // the 128-bit hash of every row, [row_words * 64][2] (K20, silo_gpu_distinct.hip): computed on the first
+   // silo_gpu_store_row_hashes of the finalized store and kept, under the store's mutex
+   DeviceArray<uint64_t> d_row_hashes;
+   bool row_hashes_ready = false;
    // the build-time planes (dev.scan / dev.extra are the views kernels get), owned until finalize releases them
    DeviceArray<uint64_t> d_scan;
    DeviceArray<uint64_t> d_extra;

@@ -1042,6 +1042,59 @@ std::unique_ptr<Expression> parseSample(const json::Value& json) {
 
 }  // namespace
 
+// ---- DistinctSequences (no counterpart in the reference) ------------------------------------------------
+std::string DistinctSequences::toString(const Database& database) const {
+   const std::string sequence_string = sequence_name.has_value() ? "the sequence '" + sequence_name.value() + "'" : "the default nucleotide sequence";
+   return "One row per distinct value of " + sequence_string + " of (" + child->toString(database) + ")";
+}
+
+std::unique_ptr<Operator> DistinctSequences::compile(const Database& database, const DatabasePartition& database_partition, AmbiguityMode mode) const {
+   const RowSpace rows = rowsOf(database_partition);
+   const actions::AlignedSequence compared =
+      actions::alignedSequence(database, sequence_name, "DistinctSequences: the field sequenceName: Database does not contain a sequence with name: ");
+   CHECK_SILO_QUERY(
+      database.shard_world <= 1, "DistinctSequences is not supported on a sharded database yet: the rows of a selection on the other ranks take part in "
+                                 "the choice, and a row's number in the database is not known to a rank"
+   )
+   // the child of every partition that has rows, with the number of its first row in the database: the choice is one over all of them
+   std::vector<operators::DistinctSelection::Part> parts;
+   std::optional<uint32_t> own;
+   uint64_t first_row = 0;
+   for (const DatabasePartition& partition : database.partitions) {
+      if (first_row + partition.sequence_count >= (uint64_t{1} << 32) - 1) {
+         throw QueryCompilationException(
+            "DistinctSequences numbers the rows of the database with 32 bits: it needs a database of fewer than 2^32 - 1 rows"
+         );
+      }
+      if (partition.sequence_count != 0) {
+         if (&partition == &database_partition) {
+            own = static_cast<uint32_t>(parts.size());
+         }
+         parts.push_back({child->compile(database, partition, mode), compared.seqstoreOf(partition), static_cast<uint32_t>(first_row)});
+      }
+      first_row += partition.sequence_count;
+   }
+   if (!own.has_value()) {
+      return std::make_unique<operators::Empty>(rows);
+   }
+   return std::make_unique<operators::DistinctSelection>(std::move(parts), *own, first_row, rows);
+}
+
+namespace {
+
+std::unique_ptr<Expression> parseDistinctSequences(const json::Value& json) {
+   CHECK_SILO_QUERY(json.contains("child"), "The field 'child' is required in a DistinctSequences expression")
+   CHECK_SILO_QUERY(json["child"].is_object(), "The field 'child' in a DistinctSequences expression needs to be an object")
+   std::optional<std::string> sequence_name;
+   if (json.contains("sequenceName")) {
+      CHECK_SILO_QUERY(json["sequenceName"].is_string(), "The field 'sequenceName' in a DistinctSequences expression, if present, needs to be a string")
+      sequence_name = json["sequenceName"].as_string();
+   }
+   return std::make_unique<DistinctSequences>(parseExpression(json["child"]), std::move(sequence_name));
+}
+
+}  // namespace
+
 // ---- JSON -> Expression (the from_json functions) ------------------------------------------------------
 namespace {
 
@@ -1278,6 +1331,9 @@ std::unique_ptr<Expression> parseExpression(const json::Value& json) {  // expre
    }
    if (expression_type == "Sample") {
       return parseSample(json);
+   }
+   if (expression_type == "DistinctSequences") {
+      return parseDistinctSequences(json);
    }
    throw QueryParseException("Unknown object filter type '" + expression_type + "'");
 }

@@ -741,6 +741,63 @@ uint32_t SampleSelection::lower(ProgramBuilder& builder) const {
    return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
 }
 
+// ---- DistinctSelection (no counterpart in the reference) ------------------------------------------------
+std::string DistinctSelection::toString() const {
+   return "DistinctSelection[" + std::to_string(parts.size()) + " partitions](" + parts[own].child->toString() + ")";
+}
+std::unique_ptr<Operator> DistinctSelection::copy() const {
+   std::vector<Part> copies;
+   for (const Part& part : parts) {
+      copies.push_back({part.child->copy(), part.seqstore_id, part.first_row});
+   }
+   return std::make_unique<DistinctSelection>(std::move(copies), own, database_rows, rows);
+}
+std::unique_ptr<Operator> DistinctSelection::negate() const {
+   return std::make_unique<Complement>(this->copy(), rows);
+}
+uint32_t DistinctSelection::lower(ProgramBuilder& builder) const {
+   // every partition's rows of the child and its store's kept row hashes (the first query on a store computes them and waits: that
+   // request pays for the build) never leave the device.  One owner table takes the rows of all partitions, so a class is
+   // represented by its smallest row number in the database however the database is cut; every launch is on the query's stream,
+   // ahead of the fused program.
+   std::vector<silo_gpu_distinct_part> described;
+   std::vector<const uint64_t*> filters;
+   for (const Part& part : parts) {
+      const DatabasePartition& partition = *part.child->rows.partition;
+      OperatorResult result = part.child->evaluate();
+      filters.push_back(result.bitset());
+      builder.keep(std::move(result));
+      const uint64_t* hashes = nullptr;
+      checkGpu(silo_gpu_store_row_hashes(partition.store, part.seqstore_id, &hashes, queryStream()), "silo_gpu_store_row_hashes");
+      described.push_back({hashes, part.first_row, partition.sequence_count, partition.rowWords(), 0});
+   }
+   uint64_t slots = 2;
+   while (slots < 2 * database_rows) {
+      slots <<= 1;
+   }
+   if (slots > (uint64_t{1} << 31)) {
+      throw std::runtime_error("DistinctSequences: the owner table of a database of more than 2^30 rows exceeds 2^31 slots");
+   }
+   const size_t parts_bytes = described.size() * sizeof(silo_gpu_distinct_part);
+   auto* device_parts = static_cast<silo_gpu_distinct_part*>(builder.temporaryBuffer(parts_bytes));
+   void* table = builder.temporaryBuffer(SILO_GPU_DISTINCT_TABLE_BYTES(slots));
+   checkGpu(silo_gpu_memcpy_h2d(device_parts, described.data(), parts_bytes, queryStream()), "silo_gpu_memcpy_h2d");
+   const auto n_parts = static_cast<uint32_t>(described.size());
+   checkGpu(silo_gpu_distinct_begin(table, static_cast<uint32_t>(slots), queryStream()), "silo_gpu_distinct_begin");
+   for (uint32_t part = 0; part < n_parts; ++part) {
+      checkGpu(
+         silo_gpu_distinct_insert(table, static_cast<uint32_t>(slots), device_parts, n_parts, part, filters[part], queryStream()),
+         "silo_gpu_distinct_insert"
+      );
+   }
+   uint64_t* bitset = builder.temporaryBitset();
+   checkGpu(
+      silo_gpu_distinct_select(table, static_cast<uint32_t>(slots), device_parts, n_parts, own, filters[own], bitset, queryStream()),
+      "silo_gpu_distinct_select"
+   );
+   return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
+}
+
 // ---- BitmapSelection (bitmap_selection.cpp:33-71) -----------------------------------------------
 std::unique_ptr<Operator> BitmapSelection::copy() const {
    auto out = std::make_unique<BitmapSelection>(*this);

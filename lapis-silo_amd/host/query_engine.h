@@ -197,7 +197,7 @@ class ProgramBuilder {
 namespace operators {
 
 enum Type {
-   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION, SAMPLE_SELECTION
+   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION, SAMPLE_SELECTION, DISTINCT_SELECTION
 };
 
 /// What lowering a sub-tree into a program takes at most.  `slots`: the slots that are live at once while it is lowered, its
@@ -446,6 +446,35 @@ class SampleSelection : public Operator {
    std::vector<uint32_t> range_bounds;  // (from, to) per date range as K7 takes them; empty: one group of all rows
 };
 
+/// One row per distinct aligned sequence among the rows a child selects (the filter expression DistinctSequences; no counterpart in
+/// the reference): of every class of rows with equal 128-bit row hashes (K20) the row with the smallest number in the database.  Like
+/// SampleSelection the choice is one over ALL partitions, so the operator of a partition holds the child of every partition:
+/// lower() evaluates each of them, takes every store's kept hashes (silo_gpu_store_row_hashes: the first query on a store computes
+/// them), fills one owner table (silo_gpu_distinct_begin, silo_gpu_distinct_insert per partition) and writes its own partition's
+/// bitset (silo_gpu_distinct_select), all on the lowering thread's stream ahead of the fused program, which reads the bitset as a
+/// leaf.  The table, the uploaded parts and the children's results belong to the builder, like SampleSelection's.
+class DistinctSelection : public Operator {
+  public:
+   /// A partition of the database that has rows, in the database's order.
+   struct Part {
+      std::unique_ptr<Operator> child;
+      uint32_t seqstore_id = 0;  // of the compared sequence in this partition's store
+      uint32_t first_row = 0;    // the number of the partition's first row in the database
+   };
+   DistinctSelection(std::vector<Part> parts, uint32_t own, uint64_t database_rows, RowSpace rows)
+       : Operator(rows), parts(std::move(parts)), own(own), database_rows(database_rows) {}
+   Type type() const override { return DISTINCT_SELECTION; }
+   std::string toString() const override;
+   std::unique_ptr<Operator> copy() const override;
+   std::unique_ptr<Operator> negate() const override;
+   uint32_t lower(ProgramBuilder& builder) const override;
+   Cost cost() const override { return {1, 1}; }
+
+   std::vector<Part> parts;
+   uint32_t own;            // the part this operator answers for
+   uint64_t database_rows;  // what the owner table is sized for
+};
+
 class Threshold : public Operator {
   public:
    Threshold(OperatorVector&& non_negated_children, OperatorVector&& negated_children, uint32_t number_of_matchers, bool match_exactly, RowSpace rows);
@@ -647,6 +676,18 @@ struct Sample : public Expression {
    uint64_t seed;
    std::optional<std::string> date_field;  // with it: range_bounds, (from, to) per range as K7 takes them
    std::vector<uint32_t> range_bounds;
+};
+/// DistinctSequences (no counterpart in the reference): of the rows the child selects over the WHOLE database, one per distinct
+/// aligned sequence of `sequence_name` (the default nucleotide sequence when absent) — the row with the smallest number in the
+/// database of every class of rows with equal row hashes (K20: 128 bits; rows with equal hashes are treated as identical).  The
+/// selection depends on the child's rows, their sequences and their numbers in the database alone.  The child is compiled in the mode
+/// DistinctSequences is compiled in, for every partition, as for Sample.
+struct DistinctSequences : public Expression {
+   DistinctSequences(std::unique_ptr<Expression> child, std::optional<std::string> sequence_name)
+       : child(std::move(child)), sequence_name(std::move(sequence_name)) {}
+   SILO_DECLARE_EXPRESSION_METHODS
+   std::unique_ptr<Expression> child;
+   std::optional<std::string> sequence_name;
 };
 struct DateBetween : public Expression {  // date_between.cpp
    DateBetween(std::string column, std::optional<common::Date> date_from, std::optional<common::Date> date_to)

@@ -122,6 +122,8 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_sequence_differences",
     "silo_gpu_sample_key", "silo_gpu_sample_groups", "silo_gpu_sample_begin", "silo_gpu_sample_count", "silo_gpu_sample_advance",
     "silo_gpu_sample_select",
+    "silo_gpu_row_hash_term", "silo_gpu_row_hashes", "silo_gpu_store_row_hashes", "silo_gpu_distinct_begin", "silo_gpu_distinct_insert",
+    "silo_gpu_distinct_select",
 ]
 
 _lib = None
@@ -221,6 +223,13 @@ def load_library():
     lib.silo_gpu_sample_count.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp]
     lib.silo_gpu_sample_advance.argtypes = [vp, ctypes.c_uint32, vp]
     lib.silo_gpu_sample_select.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_row_hash_term.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+    lib.silo_gpu_row_hash_term.restype = ctypes.c_uint64
+    lib.silo_gpu_row_hashes.argtypes = [vp, ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_store_row_hashes.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(vp), vp]
+    lib.silo_gpu_distinct_begin.argtypes = [vp, ctypes.c_uint32, vp]
+    lib.silo_gpu_distinct_insert.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_distinct_select.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -1127,6 +1136,72 @@ def sample(partitions, size, seed=0, n_groups=1, fill=None, guard_words=0, strea
                     device_free(ptr)
 
 
+ROW_HASH_NO_SYMBOL = 31        # SILO_GPU_ROW_HASH_NO_SYMBOL: a cell that nothing stored claims
+DISTINCT_EMPTY = 0xFFFFFFFF    # SILO_GPU_DISTINCT_EMPTY: a slot of the owner table without an owner
+DISTINCT_PART_DTYPE = np.dtype([("hashes_dev", np.uint64), ("first_row", np.uint32), ("sequence_count", np.uint32),
+                                ("row_words", np.uint32), ("reserved", np.uint32)])   # silo_gpu_distinct_part
+
+
+def row_hash_scratch_bytes(positions):
+    """SILO_GPU_ROW_HASH_SCRATCH_BYTES: the scratch silo_gpu_row_hashes needs."""
+    return int(positions) * 17 + 1024
+
+
+def distinct_table_bytes(slots):
+    """SILO_GPU_DISTINCT_TABLE_BYTES: `slots` owners and the overflow counter behind them."""
+    return (int(slots) + 1) * 4
+
+
+def distinct_slots(rows):
+    """The smallest power of two >= 2 x rows (at least 2): the table size the engine takes for a database of `rows` rows."""
+    slots = 2
+    while slots < 2 * int(rows):
+        slots *= 2
+    return slots
+
+
+def row_hash_term(position, symbol, lane):
+    """silo_gpu_row_hash_term: H0 (lane 0) / H1 (lane 1) of a cell (host function; the kernels compile the same code)."""
+    return int(load_library().silo_gpu_row_hash_term(int(position), int(symbol), int(lane)))
+
+
+def distinct(parts, slots, fill=None, guard_words=0, calls=1, described=None, stream=None):
+    """A whole K20 selection over host arrays: silo_gpu_distinct_begin, silo_gpu_distinct_insert per part, silo_gpu_distinct_select
+    per part; the whole sequence `calls` times.  parts: a list of dicts {hashes: uint64 [row_words * 64][2], filter: uint64
+    [row_words], first_row, sequence_count, row_words}, ordered by first_row.  Returns (outputs, owners, overflow): per part the
+    row_words words silo_gpu_distinct_select writes followed by `guard_words` words behind them that it must not touch (every
+    output is filled with the byte `fill` before the launches), the `slots` owners and the overflow counter."""
+    lib = load_library()
+    table = device_malloc(distinct_table_bytes(slots), fill, stream)
+    device = []
+    parts_dev = None
+    try:
+        records = np.zeros(len(parts), dtype=DISTINCT_PART_DTYPE)
+        for k, part in enumerate(parts):
+            hashes = np.ascontiguousarray(part["hashes"], dtype=np.uint64)
+            device.append({"hashes": _upload(hashes, stream), "filter": _upload(np.ascontiguousarray(part["filter"], dtype=np.uint64), stream),
+                           "out": device_malloc((int(part["row_words"]) + int(guard_words)) * 8, fill, stream)})
+            records[k] = (device[k]["hashes"].value, part["first_row"], part["sequence_count"], part["row_words"], 0)
+        parts_dev = _upload(records, stream)
+        for _ in range(calls):
+            _check(lib.silo_gpu_distinct_begin(table, slots, stream))
+            for k, dev in enumerate(device):
+                _check(lib.silo_gpu_distinct_insert(table, slots, parts_dev, len(parts), k, dev["filter"], stream))
+            for k, dev in enumerate(device):
+                _check(lib.silo_gpu_distinct_select(table, slots, parts_dev, len(parts), k, dev["filter"], dev["out"], stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        outputs = [device_read(dev["out"], np.uint64, int(part["row_words"]) + int(guard_words), stream) for part, dev in zip(parts, device)]
+        words = device_read(table, np.uint32, int(slots) + 1, stream)
+        return outputs, words[:-1].copy(), int(words[-1])
+    finally:
+        device_free(table)
+        if parts_dev is not None:
+            device_free(parts_dev)
+        for dev in device:
+            for ptr in dev.values():
+                device_free(ptr)
+
+
 class GpuStore:
     """One device shard: the dense restatement of a DatabasePartition's sequence stores."""
 
@@ -1583,6 +1658,28 @@ class GpuStore:
                 self.free(scratch)
             if out_ptr is None and table is not None:
                 self.free(table)
+
+    def row_hashes(self, seqstore_id, fill=None, guard_rows=0, stream=None):
+        """silo_gpu_row_hashes (K20) into a table for the call, filled with the byte `fill` before the launches so that a test can
+        see that every cell is written: returns uint64 [row_words * 64 + guard_rows][2], the last `guard_rows` rows untouched."""
+        rows = self.row_words * 64 + int(guard_rows)
+        scratch = self.malloc(row_hash_scratch_bytes(self.positions(seqstore_id)))
+        table = self.malloc(max(16, 16 * rows))
+        try:
+            if fill is not None:
+                self.memset(table, fill, max(16, 16 * rows), stream)
+            _check(self.lib.silo_gpu_row_hashes(self.handle, seqstore_id, table, scratch, stream))
+            self.synchronize(stream)
+            return self.read(table, np.uint64, rows * 2, stream).reshape(-1, 2)
+        finally:
+            self.free(scratch)
+            self.free(table)
+
+    def kept_row_hashes(self, seqstore_id, stream=None):
+        """silo_gpu_store_row_hashes (K20): the device address of the store's own table of row hashes (computed on the first call)."""
+        out = ctypes.c_void_p()
+        _check(self.lib.silo_gpu_store_row_hashes(self.handle, seqstore_id, ctypes.byref(out), stream))
+        return out.value
 
     def position_symbols(self, seqstore_id, positions, fill=None, guard_bytes=0, calls=1, null=(), n_positions=None, stream=None):
         """silo_gpu_position_symbols (K16).  positions: 0-based, any order, repeats allowed.  Returns (symbols uint8
