@@ -1066,6 +1066,48 @@ int silo_gpu_distinct_select(
    const uint64_t* filter_dev, uint64_t* out_bitset_dev, void* stream
 );
 
+/* ---- K21: the sizes of a selection's sequence classes (the action DistinctSequenceCounts) -----------------
+ * On a table that silo_gpu_distinct_begin and EVERY part's silo_gpu_distinct_insert have filled, with the same slots, parts and
+ * filters as those calls.  A row COUNTS as for K20.  The slot of a counting row's class is where the read-only probe of
+ * silo_gpu_distinct_select ends: at the slot the row owns, or at the first slot whose owner has the row's hash.
+ * silo_gpu_distinct_count, once per part after every part's insert: adds to counts_dev[slot] (uint32 [slots],
+ *     SILO_GPU_DISTINCT_COUNTS_BYTES(slots) bytes, cleared by the caller) the part's counting rows whose class sits in `slot`.
+ *     ACCUMULATED over the parts, like K19's histogram: after the calls of all parts counts_dev[slot] is the size of the class that
+ *     owns `slot` and 0 for every other slot.  A wave adds once per distinct slot among its 64 rows (the first lane's slot, a ballot
+ *     of the lanes that share it) for a bounded number of rounds, then once per row: integer adds only, so the counts depend neither
+ *     on that bound nor on the schedule.  A counting row whose probe finds neither itself nor its class — there is none after the
+ *     inserts — adds 1 to the table's overflow counter and to nothing else.  Writes nothing else of the table.
+ * silo_gpu_distinct_classes, once per part after every part's count: every counting row that OWNS its slot and whose
+ *     counts_dev[slot] >= min_count appends the key  (uint64)(0xFFFFFFFF - count) << 32 | global row  to keys_dev — ascending keys are
+ *     descending counts, then ascending representatives.  Appends ACCUMULATE over the parts from *n_keys_dev, which the caller
+ *     clears: one atomic add per wave and step of 16 filter words.  Nothing is written at or past keys_dev[capacity], but *n_keys_dev counts every class that
+ *     qualifies, so a caller sees a list that was too short.  The order of keys_dev is unspecified, its set is not.
+ * silo_gpu_smallest_keys takes no table: of the n = min(*n_keys_dev, capacity) keys of keys_dev, which have to be PAIRWISE DISTINCT,
+ *     it WRITES the k smallest (all n if n <= k) to out_dev in unspecified order and *out_count_dev = min(n, k); entries of out_dev
+ *     at or past that count are untouched.  n is read on the device.  A radix select as K19's with one group: eight rounds of 8 key
+ *     bits, most significant first, each a histogram launch (a block's 256 cells in LDS, its non-zero cells added to the table) and
+ *     a one-block launch that fixes the digit; then one launch that appends every key <= the k-th smallest.  With equal keys more
+ *     than k may qualify: never more than k entries are written, which of them is then unspecified.  scratch_dev:
+ *     SILO_GPU_SMALLEST_KEYS_SCRATCH_BYTES bytes, 8-byte aligned; the call clears it.
+ * All launch on `stream`; count and classes read parts_dev[part] back first, as insert and select do, and nothing else returns to
+ * the host.  Each fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for whatever insert and select refuse, a NULL pointer,
+ * capacity == 0, min_count == 0, k == 0 or k > SILO_GPU_MAX_DISTINCT_CLASSES. */
+#define SILO_GPU_MAX_DISTINCT_CLASSES 16384
+#define SILO_GPU_DISTINCT_COUNTS_BYTES(slots) ((size_t)(slots) * 4u)
+#define SILO_GPU_SMALLEST_KEYS_SCRATCH_BYTES 1088u /* 256 histogram cells and 16 words of state */
+int silo_gpu_distinct_count(
+   void* table_dev, uint32_t slots, uint32_t* counts_dev, const silo_gpu_distinct_part* parts_dev, uint32_t n_parts, uint32_t part,
+   const uint64_t* filter_dev, void* stream
+);
+int silo_gpu_distinct_classes(
+   void* table_dev, uint32_t slots, const uint32_t* counts_dev, const silo_gpu_distinct_part* parts_dev, uint32_t n_parts, uint32_t part,
+   const uint64_t* filter_dev, uint32_t min_count, uint64_t* keys_dev, uint32_t capacity, uint32_t* n_keys_dev, void* stream
+);
+int silo_gpu_smallest_keys(
+   const uint64_t* keys_dev, const uint32_t* n_keys_dev, uint32_t capacity, uint32_t k, uint64_t* out_dev, uint32_t* out_count_dev, void* scratch_dev,
+   void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

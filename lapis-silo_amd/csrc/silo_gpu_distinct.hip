@@ -9,7 +9,8 @@
 //   k_row_hash_escapes   a thread per escape key: H(p, its symbol) - H(p, what the planes said)
 //   k_row_hash_runs      a thread per run [a, e) of the missing symbol: two lookups in a prefix array of those differences
 //   k_row_hash_sparse    a thread per sparse key (ambiguity code)
-// The selection, on row bitsets and arrays of hashes, takes no store:
+// The selection, on row bitsets and arrays of hashes, takes no store (what it shares with the class counts of K21 — the hash of a
+// global row, the load of an owner, the refusals — is in distinct_table.h):
 //   k_distinct_begin     every slot of the owner table empty, the overflow counter 0
 //   k_distinct_insert    a wave per filter word, a lane per selected row: linear probing with compare-and-swap / atomic min
 //   k_distinct_select    a thread per row, a wave's ballot per word: the rows that own their class's slot
@@ -22,24 +23,21 @@
 #include <string>
 #include <vector>
 
+#include "distinct_table.h"
 #include "row_hash.h"
 #include "store_internal.h"
 
 using namespace silo_gpu_detail;
+using namespace silo_gpu_distinct_table;
 using silo_gpu_row_hash::NO_SYMBOL;
 using silo_gpu_row_hash::term;
 
 namespace {
 
-constexpr uint32_t THREADS = 256;  // four waves: four neighbouring row words per block
-constexpr uint32_t WORDS_PER_BLOCK = THREADS / 64u;
 constexpr uint32_t MAX_EXTRA = 16;
 constexpr uint32_t SCAN_SLOTS = 32;  // scan symbol indices a key can name (5 bits)
 constexpr uint8_t NO_SCAN_SYMBOL = 0xFF;
-constexpr uint32_t EMPTY = SILO_GPU_DISTINCT_EMPTY;
-constexpr uint32_t MAX_INSERT_BLOCKS = 4096;
 static_assert(NO_SYMBOL == SILO_GPU_ROW_HASH_NO_SYMBOL && NO_SYMBOL >= SILO_GPU_MAX_SYMBOLS && NO_SYMBOL < 32u);
-static_assert(sizeof(silo_gpu_distinct_part) == 24);
 
 struct HashArgs {
    SeqStoreDev dev;
@@ -184,30 +182,7 @@ __global__ __launch_bounds__(THREADS) void k_distinct_begin(uint32_t* __restrict
    }
 }
 
-/// The hash of global row `g`: the part is the last one whose first_row is <= g.
-__device__ __forceinline__ ulonglong2 hashOfGlobalRow(const silo_gpu_distinct_part* __restrict__ parts, uint32_t n_parts, uint32_t g) {
-   uint32_t lo = 0, hi = n_parts;
-   while (lo < hi) {  // first part whose first_row is beyond g
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if (parts[mid].first_row <= g) {
-         lo = mid + 1u;
-      } else {
-         hi = mid;
-      }
-   }
-   const silo_gpu_distinct_part& part = parts[lo != 0 ? lo - 1u : 0u];
-   const uint32_t row = g - part.first_row;
-   if (row >= part.sequence_count) {  // (no inserted row: cannot be an owner)
-      return make_ulonglong2(0ull, 0ull);
-   }
-   return reinterpret_cast<const ulonglong2*>(part.hashes_dev)[row];
-}
-
-__device__ __forceinline__ uint32_t loadOwner(const uint32_t* slot) {
-   return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-/// grid <= MAX_INSERT_BLOCKS; a wave takes the filter words wave, wave + waves of the grid, ...  No lane waits for another: every
+/// grid <= MAX_WALK_BLOCKS; a wave takes the filter words wave, wave + waves of the grid, ...  No lane waits for another: every
 /// step of the probe is one atomic whose outcome is final for that slot's class.
 __global__ __launch_bounds__(THREADS) void k_distinct_insert(
    uint32_t* __restrict__ table, uint32_t slots, const silo_gpu_distinct_part* __restrict__ parts, uint32_t n_parts, uint32_t part,
@@ -295,38 +270,6 @@ __global__ __launch_bounds__(THREADS) void k_distinct_select(
    if (lane == 0) {
       out[word] = ballot;
    }
-}
-
-/// What insert and select refuse; reads parts_dev[part] back into `mine`.
-int checkSelection(
-   const char* what, const void* table, uint32_t slots, const silo_gpu_distinct_part* parts_dev, uint32_t n_parts, uint32_t part, const void* filter,
-   const void* out, hipStream_t hip_stream, silo_gpu_distinct_part& mine
-) {
-   if (table == nullptr || parts_dev == nullptr || filter == nullptr || out == nullptr) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(what) + ": bad arguments");
-   }
-   if (slots == 0 || (slots & (slots - 1u)) != 0) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(what) + ": slots has to be a power of two");
-   }
-   if (n_parts == 0 || part >= n_parts) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(what) + ": no parts, or a part past the last one");
-   }
-   HIP_TRY(hipMemcpyAsync(&mine, parts_dev + part, sizeof(mine), hipMemcpyDeviceToHost, hip_stream));
-   HIP_TRY(hipStreamSynchronize(hip_stream));
-   if (mine.hashes_dev == nullptr) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(what) + ": the part has no hashes");
-   }
-   if (mine.row_words == 0 || mine.sequence_count > static_cast<uint64_t>(mine.row_words) * 64u) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(what) + ": no row words, or fewer rows than sequence_count");
-   }
-   if (static_cast<uint64_t>(mine.first_row) + mine.sequence_count >= 0xFFFFFFFFull) {
-      return fail(SILO_GPU_ERR_INVALID_ARGUMENT, std::string(what) + ": first_row + sequence_count has to stay below 2^32 - 1");
-   }
-   return SILO_GPU_OK;
-}
-
-uint32_t blocksOfWords(uint32_t row_words) {
-   return row_words / WORDS_PER_BLOCK + (row_words % WORDS_PER_BLOCK != 0 ? 1u : 0u);
 }
 
 }  // namespace
@@ -466,7 +409,7 @@ int silo_gpu_distinct_insert(
        status != SILO_GPU_OK) {
       return status;
    }
-   k_distinct_insert<<<std::min(blocksOfWords(mine.row_words), MAX_INSERT_BLOCKS), THREADS, 0, hip_stream>>>(
+   k_distinct_insert<<<std::min(blocksOfWords(mine.row_words), MAX_WALK_BLOCKS), THREADS, 0, hip_stream>>>(
       static_cast<uint32_t*>(table_dev), slots, parts_dev, n_parts, part, filter_dev
    );
    HIP_TRY(hipGetLastError());

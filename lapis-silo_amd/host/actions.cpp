@@ -880,6 +880,7 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"AminoAcidHaplotypes", parseHaplotypes<AminoAcid>},
    {"MutationsPerSequence", parseMutationsPerSequence<Nucleotide>},
    {"AminoAcidMutationsPerSequence", parseMutationsPerSequence<AminoAcid>},
+   {"DistinctSequenceCounts", parseDistinctSequenceCounts},
 };
 
 }  // namespace

@@ -8,6 +8,8 @@
 //   NearestAmong          two selections: per row of the one its nearest rows of the other (K14)
 //   NearestNeighbours     the rows of the whole database closest to one query sequence (K11); resolveQuerySequence, which
 //                         WithinDistance shares with it
+//   DistinctSequenceCounts  the selection's classes of equal sequences — distance 0 with N and ambiguity codes as characters —
+//                         with their sizes (K20's owner table, K21)
 // The first four gather and pack the rows they compare in the same way: that is here once, as PackedSelection, over the walk that
 // every action on the selected rows' sequences shares (SelectedSequences, sequence_actions.cpp).
 #include <algorithm>
@@ -663,6 +665,140 @@ std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json) {
    // (INT64_MIN: see parseDistanceMatrix)
    const std::optional<uint32_t> max_distance = integerField(json, "maxDistance", "NearestNeighbours", false, INT64_MIN, INT32_MAX, NON_NEGATIVE_INTEGER);
    return std::make_unique<NearestNeighbours>(std::move(sequence_name), std::move(primary_key), std::move(sequence), neighbours, max_distance);
+}
+
+// ---- DistinctSequenceCounts ------------------------------------------------------------------------------
+// The largest classes of rows with equal aligned sequences among the selected rows, each with its size and its representative's
+// primary key — the weights of the rows the filter expression DistinctSequences keeps — from K20's owner table, the two class-count
+// passes and the selection of the smallest keys (K21).
+void DistinctSequenceCounts::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"primaryKey", "count"});
+}
+
+QueryResult DistinctSequenceCounts::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const AlignedSequence compared =
+      alignedSequence(database, sequence_name, "DistinctSequenceCounts: the field sequenceName: Database does not contain a sequence with name: ");
+   CHECK_SILO_QUERY(
+      database.shard_world <= 1, "DistinctSequenceCounts is not supported on a sharded database yet: the rows of a selection on the other ranks take part in "
+                                 "the choice, and a row's number in the database is not known to a rank"
+   )
+   // every partition that has rows, with the number of its first row in the database: the classes are those of all of them
+   std::vector<operators::DistinctTable::Part> parts;
+   std::vector<size_t> partition_of_part;
+   std::vector<uint32_t> first_rows;
+   uint64_t database_rows = 0;
+   for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+      const DatabasePartition& partition = database.partitions[partition_id];
+      if (database_rows + partition.sequence_count >= (uint64_t{1} << 32) - 1) {
+         throw QueryCompilationException(
+            "DistinctSequenceCounts numbers the rows of the database with 32 bits: it needs a database of fewer than 2^32 - 1 rows"
+         );
+      }
+      if (partition.sequence_count != 0) {
+         parts.push_back({&partition, compared.seqstoreOf(partition), static_cast<uint32_t>(database_rows)});
+         partition_of_part.push_back(partition_id);
+         first_rows.push_back(static_cast<uint32_t>(database_rows));
+      }
+      database_rows += partition.sequence_count;
+   }
+   QueryResult results;
+   if (selectedCount(database, bitmap_filter) == 0) {
+      return results;
+   }
+   const auto capacity = static_cast<uint32_t>(database_rows);  // of the list of keys: no more classes than rows
+   const uint32_t k = max_classes;
+   // what is fetched, in one piece: the k smallest keys, then how many of them there are and how many classes were listed
+   const size_t count_offset = static_cast<size_t>(k) * sizeof(uint64_t);
+   const size_t result_bytes = count_offset + 2u * sizeof(uint32_t);
+
+   std::vector<uint64_t> keys;  // ascending: by count descending, then by the representative's row in the database
+   {
+      // nothing in here returns to the pool before the stream has been waited for: the launches read and write it
+      DevicePool& pool = database.partitions.front().pool;
+      std::vector<DeviceBuffer> live;  // the uploaded parts and the owner table
+      const DeviceBuffer device_keys = pool.acquire(static_cast<size_t>(capacity) * sizeof(uint64_t));
+      const DeviceBuffer device_scratch = pool.acquire(SILO_GPU_SMALLEST_KEYS_SCRATCH_BYTES);
+      const DeviceBuffer device_result = pool.acquire(result_bytes);
+      DeviceBuffer device_counts;  // (sized with the table)
+      auto* device_out = device_result.as<uint64_t>();
+      auto* device_out_count = reinterpret_cast<uint32_t*>(device_result.as<char>() + count_offset);
+      uint32_t* device_n_keys = device_out_count + 1;
+      launchAndWait([&] {
+         const operators::DistinctTable built = operators::buildDistinctTable(
+            parts, database_rows, [&](size_t part) { return bitmap_filter[partition_of_part[part]].bitset(); },
+            [&](size_t bytes) { return live.emplace_back(pool.acquire(std::max<size_t>(bytes, 1))).get(); }, "DistinctSequenceCounts"
+         );
+         device_counts = pool.acquire(SILO_GPU_DISTINCT_COUNTS_BYTES(built.slots));
+         checkGpu(silo_gpu_memset_async(device_counts.get(), 0, SILO_GPU_DISTINCT_COUNTS_BYTES(built.slots), queryStream()), "silo_gpu_memset_async");
+         checkGpu(silo_gpu_memset_async(device_n_keys, 0, sizeof(uint32_t), queryStream()), "silo_gpu_memset_async");
+         for (uint32_t part = 0; part < built.n_parts; ++part) {
+            checkGpu(
+               silo_gpu_distinct_count(
+                  built.table, built.slots, device_counts.as<uint32_t>(), built.device_parts, built.n_parts, part, built.filters[part], queryStream()
+               ),
+               "silo_gpu_distinct_count"
+            );
+         }
+         for (uint32_t part = 0; part < built.n_parts; ++part) {
+            checkGpu(
+               silo_gpu_distinct_classes(
+                  built.table, built.slots, device_counts.as<uint32_t>(), built.device_parts, built.n_parts, part, built.filters[part], min_count,
+                  device_keys.as<uint64_t>(), capacity, device_n_keys, queryStream()
+               ),
+               "silo_gpu_distinct_classes"
+            );
+         }
+         checkGpu(
+            silo_gpu_smallest_keys(device_keys.as<uint64_t>(), device_n_keys, capacity, k, device_out, device_out_count, device_scratch.get(), queryStream()),
+            "silo_gpu_smallest_keys"
+         );
+         HostFetch fetch(device_result.get(), result_bytes, queryStream());
+         HostFetch overflow_fetch(static_cast<const uint32_t*>(built.table) + built.slots, sizeof(uint32_t), queryStream());
+         const auto* host = static_cast<const char*>(fetch.wait());
+         uint32_t counters[2];  // the keys selected, the classes listed
+         std::memcpy(counters, host + count_offset, sizeof(counters));
+         uint32_t overflow = 0;
+         std::memcpy(&overflow, overflow_fetch.wait(), sizeof(overflow));
+         if (overflow != 0) {
+            throw std::runtime_error("DistinctSequenceCounts: a selected row was not found in the owner table");
+         }
+         if (counters[1] > capacity) {
+            throw std::runtime_error("DistinctSequenceCounts: more classes than the database has rows");
+         }
+         if (counters[0] != std::min(counters[1], k)) {
+            throw std::runtime_error("DistinctSequenceCounts: the selection of the largest classes lost or made up a class");
+         }
+         keys.resize(counters[0]);
+         std::memcpy(keys.data(), host, keys.size() * sizeof(uint64_t));
+      });
+   }
+
+   std::sort(keys.begin(), keys.end());
+   const std::string& primary_key_column = database.database_config.primary_key;
+   results.query_result.reserve(keys.size());
+   for (const uint64_t key : keys) {
+      const auto global_row = static_cast<uint32_t>(key);
+      const uint32_t count = 0xFFFFFFFFu - static_cast<uint32_t>(key >> 32);
+      // the part is the last one whose first row is <= the row
+      const size_t part = static_cast<size_t>(std::upper_bound(first_rows.begin(), first_rows.end(), global_row) - first_rows.begin());
+      if (part == 0 || global_row - first_rows[part - 1] >= parts[part - 1].partition->sequence_count || count == 0) {
+         throw std::runtime_error("DistinctSequenceCounts: a key names no row of the database, or a class without rows");
+      }
+      const DatabasePartition& partition = *parts[part - 1].partition;
+      QueryResultEntry& entry = results.query_result.emplace_back();
+      entry.fields.emplace("count", static_cast<int32_t>(count));
+      entry.fields.emplace("primaryKey", columnOf(partition, primary_key_column).jsonOfRow(global_row - first_rows[part - 1]));
+   }
+   return results;
+}
+
+std::unique_ptr<Action> parseDistinctSequenceCounts(const json::Value& json) {
+   std::optional<std::string> sequence_name = optionalStringField(json, "sequenceName", "DistinctSequenceCounts");
+   const uint32_t min_count = integerField(json, "minCount", "DistinctSequenceCounts", false, 1, INT32_MAX, "an integer of at least 1").value_or(1);
+   const std::string classes_form = "an integer from 1 to " + std::to_string(DistinctSequenceCounts::CLASS_LIMIT);
+   const uint32_t max_classes = integerField(json, "maxClasses", "DistinctSequenceCounts", false, 1, DistinctSequenceCounts::CLASS_LIMIT, classes_form)
+                                   .value_or(DistinctSequenceCounts::DEFAULT_CLASSES);
+   return std::make_unique<DistinctSequenceCounts>(std::move(sequence_name), min_count, max_classes);
 }
 
 }  // namespace silo::query_engine::actions

@@ -755,44 +755,64 @@ std::unique_ptr<Operator> DistinctSelection::copy() const {
 std::unique_ptr<Operator> DistinctSelection::negate() const {
    return std::make_unique<Complement>(this->copy(), rows);
 }
-uint32_t DistinctSelection::lower(ProgramBuilder& builder) const {
-   // every partition's rows of the child and its store's kept row hashes (the first query on a store computes them and waits: that
-   // request pays for the build) never leave the device.  One owner table takes the rows of all partitions, so a class is
-   // represented by its smallest row number in the database however the database is cut; every launch is on the query's stream,
-   // ahead of the fused program.
+DistinctTable buildDistinctTable(
+   const std::vector<DistinctTable::Part>& parts, uint64_t database_rows, const std::function<const uint64_t*(size_t part)>& rows_of,
+   const std::function<void*(size_t bytes)>& allocate, const std::string& what
+) {
+   DistinctTable built;
    std::vector<silo_gpu_distinct_part> described;
-   std::vector<const uint64_t*> filters;
-   for (const Part& part : parts) {
-      const DatabasePartition& partition = *part.child->rows.partition;
-      OperatorResult result = part.child->evaluate();
-      filters.push_back(result.bitset());
-      builder.keep(std::move(result));
+   for (size_t part = 0; part < parts.size(); ++part) {
+      const DatabasePartition& partition = *parts[part].partition;
+      built.filters.push_back(rows_of(part));
       const uint64_t* hashes = nullptr;
-      checkGpu(silo_gpu_store_row_hashes(partition.store, part.seqstore_id, &hashes, queryStream()), "silo_gpu_store_row_hashes");
-      described.push_back({hashes, part.first_row, partition.sequence_count, partition.rowWords(), 0});
+      checkGpu(silo_gpu_store_row_hashes(partition.store, parts[part].seqstore_id, &hashes, queryStream()), "silo_gpu_store_row_hashes");
+      described.push_back({hashes, parts[part].first_row, partition.sequence_count, partition.rowWords(), 0});
    }
    uint64_t slots = 2;
    while (slots < 2 * database_rows) {
       slots <<= 1;
    }
    if (slots > (uint64_t{1} << 31)) {
-      throw std::runtime_error("DistinctSequences: the owner table of a database of more than 2^30 rows exceeds 2^31 slots");
+      throw std::runtime_error(what + ": the owner table of a database of more than 2^30 rows exceeds 2^31 slots");
    }
    const size_t parts_bytes = described.size() * sizeof(silo_gpu_distinct_part);
-   auto* device_parts = static_cast<silo_gpu_distinct_part*>(builder.temporaryBuffer(parts_bytes));
-   void* table = builder.temporaryBuffer(SILO_GPU_DISTINCT_TABLE_BYTES(slots));
-   checkGpu(silo_gpu_memcpy_h2d(device_parts, described.data(), parts_bytes, queryStream()), "silo_gpu_memcpy_h2d");
-   const auto n_parts = static_cast<uint32_t>(described.size());
-   checkGpu(silo_gpu_distinct_begin(table, static_cast<uint32_t>(slots), queryStream()), "silo_gpu_distinct_begin");
-   for (uint32_t part = 0; part < n_parts; ++part) {
+   built.device_parts = static_cast<silo_gpu_distinct_part*>(allocate(parts_bytes));
+   built.table = allocate(SILO_GPU_DISTINCT_TABLE_BYTES(slots));
+   built.slots = static_cast<uint32_t>(slots);
+   built.n_parts = static_cast<uint32_t>(described.size());
+   checkGpu(silo_gpu_memcpy_h2d(built.device_parts, described.data(), parts_bytes, queryStream()), "silo_gpu_memcpy_h2d");
+   checkGpu(silo_gpu_distinct_begin(built.table, built.slots, queryStream()), "silo_gpu_distinct_begin");
+   for (uint32_t part = 0; part < built.n_parts; ++part) {
       checkGpu(
-         silo_gpu_distinct_insert(table, static_cast<uint32_t>(slots), device_parts, n_parts, part, filters[part], queryStream()),
+         silo_gpu_distinct_insert(built.table, built.slots, built.device_parts, built.n_parts, part, built.filters[part], queryStream()),
          "silo_gpu_distinct_insert"
       );
    }
+   return built;
+}
+
+uint32_t DistinctSelection::lower(ProgramBuilder& builder) const {
+   // every partition's rows of the child and its store's kept row hashes (the first query on a store computes them and waits: that
+   // request pays for the build) never leave the device.  One owner table takes the rows of all partitions, so a class is
+   // represented by its smallest row number in the database however the database is cut; every launch is on the query's stream,
+   // ahead of the fused program.
+   std::vector<DistinctTable::Part> described;
+   for (const Part& part : parts) {
+      described.push_back({part.child->rows.partition, part.seqstore_id, part.first_row});
+   }
+   const DistinctTable built = buildDistinctTable(
+      described, database_rows,
+      [&](size_t part) {
+         OperatorResult result = parts[part].child->evaluate();
+         const uint64_t* filter = result.bitset();
+         builder.keep(std::move(result));
+         return filter;
+      },
+      [&](size_t bytes) { return builder.temporaryBuffer(bytes); }, "DistinctSequences"
+   );
    uint64_t* bitset = builder.temporaryBitset();
    checkGpu(
-      silo_gpu_distinct_select(table, static_cast<uint32_t>(slots), device_parts, n_parts, own, filters[own], bitset, queryStream()),
+      silo_gpu_distinct_select(built.table, built.slots, built.device_parts, built.n_parts, own, built.filters[own], bitset, queryStream()),
       "silo_gpu_distinct_select"
    );
    return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);

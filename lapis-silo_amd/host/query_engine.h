@@ -475,6 +475,31 @@ class DistinctSelection : public Operator {
    uint64_t database_rows;  // what the owner table is sized for
 };
 
+/// K20's owner table over the rows that a filter selects in every partition that has rows — what DistinctSelection::lower and the
+/// action DistinctSequenceCounts (distance_actions.cpp) both begin with.  buildDistinctTable takes each partition in the database's
+/// order: its rows (`rows_of(part)`: the caller evaluates or hands over the filter's bitset and keeps it alive), then its store's
+/// kept row hashes (silo_gpu_store_row_hashes: the first query on a store computes them and waits).  It sizes the table as the
+/// smallest power of two >= 2 x database_rows slots, uploads the parts and enqueues silo_gpu_distinct_begin and one
+/// silo_gpu_distinct_insert per partition on queryStream().  The two device arrays come from `allocate` and belong to the caller:
+/// they must outlive the wait for the stream.  `what` names the caller in the refusal of a table of more than 2^31 slots.
+struct DistinctTable {
+   /// A partition of the database that has rows, in the database's order.
+   struct Part {
+      const DatabasePartition* partition;
+      uint32_t seqstore_id;  // of the compared sequence in this partition's store
+      uint32_t first_row;    // the number of the partition's first row in the database
+   };
+   silo_gpu_distinct_part* device_parts = nullptr;
+   void* table = nullptr;  // SILO_GPU_DISTINCT_TABLE_BYTES(slots)
+   uint32_t slots = 0;
+   uint32_t n_parts = 0;
+   std::vector<const uint64_t*> filters;  // per part, as rows_of returned them
+};
+DistinctTable buildDistinctTable(
+   const std::vector<DistinctTable::Part>& parts, uint64_t database_rows, const std::function<const uint64_t*(size_t part)>& rows_of,
+   const std::function<void*(size_t bytes)>& allocate, const std::string& what
+);
+
 class Threshold : public Operator {
   public:
    Threshold(OperatorVector&& non_negated_children, OperatorVector&& negated_children, uint32_t number_of_matchers, bool match_exactly, RowSpace rows);
@@ -819,6 +844,8 @@ std::unique_ptr<Action> parseClusters(const json::Value& json);
 std::unique_ptr<Action> parseMinimumSpanningTree(const json::Value& json);
 std::unique_ptr<Action> parseNearestAmong(const json::Value& json);
 std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json);
+/// The parser of the action over the classes of equal sequences (distance_actions.cpp).
+std::unique_ptr<Action> parseDistinctSequenceCounts(const json::Value& json);
 
 /// Two kinds of field that many action parsers read, with one wording of the complaint (actions.cpp).  An optional field of type
 /// string: none when absent; "<action_name> action: the field <field>, if present, must be of type string".
@@ -1158,6 +1185,27 @@ class NearestNeighbours : public Action {
          sequence(std::move(sequence)),
          neighbours(neighbours),
          max_distance(max_distance) {}
+};
+
+/// DistinctSequenceCounts (distance_actions.cpp; no counterpart in the reference): the largest classes of rows with equal aligned
+/// sequences among the rows the filter selects — the classes of the filter expression DistinctSequences (equal 128-bit row hashes,
+/// K20), each with its size and the primary key of its representative, the row DistinctSequences keeps.  Of the classes of at
+/// least minCount rows the first maxClasses by (count descending, representative's row number in the database ascending), one
+/// response row {count, primaryKey} each, in that order.  All on the device (K21): the owner table DistinctSelection builds
+/// (operators::buildDistinctTable), silo_gpu_distinct_count and silo_gpu_distinct_classes per partition, silo_gpu_smallest_keys, and
+/// one download of at most maxClasses keys.
+class DistinctSequenceCounts : public Action {
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   uint32_t min_count;
+   uint32_t max_classes;
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+
+  public:
+   static constexpr uint32_t CLASS_LIMIT = SILO_GPU_MAX_DISTINCT_CLASSES;
+   static constexpr uint32_t DEFAULT_CLASSES = 1024;
+   DistinctSequenceCounts(std::optional<std::string> sequence_name, uint32_t min_count, uint32_t max_classes)
+       : sequence_name(std::move(sequence_name)), min_count(min_count), max_classes(max_classes) {}
 };
 
 template <typename SymbolType>

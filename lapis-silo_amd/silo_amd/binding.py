@@ -124,6 +124,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_sample_select",
     "silo_gpu_row_hash_term", "silo_gpu_row_hashes", "silo_gpu_store_row_hashes", "silo_gpu_distinct_begin", "silo_gpu_distinct_insert",
     "silo_gpu_distinct_select",
+    "silo_gpu_distinct_count", "silo_gpu_distinct_classes", "silo_gpu_smallest_keys",
 ]
 
 _lib = None
@@ -230,6 +231,10 @@ def load_library():
     lib.silo_gpu_distinct_begin.argtypes = [vp, ctypes.c_uint32, vp]
     lib.silo_gpu_distinct_insert.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_distinct_select.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_distinct_count.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_distinct_classes.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, vp, ctypes.c_uint32,
+                                              vp, vp]
+    lib.silo_gpu_smallest_keys.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -1200,6 +1205,87 @@ def distinct(parts, slots, fill=None, guard_words=0, calls=1, described=None, st
         for dev in device:
             for ptr in dev.values():
                 device_free(ptr)
+
+
+MAX_DISTINCT_CLASSES = 16384          # SILO_GPU_MAX_DISTINCT_CLASSES: the most keys silo_gpu_smallest_keys selects
+SMALLEST_KEYS_SCRATCH_BYTES = 1088    # SILO_GPU_SMALLEST_KEYS_SCRATCH_BYTES
+
+
+def distinct_counts_bytes(slots):
+    """SILO_GPU_DISTINCT_COUNTS_BYTES: one uint32 per slot of the owner table."""
+    return int(slots) * 4
+
+
+def distinct_class_key(count, global_row):
+    """The key silo_gpu_distinct_classes appends for a class: ascending keys are descending counts, then ascending rows."""
+    return ((0xFFFFFFFF - int(count)) << 32) | int(global_row)
+
+
+def distinct_counts(parts, slots, min_count=1, capacity=1, fill=None, guard_words=0, calls=1, stream=None):
+    """K20's table and K21's class counts over host arrays: silo_gpu_distinct_begin and silo_gpu_distinct_insert per part, then
+    `calls` times { counts and the key counter cleared, silo_gpu_distinct_count per part, silo_gpu_distinct_classes per part }.
+    parts as for distinct().  Returns a dict: owners uint32 [slots], overflow, counts uint32 [slots + guard_words], keys uint64
+    [capacity + guard_words] and n_keys, what *n_keys_dev holds — the words behind `slots` counts and behind `capacity` keys are
+    guards that no call may touch (counts apart, every array is filled with the byte `fill` before the launches)."""
+    lib = load_library()
+    table = device_malloc(distinct_table_bytes(slots), fill, stream)
+    counts = device_malloc((int(slots) + int(guard_words)) * 4, fill, stream)
+    keys = device_malloc((int(capacity) + int(guard_words)) * 8, fill, stream)
+    n_keys = device_malloc(4, fill, stream)
+    device = []
+    parts_dev = None
+    try:
+        records = np.zeros(len(parts), dtype=DISTINCT_PART_DTYPE)
+        for k, part in enumerate(parts):
+            hashes = np.ascontiguousarray(part["hashes"], dtype=np.uint64)
+            device.append({"hashes": _upload(hashes, stream), "filter": _upload(np.ascontiguousarray(part["filter"], dtype=np.uint64), stream)})
+            records[k] = (device[k]["hashes"].value, part["first_row"], part["sequence_count"], part["row_words"], 0)
+        parts_dev = _upload(records, stream)
+        _check(lib.silo_gpu_distinct_begin(table, slots, stream))
+        for k, dev in enumerate(device):
+            _check(lib.silo_gpu_distinct_insert(table, slots, parts_dev, len(parts), k, dev["filter"], stream))
+        for _ in range(calls):
+            _check(lib.silo_gpu_memset_async(counts, 0, distinct_counts_bytes(slots), stream))
+            _check(lib.silo_gpu_memset_async(n_keys, 0, 4, stream))
+            for k, dev in enumerate(device):
+                _check(lib.silo_gpu_distinct_count(table, slots, counts, parts_dev, len(parts), k, dev["filter"], stream))
+            for k, dev in enumerate(device):
+                _check(lib.silo_gpu_distinct_classes(table, slots, counts, parts_dev, len(parts), k, dev["filter"], min_count, keys, capacity,
+                                                     n_keys, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        words = device_read(table, np.uint32, int(slots) + 1, stream)
+        return {"owners": words[:-1].copy(), "overflow": int(words[-1]),
+                "counts": device_read(counts, np.uint32, int(slots) + int(guard_words), stream),
+                "keys": device_read(keys, np.uint64, int(capacity) + int(guard_words), stream),
+                "n_keys": int(device_read(n_keys, np.uint32, 1, stream)[0])}
+    finally:
+        for ptr in (table, counts, keys, n_keys):
+            device_free(ptr)
+        if parts_dev is not None:
+            device_free(parts_dev)
+        for dev in device:
+            for ptr in dev.values():
+                device_free(ptr)
+
+
+def smallest_keys(keys, n, k, fill=None, guard_words=0, calls=1, stream=None):
+    """silo_gpu_smallest_keys over a host array: keys uint64 [capacity] of which the first `n` are the list (n reaches the device
+    as *n_keys_dev only).  Returns (out, count): uint64 [k + guard_words], filled with the byte `fill` before the launches, and
+    what *out_count_dev holds after `calls` calls."""
+    lib = load_library()
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    keys_dev, n_dev = _upload(keys, stream), _upload(np.array([n], dtype=np.uint32), stream)
+    out = device_malloc((int(k) + int(guard_words)) * 8, fill, stream)
+    out_count = device_malloc(4, fill, stream)
+    scratch = device_malloc(SMALLEST_KEYS_SCRATCH_BYTES, fill, stream)
+    try:
+        for _ in range(calls):
+            _check(lib.silo_gpu_smallest_keys(keys_dev, n_dev, len(keys), k, out, out_count, scratch, stream))
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(out, np.uint64, int(k) + int(guard_words), stream), int(device_read(out_count, np.uint32, 1, stream)[0])
+    finally:
+        for ptr in (keys_dev, n_dev, out, out_count, scratch):
+            device_free(ptr)
 
 
 class GpuStore:
