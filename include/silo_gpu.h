@@ -1108,6 +1108,54 @@ int silo_gpu_smallest_keys(
    void* stream
 );
 
+/* ---- K22: each row's cell counts, kept by the store (the filter expression CellCount, the action CellCountDistribution) ----
+ * The class of the cell of row r at position p is K18's, word for word, with sym(r, p) as for K20 and ref[p] the sequence store's own
+ * reference: MISSING where sym is the missing symbol (N / X) whatever the reference holds; AMBIGUOUS where it is any other symbol
+ * that is no valid mutation symbol, or 31; SAME where it is valid and equals ref[p]; DELETION where it is valid, differs and is '-';
+ * SUBSTITUTION otherwise.  A reference symbol that is not valid differs from every valid symbol.  cells(r) is four uint32 in the
+ * order of K18's stats — substitutions, deletions, missing, ambiguous — over ALL positions: what silo_gpu_sequence_differences
+ * reports for the characters silo_gpu_reconstruct_sequences gives for row r.
+ * silo_gpu_row_cell_counts WRITES out_dev[r] = cells(r) for every r < sequence_count and (0, 0, 0, 0) for every other
+ *     r < row_words * 64, for a finalized store in any layout, as silo_gpu_row_hashes writes its hashes: the plane pass stores each
+ *     row's counts over what the planes say (an open cell counts as the position's derived symbol, or as 31), then a thread per
+ *     escape key, per run of the missing symbol and per sparse key adds the difference between its symbol's class and the one the
+ *     plane pass assumed (32-bit integer atomics: exact, whatever the schedule).  scratch_dev:
+ *     SILO_GPU_ROW_CELL_COUNT_SCRATCH_BYTES(positions) bytes, 256-byte aligned, for two per-position tables built on the host;
+ *     uploads them and waits for the stream once, ahead of its launches.
+ * silo_gpu_store_row_cell_counts returns the store's own copy of that table: the first call per sequence store allocates 16 bytes x
+ *     row_words * 64 (from then on part of silo_gpu_store_device_bytes), runs silo_gpu_row_cell_counts on `stream` and waits; every
+ *     later call returns the same pointer without device work.  Thread-safe.  The table lives as long as the store.
+ * Both fail with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer, a seqstore_id out of range or a store that is
+ * not finalized.
+ *
+ * The two readers take no store, only such a table (16-byte aligned).  value(r) is the sum of the counts of row r whose bit is set
+ * in kinds_mask (bit k = entry k of cells(r)), a 64-bit sum.
+ * silo_gpu_bitset_from_cell_counts WRITES every one of the row_words words of out_bitset_dev and nothing behind them:
+ *     bit r = r < sequence_count && at_least <= value(r) <= at_most   (at_least > at_most selects nothing).
+ * silo_gpu_cell_count_histogram ADDS to bins_dev[min(value(r) / bin_width, n_bins - 1)] (uint64 [n_bins], cleared by the caller;
+ *     partitions accumulate into one array) one for every row r < sequence_count whose bit in filter_dev is set (NULL: every row;
+ *     padding bits never count).  A block counts in LDS and adds its non-zero cells to bins_dev with 64-bit integer atomics.
+ * Both launch on `stream` and return without waiting.  Each fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL
+ * table or output, row_words == 0, sequence_count == 0 or > row_words * 64, kinds_mask == 0 or > 15; the histogram also for
+ * bin_width == 0, n_bins == 0 or n_bins > SILO_GPU_MAX_CELL_COUNT_BINS. */
+#define SILO_GPU_CELL_COUNT_KINDS 4
+#define SILO_GPU_CELL_COUNT_SUBSTITUTIONS 1u
+#define SILO_GPU_CELL_COUNT_DELETIONS 2u
+#define SILO_GPU_CELL_COUNT_MISSING 4u
+#define SILO_GPU_CELL_COUNT_AMBIGUOUS 8u
+#define SILO_GPU_MAX_CELL_COUNT_BINS 4096
+#define SILO_GPU_ROW_CELL_COUNT_SCRATCH_BYTES(positions) ((size_t)(positions) * 17u + 1024u)
+int silo_gpu_row_cell_counts(const silo_gpu_store* store, uint32_t seqstore_id, uint32_t* out_dev, void* scratch_dev, void* stream);
+int silo_gpu_store_row_cell_counts(silo_gpu_store* store, uint32_t seqstore_id, const uint32_t** out_dev, void* stream);
+int silo_gpu_bitset_from_cell_counts(
+   const uint32_t* table_dev, uint32_t row_words, uint32_t sequence_count, uint32_t kinds_mask, uint32_t at_least, uint32_t at_most,
+   uint64_t* out_bitset_dev, void* stream
+);
+int silo_gpu_cell_count_histogram(
+   const uint32_t* table_dev, uint32_t row_words, uint32_t sequence_count, const uint64_t* filter_dev, uint32_t kinds_mask, uint32_t bin_width,
+   uint32_t n_bins, uint64_t* bins_dev, void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

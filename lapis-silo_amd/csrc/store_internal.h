@@ -290,6 +290,10 @@ struct SeqStoreHost {
    // silo_gpu_store_row_hashes of the finalized store and kept, under the store's mutex
    DeviceArray<uint64_t> d_row_hashes;
    bool row_hashes_ready = false;
+   // the four cell counts of every row against `reference`, [row_words * 64][4] (K22, silo_gpu_cell_counts.hip): computed on the
+   // first silo_gpu_store_row_cell_counts of the finalized store and kept, under the store's mutex
+   DeviceArray<uint32_t> d_row_cell_counts;
+   bool row_cell_counts_ready = false;
    // the build-time planes (dev.scan / dev.extra are the views kernels get), owned until finalize releases them
    DeviceArray<uint64_t> d_scan;
    DeviceArray<uint64_t> d_extra;

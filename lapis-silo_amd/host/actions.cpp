@@ -881,6 +881,7 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"MutationsPerSequence", parseMutationsPerSequence<Nucleotide>},
    {"AminoAcidMutationsPerSequence", parseMutationsPerSequence<AminoAcid>},
    {"DistinctSequenceCounts", parseDistinctSequenceCounts},
+   {"CellCountDistribution", parseCellCountDistribution},
 };
 
 }  // namespace

@@ -928,6 +928,96 @@ std::unique_ptr<Expression> parseWithinDistance(const json::Value& json) {
 
 }  // namespace
 
+// ---- CellCount (no counterpart in the reference) --------------------------------------------------------
+namespace {
+constexpr std::string_view CELL_KINDS[] = {"substitutions", "deletions", "missing", "ambiguous"};  // bit k of a mask: K18's stats order
+}
+
+std::string cellKindsString(uint32_t kinds_mask) {
+   std::string joined;
+   for (uint32_t k = 0; k < std::size(CELL_KINDS); ++k) {
+      if (((kinds_mask >> k) & 1u) != 0) {
+         joined += (joined.empty() ? "" : "+") + std::string(CELL_KINDS[k]);
+      }
+   }
+   return joined;
+}
+
+uint32_t parseCellKinds(const json::Value& cells, const std::string& complaint) {
+   const auto bit_of = [&](const json::Value& kind) {
+      CHECK_SILO_QUERY(kind.is_string(), complaint)
+      const auto* found = std::find(std::begin(CELL_KINDS), std::end(CELL_KINDS), kind.as_string());
+      CHECK_SILO_QUERY(found != std::end(CELL_KINDS), complaint)
+      return 1u << static_cast<uint32_t>(found - std::begin(CELL_KINDS));
+   };
+   if (!cells.is_array()) {
+      return bit_of(cells);
+   }
+   uint32_t mask = 0;
+   for (const json::Value& kind : cells.items()) {
+      const uint32_t bit = bit_of(kind);
+      CHECK_SILO_QUERY((mask & bit) == 0, complaint)
+      mask |= bit;
+   }
+   CHECK_SILO_QUERY(mask != 0, complaint)
+   return mask;
+}
+
+std::string CellCount::toString(const Database& /*database*/) const {
+   const std::string sequence_string = sequence_name.has_value() ? "The sequence '" + sequence_name.value() + "'" : "The default nucleotide sequence";
+   return sequence_string + " has between " + std::to_string(at_least) + " and " + std::to_string(at_most) + " cells that are " + cellKindsString(kinds_mask);
+}
+
+std::unique_ptr<Operator> CellCount::compile(const Database& database, const DatabasePartition& database_partition, AmbiguityMode /*mode*/) const {
+   // the counts are exact numbers of the stored symbols: there is no upper or lower bound of them to take
+   const RowSpace rows = rowsOf(database_partition);
+   const actions::AlignedSequence counted =
+      actions::alignedSequence(database, sequence_name, "CellCount: the field sequenceName: Database does not contain a sequence with name: ");
+   CHECK_SILO_QUERY(
+      database.shard_world <= 1, "CellCount is not supported on a sharded database yet: the table of cell counts of a position shard is partial"
+   )
+   // what the number of positions decides, without the store (whose table of counts such a query never builds): a row has
+   // `positions` cells, so its value lies in [0, positions] whatever the kinds
+   if (database_partition.sequence_count == 0 || at_least > at_most || at_least > counted.positions) {
+      return std::make_unique<operators::Empty>(rows);
+   }
+   if (at_least == 0 && at_most >= counted.positions) {
+      return std::make_unique<operators::Full>(rows);
+   }
+   return std::make_unique<operators::CellCountSelection>(counted.seqstoreOf(database_partition), kinds_mask, at_least, at_most, rows);
+}
+
+namespace {
+
+std::unique_ptr<Expression> parseCellCount(const json::Value& json) {
+   std::optional<std::string> sequence_name;
+   if (json.contains("sequenceName")) {
+      CHECK_SILO_QUERY(json["sequenceName"].is_string(), "The field 'sequenceName' in a CellCount expression, if present, needs to be a string")
+      sequence_name = json["sequenceName"].as_string();
+   }
+   CHECK_SILO_QUERY(json.contains("cells"), "The field 'cells' is required in a CellCount expression")
+   const uint32_t kinds_mask = parseCellKinds(
+      json["cells"], "The field 'cells' in a CellCount expression needs to be one of \"substitutions\", \"deletions\", \"missing\", \"ambiguous\" or a "
+                     "non-empty list of them without repeats"
+   );
+   CHECK_SILO_QUERY(json.contains("atLeast") || json.contains("atMost"), "At least one of the fields 'atLeast' and 'atMost' is required in a CellCount expression")
+   uint32_t bounds[2] = {0, UINT32_MAX};
+   const char* const fields[2] = {"atLeast", "atMost"};
+   for (size_t k = 0; k < 2; ++k) {
+      if (json.contains(fields[k])) {
+         const json::Value& bound = json[fields[k]];
+         CHECK_SILO_QUERY(
+            bound.is_number_unsigned() && bound.as_int64() >= 0 && bound.as_int64() <= static_cast<int64_t>(UINT32_MAX),
+            "The field '" + std::string(fields[k]) + "' in a CellCount expression, if present, needs to be an integer from 0 to 4294967295"
+         )
+         bounds[k] = bound.as_uint32();
+      }
+   }
+   return std::make_unique<CellCount>(std::move(sequence_name), kinds_mask, bounds[0], bounds[1]);
+}
+
+}  // namespace
+
 // ---- Sample (no counterpart in the reference) -----------------------------------------------------------
 std::string Sample::toString(const Database& database) const {
    const std::string strata = date_field.has_value() ? " of each of " + std::to_string(range_bounds.size() / 2) + " ranges of '" + *date_field + "'" : "";
@@ -1334,6 +1424,9 @@ std::unique_ptr<Expression> parseExpression(const json::Value& json) {  // expre
    }
    if (expression_type == "DistinctSequences") {
       return parseDistinctSequences(json);
+   }
+   if (expression_type == "CellCount") {
+      return parseCellCount(json);
    }
    throw QueryParseException("Unknown object filter type '" + expression_type + "'");
 }

@@ -680,6 +680,30 @@ uint32_t DistanceSelection::lower(ProgramBuilder& builder) const {
    return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
 }
 
+// ---- CellCountSelection (no counterpart in the reference) -----------------------------------------------
+std::string CellCountSelection::toString() const {
+   return "CellCountSelection[" + std::to_string(at_least) + " <= " + filter_expressions::cellKindsString(kinds_mask) + " <= " + std::to_string(at_most) + "]";
+}
+std::unique_ptr<Operator> CellCountSelection::copy() const {
+   return std::make_unique<CellCountSelection>(seqstore_id, kinds_mask, at_least, at_most, rows);
+}
+std::unique_ptr<Operator> CellCountSelection::negate() const {
+   return std::make_unique<Complement>(this->copy(), rows);
+}
+uint32_t CellCountSelection::lower(ProgramBuilder& builder) const {
+   // 16 bytes per row that the store keeps from its first query on (that one computes them and waits); the kernel that makes
+   // the bitset reads them once, on the query's stream ahead of the fused program; the bitset lives as long as the builder
+   const DatabasePartition& partition = *rows.partition;
+   const uint32_t* table = nullptr;
+   checkGpu(silo_gpu_store_row_cell_counts(partition.store, seqstore_id, &table, queryStream()), "silo_gpu_store_row_cell_counts");
+   uint64_t* bitset = builder.temporaryBitset();
+   checkGpu(
+      silo_gpu_bitset_from_cell_counts(table, partition.rowWords(), partition.sequence_count, kinds_mask, at_least, at_most, bitset, queryStream()),
+      "silo_gpu_bitset_from_cell_counts"
+   );
+   return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
+}
+
 // ---- SampleSelection (no counterpart in the reference) --------------------------------------------------
 std::string SampleSelection::toString() const {
    return "SampleSelection[" + std::to_string(size) + " rows" + (range_bounds.empty() ? "" : " of each of " + std::to_string(range_bounds.size() / 2) + " date ranges") +

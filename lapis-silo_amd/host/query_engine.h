@@ -197,7 +197,7 @@ class ProgramBuilder {
 namespace operators {
 
 enum Type {
-   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION, SAMPLE_SELECTION, DISTINCT_SELECTION
+   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION, SAMPLE_SELECTION, DISTINCT_SELECTION, CELL_COUNT_SELECTION
 };
 
 /// What lowering a sub-tree into a program takes at most.  `slots`: the slots that are live at once while it is lowered, its
@@ -500,6 +500,29 @@ DistinctTable buildDistinctTable(
    const std::function<void*(size_t bytes)>& allocate, const std::string& what
 );
 
+/// The rows whose cell counts against the reference — substitutions, deletions, missing, ambiguous (K22) — sum, over the kinds of
+/// `kinds_mask`, to a value in [at_least, at_most] (the filter expression CellCount; no counterpart in the reference).  lower() takes
+/// the store's kept table of cell counts (silo_gpu_store_row_cell_counts: the first query on a store computes it and waits, so that
+/// request pays for the build) and turns it into a row bitset on the device (silo_gpu_bitset_from_cell_counts) on the lowering
+/// thread's stream ahead of the fused program, which reads the bitset as a leaf.  The bitset belongs to the builder, like
+/// DistanceSelection's buffers; the table belongs to the store.
+class CellCountSelection : public Operator {
+  public:
+   CellCountSelection(uint32_t seqstore_id, uint32_t kinds_mask, uint32_t at_least, uint32_t at_most, RowSpace rows)
+       : Operator(rows), seqstore_id(seqstore_id), kinds_mask(kinds_mask), at_least(at_least), at_most(at_most) {}
+   Type type() const override { return CELL_COUNT_SELECTION; }
+   std::string toString() const override;
+   std::unique_ptr<Operator> copy() const override;
+   std::unique_ptr<Operator> negate() const override;
+   uint32_t lower(ProgramBuilder& builder) const override;
+   Cost cost() const override { return {1, 1}; }
+
+   uint32_t seqstore_id;
+   uint32_t kinds_mask;  // SILO_GPU_CELL_COUNT_* bits
+   uint32_t at_least;
+   uint32_t at_most;
+};
+
 class Threshold : public Operator {
   public:
    Threshold(OperatorVector&& non_negated_children, OperatorVector&& negated_children, uint32_t number_of_matchers, bool match_exactly, RowSpace rows);
@@ -714,6 +737,24 @@ struct DistinctSequences : public Expression {
    std::unique_ptr<Expression> child;
    std::optional<std::string> sequence_name;
 };
+/// CellCount (no counterpart in the reference): the rows whose number of cells of the listed kinds — substitutions, deletions,
+/// missing, ambiguous against the reference of `sequence_name` (the default nucleotide sequence when absent), the four counts of
+/// MutationsPerSequence over all positions — lies in [at_least, at_most].  An absent bound is 0 / 2^32 - 1.  The parsed expression
+/// holds only what the query text says; compile answers what the number of positions alone decides without touching the store.
+struct CellCount : public Expression {
+   CellCount(std::optional<std::string> sequence_name, uint32_t kinds_mask, uint32_t at_least, uint32_t at_most)
+       : sequence_name(std::move(sequence_name)), kinds_mask(kinds_mask), at_least(at_least), at_most(at_most) {}
+   SILO_DECLARE_EXPRESSION_METHODS
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   uint32_t kinds_mask;                       // SILO_GPU_CELL_COUNT_* bits
+   uint32_t at_least;
+   uint32_t at_most;
+};
+/// The field `cells` of CellCount and CellCountDistribution: one kind or a non-empty list of kinds without repeats, as a mask of
+/// SILO_GPU_CELL_COUNT_* bits; anything else is a bad request with the message `complaint` (filter_expressions.cpp).
+uint32_t parseCellKinds(const json::Value& cells, const std::string& complaint);
+/// "substitutions+missing": the kinds of a mask in their order.
+std::string cellKindsString(uint32_t kinds_mask);
 struct DateBetween : public Expression {  // date_between.cpp
    DateBetween(std::string column, std::optional<common::Date> date_from, std::optional<common::Date> date_to)
        : column(std::move(column)), date_from(date_from), date_to(date_to) {}
@@ -846,6 +887,8 @@ std::unique_ptr<Action> parseNearestAmong(const json::Value& json);
 std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json);
 /// The parser of the action over the classes of equal sequences (distance_actions.cpp).
 std::unique_ptr<Action> parseDistinctSequenceCounts(const json::Value& json);
+/// The parser of the histogram of the selection's cell counts (sequence_actions.cpp).
+std::unique_ptr<Action> parseCellCountDistribution(const json::Value& json);
 
 /// Two kinds of field that many action parsers read, with one wording of the complaint (actions.cpp).  An optional field of type
 /// string: none when absent; "<action_name> action: the field <field>, if present, must be of type string".
@@ -1206,6 +1249,26 @@ class DistinctSequenceCounts : public Action {
    static constexpr uint32_t DEFAULT_CLASSES = 1024;
    DistinctSequenceCounts(std::optional<std::string> sequence_name, uint32_t min_count, uint32_t max_classes)
        : sequence_name(std::move(sequence_name)), min_count(min_count), max_classes(max_classes) {}
+};
+
+/// CellCountDistribution (sequence_actions.cpp; no counterpart in the reference): the histogram of value(r) — the sum of the listed
+/// kinds of row r's cell counts, as the filter expression CellCount bounds it — over the rows the filter selects.  Bin b =
+/// min(value / binWidth, maxBins - 1); one response row {from, to, count} per non-empty bin, ascending; the last bin is open
+/// ("to": null).  All on the device (K22): every store's kept table (silo_gpu_store_row_cell_counts), one
+/// silo_gpu_cell_count_histogram per partition with selected rows into one array of bins, and one download of it.
+class CellCountDistribution : public Action {
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   uint32_t kinds_mask;
+   uint32_t bin_width;
+   uint32_t max_bins;
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+
+  public:
+   static constexpr uint32_t BIN_LIMIT = SILO_GPU_MAX_CELL_COUNT_BINS;
+   static constexpr uint32_t DEFAULT_BINS = 1024;
+   CellCountDistribution(std::optional<std::string> sequence_name, uint32_t kinds_mask, uint32_t bin_width, uint32_t max_bins)
+       : sequence_name(std::move(sequence_name)), kinds_mask(kinds_mask), bin_width(bin_width), max_bins(max_bins) {}
 };
 
 template <typename SymbolType>

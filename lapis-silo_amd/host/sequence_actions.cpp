@@ -6,6 +6,7 @@
 // them: selectedRows, selectedCount, the description of an aligned sequence by name (alignedSequence), and the one walk over the
 // selection that uploads a partition's row ids and hands them to the caller's gather (SelectedSequences).
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 
 #include "query_engine.h"
@@ -470,5 +471,98 @@ std::unique_ptr<Action> parseMutationsPerSequence(const json::Value& json) {
 
 template std::unique_ptr<Action> parseMutationsPerSequence<Nucleotide>(const json::Value& json);
 template std::unique_ptr<Action> parseMutationsPerSequence<AminoAcid>(const json::Value& json);
+
+// ---- CellCountDistribution (no counterpart in the reference) -------------------------------------------------
+// The histogram of the selected rows' cell counts — the sum of the listed kinds of the four counts of MutationsPerSequence, taken
+// from every store's kept table (K22) — in bins of binWidth, the last of maxBins bins open: what a user reads a threshold for the
+// filter expression CellCount from.
+void CellCountDistribution::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"from", "count"});
+}
+
+QueryResult CellCountDistribution::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const AlignedSequence counted =
+      alignedSequence(database, sequence_name, "CellCountDistribution: the field sequenceName: Database does not contain a sequence with name: ");
+   requireUnsharded(database, "CellCountDistribution");
+   QueryResult results;
+   const size_t total_count = selectedCount(database, bitmap_filter);
+   if (total_count == 0) {
+      return results;
+   }
+   std::vector<uint64_t> bins(max_bins, 0);
+   if (counted.positions == 0) {  // no cell to count: every row has the value 0, and no store a table
+      bins[0] = total_count;
+   } else {
+      // nothing in here returns to the pool before the stream has been waited for: the launches write it
+      const size_t bins_bytes = static_cast<size_t>(max_bins) * sizeof(uint64_t);
+      const DeviceBuffer device_bins = database.partitions.front().pool.acquire(bins_bytes);
+      launchAndWait([&] {
+         checkGpu(silo_gpu_memset_async(device_bins.get(), 0, bins_bytes, queryStream()), "silo_gpu_memset_async");
+         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+            const DatabasePartition& partition = database.partitions[partition_id];
+            if (partition.sequence_count == 0 || bitmap_filter[partition_id].cardinality() == 0) {
+               continue;
+            }
+            const uint32_t* table = nullptr;
+            checkGpu(
+               silo_gpu_store_row_cell_counts(partition.store, counted.seqstoreOf(partition), &table, queryStream()), "silo_gpu_store_row_cell_counts"
+            );
+            checkGpu(
+               silo_gpu_cell_count_histogram(
+                  table, partition.rowWords(), partition.sequence_count, bitmap_filter[partition_id].bitset(), kinds_mask, bin_width, max_bins,
+                  device_bins.as<uint64_t>(), queryStream()
+               ),
+               "silo_gpu_cell_count_histogram"
+            );
+         }
+         const HostFetch fetch(device_bins.get(), bins_bytes, queryStream());
+         std::memcpy(bins.data(), fetch.wait(), bins_bytes);
+      });
+   }
+   uint64_t counted_rows = 0;
+   for (const uint64_t count : bins) {
+      counted_rows += count;
+   }
+   if (counted_rows != total_count) {
+      throw std::runtime_error(
+         "CellCountDistribution: the bins hold " + std::to_string(counted_rows) + " rows where the filters select " + std::to_string(total_count)
+      );
+   }
+   for (uint32_t bin = 0; bin < max_bins; ++bin) {
+      if (bins[bin] == 0) {
+         continue;
+      }
+      // (bin + 1) * binWidth <= maxBins * binWidth <= 2^31: checked where the action is parsed
+      const uint64_t from = static_cast<uint64_t>(bin) * bin_width;
+      QueryResultEntry& entry = results.query_result.emplace_back();
+      entry.fields.emplace("from", static_cast<int32_t>(from));
+      if (bin + 1u == max_bins) {
+         entry.fields.emplace("to", std::nullopt);
+      } else {
+         entry.fields.emplace("to", static_cast<int32_t>(from + bin_width - 1u));
+      }
+      entry.fields.emplace("count", static_cast<int32_t>(bins[bin]));
+   }
+   return results;
+}
+
+std::unique_ptr<Action> parseCellCountDistribution(const json::Value& json) {
+   const std::string action_name = "CellCountDistribution";
+   std::optional<std::string> sequence_name = optionalStringField(json, "sequenceName", action_name);
+   CHECK_SILO_QUERY(json.contains("cells"), action_name + " action: the field cells is required")
+   const uint32_t kinds_mask = filter_expressions::parseCellKinds(
+      json["cells"], action_name + " action: the field cells must be one of \"substitutions\", \"deletions\", \"missing\", \"ambiguous\" or a non-empty list "
+                                   "of them without repeats"
+   );
+   const uint32_t bin_width = integerField(json, "binWidth", action_name, false, 1, INT32_MAX, "an integer of at least 1").value_or(1);
+   const std::string bins_form = "an integer from 1 to " + std::to_string(CellCountDistribution::BIN_LIMIT);
+   const uint32_t max_bins =
+      integerField(json, "maxBins", action_name, false, 1, CellCountDistribution::BIN_LIMIT, bins_form).value_or(CellCountDistribution::DEFAULT_BINS);
+   CHECK_SILO_QUERY(
+      static_cast<uint64_t>(bin_width) * max_bins <= (uint64_t{1} << 31),
+      action_name + " action: the fields binWidth and maxBins: their product must not exceed 2147483648, so that every bin's bounds are 32-bit numbers"
+   )
+   return std::make_unique<CellCountDistribution>(std::move(sequence_name), kinds_mask, bin_width, max_bins);
+}
 
 }  // namespace silo::query_engine::actions

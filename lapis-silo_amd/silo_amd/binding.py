@@ -125,6 +125,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_row_hash_term", "silo_gpu_row_hashes", "silo_gpu_store_row_hashes", "silo_gpu_distinct_begin", "silo_gpu_distinct_insert",
     "silo_gpu_distinct_select",
     "silo_gpu_distinct_count", "silo_gpu_distinct_classes", "silo_gpu_smallest_keys",
+    "silo_gpu_row_cell_counts", "silo_gpu_store_row_cell_counts", "silo_gpu_bitset_from_cell_counts", "silo_gpu_cell_count_histogram",
 ]
 
 _lib = None
@@ -235,6 +236,10 @@ def load_library():
     lib.silo_gpu_distinct_classes.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, vp, ctypes.c_uint32,
                                               vp, vp]
     lib.silo_gpu_smallest_keys.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
+    lib.silo_gpu_row_cell_counts.argtypes = [vp, ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_store_row_cell_counts.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(vp), vp]
+    lib.silo_gpu_bitset_from_cell_counts.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_cell_count_histogram.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -1141,6 +1146,74 @@ def sample(partitions, size, seed=0, n_groups=1, fill=None, guard_words=0, strea
                     device_free(ptr)
 
 
+CELL_COUNT_KINDS = 4           # SILO_GPU_CELL_COUNT_KINDS: substitutions, deletions, missing, ambiguous (K18's stats order)
+CELL_COUNT_SUBSTITUTIONS, CELL_COUNT_DELETIONS, CELL_COUNT_MISSING, CELL_COUNT_AMBIGUOUS = 1, 2, 4, 8   # SILO_GPU_CELL_COUNT_*: bits of a kinds mask
+MAX_CELL_COUNT_BINS = 4096     # SILO_GPU_MAX_CELL_COUNT_BINS
+
+
+def row_cell_count_scratch_bytes(positions):
+    """SILO_GPU_ROW_CELL_COUNT_SCRATCH_BYTES: the scratch silo_gpu_row_cell_counts needs."""
+    return int(positions) * 17 + 1024
+
+
+def bitset_from_cell_counts_call(table_ptr, row_words, sequence_count, kinds_mask, at_least, at_most, out_ptr, stream=None):
+    """silo_gpu_bitset_from_cell_counts (K22) on the caller's device buffers, waited for."""
+    lib = load_library()
+    _check(lib.silo_gpu_bitset_from_cell_counts(table_ptr, row_words, sequence_count, kinds_mask, at_least, at_most, out_ptr, stream))
+    _check(lib.silo_gpu_stream_synchronize(stream))
+
+
+def bitset_from_cell_counts(table, row_words, sequence_count, kinds_mask, at_least=0, at_most=0xFFFFFFFF, fill=None, stream=None, guard_words=0):
+    """silo_gpu_bitset_from_cell_counts (K22) over a host table uint32 [row_words * 64][4] as silo_gpu_row_cell_counts leaves it:
+    bit r = r < sequence_count and at_least <= (the sum of the kinds of kinds_mask of row r) <= at_most.  Returns the row_words words
+    the call writes, followed by `guard_words` words behind them that it must not touch: those hold the byte `fill` repeated (the
+    whole allocation is filled with it before the launch), or whatever the allocation held."""
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    words = int(row_words) + int(guard_words)
+    table_dev = _upload(table, stream)
+    out = device_malloc(words * 8, fill, stream)
+    try:
+        bitset_from_cell_counts_call(table_dev, row_words, sequence_count, kinds_mask, at_least, at_most, out, stream)
+        return device_read(out, np.uint64, words, stream)
+    finally:
+        device_free(table_dev)
+        device_free(out)
+
+
+def cell_count_histogram_call(table_ptr, row_words, sequence_count, filter_ptr, kinds_mask, bin_width, n_bins, bins_ptr, stream=None):
+    """silo_gpu_cell_count_histogram (K22) on the caller's device buffers, waited for."""
+    lib = load_library()
+    _check(lib.silo_gpu_cell_count_histogram(table_ptr, row_words, sequence_count, filter_ptr, kinds_mask, bin_width, n_bins, bins_ptr, stream))
+    _check(lib.silo_gpu_stream_synchronize(stream))
+
+
+def cell_count_histogram(parts, kinds_mask, bin_width, n_bins, initial=None, guard_words=4, fill=0xA5, stream=None):
+    """silo_gpu_cell_count_histogram (K22), one call per part into ONE array of bins.  parts: a list of dicts {table: uint32
+    [row_words * 64][4], row_words, sequence_count, filter: uint64 [row_words] or None (every row)}.  initial: what the bins hold
+    before the first call (uint64 [n_bins]; None = zeros).  Returns uint64 [n_bins + guard_words]: the bins, then `guard_words`
+    words behind them that hold the byte `fill` repeated and that no call may touch."""
+    lib = load_library()
+    start = np.zeros(int(n_bins), dtype=np.uint64) if initial is None else np.ascontiguousarray(initial, dtype=np.uint64)
+    bins = device_malloc((int(n_bins) + int(guard_words)) * 8, fill, stream)
+    live = []
+    try:
+        if start.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(bins, _ptr(start), start.nbytes, stream))
+        for part in parts:
+            table_dev = _upload(np.ascontiguousarray(part["table"], dtype=np.uint32), stream)
+            live.append(table_dev)
+            filter_dev = None
+            if part.get("filter") is not None:
+                filter_dev = _upload(np.ascontiguousarray(part["filter"], dtype=np.uint64), stream)
+                live.append(filter_dev)
+            cell_count_histogram_call(table_dev, part["row_words"], part["sequence_count"], filter_dev, kinds_mask, bin_width, n_bins, bins, stream)
+        return device_read(bins, np.uint64, int(n_bins) + int(guard_words), stream)
+    finally:
+        device_free(bins)
+        for ptr in live:
+            device_free(ptr)
+
+
 ROW_HASH_NO_SYMBOL = 31        # SILO_GPU_ROW_HASH_NO_SYMBOL: a cell that nothing stored claims
 DISTINCT_EMPTY = 0xFFFFFFFF    # SILO_GPU_DISTINCT_EMPTY: a slot of the owner table without an owner
 DISTINCT_PART_DTYPE = np.dtype([("hashes_dev", np.uint64), ("first_row", np.uint32), ("sequence_count", np.uint32),
@@ -1765,6 +1838,29 @@ class GpuStore:
         """silo_gpu_store_row_hashes (K20): the device address of the store's own table of row hashes (computed on the first call)."""
         out = ctypes.c_void_p()
         _check(self.lib.silo_gpu_store_row_hashes(self.handle, seqstore_id, ctypes.byref(out), stream))
+        return out.value
+
+    def row_cell_counts(self, seqstore_id, fill=None, guard_rows=0, stream=None):
+        """silo_gpu_row_cell_counts (K22) into a table for the call, filled with the byte `fill` before the launches so that a test
+        can see that every cell is written: returns uint32 [row_words * 64 + guard_rows][4] (substitutions, deletions, missing,
+        ambiguous), the last `guard_rows` rows untouched."""
+        rows = self.row_words * 64 + int(guard_rows)
+        scratch = self.malloc(row_cell_count_scratch_bytes(self.positions(seqstore_id)))
+        table = self.malloc(max(16, 16 * rows))
+        try:
+            if fill is not None:
+                self.memset(table, fill, max(16, 16 * rows), stream)
+            _check(self.lib.silo_gpu_row_cell_counts(self.handle, seqstore_id, table, scratch, stream))
+            self.synchronize(stream)
+            return self.read(table, np.uint32, rows * 4, stream).reshape(-1, 4)
+        finally:
+            self.free(scratch)
+            self.free(table)
+
+    def kept_row_cell_counts(self, seqstore_id, stream=None):
+        """silo_gpu_store_row_cell_counts (K22): the device address of the store's own table of cell counts (computed on the first call)."""
+        out = ctypes.c_void_p()
+        _check(self.lib.silo_gpu_store_row_cell_counts(self.handle, seqstore_id, ctypes.byref(out), stream))
         return out.value
 
     def position_symbols(self, seqstore_id, positions, fill=None, guard_bytes=0, calls=1, null=(), n_positions=None, stream=None):
