@@ -1187,6 +1187,10 @@ enum { SILO_GPU_TUNE_SCAN_ROWS_PER_BLOCK = 0, SILO_GPU_TUNE_SCAN_VARIANT = 1, SI
                                       them in a launch of their own behind the row launch; < 0 reads the rows — the same tables either way, for A/B runs */,
        SILO_GPU_TUNE_FUSED_SELECT = 13 /* silo_gpu_mutations_scan_select: 0 (default) lets the finish kernel of the scan overwrite the tables and select the
                                           rows where the call allows it, < 0 always clears, scans and selects in launches of their own (comparisons) */,
+       SILO_GPU_TUNE_ESCAPE_BLOCKS = 14 /* the blocks that walk the items — (range, slice, share) — of a sliced escape-key launch (k_scan_escapes_sliced):
+                                           0 (default) one block per item, < 0 as many blocks as the chip holds at once, n > 0 exactly min(n, items)
+                                           blocks, planned as for a chip of n places (tests) — the same tables whatever the value; one block per item
+                                           is the faster on the headline (profiles/r10_escape_items.md), the others are kept for A/B runs */,
        SILO_GPU_TUNE_SCAN_SPARSE_DIVISOR = 3 /* a filter with a set bit in <= row_words / divisor of its 64-byte sectors takes the gather scan (K1s); 0 = default 16, < 0 = off */ };
 int silo_gpu_tune(int knob, int value);
 
@@ -1222,6 +1226,9 @@ int silo_gpu_broadcast_bytes(silo_gpu_comm* comm, void* bytes_dev, size_t n_byte
 
 /* Name of the last kernel variant silo_gpu_mutations_scan launched (for roofline attribution). */
 const char* silo_gpu_last_scan_kernel(void);
+/* Items — (range, slice, share) — of the calling thread's last launch of k_scan_escapes_sliced (0 before the first); the blocks that
+ * walked them are the launch's `blocks` in the timing log (SILO_GPU_TUNE_ESCAPE_BLOCKS). */
+uint32_t silo_gpu_last_escape_items(void);
 
 /* Per-launch timing of a scan (measurement only).  With SILO_GPU_TUNE_SCAN_TIMING set to 1, every k_scan_sliced,
  * k_scan_escapes_sliced, k_scan_missing_runs and k_count_sparse_keys launch of the calling thread's scans is bracketed by HIP
@@ -1236,9 +1243,10 @@ typedef struct silo_gpu_scan_timing {
                              events and the residual keys); plane_rows and bytes stay those of ALL its rows */
    uint64_t plane_rows;   /* plane rows a k_scan_sliced launch streams (0 for the other kernels) */
    uint64_t bytes;        /* what the launch has to read, each byte once: plane rows + filter rows; 8 bytes per escape key (+ a filter
-                             slice per block); 12 bytes per run of the missing symbol; 8 per sparse key */
+                             slice per item of k_scan_escapes_sliced, however many blocks walk the items); 12 bytes per run of the missing
+                             symbol; 8 per sparse key */
    uint32_t filters;
-   uint32_t blocks;
+   uint32_t blocks;       /* of the grid as launched */
    float ms;
 } silo_gpu_scan_timing;
 int silo_gpu_scan_timings(silo_gpu_scan_timing* out, uint32_t capacity, uint32_t* n_out);

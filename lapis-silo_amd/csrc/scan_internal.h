@@ -212,6 +212,7 @@ int scanPiecesGather(const std::vector<ScanPiece> (&pieces)[N_SCAN_LAYOUTS], con
    const uint32_t* sparse_sectors, uint32_t sparse_capacity, const uint32_t* sector_index, uint32_t stride, hipStream_t hip_stream);
 
 // silo_gpu_scan_keys.hip
+extern thread_local uint32_t g_last_escape_items;  // items of the thread's last launch of k_scan_escapes_sliced (silo_gpu_last_escape_items)
 int scanEscapes(const std::vector<ScanRange>& ranges, const uint64_t* const* filters, uint32_t q_count, hipStream_t hip_stream, const std::vector<ScanRange>* gaps, const ScanPruning* pruning,
    const std::vector<ScanRange>* ends = nullptr, bool only_ends = false);
 

@@ -30,6 +30,7 @@ std::atomic<int> g_tune_gap_events{0};
 std::atomic<int> g_tune_prune_keys{0};
 std::atomic<int> g_tune_end_runs{0};
 std::atomic<int> g_tune_fused_select{0};
+std::atomic<int> g_tune_escape_blocks{0};
 
 namespace {
 thread_local std::string g_last_error;
@@ -90,6 +91,9 @@ int silo_gpu_tune(int knob, int value) {
    }
    if (knob == SILO_GPU_TUNE_FUSED_SELECT) {
       return g_tune_fused_select.exchange(value);
+   }
+   if (knob == SILO_GPU_TUNE_ESCAPE_BLOCKS) {
+      return g_tune_escape_blocks.exchange(value);
    }
    return -1;
 }

@@ -2,7 +2,7 @@
 // §3, "K1 design" to "K1c / batched queries"; "Host side").  The passes and their kernels live in files of their own
 // (scan_internal.h); here is what ties them together: the ranges cut into pieces by layout, the timing log, the pool of
 // scratch blocks, the side streams, the order of the passes; and the C entries silo_gpu_mutations_scan*, silo_gpu_scan_timings,
-// silo_gpu_last_scan_kernel and the silo_gpu_store_scan_* statistics.
+// silo_gpu_last_scan_kernel, silo_gpu_last_escape_items and the silo_gpu_store_scan_* statistics.
 //
 // Kernels:
 //   k_add_u32   the cached totals of the unfiltered store added to a count table (silo_gpu_mutations_scan without a filter)
@@ -558,6 +558,10 @@ extern "C" {
 
 const char* silo_gpu_last_scan_kernel(void) {
    return g_last_scan_kernel;
+}
+
+uint32_t silo_gpu_last_escape_items(void) {
+   return g_last_escape_items;
 }
 
 int silo_gpu_mutations_scan_ranges(

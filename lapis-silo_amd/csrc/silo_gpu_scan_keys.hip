@@ -4,7 +4,7 @@
 // keys of its covered rows ("The gap symbol's end runs instead of its rows").
 //
 // Kernels:
-//   k_scan_escapes_sliced<FILTERS>   the slice-major 4-byte keys against a slice of 1, 2, 4 or 8 filters in LDS
+//   k_scan_escapes_sliced<FILTERS, WALK>   the slice-major 4-byte keys against a slice of 1, 2, 4 or 8 filters in LDS; a block per item, or blocks that walk the items
 //   k_scan_escapes_overflow          the few keys that do not fit the packed form
 //   k_scan_escapes                   the position-major 8-byte keys (stores of more than 512 slices; an independent check)
 // Exported (scan_internal.h): scanEscapes.
@@ -15,11 +15,13 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
 
+#include "escape_item_plan.h"
 #include "scan_internal.h"
 
 using namespace silo_gpu_detail;
@@ -67,15 +69,17 @@ __global__ __launch_bounds__(256) void k_scan_escapes(
 }
 
 /// One launch for up to ESCAPE_MAX_RANGES position ranges (the 12 genes of an AminoAcidMutations query), each over the
-/// escape keys or the gap events of its store: grid = (the blocks of every range — blocks_per_slice per slice, slice by slice
-/// —, 1, filters / FILTERS); where a slice's keys of the scanned positions begin and end is read from the store's slice index
-/// on the device.
+/// escape keys or the gap events of its store.  The work is numbered as ITEMS — every range items_per_slice per slice, slice by
+/// slice, the ranges that are never pruned first (escape_item_plan.h) —; grid = (blocks that walk the items in turn, 1,
+/// filters / FILTERS); where a slice's keys of the scanned positions begin and end is read from the store's slice index on the
+/// device.
 struct EscapeSliceArgs {
    const uint64_t* filters[SILO_GPU_MAX_SCAN_BATCH];
    uint32_t row_words;
    uint32_t n_slices;
    uint32_t n_ranges;
-   uint32_t block_keys;  // keys of a block's share: whole granules, at most ESCAPE_GRANULES_PER_BLOCK
+   uint32_t block_keys;  // keys of an item's share: whole granules, at most ESCAPE_GRANULES_PER_BLOCK
+   uint32_t n_items;     // block b takes the items b, b + gridDim.x, ... below it
    // a scan that may leave out keys no Mutations row can come from (silo_gpu_mutations_scan_ranges_min_proportion): the counters of
    // the prepare step ([q * SPARSE_COUNTER_STRIDE + 2] = the cardinality of filter q) and every filter's proportion; a range
    // with bounds per granule (heaviest, without) skips the granules that granulePrunable() names for EVERY filter of the pass
@@ -93,8 +97,8 @@ struct EscapeSliceArgs {
       uint32_t out_symbols;       // counters per position: the store's scan symbols (keys), 2 (gap events: starts, ends)
       uint32_t key_from;          // the position whose keys a slice's are read from: pos_begin, or 0 for gap events, whose
                                   // events before pos_begin count on pos_begin's counters (a gap open there counts as begun)
-      uint32_t first_block;       // the blocks of the ranges before
-      uint32_t blocks_per_slice;
+      uint32_t first_item;        // the items of the ranges before
+      uint32_t items_per_slice;
       uint32_t* counts[SILO_GPU_MAX_SCAN_BATCH];  // of the range's first position
    } ranges[ESCAPE_MAX_RANGES];
 };
@@ -137,8 +141,23 @@ constexpr uint32_t escapeLdsBytes() {
    return (FILTERS * (ESCAPE_SLICE_WORDS32 + escapeWindow<FILTERS>()) + 3u * ESCAPE_GRANULES_PER_BLOCK + 4u + 64u) * static_cast<uint32_t>(sizeof(uint32_t));
 }
 
-template <int FILTERS>
-__global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_scan_escapes_sliced(const EscapeSliceArgs args, uint32_t n_filters) {
+/// What a block keeps in LDS from one item to the next (both uniform).
+struct EscapeBlockState {
+   uint32_t slice;  // the slice whose filters are in LDS; ~0: none yet
+   bool any_row;    // ... and whether any of its rows is selected by a filter of the pass
+   bool zeroed;     // the counter windows have been zeroed: by the block's first item that gets as far as its filter slices
+};
+
+/// One ITEM of k_scan_escapes_sliced (see there): the share `item` numbers — (range, slice, share) — counted by the whole block.
+/// Every `return` is taken by all 16 waves, and a barrier lies between the last read of an item's list of granules or of the
+/// filter slices and the next item's rewrite of them: the last one of flushChunk, the one behind the filter slices, or the one
+/// of the exit without a live granule.  The counter windows are zeroed ONCE per block, by its first item that gets past the exits
+/// without keys or live granules (a block that only finds such items never pays for it): flushChunk leaves every counter it
+/// flushed at zero, and an item that leaves early has not touched them.
+/// WALK = false: the block has this one item — nothing is kept, no exit needs a barrier, and the code is that of a kernel
+/// without items (the launch of one block per item, the default, pays nothing for the walk).
+template <int FILTERS, bool WALK>
+__device__ __forceinline__ void scanEscapeItem(const EscapeSliceArgs& args, const uint32_t n_filters, const uint32_t item, EscapeBlockState& kept) {
    constexpr uint32_t WINDOW = escapeWindow<FILTERS>();
    static_assert(ESCAPE_GRANULE_KEYS == ESCAPE_SLICE_THREADS * 4u, "a granule is one 16-byte load per thread of the block");
    extern __shared__ uint32_t s_filter[];  // [FILTERS][ESCAPE_SLICE_WORDS32], then the counters [FILTERS][WINDOW], the granules' bases, the chunks' last keys
@@ -152,20 +171,25 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
    uint32_t* s_nowhere = s_live + ESCAPE_GRANULES_PER_BLOCK + 4u;  // [64] a word per lane: where an add of nothing goes
    const uint32_t first_filter = blockIdx.z * FILTERS;
    uint32_t r = 0;
-   while (r + 1u < args.n_ranges && blockIdx.x >= args.ranges[r + 1u].first_block) {  // (uniform)
+   while (r + 1u < args.n_ranges && item >= args.ranges[r + 1u].first_item) {  // (uniform)
       ++r;
    }
    const EscapeSliceArgs::Range& range = args.ranges[r];
-   const uint32_t slice = (blockIdx.x - range.first_block) / range.blocks_per_slice;
-   const uint32_t share = (blockIdx.x - range.first_block) % range.blocks_per_slice;
+   const uint32_t slice = (item - range.first_item) / range.items_per_slice;
+   const uint32_t share = (item - range.first_item) % range.items_per_slice;
    const uint32_t out_symbols = range.out_symbols;
    const uint32_t* first = range.slice_first + static_cast<size_t>(slice) * (range.positions + 1u);
    const uint32_t key_begin = first[range.key_from];
    const uint32_t key_end = first[range.pos_end];
-   // the block's share: args.block_keys keys (whole granules)
+   // the item's share: args.block_keys keys (whole granules)
    const uint32_t share_begin = key_begin / ESCAPE_GRANULE_KEYS * ESCAPE_GRANULE_KEYS + share * args.block_keys;
    if (share_begin >= key_end) {
-      return;  // (uniform) no keys for this block
+      return;  // (uniform) no keys for this item
+   }
+   // the filter slices stay in LDS while the block's items stay in one slice; a slice none of whose rows is selected is left at once
+   const bool reload = !WALK || slice != kept.slice;  // (uniform)
+   if (!reload && !kept.any_row) {
+      return;
    }
    const uint32_t share_end = min(share_begin + args.block_keys, key_end);
    const uint32_t range_first = range.pos_begin * out_symbols;
@@ -225,6 +249,9 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
       __syncthreads();
       n_live = liveGranule(ESCAPE_GRANULES_PER_BLOCK);
       if (n_live == 0) {
+         if constexpr (WALK) {
+            ldsBarrier();  // (every wave has read the count before the next item's list overwrites it)
+         }
          return;
       }
    }
@@ -234,14 +261,14 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
    uint64_t any_bit = 0;
    ulonglong2 filter_part[FILTERS][ESCAPE_SLICE_WORDS32 / 4u / ESCAPE_SLICE_THREADS];
 #pragma unroll
-   for (int f = 0; f < FILTERS; ++f) {  // this slice of every filter: 16 bytes per thread, zeros past the end of the row (and for a filter past the last)
+   for (int f = 0; f < FILTERS; ++f) {  // this slice of every filter, unless LDS has it: 16 bytes per thread, zeros past the end of the row (and for a filter past the last)
       const uint32_t first_word = slice * (ESCAPE_SLICE_WORDS32 / 2u);
       const bool present = first_filter + f < n_filters;
       const uint64_t* filter = args.filters[present ? first_filter + f : first_filter];
 #pragma unroll
       for (uint32_t j = 0; j < ESCAPE_SLICE_WORDS32 / 4u / ESCAPE_SLICE_THREADS; ++j) {
          const uint32_t word = first_word + (j * ESCAPE_SLICE_THREADS + threadIdx.x) * 2u;  // 16-byte chunk of the slice
-         filter_part[f][j] = present && word < args.row_words ? *reinterpret_cast<const ulonglong2*>(filter + word) : make_ulonglong2(0, 0);
+         filter_part[f][j] = reload && present && word < args.row_words ? *reinterpret_cast<const ulonglong2*>(filter + word) : make_ulonglong2(0, 0);
       }
    }
    // three granules in flight per wave, in registers of their own (without pruning the list is not written yet: granule k is live granule k)
@@ -256,39 +283,48 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
    // per granule and wave).  A thread holds the 128 rows of its 16-byte part of every filter and writes their 128 bytes.
    constexpr bool BYTE_PER_ROW = FILTERS == 8;
    static_assert(ESCAPE_SLICE_WORDS32 / 4u / ESCAPE_SLICE_THREADS == 1u, "a thread holds one 16-byte part of a filter slice");
-#pragma unroll
-   for (int f = 0; f < FILTERS; ++f) {
-      for (uint32_t j = threadIdx.x * 4u; j < WINDOW; j += ESCAPE_SLICE_THREADS * 4u) {  // (16 bytes per store; WINDOW is a multiple of 4)
-         *reinterpret_cast<uint4*>(s_count + f * WINDOW + j) = make_uint4(0, 0, 0, 0);
+   if (!WALK || !kept.zeroed) {  // (uniform; the barrier below stands between these stores and the first add)
+      for (uint32_t j = threadIdx.x * 4u; j < FILTERS * WINDOW; j += ESCAPE_SLICE_THREADS * 4u) {  // (16 bytes per store; WINDOW is a multiple of 4)
+         *reinterpret_cast<uint4*>(s_count + j) = make_uint4(0, 0, 0, 0);
       }
-      if constexpr (!BYTE_PER_ROW) {
-         *reinterpret_cast<ulonglong2*>(s_filter + f * ESCAPE_SLICE_WORDS32 + threadIdx.x * 4u) = filter_part[f][0];
-      }
-      any_bit |= filter_part[f][0].x | filter_part[f][0].y;
+      kept.zeroed = true;
    }
-   if constexpr (BYTE_PER_ROW) {
+   if (!reload) {
+      ldsBarrier();  // (the list of granules, where the first wave has just written it)
+   } else {
 #pragma unroll
-      for (uint32_t quarter = 0; quarter < 4; ++quarter) {  // 32 rows of the thread's 128: 32 bytes
-         uint32_t bytes[8];
-#pragma unroll
-         for (uint32_t k = 0; k < 8; ++k) {
-            bytes[k] = 0;
+      for (int f = 0; f < FILTERS; ++f) {
+         if constexpr (!BYTE_PER_ROW) {
+            *reinterpret_cast<ulonglong2*>(s_filter + f * ESCAPE_SLICE_WORDS32 + threadIdx.x * 4u) = filter_part[f][0];
          }
+         any_bit |= filter_part[f][0].x | filter_part[f][0].y;
+      }
+      if constexpr (BYTE_PER_ROW) {
 #pragma unroll
-         for (int f = 0; f < FILTERS; ++f) {
-            const uint64_t half = quarter < 2 ? filter_part[f][0].x : filter_part[f][0].y;
-            const uint32_t rows32 = static_cast<uint32_t>(half >> (32u * (quarter & 1u)));
+         for (uint32_t quarter = 0; quarter < 4; ++quarter) {  // 32 rows of the thread's 128: 32 bytes
+            uint32_t bytes[8];
 #pragma unroll
-            for (uint32_t k = 0; k < 8; ++k) {  // four rows -> the low bits of four bytes
-               bytes[k] |= ((((rows32 >> (4u * k)) & 0xFu) * 0x00204081u) & 0x01010101u) << f;
+            for (uint32_t k = 0; k < 8; ++k) {
+               bytes[k] = 0;
             }
+#pragma unroll
+            for (int f = 0; f < FILTERS; ++f) {
+               const uint64_t half = quarter < 2 ? filter_part[f][0].x : filter_part[f][0].y;
+               const uint32_t rows32 = static_cast<uint32_t>(half >> (32u * (quarter & 1u)));
+#pragma unroll
+               for (uint32_t k = 0; k < 8; ++k) {  // four rows -> the low bits of four bytes
+                  bytes[k] |= ((((rows32 >> (4u * k)) & 0xFu) * 0x00204081u) & 0x01010101u) << f;
+               }
+            }
+            uint32_t* out = s_filter + threadIdx.x * 32u + quarter * 8u;  // (row r of the slice = byte r)
+            *reinterpret_cast<uint4*>(out) = make_uint4(bytes[0], bytes[1], bytes[2], bytes[3]);
+            *reinterpret_cast<uint4*>(out + 4) = make_uint4(bytes[4], bytes[5], bytes[6], bytes[7]);
          }
-         uint32_t* out = s_filter + threadIdx.x * 32u + quarter * 8u;  // (row r of the slice = byte r)
-         *reinterpret_cast<uint4*>(out) = make_uint4(bytes[0], bytes[1], bytes[2], bytes[3]);
-         *reinterpret_cast<uint4*>(out + 4) = make_uint4(bytes[4], bytes[5], bytes[6], bytes[7]);
       }
+      kept.any_row = __syncthreads_or(any_bit != 0 ? 1 : 0) != 0;
+      kept.slice = slice;
    }
-   if (__syncthreads_or(any_bit != 0 ? 1 : 0) == 0) {
+   if (!kept.any_row) {
       return;  // no row of this slice is selected: none of its keys counts
    }
    const uint32_t lane = __lane_id();
@@ -492,6 +528,25 @@ __global__ __launch_bounds__(ESCAPE_SLICE_THREADS, FILTERS <= 4 ? 8 : 4) void k_
    flushChunk();
 }
 
+/// WALK: the blocks of the launch walk its items in turn — block b takes the items b, b + gridDim.x, ... below args.n_items; any
+/// number of blocks gives the same tables, and nothing passes between blocks but the adds to the tables.  !WALK: gridDim.x =
+/// args.n_items, block b counts item b.  The host chooses (escape_item_plan.h, SILO_GPU_TUNE_ESCAPE_BLOCKS): one block per
+/// item by default — measured, the chip's own dealing of more blocks than it holds evens out the items better than a strided
+/// deal to resident blocks saves in block starts (profiles/r10_escape_items.md).
+/// (Registers: one and two filters run two blocks to a CU and stay within 64 VGPRs; four and eight filters fill the LDS of a CU
+/// with one block, 4 waves per SIMD; the walk of four filters needs more than 64 VGPRs for what it keeps and may take 128.)
+template <int FILTERS, bool WALK>
+__global__ __launch_bounds__(ESCAPE_SLICE_THREADS, (FILTERS <= 2 || (FILTERS <= 4 && !WALK)) ? 8 : 4) void k_scan_escapes_sliced(const EscapeSliceArgs args, uint32_t n_filters) {
+   EscapeBlockState kept{~0u, false, false};
+   if constexpr (!WALK) {
+      scanEscapeItem<FILTERS, false>(args, n_filters, blockIdx.x, kept);
+   } else {
+      for (uint32_t item = blockIdx.x; item < args.n_items; item += gridDim.x) {  // (uniform; n_items + gridDim.x does not wrap: ESCAPE_PLAN_MAX_ITEMS)
+         scanEscapeItem<FILTERS, true>(args, n_filters, item, kept);
+      }
+   }
+}
+
 /// The few keys of a store that do not fit the packed form (SliceMajorKeys::d_overflow of SeqStoreHost::Layout::escapes_sliced: counter << 32 | sequence),
 /// for the positions [pos_begin, pos_end): one global filter lookup and one atomic each; grid.y = filter.
 __global__ __launch_bounds__(256) void k_scan_escapes_overflow(
@@ -510,6 +565,71 @@ __global__ __launch_bounds__(256) void k_scan_escapes_overflow(
    }
 }
 
+static_assert(ESCAPE_PLAN_MAX_ENTRIES == ESCAPE_MAX_RANGES && ESCAPE_PLAN_GRANULE_KEYS == ESCAPE_GRANULE_KEYS && ESCAPE_PLAN_GRANULES_PER_ITEM == ESCAPE_GRANULES_PER_BLOCK,
+   "escape_item_plan.h repeats these constants so that it needs no HIP");
+
+/// k_scan_escapes_sliced<FILTERS, WALK>: what a launch needs of an instantiation.
+template <int FILTERS, bool WALK>
+void launchEscapes(const dim3 grid, hipStream_t stream, const EscapeSliceArgs& args, uint32_t n_filters) {
+   k_scan_escapes_sliced<FILTERS, WALK><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<FILTERS>(), stream>>>(args, n_filters);
+}
+template <int FILTERS, bool WALK>
+hipError_t prepareEscapes(int* blocks_per_cu) {  // more dynamic LDS than a kernel may ask for by default; its resident blocks per CU
+   if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_escapes_sliced<FILTERS, WALK>), hipFuncAttributeMaxDynamicSharedMemorySize, escapeLdsBytes<FILTERS>());
+       e != hipSuccess) {
+      return e;
+   }
+   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_scan_escapes_sliced<FILTERS, WALK>, ESCAPE_SLICE_THREADS, escapeLdsBytes<FILTERS>());
+}
+template <bool WALK>
+void launchEscapes(uint32_t per_block, const dim3 grid, hipStream_t stream, const EscapeSliceArgs& args, uint32_t n_filters) {
+   switch (per_block) {
+      case 1: launchEscapes<1, WALK>(grid, stream, args, n_filters); break;
+      case 2: launchEscapes<2, WALK>(grid, stream, args, n_filters); break;
+      case 4: launchEscapes<4, WALK>(grid, stream, args, n_filters); break;
+      default: launchEscapes<8, WALK>(grid, stream, args, n_filters); break;
+   }
+}
+template <bool WALK>
+hipError_t prepareEscapes(uint32_t per_block, int* blocks_per_cu) {
+   switch (per_block) {
+      case 1: return prepareEscapes<1, WALK>(blocks_per_cu);
+      case 2: return prepareEscapes<2, WALK>(blocks_per_cu);
+      case 4: return prepareEscapes<4, WALK>(blocks_per_cu);
+      default: return prepareEscapes<8, WALK>(blocks_per_cu);
+   }
+}
+
+/// Blocks of k_scan_escapes_sliced<per_block, walk> that the current device holds at once: resident blocks per CU (the occupancy
+/// query, with the kernel's LDS) x CUs.  Asked once per device and instantiation, with the kernel's LDS attribute set in the same
+/// step; afterwards one relaxed load (two threads that ask at once both ask the runtime and store the same answer).
+hipError_t escapePlaces(uint32_t per_block, bool walk, uint32_t* out) {
+   constexpr int MAX_DEVICES = 64;
+   static std::atomic<uint32_t> cached[MAX_DEVICES][4][2];
+   int device = 0;
+   if (const hipError_t e = hipGetDevice(&device); e != hipSuccess) {
+      return e;
+   }
+   if (device < 0 || device >= MAX_DEVICES) {
+      return hipErrorInvalidDevice;
+   }
+   std::atomic<uint32_t>& slot = cached[device][per_block == 1 ? 0 : (per_block == 2 ? 1 : (per_block == 4 ? 2 : 3))][walk ? 1 : 0];
+   *out = slot.load(std::memory_order_relaxed);
+   if (*out != 0) {
+      return hipSuccess;
+   }
+   int per_cu = 0, cus = 0;
+   if (const hipError_t e = walk ? prepareEscapes<true>(per_block, &per_cu) : prepareEscapes<false>(per_block, &per_cu); e != hipSuccess) {
+      return e;
+   }
+   if (const hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device); e != hipSuccess) {
+      return e;
+   }
+   *out = static_cast<uint32_t>(std::max(1, per_cu)) * static_cast<uint32_t>(std::max(1, cus));
+   slot.store(*out, std::memory_order_relaxed);
+   return hipSuccess;
+}
+
 /// The launch descriptor of the position-major and the overflow keys of `range`: its filters and its count tables.
 ScanBatchArgs keyBatch(const ScanRange& range, const uint64_t* const* filters, uint32_t q_count) {
    ScanBatchArgs batch{};
@@ -522,6 +642,8 @@ ScanBatchArgs keyBatch(const ScanRange& range, const uint64_t* const* filters, u
 }  // namespace
 
 namespace silo_gpu_detail {
+
+thread_local uint32_t g_last_escape_items = 0;
 
 /// The rows the code planes do not carry: one pass over the escape keys of every range, for all filters (dense and
 /// sparse alike: the gather reads the same planes); with `gaps` (one entry per range: its store and positions, counts = the range's gap tables,
@@ -545,57 +667,60 @@ int scanEscapes(
       sliced.counters = pruning->counters;
    }
    uint32_t n_sliced = 0;
-   std::array<uint32_t, ESCAPE_MAX_RANGES> most_keys{};  // of one (range, slice)
+   std::array<EscapeEntryShape, ESCAPE_MAX_RANGES> shapes{};  // most_keys: of one (range, slice)
    uint64_t total_keys = 0;  // of the ranges of the launch
    bool end_entries = false;  // the launch has end events or residual keys (", ends" behind the kernel's name in the timing log)
    const auto launchSliced = [&]() -> int {
       if (n_sliced == 0) {
          return SILO_GPU_OK;
       }
-      static std::once_flag lds_once;
-      std::call_once(lds_once, [] {  // filter slices + counter windows: beyond what a kernel may ask for by default
-         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_escapes_sliced<1>), hipFuncAttributeMaxDynamicSharedMemorySize, escapeLdsBytes<1>());
-         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_escapes_sliced<2>), hipFuncAttributeMaxDynamicSharedMemorySize, escapeLdsBytes<2>());
-         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_escapes_sliced<4>), hipFuncAttributeMaxDynamicSharedMemorySize, escapeLdsBytes<4>());
-         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan_escapes_sliced<8>), hipFuncAttributeMaxDynamicSharedMemorySize, escapeLdsBytes<8>());
-      });
       const uint32_t per_block = q_count <= 1 ? 1 : (q_count <= 2 ? 2 : (q_count <= 4 ? 4 : 8));  // filters per pass over the keys
-      // a block's share of a slice's keys: whole granules, about five shares to each of the 512 places of the chip (the slices
-      // differ in their keys, and a share's time in how its keys lie), at most ESCAPE_GRANULES_PER_BLOCK
       const uint32_t passes = (q_count + per_block - 1) / per_block;
-      const uint64_t granules = (total_keys + ESCAPE_GRANULE_KEYS - 1) / ESCAPE_GRANULE_KEYS * passes;
-      const uint32_t block_granules = static_cast<uint32_t>(std::min<uint64_t>(ESCAPE_GRANULES_PER_BLOCK, std::max<uint64_t>(1, granules / 1280)));  // (flat between 640 and 2 560: profiles/r03_notes.md)
-      const uint32_t block_keys = block_granules * ESCAPE_GRANULE_KEYS;
-      sliced.block_keys = block_keys;
-      sliced.n_ranges = n_sliced;
-      uint32_t blocks = 0;  // every range as many per slice as its slice with the most keys needs
-      for (uint32_t k = 0; k < n_sliced; ++k) {
-         sliced.ranges[k].first_block = blocks;
-         sliced.ranges[k].blocks_per_slice = std::max<uint32_t>(1, (most_keys[k] + block_keys - 1) / block_keys);
-         blocks += sliced.ranges[k].blocks_per_slice * sliced.n_slices;
+      // The items of the launch — every range as many per slice as its slice with the most keys needs, the never-pruned ranges
+      // first —, their size and the blocks that walk them: escape_item_plan.h.  The ranges go to the kernel in the items' order.
+      const int knob = g_tune_escape_blocks.load();
+      uint32_t places = 0, walk_places = 0;
+      HIP_TRY(escapePlaces(per_block, false, &places));
+      if (knob != 0) {  // (the walking instantiation: its own attribute, and its own places where the knob asks for resident blocks)
+         HIP_TRY(escapePlaces(per_block, true, knob < 0 ? &places : &walk_places));
       }
-      const dim3 grid(blocks, 1, passes);
+      const EscapeItemPlan plan = planEscapeItems(shapes.data(), n_sliced, sliced.n_slices, passes, places, knob);
+      if (!plan.ok) {
+         return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "scanEscapes: the launch has more items than the escape kernel numbers");
+      }
+      sliced.block_keys = plan.block_keys;
+      sliced.n_ranges = n_sliced;
+      sliced.n_items = plan.n_items;
+      std::array<EscapeSliceArgs::Range, ESCAPE_MAX_RANGES> as_added{};
+      std::copy_n(sliced.ranges, n_sliced, as_added.begin());
+      for (uint32_t k = 0; k < n_sliced; ++k) {
+         sliced.ranges[k] = as_added[plan.order[k]];
+         sliced.ranges[k].first_item = plan.first_item[k];
+         sliced.ranges[k].items_per_slice = plan.items_per_slice[k];
+      }
+      g_last_escape_items = plan.n_items;
+      const dim3 grid(plan.grid, 1, passes);
       char name[64];
       bool bounds = false;  // a launch that may skip granules says so in the timing log (", pruning" behind the kernel's name)
       for (uint32_t k = 0; k < n_sliced; ++k) {
          bounds = bounds || sliced.ranges[k].heaviest != nullptr;
       }
       std::snprintf(name, sizeof(name), "k_scan_escapes_sliced<%u>%s%s", per_block, bounds ? ", pruning" : "", end_entries ? ", ends" : "");
-      // bytes: the keys and gap events (4 each) once per pass of `per_block` filters, plus a 16 KiB filter slice per block and filter
+      // bytes: the keys and gap events (4 each) once per pass of `per_block` filters, plus a 16 KiB filter slice per ITEM and filter
+      // (what one block per item reads: the figure stays comparable whatever the grid); blocks: the grid as launched
       ScanLaunchTiming* timing = startLaunchTiming(
-         name, 0, total_keys * sizeof(uint32_t) * grid.z + static_cast<uint64_t>(grid.x) * q_count * ESCAPE_SLICE_WORDS32 * sizeof(uint32_t), q_count,
+         name, 0, total_keys * sizeof(uint32_t) * grid.z + static_cast<uint64_t>(plan.n_items) * q_count * ESCAPE_SLICE_WORDS32 * sizeof(uint32_t), q_count,
          grid.x * grid.z, hip_stream
       );
-      switch (per_block) {
-         case 1: k_scan_escapes_sliced<1><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<1>(), hip_stream>>>(sliced, q_count); break;
-         case 2: k_scan_escapes_sliced<2><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<2>(), hip_stream>>>(sliced, q_count); break;
-         case 4: k_scan_escapes_sliced<4><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<4>(), hip_stream>>>(sliced, q_count); break;
-         default: k_scan_escapes_sliced<8><<<grid, ESCAPE_SLICE_THREADS, escapeLdsBytes<8>(), hip_stream>>>(sliced, q_count); break;
+      if (plan.grid < plan.n_items) {
+         launchEscapes<true>(per_block, grid, hip_stream, sliced, q_count);
+      } else {
+         launchEscapes<false>(per_block, grid, hip_stream, sliced, q_count);
       }
       HIP_TRY(hipGetLastError());
       finishLaunchTiming(timing, hip_stream);
       n_sliced = 0;
-      most_keys.fill(0);
+      shapes.fill(EscapeEntryShape{});
       total_keys = 0;
       end_entries = false;
       return SILO_GPU_OK;
@@ -627,8 +752,10 @@ int scanEscapes(
       for (uint32_t slice = 0; slice < n_slices; ++slice) {
          const uint32_t n = stream.slice_first[slice * stride + range.pos_end] - stream.slice_first[slice * stride + key_from];
          total_keys += n;
-         most_keys[n_sliced] = std::max(most_keys[n_sliced], n + ESCAPE_GRANULE_KEYS - 1u);  // (blocks start at a granule boundary)
+         shapes[n_sliced].keys += n;
+         shapes[n_sliced].most_keys = std::max(shapes[n_sliced].most_keys, n + ESCAPE_GRANULE_KEYS - 1u);  // (items start at a granule boundary)
       }
+      shapes[n_sliced].prunable = heaviest != nullptr;
       ++n_sliced;
       return SILO_GPU_OK;
    };

@@ -38,6 +38,7 @@ extern std::atomic<int> g_tune_gap_events;      // < 0: scans of derived symbols
 extern std::atomic<int> g_tune_prune_keys;      // silo_gpu_mutations_scan_ranges_min_proportion: < 0 skips nothing, 0 granules of escape keys and one-hot rows, 1 keys only (ScanPruning, scan_internal.h)
 extern std::atomic<int> g_tune_end_runs;        // < 0: a Mutations scan reads the covered rows of the gap symbol instead of counting its end runs (DerivedPlan::end_runs)
 extern std::atomic<int> g_tune_fused_select;    // < 0: silo_gpu_mutations_scan_select always clears, scans and selects in launches of their own (canFuseSelect, silo_gpu_scan.hip)
+extern std::atomic<int> g_tune_escape_blocks;   // blocks of a launch of k_scan_escapes_sliced: 0 one per item, < 0 as many as the chip holds, n > 0 min(n, items) (escape_item_plan.h)
 extern std::atomic<int> g_tune_side_stream;     // the side passes of a scan: see forkSidePasses (silo_gpu_scan.hip)
 extern std::atomic<int> g_tune_scan_timing;     // 1: HIP events around every launch of a scan (silo_gpu_scan_timings)
 extern std::atomic<int> g_tune_missing_runs;    // < 0: finalize keeps the plane of the missing symbol instead of turning it into runs

@@ -105,7 +105,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_malloc", "silo_gpu_memcpy_d2h", "silo_gpu_memcpy_h2d", "silo_gpu_stream_synchronize", "silo_gpu_stream_create", "silo_gpu_set_device", "silo_gpu_stream_destroy", "silo_gpu_store_plane",
     "silo_gpu_store_sparse_plane", "silo_gpu_filter_eval", "silo_gpu_filter_eval_batch", "silo_gpu_popcount", "silo_gpu_mutations_scan", "silo_gpu_mutations_scan_batch", "silo_gpu_mutations_scan_ranges", "silo_gpu_mutations_grouped", "silo_gpu_store_scan_planes", "silo_gpu_store_scan_escapes", "silo_gpu_store_scan_overflow_keys", "silo_gpu_store_scan_rows", "silo_gpu_store_scan_runs", "silo_gpu_row_slot_create", "silo_gpu_row_slot_destroy", "silo_gpu_mutations_select_to_slot", "silo_gpu_row_slot_wait", "silo_gpu_store_scan_sparse_keys", "silo_gpu_store_finalize_seqstore", "silo_gpu_store_build_pass", "silo_gpu_store_build_mode", "silo_gpu_store_memory_info", "silo_gpu_store_import_position", "silo_gpu_store_import_missing_rows",
     "silo_gpu_memset_async", "silo_gpu_event_create", "silo_gpu_event_record", "silo_gpu_event_elapsed_ms",
-    "silo_gpu_event_destroy", "silo_gpu_event_synchronize", "silo_gpu_host_alloc", "silo_gpu_host_free", "silo_gpu_memcpy_d2h_async", "silo_gpu_mutations_select", "silo_gpu_upload_bytes", "silo_gpu_upload_column", "silo_gpu_bitset_from_compare", "silo_gpu_group_count", "silo_gpu_group_count_hashed", "silo_gpu_reconstruct_sequences", "silo_gpu_bitset_from_pairs", "silo_gpu_count_pairs", "silo_gpu_count_slot_create", "silo_gpu_count_slot_destroy", "silo_gpu_filter_eval_count", "silo_gpu_count_slot_wait", "silo_gpu_tune", "silo_gpu_last_scan_kernel", "silo_gpu_scan_timings", "silo_gpu_stream_read_probe", "silo_gpu_last_error",
+    "silo_gpu_event_destroy", "silo_gpu_event_synchronize", "silo_gpu_host_alloc", "silo_gpu_host_free", "silo_gpu_memcpy_d2h_async", "silo_gpu_mutations_select", "silo_gpu_upload_bytes", "silo_gpu_upload_column", "silo_gpu_bitset_from_compare", "silo_gpu_group_count", "silo_gpu_group_count_hashed", "silo_gpu_reconstruct_sequences", "silo_gpu_bitset_from_pairs", "silo_gpu_count_pairs", "silo_gpu_count_slot_create", "silo_gpu_count_slot_destroy", "silo_gpu_filter_eval_count", "silo_gpu_count_slot_wait", "silo_gpu_tune", "silo_gpu_last_scan_kernel", "silo_gpu_last_escape_items", "silo_gpu_scan_timings", "silo_gpu_stream_read_probe", "silo_gpu_last_error",
     "silo_gpu_comm_unique_id", "silo_gpu_comm_create", "silo_gpu_comm_destroy", "silo_gpu_comm_rank", "silo_gpu_comm_world",
     "silo_gpu_allreduce_counts", "silo_gpu_broadcast_bytes",
     "silo_gpu_mutations_scan_select",
@@ -268,6 +268,8 @@ def load_library():
     lib.silo_gpu_event_destroy.restype = None
     lib.silo_gpu_tune.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.silo_gpu_last_scan_kernel.restype = ctypes.c_char_p
+    lib.silo_gpu_last_escape_items.argtypes = []
+    lib.silo_gpu_last_escape_items.restype = ctypes.c_uint32
     lib.silo_gpu_store_build_pass.argtypes = [vp, ctypes.c_uint32, ctypes.c_int]
     lib.silo_gpu_store_build_pass.restype = ctypes.c_int
     lib.silo_gpu_store_build_mode.argtypes = [vp, ctypes.c_uint32]
