@@ -98,8 +98,4 @@ inline int checkSelection(
    return SILO_GPU_OK;
 }
 
-inline uint32_t blocksOfWords(uint32_t row_words) {
-   return row_words / WORDS_PER_BLOCK + (row_words % WORDS_PER_BLOCK != 0 ? 1u : 0u);
-}
-
 }  // namespace silo_gpu_distinct_table

@@ -76,4 +76,20 @@ class DeviceArray {
    T* ptr_ = nullptr;
 };
 
+/// `bytes` rounded up to the 256-byte alignment of the parts of a scratch buffer.
+inline size_t align256(size_t bytes) {
+   return (bytes + 255u) / 256u * 256u;
+}
+
+/// The blocks of `threads` threads of a grid-stride pass with a thread per item: one thread each up to 4 096 blocks.
+inline uint32_t strideBlocks(uint32_t items, uint32_t threads) {
+   const uint32_t blocks = (items + threads - 1u) / threads;
+   return blocks < 4096u ? blocks : 4096u;
+}
+
+/// The blocks of a pass with a wave per row word, `words_per_block` waves to a block.
+inline uint32_t blocksOfWords(uint32_t row_words, uint32_t words_per_block) {
+   return row_words / words_per_block + (row_words % words_per_block != 0 ? 1u : 0u);
+}
+
 }  // namespace silo_gpu_detail

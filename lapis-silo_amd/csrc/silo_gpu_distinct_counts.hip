@@ -265,7 +265,7 @@ __global__ __launch_bounds__(THREADS) void k_keys_gather(
 }
 
 uint32_t walkBlocks(uint32_t row_words) {
-   return std::min(blocksOfWords(row_words), MAX_WALK_BLOCKS);
+   return std::min(blocksOfWords(row_words, WORDS_PER_BLOCK), MAX_WALK_BLOCKS);
 }
 
 }  // namespace

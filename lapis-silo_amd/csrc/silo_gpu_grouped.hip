@@ -396,10 +396,6 @@ __global__ __launch_bounds__(POSITION_THREADS) void k_grouped_filter_counts(cons
    }
 }
 
-size_t align256(size_t bytes) {
-   return (bytes + 255u) / 256u * 256u;
-}
-
 /// The ranges in order of their start (`order`: request indices; a range's group is its request index); they must be disjoint
 /// with both ends inclusive.  Returns what is wrong with them, nullptr if nothing.
 const char* orderRanges(const uint32_t* range_bounds, uint32_t n_ranges, std::vector<uint32_t>& order) {

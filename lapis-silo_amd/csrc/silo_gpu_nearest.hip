@@ -252,14 +252,6 @@ __global__ __launch_bounds__(256) void k_query_sparse_keys(const QueryArgs args)
    }
 }
 
-size_t align256(size_t bytes) {
-   return (bytes + 255u) / 256u * 256u;
-}
-
-uint32_t strideBlocks(uint32_t items) {
-   return std::min<uint32_t>((items + 255u) / 256u, 4096u);
-}
-
 // ---- the k smallest -------------------------------------------------------------------------------------
 constexpr uint32_t DIGIT_BITS = 12;
 constexpr uint32_t DIGIT_BINS = 1u << DIGIT_BITS;  // 16 KiB of LDS
@@ -564,16 +556,16 @@ int silo_gpu_query_distances(
       HIP_TRY(hipGetLastError());
    }
    if (args.n_escapes != 0) {
-      k_query_escapes<<<strideBlocks(args.n_escapes), 256, 0, hip_stream>>>(args);
+      k_query_escapes<<<strideBlocks(args.n_escapes, 256u), 256, 0, hip_stream>>>(args);
       HIP_TRY(hipGetLastError());
    }
    if (t_pref_q[P] != 0) {  // only derived positions have rows to take back
       if (dev.kind[dev.missing_symbol] == PLANE_RUNS && dev.n_missing_runs != 0) {
-         k_query_missing_runs<<<strideBlocks(dev.n_missing_runs), 256, 0, hip_stream>>>(args);
+         k_query_missing_runs<<<strideBlocks(dev.n_missing_runs, 256u), 256, 0, hip_stream>>>(args);
          HIP_TRY(hipGetLastError());
       }
       if (args.n_sparse != 0) {
-         k_query_sparse_keys<<<strideBlocks(args.n_sparse), 256, 0, hip_stream>>>(args);
+         k_query_sparse_keys<<<strideBlocks(args.n_sparse, 256u), 256, 0, hip_stream>>>(args);
          HIP_TRY(hipGetLastError());
       }
    }

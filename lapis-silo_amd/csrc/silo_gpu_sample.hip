@@ -238,10 +238,6 @@ int checkRows(const char* what, const void* state, const void* filter, const voi
    return SILO_GPU_OK;
 }
 
-uint32_t blocksOfWords(uint32_t row_words) {
-   return row_words / WORDS_PER_BLOCK + (row_words % WORDS_PER_BLOCK != 0 ? 1u : 0u);
-}
-
 }  // namespace
 
 extern "C" {
@@ -320,7 +316,7 @@ int silo_gpu_sample_count(
    if (round >= SILO_GPU_SAMPLE_ROUNDS) {
       return fail(SILO_GPU_ERR_INVALID_ARGUMENT, "silo_gpu_sample_count: there are rounds 0 .. 3");
    }
-   k_sample_count<<<std::min(blocksOfWords(row_words), MAX_COUNT_BLOCKS), THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+   k_sample_count<<<std::min(blocksOfWords(row_words, WORDS_PER_BLOCK), MAX_COUNT_BLOCKS), THREADS, 0, static_cast<hipStream_t>(stream)>>>(
       static_cast<uint32_t*>(state_dev), filter_dev, groups_dev, sequence_count, row_words, first_row, round
    );
    HIP_TRY(hipGetLastError());
@@ -343,7 +339,7 @@ int silo_gpu_sample_select(
    if (const int status = checkRows("silo_gpu_sample_select", state_dev, filter_dev, out_bitset_dev, sequence_count, row_words, first_row); status != SILO_GPU_OK) {
       return status;
    }
-   k_sample_select<<<blocksOfWords(row_words), THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+   k_sample_select<<<blocksOfWords(row_words, WORDS_PER_BLOCK), THREADS, 0, static_cast<hipStream_t>(stream)>>>(
       static_cast<const uint32_t*>(state_dev), filter_dev, groups_dev, sequence_count, row_words, first_row, out_bitset_dev
    );
    HIP_TRY(hipGetLastError());
