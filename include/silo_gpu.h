@@ -1156,6 +1156,50 @@ int silo_gpu_cell_count_histogram(
    uint32_t n_bins, uint64_t* bins_dev, void* stream
 );
 
+/* ---- K23: cell counts over position ranges (the filter expression CellCount with positionFrom / positionTo, the action
+ * CellCountByRegion) ----
+ * A region is a range [first, end) of 0-based positions of one sequence store.  value(r, g) is the number of positions p of region g
+ * whose cell of row r has a class (K22's, word for word) whose bit is set in kinds_mask; for the region [0, positions) it is K22's
+ * value(r).  Nothing is kept by the store.
+ * silo_gpu_region_cell_values WRITES values_dev[g * row_words * 64 + r] = value(r, g) for every r < sequence_count and 0 for every
+ *     other r < row_words * 64, for each of the n_ranges regions of `ranges` (HOST memory, uint32 [n_ranges][2] = first, end; read
+ *     before the call returns), for a finalized store in any layout: region g's column is a plain array of 4 bytes per row.  The
+ *     ranges are ascending, pairwise disjoint and non-empty, end <= positions.  It is K22's decomposition with a 0/1 weight in place
+ *     of a class vector: a plane pass with a wave per (row word, region) that walks the region's positions only and stores the
+ *     value once; then a thread per escape key and per sparse key of the ranges' slices of the position-major key lists (the
+ *     slices of all ranges flattened into one index space: one launch each), and a thread per run of the missing symbol that
+ *     visits the regions the run meets with two lookups in a prefix array each — all adding the difference between the weight of
+ *     their symbol and the one the plane pass assumed (32-bit integer atomics: exact, whatever the schedule).  scratch_dev:
+ *     SILO_GPU_REGION_VALUE_SCRATCH_BYTES(positions) bytes, 256-byte aligned, for per-position and per-range tables built on the
+ *     host; uploads them and waits for the stream once, ahead of its launches.
+ *     Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer, a seqstore_id out of range, a store that is not
+ *     finalized, n_ranges == 0 or > SILO_GPU_MAX_REGIONS, a range that is empty, out of order, overlapping or past the end,
+ *     kinds_mask == 0 or > 15.
+ * The two readers take no store, only columns of such values.
+ * silo_gpu_bitset_from_values WRITES every one of the row_words words of out_bitset_dev and nothing behind them, from ONE column:
+ *     bit r = r < sequence_count && at_least <= values_dev[r] <= at_most   (at_least > at_most selects nothing).
+ * silo_gpu_count_values ADDS to counts_dev[c] (uint64 [n_columns], cleared by the caller; partitions and chunks accumulate), for
+ *     each of the n_columns columns of values_dev (uint32 [n_columns][row_words * 64]), the number of rows r < sequence_count whose
+ *     bit in filter_dev is set (NULL: every row; padding bits never count) and bounds[c][0] <= values_dev[c][r] <= bounds[c][1]
+ *     (`bounds`: HOST memory, uint32 [n_columns][2], passed on as kernel arguments).  A block sums its waves' popcounts and adds a
+ *     non-zero sum with one 64-bit integer atomic per column.  n_columns is 1 .. SILO_GPU_MAX_REGIONS.
+ * Both launch on `stream` and return without waiting.  Each fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for a NULL
+ * values, output or bounds pointer, row_words == 0, sequence_count == 0 or > row_words * 64; the count also for n_columns == 0 or
+ * > SILO_GPU_MAX_REGIONS. */
+#define SILO_GPU_MAX_REGIONS 256
+#define SILO_GPU_REGION_VALUE_SCRATCH_BYTES(positions) ((size_t)(positions) * 7u + 8192u)
+int silo_gpu_region_cell_values(
+   const silo_gpu_store* store, uint32_t seqstore_id, const uint32_t* ranges, uint32_t n_ranges, uint32_t kinds_mask, uint32_t* values_dev,
+   void* scratch_dev, void* stream
+);
+int silo_gpu_bitset_from_values(
+   const uint32_t* values_dev, uint32_t row_words, uint32_t sequence_count, uint32_t at_least, uint32_t at_most, uint64_t* out_bitset_dev, void* stream
+);
+int silo_gpu_count_values(
+   const uint32_t* values_dev, uint32_t n_columns, uint32_t row_words, uint32_t sequence_count, const uint64_t* filter_dev, const uint32_t* bounds,
+   uint64_t* counts_dev, void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

@@ -8,7 +8,9 @@
 //   foldEscapes   a thread per escape key
 //   foldRuns      a thread per run [a, e) of the missing symbol: two lookups in a prefix array of those differences
 //   foldSparse    a thread per sparse key (ambiguity code)
-// Which symbol a cell holds — the claim rule — is decided here and nowhere else.  What a symbol is worth comes from a policy `Fold`, a
+// Which symbol a cell holds — the claim rule — is decided here and nowhere else: cellSymbol is what the planes say of one cell, and
+// the region values of K23 (silo_gpu_region_counts.hip), which walk position ranges instead of whole rows, call it too, with
+// fillBaseSymbols and layoutArgsOf for the tables and arguments it reads.  What a symbol is worth comes from a policy `Fold`, a
 // trivially copyable struct passed by value beside the shared arguments:
 //   Value                                           the running value of a row, the entry of the prefix array and the 16 bytes stored
 //   run_prefix                                      const Value*, [P + 1]: set by foldRows
@@ -71,9 +73,44 @@ __device__ __forceinline__ void fillSymbolOfScan(uint8_t* s_symbol_of_scan, cons
    __syncthreads();
 }
 
-/// grid = row_words / FOLD_WORDS_PER_BLOCK rounded up.  The plane words of a position are the same for the whole wave: where all of
-/// them are 0 — nearly always at a position that derives its symbol — every lane holds the position's base symbol and the
-/// per-lane decode is skipped.
+/// What the planes say the cell of row `word * 64 + lane` at `position` holds — the claim rule of the plane pass: the lane's code
+/// at the position (code planes, one-hot rows) selects the symbol, an open cell is the position's base symbol, and an extra plane
+/// that has the row's bit overrides both.  The plane words of a position are the same for the whole wave: where all of them are
+/// 0 — nearly always at a position that derives its symbol — every lane holds the base symbol and the per-lane decode is skipped.
+/// `s_symbol_of_scan` is fillSymbolOfScan's table; `has_extra` is args.n_extra != 0 && args.dev.extra != nullptr.
+__device__ __forceinline__ uint32_t cellSymbol(
+   const LayoutArgs& args, const uint8_t* s_symbol_of_scan, uint32_t position, uint32_t word, uint32_t lane, bool has_extra
+) {
+   const uint32_t row_words = args.dev.row_words;
+   const PositionLayout layout = layoutOf(args.dev, position);
+   uint32_t code = 0;
+   uint64_t any = 0;
+   for (uint32_t plane = 0; plane < layout.bits; ++plane) {
+      const uint64_t plane_word = layout.rows[static_cast<size_t>(plane) * row_words + word];
+      any |= plane_word;
+      const uint32_t set = static_cast<uint32_t>((plane_word >> lane) & 1ull);
+      code = layout.one_hot ? (set != 0 ? plane + 1u : code) : (code | (set << plane));
+   }
+   uint32_t symbol = args.base_symbol[position];
+   if (any != 0 && code != 0) {
+      const uint32_t scan_index = layout.identity ? code - 1u : (code < CODE_MAP_STRIDE ? layout.map[code] : NO_SCAN_SYMBOL);
+      if (scan_index < args.dev.n_scan && scan_index < SCAN_SLOTS) {
+         const uint32_t coded = s_symbol_of_scan[scan_index];
+         symbol = coded != NO_SCAN_SYMBOL ? coded : symbol;
+      }
+   }
+   if (has_extra) {
+      for (uint32_t e = 0; e < args.n_extra; ++e) {
+         const uint32_t extra_symbol = args.extra_symbols[e];
+         if (((planePtr(args.dev, position, extra_symbol)[word] >> lane) & 1ull) != 0) {
+            symbol = extra_symbol;
+         }
+      }
+   }
+   return symbol;
+}
+
+/// grid = row_words / FOLD_WORDS_PER_BLOCK rounded up: a wave per row word, a lane per row, all positions.
 template <typename Fold>
 __device__ __forceinline__ void foldPlanes(const LayoutArgs& args, const Fold& fold) {
    __shared__ uint8_t s_symbol_of_scan[SCAN_SLOTS];
@@ -84,36 +121,10 @@ __device__ __forceinline__ void foldPlanes(const LayoutArgs& args, const Fold& f
       return;
    }
    const uint32_t lane = threadIdx.x & 63u;
-   const uint32_t n_scan = args.dev.n_scan;
    const bool has_extra = args.n_extra != 0 && args.dev.extra != nullptr;
    typename Fold::Value value = Fold::zero();
    for (uint32_t position = 0; position < args.dev.positions; ++position) {
-      const PositionLayout layout = layoutOf(args.dev, position);
-      uint32_t code = 0;
-      uint64_t any = 0;
-      for (uint32_t plane = 0; plane < layout.bits; ++plane) {
-         const uint64_t plane_word = layout.rows[static_cast<size_t>(plane) * row_words + word];
-         any |= plane_word;
-         const uint32_t set = static_cast<uint32_t>((plane_word >> lane) & 1ull);
-         code = layout.one_hot ? (set != 0 ? plane + 1u : code) : (code | (set << plane));
-      }
-      uint32_t symbol = args.base_symbol[position];
-      if (any != 0 && code != 0) {
-         const uint32_t scan_index = layout.identity ? code - 1u : (code < CODE_MAP_STRIDE ? layout.map[code] : NO_SCAN_SYMBOL);
-         if (scan_index < n_scan && scan_index < SCAN_SLOTS) {
-            const uint32_t coded = s_symbol_of_scan[scan_index];
-            symbol = coded != NO_SCAN_SYMBOL ? coded : symbol;
-         }
-      }
-      if (has_extra) {
-         for (uint32_t e = 0; e < args.n_extra; ++e) {
-            const uint32_t extra_symbol = args.extra_symbols[e];
-            if (((planePtr(args.dev, position, extra_symbol)[word] >> lane) & 1ull) != 0) {
-               symbol = extra_symbol;
-            }
-         }
-      }
-      fold.add(value, position, symbol);
+      fold.add(value, position, cellSymbol(args, s_symbol_of_scan, position, word, lane, has_extra));
    }
    const uint64_t row = static_cast<uint64_t>(word) * 64u + lane;
    fold.store(row, row < args.sequence_count ? value : Fold::zero());
@@ -171,6 +182,54 @@ struct FoldKernels {
    void (*sparse)(LayoutArgs, Fold);
 };
 
+/// Whether the finalized store has a code map, and with it derived symbols and escape keys.
+inline bool hasCodeMap(const SeqStoreHost& seqstore) {
+   return seqstore.dev.code_map != nullptr && !seqstore.layout.code_map.empty();
+}
+
+/// What the plane pass takes an open cell of each position for, into t_base[P]: the position's derived symbol, or NO_SYMBOL.
+inline void fillBaseSymbols(const SeqStoreHost& seqstore, uint8_t* t_base) {
+   const SeqStoreDev& dev = seqstore.dev;
+   uint8_t symbol_of_scan[SCAN_SLOTS];
+   std::fill(symbol_of_scan, symbol_of_scan + SCAN_SLOTS, NO_SCAN_SYMBOL);
+   for (uint32_t symbol = 0; symbol < dev.n_symbols; ++symbol) {
+      if (dev.kind[symbol] == PLANE_SCAN && dev.index[symbol] < SCAN_SLOTS) {
+         symbol_of_scan[dev.index[symbol]] = static_cast<uint8_t>(symbol);
+      }
+   }
+   const bool has_map = hasCodeMap(seqstore);
+   for (uint32_t p = 0; p < dev.positions; ++p) {
+      uint32_t base = NO_SYMBOL;
+      if (has_map) {
+         const uint8_t* map = seqstore.layout.code_map.data() + static_cast<size_t>(p) * CODE_MAP_STRIDE;
+         if ((map[0] & LAYOUT_IMPLICIT) != 0 && map[IMPLICIT_SLOT] < SCAN_SLOTS && symbol_of_scan[map[IMPLICIT_SLOT]] != NO_SCAN_SYMBOL) {
+            base = symbol_of_scan[map[IMPLICIT_SLOT]];
+         }
+      }
+      t_base[p] = static_cast<uint8_t>(base);
+   }
+}
+
+/// The shared arguments of the passes over `seqstore`, with the uploaded base symbols at `base_symbol_dev`.
+inline LayoutArgs layoutArgsOf(const silo_gpu_store* store, const SeqStoreHost& seqstore, const uint8_t* base_symbol_dev) {
+   const SeqStoreDev& dev = seqstore.dev;
+   LayoutArgs args{};
+   args.dev = dev;
+   args.base_symbol = base_symbol_dev;
+   args.sparse_keys = seqstore.d_sparse.get();
+   args.n_sparse = seqstore.d_sparse.get() != nullptr ? static_cast<uint32_t>(seqstore.sparse_sorted.size()) : 0u;
+   args.n_escapes = hasCodeMap(seqstore) && dev.escapes != nullptr && !seqstore.layout.escape_first.empty() ? seqstore.layout.escape_first.back() : 0u;
+   args.sequence_count = store->sequence_count;
+   if (dev.extra != nullptr) {
+      for (uint32_t symbol = 0; symbol < dev.n_symbols; ++symbol) {
+         if (dev.kind[symbol] == PLANE_EXTRA && args.n_extra < MAX_EXTRA) {
+            args.extra_symbols[args.n_extra++] = static_cast<uint8_t>(symbol);
+         }
+      }
+   }
+   return args;
+}
+
 /// Builds the two per-position tables — what an open cell of the planes counts as, and the running sums a run of the missing
 /// symbol reads — into `scratch_dev` (256-byte aligned, `scratch_bytes` as the entry documents), uploads them, waits for the stream
 /// once, and launches the passes the store's layout needs on it without waiting.  `seqstore` is finalized and has planes.
@@ -185,14 +244,6 @@ int foldRows(
    HIP_TRY(hipSetDevice(store->device));
    const uint32_t P = dev.positions;
 
-   uint8_t symbol_of_scan[SCAN_SLOTS];
-   std::fill(symbol_of_scan, symbol_of_scan + SCAN_SLOTS, NO_SCAN_SYMBOL);
-   for (uint32_t symbol = 0; symbol < dev.n_symbols; ++symbol) {
-      if (dev.kind[symbol] == PLANE_SCAN && dev.index[symbol] < SCAN_SLOTS) {
-         symbol_of_scan[dev.index[symbol]] = static_cast<uint8_t>(symbol);
-      }
-   }
-   const bool has_map = dev.code_map != nullptr && !seqstore.layout.code_map.empty();
    const size_t base_bytes = align256(P);
    const size_t prefix_bytes = align256((static_cast<size_t>(P) + 1u) * sizeof(Value));
    if (base_bytes + prefix_bytes > scratch_bytes) {
@@ -201,36 +252,16 @@ int foldRows(
    std::vector<uint8_t> tables(base_bytes + prefix_bytes, 0);
    uint8_t* t_base = tables.data();
    auto* t_prefix = reinterpret_cast<Value*>(tables.data() + base_bytes);
+   fillBaseSymbols(seqstore, t_base);
    for (uint32_t p = 0; p < P; ++p) {
-      uint32_t base = NO_SYMBOL;
-      if (has_map) {
-         const uint8_t* map = seqstore.layout.code_map.data() + static_cast<size_t>(p) * CODE_MAP_STRIDE;
-         if ((map[0] & LAYOUT_IMPLICIT) != 0 && map[IMPLICIT_SLOT] < SCAN_SLOTS && symbol_of_scan[map[IMPLICIT_SLOT]] != NO_SCAN_SYMBOL) {
-            base = symbol_of_scan[map[IMPLICIT_SLOT]];
-         }
-      }
-      t_base[p] = static_cast<uint8_t>(base);
-      t_prefix[p + 1u] = fold.nextPrefix(t_prefix[p], p, base, seqstore);
+      t_prefix[p + 1u] = fold.nextPrefix(t_prefix[p], p, t_base[p], seqstore);
    }
    auto* scratch = static_cast<uint8_t*>(scratch_dev);
    HIP_TRY(hipMemcpyAsync(scratch, tables.data(), tables.size(), hipMemcpyHostToDevice, hip_stream));
    HIP_TRY(hipStreamSynchronize(hip_stream));  // `tables` is pageable host memory that leaves with this call
 
-   LayoutArgs args{};
-   args.dev = dev;
-   args.base_symbol = scratch;
+   const LayoutArgs args = layoutArgsOf(store, seqstore, scratch);
    fold.run_prefix = reinterpret_cast<const Value*>(scratch + base_bytes);
-   args.sparse_keys = seqstore.d_sparse.get();
-   args.n_sparse = seqstore.d_sparse.get() != nullptr ? static_cast<uint32_t>(seqstore.sparse_sorted.size()) : 0u;
-   args.n_escapes = has_map && dev.escapes != nullptr && !seqstore.layout.escape_first.empty() ? seqstore.layout.escape_first.back() : 0u;
-   args.sequence_count = store->sequence_count;
-   if (dev.extra != nullptr) {
-      for (uint32_t symbol = 0; symbol < dev.n_symbols; ++symbol) {
-         if (dev.kind[symbol] == PLANE_EXTRA && args.n_extra < MAX_EXTRA) {
-            args.extra_symbols[args.n_extra++] = static_cast<uint8_t>(symbol);
-         }
-      }
-   }
    kernels.planes<<<blocksOfWords(dev.row_words, FOLD_WORDS_PER_BLOCK), FOLD_THREADS, 0, hip_stream>>>(args, fold);
    HIP_TRY(hipGetLastError());
    if (args.n_escapes != 0) {

@@ -18,11 +18,13 @@
 #include <algorithm>
 #include <string>
 
+#include "cell_class.h"
 #include "row_fold.h"
 #include "store_internal.h"
 
 using namespace silo_gpu_detail;
 using namespace silo_gpu_row_fold;
+using namespace silo_gpu_cell_class;
 
 namespace {
 
@@ -32,30 +34,6 @@ constexpr uint32_t KINDS = SILO_GPU_CELL_COUNT_KINDS;
 constexpr uint32_t MAX_BINS = SILO_GPU_MAX_CELL_COUNT_BINS;
 constexpr uint32_t MAX_HISTOGRAM_BLOCKS = 2048;
 static_assert(KINDS == SILO_GPU_DIFFERENCE_STATS && KINDS == 4);
-
-/// The class of a cell in K18's `stats` order; SAME counts nowhere.
-enum CellClass : uint32_t { SUBSTITUTION = 0, DELETION = 1, MISSING = 2, AMBIGUOUS = 3, SAME = 4 };
-constexpr uint32_t GAP_SYMBOL = 0;  // '-' in both alphabets
-
-/// Bit s for every symbol index s that is a valid mutation symbol: -ACGT of "-ACGTRYSWKMBDHVN", and all of
-/// "-ACDEFGHIKLMNPQRSTVWYBZ*X" but B, Z and X (fillCharTable, store_internal.h).
-constexpr uint32_t VALID_NUCLEOTIDES = 0x1Fu;
-constexpr uint32_t VALID_AMINO_ACIDS = 0x1FFFFFu | (1u << 23);
-
-/// The class of the symbol index `symbol` (31, a cell that nothing stored claims: ambiguous) where the reference holds `reference`:
-/// K18's rule on indices.  A reference symbol that is not valid equals no valid symbol.
-__host__ __device__ __forceinline__ uint32_t classOf(uint32_t symbol, uint32_t reference, uint32_t missing, uint32_t valid) {
-   if (symbol == missing) {
-      return MISSING;
-   }
-   if (symbol >= 32u || ((valid >> symbol) & 1u) == 0) {
-      return AMBIGUOUS;
-   }
-   if (symbol == reference) {
-      return SAME;
-   }
-   return symbol == GAP_SYMBOL ? DELETION : SUBSTITUTION;
-}
 
 /// The policy of the layout pass (row_fold.h): a row's value is the sum of its cells' class vectors, mod 2^32 in each of the four.
 struct CellCountFold {

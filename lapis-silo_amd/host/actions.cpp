@@ -882,6 +882,7 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"AminoAcidMutationsPerSequence", parseMutationsPerSequence<AminoAcid>},
    {"DistinctSequenceCounts", parseDistinctSequenceCounts},
    {"CellCountDistribution", parseCellCountDistribution},
+   {"CellCountByRegion", parseCellCountByRegion},
 };
 
 }  // namespace

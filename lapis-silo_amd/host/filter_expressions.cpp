@@ -965,7 +965,11 @@ uint32_t parseCellKinds(const json::Value& cells, const std::string& complaint) 
 
 std::string CellCount::toString(const Database& /*database*/) const {
    const std::string sequence_string = sequence_name.has_value() ? "The sequence '" + sequence_name.value() + "'" : "The default nucleotide sequence";
-   return sequence_string + " has between " + std::to_string(at_least) + " and " + std::to_string(at_most) + " cells that are " + cellKindsString(kinds_mask);
+   std::string text = sequence_string + " has between " + std::to_string(at_least) + " and " + std::to_string(at_most) + " cells that are " + cellKindsString(kinds_mask);
+   if (position_from.has_value() || position_to.has_value()) {
+      text += " in the positions " + std::to_string(position_from.value_or(1)) + " to " + (position_to.has_value() ? std::to_string(*position_to) : "the end");
+   }
+   return text;
 }
 
 std::unique_ptr<Operator> CellCount::compile(const Database& database, const DatabasePartition& database_partition, AmbiguityMode /*mode*/) const {
@@ -976,15 +980,32 @@ std::unique_ptr<Operator> CellCount::compile(const Database& database, const Dat
    CHECK_SILO_QUERY(
       database.shard_world <= 1, "CellCount is not supported on a sharded database yet: the table of cell counts of a position shard is partial"
    )
+   // the region [first, end), 0-based: the whole sequence unless the expression names positions
+   const uint32_t first = position_from.value_or(1) - 1u;
+   const uint32_t end = position_to.value_or(counted.positions);
+   CHECK_SILO_QUERY(
+      end <= counted.positions, "CellCount: the field positionTo: " + std::to_string(end) + " is past the end of the sequence '" + counted.name + "' (" +
+                                   std::to_string(counted.positions) + " positions)"
+   )
+   CHECK_SILO_QUERY(
+      first < end || !position_from.has_value(), "CellCount: the field positionFrom: " + std::to_string(first + 1u) + " is past the end of the sequence '" +
+                                                    counted.name + "' (" + std::to_string(counted.positions) + " positions)"
+   )
+   const uint32_t length = end - first;
    // what the number of positions decides, without the store (whose table of counts such a query never builds): a row has
-   // `positions` cells, so its value lies in [0, positions] whatever the kinds
-   if (database_partition.sequence_count == 0 || at_least > at_most || at_least > counted.positions) {
+   // `length` cells there, so its value lies in [0, length] whatever the kinds
+   if (database_partition.sequence_count == 0 || at_least > at_most || at_least > length) {
       return std::make_unique<operators::Empty>(rows);
    }
-   if (at_least == 0 && at_most >= counted.positions) {
+   if (at_least == 0 && at_most >= length) {
       return std::make_unique<operators::Full>(rows);
    }
-   return std::make_unique<operators::CellCountSelection>(counted.seqstoreOf(database_partition), kinds_mask, at_least, at_most, rows);
+   if (length == counted.positions) {
+      return std::make_unique<operators::CellCountSelection>(counted.seqstoreOf(database_partition), kinds_mask, at_least, at_most, rows);
+   }
+   return std::make_unique<operators::RegionCellCountSelection>(
+      counted.seqstoreOf(database_partition), counted.positions, first, end, kinds_mask, at_least, at_most, rows
+   );
 }
 
 namespace {
@@ -1013,7 +1034,23 @@ std::unique_ptr<Expression> parseCellCount(const json::Value& json) {
          bounds[k] = bound.as_uint32();
       }
    }
-   return std::make_unique<CellCount>(std::move(sequence_name), kinds_mask, bounds[0], bounds[1]);
+   std::optional<uint32_t> region[2];
+   const char* const region_fields[2] = {"positionFrom", "positionTo"};
+   for (size_t k = 0; k < 2; ++k) {
+      if (json.contains(region_fields[k])) {
+         const json::Value& position = json[region_fields[k]];
+         CHECK_SILO_QUERY(
+            position.is_number_unsigned() && position.as_int64() >= 1 && position.as_int64() <= static_cast<int64_t>(UINT32_MAX),
+            "The field '" + std::string(region_fields[k]) + "' in a CellCount expression, if present, needs to be an integer from 1 to 4294967295"
+         )
+         region[k] = position.as_uint32();
+      }
+   }
+   CHECK_SILO_QUERY(
+      !region[0].has_value() || !region[1].has_value() || *region[0] <= *region[1],
+      "The field 'positionFrom' in a CellCount expression may not be greater than 'positionTo'"
+   )
+   return std::make_unique<CellCount>(std::move(sequence_name), kinds_mask, bounds[0], bounds[1], region[0], region[1]);
 }
 
 }  // namespace

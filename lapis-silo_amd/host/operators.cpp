@@ -704,6 +704,36 @@ uint32_t CellCountSelection::lower(ProgramBuilder& builder) const {
    return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
 }
 
+// ---- RegionCellCountSelection (no counterpart in the reference) -----------------------------------------
+std::string RegionCellCountSelection::toString() const {
+   return "RegionCellCountSelection[" + std::to_string(at_least) + " <= " + filter_expressions::cellKindsString(kinds_mask) + " in " +
+          std::to_string(first + 1u) + "-" + std::to_string(end) + " <= " + std::to_string(at_most) + "]";
+}
+std::unique_ptr<Operator> RegionCellCountSelection::copy() const {
+   return std::make_unique<RegionCellCountSelection>(seqstore_id, positions, first, end, kinds_mask, at_least, at_most, rows);
+}
+std::unique_ptr<Operator> RegionCellCountSelection::negate() const {
+   return std::make_unique<Complement>(this->copy(), rows);
+}
+uint32_t RegionCellCountSelection::lower(ProgramBuilder& builder) const {
+   // 4 bytes per row that never leave the device: the column is written by K23's first entry and read once by the kernel that
+   // makes the bitset, all on the query's stream ahead of the fused program; the three buffers live as long as the builder, and
+   // the store keeps nothing of the region
+   const DatabasePartition& partition = *rows.partition;
+   const uint32_t row_words = partition.rowWords();
+   auto* column = static_cast<uint32_t*>(builder.temporaryBuffer(static_cast<size_t>(row_words) * 64u * sizeof(uint32_t)));
+   void* scratch = builder.temporaryBuffer(SILO_GPU_REGION_VALUE_SCRATCH_BYTES(positions));
+   uint64_t* bitset = builder.temporaryBitset();
+   const uint32_t range[2] = {first, end};
+   checkGpu(
+      silo_gpu_region_cell_values(partition.store, seqstore_id, range, 1, kinds_mask, column, scratch, queryStream()), "silo_gpu_region_cell_values"
+   );
+   checkGpu(
+      silo_gpu_bitset_from_values(column, row_words, partition.sequence_count, at_least, at_most, bitset, queryStream()), "silo_gpu_bitset_from_values"
+   );
+   return SILO_GPU_LEAF_OPERAND + builder.leaf(bitset);
+}
+
 // ---- SampleSelection (no counterpart in the reference) --------------------------------------------------
 std::string SampleSelection::toString() const {
    return "SampleSelection[" + std::to_string(size) + " rows" + (range_bounds.empty() ? "" : " of each of " + std::to_string(range_bounds.size() / 2) + " date ranges") +

@@ -197,7 +197,7 @@ class ProgramBuilder {
 namespace operators {
 
 enum Type {
-   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION, SAMPLE_SELECTION, DISTINCT_SELECTION, CELL_COUNT_SELECTION
+   EMPTY, FULL, INDEX_SCAN, INTERSECTION, COMPLEMENT, RANGE_SELECTION, SELECTION, BITMAP_SELECTION, THRESHOLD, UNION, BITMAP_PRODUCER, DISTANCE_SELECTION, SAMPLE_SELECTION, DISTINCT_SELECTION, CELL_COUNT_SELECTION, REGION_CELL_COUNT_SELECTION
 };
 
 /// What lowering a sub-tree into a program takes at most.  `slots`: the slots that are live at once while it is lowered, its
@@ -523,6 +523,30 @@ class CellCountSelection : public Operator {
    uint32_t at_most;
 };
 
+/// The rows whose number of cells of the kinds of `kinds_mask` at the positions [first, end) (0-based) lies in [at_least, at_most]:
+/// the filter expression CellCount with positionFrom / positionTo (K23; no counterpart in the reference).  lower() computes the
+/// region's column of values (silo_gpu_region_cell_values, one range) and turns it into a row bitset (silo_gpu_bitset_from_values)
+/// on the lowering thread's stream ahead of the fused program, which reads the bitset as a leaf.  The column, the scratch and the
+/// bitset belong to the builder, like DistanceSelection's buffers; the store keeps nothing.
+class RegionCellCountSelection : public Operator {
+  public:
+   RegionCellCountSelection(uint32_t seqstore_id, uint32_t positions, uint32_t first, uint32_t end, uint32_t kinds_mask, uint32_t at_least, uint32_t at_most, RowSpace rows)
+       : Operator(rows), seqstore_id(seqstore_id), positions(positions), first(first), end(end), kinds_mask(kinds_mask), at_least(at_least), at_most(at_most) {}
+   Type type() const override { return REGION_CELL_COUNT_SELECTION; }
+   std::string toString() const override;
+   std::unique_ptr<Operator> copy() const override;
+   std::unique_ptr<Operator> negate() const override;
+   uint32_t lower(ProgramBuilder& builder) const override;
+   Cost cost() const override { return {1, 1}; }
+
+   uint32_t seqstore_id;
+   uint32_t positions;   // of the sequence: sizes the scratch
+   uint32_t first, end;  // 0-based, half-open
+   uint32_t kinds_mask;  // SILO_GPU_CELL_COUNT_* bits
+   uint32_t at_least;
+   uint32_t at_most;
+};
+
 class Threshold : public Operator {
   public:
    Threshold(OperatorVector&& non_negated_children, OperatorVector&& negated_children, uint32_t number_of_matchers, bool match_exactly, RowSpace rows);
@@ -741,14 +765,22 @@ struct DistinctSequences : public Expression {
 /// missing, ambiguous against the reference of `sequence_name` (the default nucleotide sequence when absent), the four counts of
 /// MutationsPerSequence over all positions — lies in [at_least, at_most].  An absent bound is 0 / 2^32 - 1.  The parsed expression
 /// holds only what the query text says; compile answers what the number of positions alone decides without touching the store.
+/// With `position_from` / `position_to` (1-based, inclusive; an absent one is 1 / the sequence's length) the cells counted are those
+/// of that range of positions alone (K23); a range that is the whole sequence compiles as if neither were given.
 struct CellCount : public Expression {
-   CellCount(std::optional<std::string> sequence_name, uint32_t kinds_mask, uint32_t at_least, uint32_t at_most)
-       : sequence_name(std::move(sequence_name)), kinds_mask(kinds_mask), at_least(at_least), at_most(at_most) {}
+   CellCount(
+      std::optional<std::string> sequence_name, uint32_t kinds_mask, uint32_t at_least, uint32_t at_most,
+      std::optional<uint32_t> position_from = std::nullopt, std::optional<uint32_t> position_to = std::nullopt
+   )
+       : sequence_name(std::move(sequence_name)), kinds_mask(kinds_mask), at_least(at_least), at_most(at_most), position_from(position_from),
+         position_to(position_to) {}
    SILO_DECLARE_EXPRESSION_METHODS
    std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
    uint32_t kinds_mask;                       // SILO_GPU_CELL_COUNT_* bits
    uint32_t at_least;
    uint32_t at_most;
+   std::optional<uint32_t> position_from;     // 1-based
+   std::optional<uint32_t> position_to;       // 1-based, inclusive
 };
 /// The field `cells` of CellCount and CellCountDistribution: one kind or a non-empty list of kinds without repeats, as a mask of
 /// SILO_GPU_CELL_COUNT_* bits; anything else is a bad request with the message `complaint` (filter_expressions.cpp).
@@ -889,6 +921,8 @@ std::unique_ptr<Action> parseNearestNeighbours(const json::Value& json);
 std::unique_ptr<Action> parseDistinctSequenceCounts(const json::Value& json);
 /// The parser of the histogram of the selection's cell counts (sequence_actions.cpp).
 std::unique_ptr<Action> parseCellCountDistribution(const json::Value& json);
+/// The parser of the per-region counts of the selection (sequence_actions.cpp).
+std::unique_ptr<Action> parseCellCountByRegion(const json::Value& json);
 
 /// Two kinds of field that many action parsers read, with one wording of the complaint (actions.cpp).  An optional field of type
 /// string: none when absent; "<action_name> action: the field <field>, if present, must be of type string".
@@ -1269,6 +1303,35 @@ class CellCountDistribution : public Action {
    static constexpr uint32_t DEFAULT_BINS = 1024;
    CellCountDistribution(std::optional<std::string> sequence_name, uint32_t kinds_mask, uint32_t bin_width, uint32_t max_bins)
        : sequence_name(std::move(sequence_name)), kinds_mask(kinds_mask), bin_width(bin_width), max_bins(max_bins) {}
+};
+
+/// CellCountByRegion (sequence_actions.cpp; no counterpart in the reference): for each of up to 256 named regions of one aligned
+/// sequence, how many of the selected rows have a number of cells of the listed kinds inside the region within the region's bounds
+/// (its own, or else the action's).  One response row {region, positionFrom, positionTo, count, total} per region, in request
+/// order; total is the number of selected rows.  All on the device (K23): the regions are coloured into chunks of pairwise
+/// disjoint regions (colourRegions); per partition with selected rows and per chunk one silo_gpu_region_cell_values and one
+/// silo_gpu_count_values into ONE array of counts, and one download of it.
+class CellCountByRegion : public Action {
+  public:
+   struct Region {
+      std::string name;
+      uint32_t first, end;  // 0-based, half-open
+      uint32_t at_least, at_most;
+   };
+   static constexpr uint32_t REGION_LIMIT = SILO_GPU_MAX_REGIONS;
+   static constexpr size_t REGION_VALUE_BUDGET_BYTES = size_t{256} << 20;  // of columns per chunk, for the largest partition
+   CellCountByRegion(std::optional<std::string> sequence_name, uint32_t kinds_mask, std::vector<Region> regions)
+       : sequence_name(std::move(sequence_name)), kinds_mask(kinds_mask), regions(std::move(regions)) {}
+   /// Chunks of indices into `ranges` ([first, end) each): sorted by start, each region goes into the first chunk in which it
+   /// overlaps none and which has fewer than `max_regions` regions; within a chunk the regions ascend.  max_regions >= 1.
+   static std::vector<std::vector<uint32_t>> colourRegions(const std::vector<std::pair<uint32_t, uint32_t>>& ranges, size_t max_regions);
+
+  private:
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   uint32_t kinds_mask;
+   std::vector<Region> regions;
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
 };
 
 template <typename SymbolType>

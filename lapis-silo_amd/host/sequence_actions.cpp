@@ -2,11 +2,14 @@
 //   Fasta                   src/silo/query_engine/actions/fasta.cpp
 //   FastaAligned            src/silo/query_engine/actions/fasta_aligned.cpp
 //   MutationsPerSequence    (not in the reference) FastaAligned's rows as each row's differences from the reference (K18)
+//   CellCountDistribution   (not in the reference) the histogram of the selected rows' cell counts (K22)
+//   CellCountByRegion       (not in the reference) per region of positions, the selected rows whose cell count there is in bounds (K23)
 // and what every action that reads the selected rows' sequences begins with, the distance actions (distance_actions.cpp) among
 // them: selectedRows, selectedCount, the description of an aligned sequence by name (alignedSequence), and the one walk over the
 // selection that uploads a partition's row ids and hands them to the caller's gather (SelectedSequences).
 #include <algorithm>
 #include <cstring>
+#include <numeric>
 #include <type_traits>
 
 #include "query_engine.h"
@@ -563,6 +566,196 @@ std::unique_ptr<Action> parseCellCountDistribution(const json::Value& json) {
       action_name + " action: the fields binWidth and maxBins: their product must not exceed 2147483648, so that every bin's bounds are 32-bit numbers"
    )
    return std::make_unique<CellCountDistribution>(std::move(sequence_name), kinds_mask, bin_width, max_bins);
+}
+
+// ---- CellCountByRegion (no counterpart in the reference) -----------------------------------------------------
+// Per named region of positions, the number of selected rows whose count of cells of the listed kinds inside the region lies within
+// the region's bounds (K23): the amplicon drop-out table of a selection in one request.  Regions may overlap and K23's first entry
+// takes disjoint ranges, so the regions are coloured into chunks of disjoint ones; disjoint chunks walk disjoint positions, so
+// chunking adds launches and not cell work.
+void CellCountByRegion::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"region", "positionFrom", "positionTo", "count"});
+}
+
+std::vector<std::vector<uint32_t>> CellCountByRegion::colourRegions(const std::vector<std::pair<uint32_t, uint32_t>>& ranges, size_t max_regions) {
+   std::vector<uint32_t> by_start(ranges.size());
+   std::iota(by_start.begin(), by_start.end(), 0u);
+   std::stable_sort(by_start.begin(), by_start.end(), [&](uint32_t a, uint32_t b) { return ranges[a].first < ranges[b].first; });
+   // taken by ascending start, a region overlaps none of a chunk exactly if it begins at or behind the end of the chunk's last one
+   std::vector<std::vector<uint32_t>> chunks;
+   for (const uint32_t region : by_start) {
+      auto chunk = std::find_if(chunks.begin(), chunks.end(), [&](const std::vector<uint32_t>& candidate) {
+         return candidate.size() < max_regions && ranges[candidate.back()].second <= ranges[region].first;
+      });
+      if (chunk == chunks.end()) {
+         chunk = chunks.emplace(chunks.end());
+      }
+      chunk->push_back(region);
+   }
+   return chunks;
+}
+
+QueryResult CellCountByRegion::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string action_name = "CellCountByRegion";
+   const AlignedSequence counted =
+      alignedSequence(database, sequence_name, action_name + ": the field sequenceName: Database does not contain a sequence with name: ");
+   requireUnsharded(database, action_name);
+   for (const Region& region : regions) {
+      CHECK_SILO_QUERY(
+         region.end <= counted.positions, action_name + ": the region '" + region.name + "': positionTo " + std::to_string(region.end) +
+                                             " is past the end of the sequence '" + counted.name + "' (" + std::to_string(counted.positions) + " positions)"
+      )
+   }
+   const size_t total_count = selectedCount(database, bitmap_filter);
+   std::vector<uint64_t> counts(regions.size(), 0);
+   if (total_count != 0) {
+      uint32_t largest_row_words = 1;
+      for (const DatabasePartition& partition : database.partitions) {
+         largest_row_words = std::max(largest_row_words, partition.rowWords());
+      }
+      const size_t column_bytes = static_cast<size_t>(largest_row_words) * 64u * sizeof(uint32_t);
+      const size_t chunk_regions = std::clamp<size_t>(REGION_VALUE_BUDGET_BYTES / column_bytes, 1, REGION_LIMIT);
+      std::vector<std::pair<uint32_t, uint32_t>> ranges;
+      for (const Region& region : regions) {
+         ranges.emplace_back(region.first, region.end);
+      }
+      const std::vector<std::vector<uint32_t>> chunks = colourRegions(ranges, chunk_regions);
+      size_t largest_chunk = 1;
+      for (const std::vector<uint32_t>& chunk : chunks) {
+         largest_chunk = std::max(largest_chunk, chunk.size());
+      }
+      // one array of counts in the regions' chunk order, so that a chunk's counts are neighbours: chunk_slot[c] is its first
+      std::vector<size_t> chunk_slot;
+      size_t slots = 0;
+      for (const std::vector<uint32_t>& chunk : chunks) {
+         chunk_slot.push_back(slots);
+         slots += chunk.size();
+      }
+      // nothing in here returns to the pool before the stream has been waited for: the launches write it
+      DevicePool& pool = database.partitions.front().pool;
+      const size_t counts_bytes = slots * sizeof(uint64_t);
+      const DeviceBuffer device_counts = pool.acquire(counts_bytes);
+      const DeviceBuffer device_columns = pool.acquire(largest_chunk * column_bytes);
+      const DeviceBuffer device_scratch = pool.acquire(SILO_GPU_REGION_VALUE_SCRATCH_BYTES(counted.positions));
+      std::vector<uint64_t> chunked_counts(slots, 0);
+      launchAndWait([&] {
+         checkGpu(silo_gpu_memset_async(device_counts.get(), 0, counts_bytes, queryStream()), "silo_gpu_memset_async");
+         for (size_t partition_id = 0; partition_id < database.partitions.size(); ++partition_id) {
+            const DatabasePartition& partition = database.partitions[partition_id];
+            if (partition.sequence_count == 0 || bitmap_filter[partition_id].cardinality() == 0) {
+               continue;
+            }
+            const uint64_t* filter = bitmap_filter[partition_id].isFull() ? nullptr : bitmap_filter[partition_id].bitset();
+            for (size_t c = 0; c < chunks.size(); ++c) {
+               std::vector<uint32_t> chunk_ranges;
+               std::vector<uint32_t> chunk_bounds;
+               for (const uint32_t region : chunks[c]) {
+                  chunk_ranges.insert(chunk_ranges.end(), {regions[region].first, regions[region].end});
+                  chunk_bounds.insert(chunk_bounds.end(), {regions[region].at_least, regions[region].at_most});
+               }
+               const auto n_columns = static_cast<uint32_t>(chunks[c].size());
+               checkGpu(
+                  silo_gpu_region_cell_values(
+                     partition.store, counted.seqstoreOf(partition), chunk_ranges.data(), n_columns, kinds_mask, device_columns.as<uint32_t>(),
+                     device_scratch.get(), queryStream()
+                  ),
+                  "silo_gpu_region_cell_values"
+               );
+               checkGpu(
+                  silo_gpu_count_values(
+                     device_columns.as<uint32_t>(), n_columns, partition.rowWords(), partition.sequence_count, filter, chunk_bounds.data(),
+                     device_counts.as<uint64_t>() + chunk_slot[c], queryStream()
+                  ),
+                  "silo_gpu_count_values"
+               );
+            }
+         }
+         const HostFetch fetch(device_counts.get(), counts_bytes, queryStream());
+         std::memcpy(chunked_counts.data(), fetch.wait(), counts_bytes);
+      });
+      for (size_t c = 0; c < chunks.size(); ++c) {
+         for (size_t k = 0; k < chunks[c].size(); ++k) {
+            counts[chunks[c][k]] = chunked_counts[chunk_slot[c] + k];
+         }
+      }
+   }
+   QueryResult results;
+   for (size_t g = 0; g < regions.size(); ++g) {
+      if (counts[g] > total_count) {
+         throw std::runtime_error(
+            action_name + ": the region '" + regions[g].name + "' counts " + std::to_string(counts[g]) + " rows where the filters select " +
+            std::to_string(total_count)
+         );
+      }
+      QueryResultEntry& entry = results.query_result.emplace_back();
+      entry.fields.emplace("region", regions[g].name);
+      entry.fields.emplace("positionFrom", static_cast<int32_t>(regions[g].first + 1u));
+      entry.fields.emplace("positionTo", static_cast<int32_t>(regions[g].end));
+      entry.fields.emplace("count", static_cast<int32_t>(counts[g]));
+      entry.fields.emplace("total", static_cast<int32_t>(total_count));
+   }
+   return results;
+}
+
+std::unique_ptr<Action> parseCellCountByRegion(const json::Value& json) {
+   const std::string action_name = "CellCountByRegion";
+   std::optional<std::string> sequence_name = optionalStringField(json, "sequenceName", action_name);
+   CHECK_SILO_QUERY(json.contains("cells"), action_name + " action: the field cells is required")
+   const uint32_t kinds_mask = filter_expressions::parseCellKinds(
+      json["cells"], action_name + " action: the field cells must be one of \"substitutions\", \"deletions\", \"missing\", \"ambiguous\" or a non-empty list "
+                                   "of them without repeats"
+   );
+   const std::string bound_form = "an integer from 0 to 4294967295";
+   const std::string position_form = "an integer from 1 to 2147483647";
+   const std::optional<uint32_t> at_least = integerField(json, "atLeast", action_name, false, 0, UINT32_MAX, bound_form);
+   const std::optional<uint32_t> at_most = integerField(json, "atMost", action_name, false, 0, UINT32_MAX, bound_form);
+   const std::string regions_form =
+      action_name + " action: the field regions must be an array of 1 to " + std::to_string(CellCountByRegion::REGION_LIMIT) + " objects";
+   CHECK_SILO_QUERY(json.contains("regions"), action_name + " action: the field regions is required")
+   CHECK_SILO_QUERY(json["regions"].is_array(), regions_form)
+   std::vector<CellCountByRegion::Region> regions;
+   for (const json::Value& item : json["regions"].items()) {
+      CHECK_SILO_QUERY(item.is_object() && regions.size() < CellCountByRegion::REGION_LIMIT, regions_form)
+      CHECK_SILO_QUERY(
+         item.contains("name") && item["name"].is_string(), action_name + " action: every region must have the field name of type string"
+      )
+      const std::string& name = item["name"].as_string();
+      const std::string region_name = action_name + " action: the region '" + name + "'";
+      CHECK_SILO_QUERY(
+         std::none_of(regions.begin(), regions.end(), [&](const CellCountByRegion::Region& other) { return other.name == name; }),
+         region_name + " is listed more than once: the names of the regions must be distinct"
+      )
+      // (integerField words its complaints as "<name> action: the field ...": the region's name stands where the action's would)
+      const std::string region_fields = action_name + " action: the region '" + name + "':";
+      const auto field = [&](std::string_view key, bool required, int64_t minimum, int64_t maximum, const std::string& form) {
+         if (!item.contains(key)) {
+            CHECK_SILO_QUERY(!required, region_fields + " the field " + std::string(key) + " is required")
+            return std::optional<uint32_t>();
+         }
+         const json::Value& value = item[key];
+         CHECK_SILO_QUERY(
+            value.is_number_unsigned() && value.as_int64() >= minimum && value.as_int64() <= maximum,
+            region_fields + " the field " + std::string(key) + (required ? " must be " : ", if present, must be ") + form
+         )
+         return std::optional<uint32_t>(value.as_uint32());
+      };
+      const uint32_t position_from = field("positionFrom", true, 1, INT32_MAX, position_form).value();
+      const uint32_t position_to = field("positionTo", true, 1, INT32_MAX, position_form).value();
+      CHECK_SILO_QUERY(position_from <= position_to, region_fields + " the field positionFrom may not be greater than positionTo")
+      const std::optional<uint32_t> own_at_least = field("atLeast", false, 0, UINT32_MAX, bound_form);
+      const std::optional<uint32_t> own_at_most = field("atMost", false, 0, UINT32_MAX, bound_form);
+      // a region's own bounds replace the action's: both of them, so that a region's bounds are read in one place
+      const bool own = own_at_least.has_value() || own_at_most.has_value();
+      CHECK_SILO_QUERY(
+         own || at_least.has_value() || at_most.has_value(),
+         region_name + " has no bound: at least one of the fields atLeast and atMost is required, in the region or in the action"
+      )
+      regions.push_back(
+         {name, position_from - 1u, position_to, (own ? own_at_least : at_least).value_or(0), (own ? own_at_most : at_most).value_or(UINT32_MAX)}
+      );
+   }
+   CHECK_SILO_QUERY(!regions.empty(), regions_form)
+   return std::make_unique<CellCountByRegion>(std::move(sequence_name), kinds_mask, std::move(regions));
 }
 
 }  // namespace silo::query_engine::actions

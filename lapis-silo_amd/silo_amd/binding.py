@@ -126,6 +126,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_distinct_select",
     "silo_gpu_distinct_count", "silo_gpu_distinct_classes", "silo_gpu_smallest_keys",
     "silo_gpu_row_cell_counts", "silo_gpu_store_row_cell_counts", "silo_gpu_bitset_from_cell_counts", "silo_gpu_cell_count_histogram",
+    "silo_gpu_region_cell_values", "silo_gpu_bitset_from_values", "silo_gpu_count_values",
 ]
 
 _lib = None
@@ -240,6 +241,9 @@ def load_library():
     lib.silo_gpu_store_row_cell_counts.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(vp), vp]
     lib.silo_gpu_bitset_from_cell_counts.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_cell_count_histogram.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_region_cell_values.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
+    lib.silo_gpu_bitset_from_values.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    lib.silo_gpu_count_values.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -1216,6 +1220,77 @@ def cell_count_histogram(parts, kinds_mask, bin_width, n_bins, initial=None, gua
             device_free(ptr)
 
 
+MAX_REGIONS = 256              # SILO_GPU_MAX_REGIONS: the regions of one silo_gpu_region_cell_values, the columns of one silo_gpu_count_values
+
+
+def region_value_scratch_bytes(positions):
+    """SILO_GPU_REGION_VALUE_SCRATCH_BYTES: the scratch silo_gpu_region_cell_values needs."""
+    return int(positions) * 7 + 8192
+
+
+def bitset_from_values_call(values_ptr, row_words, sequence_count, at_least, at_most, out_ptr, stream=None):
+    """silo_gpu_bitset_from_values (K23) on the caller's device buffers, waited for."""
+    lib = load_library()
+    _check(lib.silo_gpu_bitset_from_values(values_ptr, row_words, sequence_count, at_least, at_most, out_ptr, stream))
+    _check(lib.silo_gpu_stream_synchronize(stream))
+
+
+def bitset_from_values(values, row_words, sequence_count, at_least=0, at_most=0xFFFFFFFF, fill=None, stream=None, guard_words=0):
+    """silo_gpu_bitset_from_values (K23) over ONE host column uint32 [row_words * 64] as silo_gpu_region_cell_values leaves it:
+    bit r = r < sequence_count and at_least <= values[r] <= at_most.  Returns the row_words words the call writes, followed by
+    `guard_words` words behind them that it must not touch: those hold the byte `fill` repeated (the whole allocation is filled
+    with it before the launch), or whatever the allocation held."""
+    values = np.ascontiguousarray(values, dtype=np.uint32)
+    words = int(row_words) + int(guard_words)
+    values_dev = _upload(values, stream)
+    out = device_malloc(words * 8, fill, stream)
+    try:
+        bitset_from_values_call(values_dev, row_words, sequence_count, at_least, at_most, out, stream)
+        return device_read(out, np.uint64, words, stream)
+    finally:
+        device_free(values_dev)
+        device_free(out)
+
+
+def count_values_call(values_ptr, n_columns, row_words, sequence_count, filter_ptr, bounds, counts_ptr, stream=None):
+    """silo_gpu_count_values (K23) on the caller's device buffers, waited for.  bounds: host uint32 [n_columns][2], or None for NULL."""
+    lib = load_library()
+    if bounds is not None:
+        bounds = np.ascontiguousarray(bounds, dtype=np.uint32)
+    _check(lib.silo_gpu_count_values(values_ptr, n_columns, row_words, sequence_count, filter_ptr, None if bounds is None else _ptr(bounds), counts_ptr, stream))
+    _check(lib.silo_gpu_stream_synchronize(stream))
+
+
+def count_values(parts, bounds, initial=None, guard_words=4, fill=0xA5, stream=None):
+    """silo_gpu_count_values (K23), one call per part into ONE array of counts.  parts: a list of dicts {values: uint32 [n_columns]
+    [row_words * 64], row_words, sequence_count, filter: uint64 [row_words] or None (every row)}.  bounds: uint32 [n_columns][2] =
+    at least, at most.  initial: what the counts hold before the first call (uint64 [n_columns]; None = zeros).  Returns uint64
+    [n_columns + guard_words]: the counts, then `guard_words` words behind them that hold the byte `fill` repeated and that no call
+    may touch."""
+    lib = load_library()
+    bounds = np.ascontiguousarray(bounds, dtype=np.uint32).reshape(-1, 2)
+    n_columns = len(bounds)
+    start = np.zeros(n_columns, dtype=np.uint64) if initial is None else np.ascontiguousarray(initial, dtype=np.uint64)
+    counts = device_malloc((n_columns + int(guard_words)) * 8, fill, stream)
+    live = []
+    try:
+        if start.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(counts, _ptr(start), start.nbytes, stream))
+        for part in parts:
+            values_dev = _upload(np.ascontiguousarray(part["values"], dtype=np.uint32), stream)
+            live.append(values_dev)
+            filter_dev = None
+            if part.get("filter") is not None:
+                filter_dev = _upload(np.ascontiguousarray(part["filter"], dtype=np.uint64), stream)
+                live.append(filter_dev)
+            count_values_call(values_dev, n_columns, part["row_words"], part["sequence_count"], filter_dev, bounds, counts, stream)
+        return device_read(counts, np.uint64, n_columns + int(guard_words), stream)
+    finally:
+        device_free(counts)
+        for ptr in live:
+            device_free(ptr)
+
+
 ROW_HASH_NO_SYMBOL = 31        # SILO_GPU_ROW_HASH_NO_SYMBOL: a cell that nothing stored claims
 DISTINCT_EMPTY = 0xFFFFFFFF    # SILO_GPU_DISTINCT_EMPTY: a slot of the owner table without an owner
 DISTINCT_PART_DTYPE = np.dtype([("hashes_dev", np.uint64), ("first_row", np.uint32), ("sequence_count", np.uint32),
@@ -1864,6 +1939,25 @@ class GpuStore:
         out = ctypes.c_void_p()
         _check(self.lib.silo_gpu_store_row_cell_counts(self.handle, seqstore_id, ctypes.byref(out), stream))
         return out.value
+
+    def region_cell_values(self, seqstore_id, ranges, kinds_mask, fill=None, guard_rows=0, stream=None):
+        """silo_gpu_region_cell_values (K23) into columns for the call, filled with the byte `fill` before the launches so that a
+        test can see that every cell is written.  ranges: 0-based half-open [first, end), ascending and disjoint.  Returns uint32
+        [len(ranges) * row_words * 64 + guard_rows]: the columns region-major (reshape the first part to [len(ranges)][row_words *
+        64]), the last `guard_rows` cells untouched."""
+        ranges = np.ascontiguousarray(ranges, dtype=np.uint32).reshape(-1, 2)
+        cells = len(ranges) * self.row_words * 64 + int(guard_rows)
+        scratch = self.malloc(region_value_scratch_bytes(self.positions(seqstore_id)))
+        columns = self.malloc(max(4, 4 * cells))
+        try:
+            if fill is not None:
+                self.memset(columns, fill, max(4, 4 * cells), stream)
+            _check(self.lib.silo_gpu_region_cell_values(self.handle, seqstore_id, _ptr(ranges), len(ranges), kinds_mask, columns, scratch, stream))
+            self.synchronize(stream)
+            return self.read(columns, np.uint32, cells, stream)
+        finally:
+            self.free(scratch)
+            self.free(columns)
 
     def position_symbols(self, seqstore_id, positions, fill=None, guard_bytes=0, calls=1, null=(), n_positions=None, stream=None):
         """silo_gpu_position_symbols (K16).  positions: 0-based, any order, repeats allowed.  Returns (symbols uint8
