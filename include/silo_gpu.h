@@ -1200,6 +1200,42 @@ int silo_gpu_count_values(
    uint64_t* counts_dev, void* stream
 );
 
+/* ---- K24: pairwise sums of count tables (MeanDistances / AminoAcidMeanDistances) --------------------------
+ * Takes no store.  counts_dev is as for silo_gpu_mutations_compare: 1 <= n_tables <= SILO_GPU_MAX_PAIR_SUM_TABLES tables back to
+ * back, n_positions x n_symbols words each (n_symbols = 5 / 22), 4-byte aligned.  `ranges` (HOST memory, uint32 [n_ranges][2] =
+ * first, end, 0-based; read before the call returns): 1 <= n_ranges <= SILO_GPU_MAX_PAIR_SUM_RANGES ranges of positions, each
+ * non-empty with end <= n_positions, in any order; they may overlap.  With c[t][p][s] a cell and cov[t][p] = sum_s c[t][p][s] (a
+ * uint32: no wrap is defined), WRITES out_dev: for every range r and every pair of tables g <= h, in the order r, g, h, one record
+ * of SILO_GPU_PAIR_SUM_WORDS uint64 words, n_ranges * G (G + 1) / 2 records for G = n_tables, 8-byte aligned:
+ *     {diff_lo, diff_hi}   the 128-bit sum over the positions p of the range of
+ *                              g < h    cov[g][p] * cov[h][p] - sum_s c[g][p][s] * c[h][p][s]
+ *                              g == h   (cov[g][p]^2 - sum_s c[g][p][s]^2) / 2 (an integer: the unordered pairs of rows that differ)
+ *     {cmp_lo, cmp_hi}     the 128-bit sum of cov[g][p] * cov[h][p] for g < h, of cov[g][p] * (cov[g][p] - 1) / 2 for g == h
+ *     sites                g == h   the positions of the range where at least two symbols have a count above 0 (segregating sites)
+ *                          g < h    the positions where cov[g][p] * cov[h][p] > 0 and sum_s c[g][p][s] * c[h][p][s] == 0 (fixed
+ *                                   differences: both tables covered, no symbol in both)
+ * They are the sums, over every pair of a row of g and a row of h (for g == h: every unordered pair of two rows), of K10's
+ * `distance` and `compared` of the pair restricted to the range, when the tables are exact Mutations tables of the rows.
+ * Integers only.  A position's term fits 64 bits; a thread carries the high word of its sums itself and a block adds what it has
+ * with 64-bit integer atomics, one more on the high word where its add on the low word wrapped: exact, whatever the schedule.  The
+ * entry clears the records itself, on `stream`, so a second call gives the same bytes; the caller clears nothing.  One kernel
+ * launch: a block of 256 threads owns a tile of SILO_GPU_PAIR_SUM_TILE x SILO_GPU_PAIR_SUM_TILE pairs of the upper triangle and up to
+ * SILO_GPU_PAIR_SUM_CHUNK positions of one range, which it stages through LDS SILO_GPU_PAIR_SUM_POSITION_TILE positions at a time; the
+ * jobs (range, chunk, tile of pairs) of all ranges are one grid.  Returns without waiting.
+ * Fails with SILO_GPU_ERR_INVALID_ARGUMENT, nothing written, for an alphabet other than the two, a NULL pointer, tables that are not
+ * 4-byte or records that are not 8-byte aligned, n_tables == 0 or above the limit, n_ranges == 0 or above the limit, n_positions ==
+ * 0, a range that is empty or ends past n_positions, or more jobs than a grid holds (2^31 - 1). */
+#define SILO_GPU_MAX_PAIR_SUM_TABLES 64
+#define SILO_GPU_MAX_PAIR_SUM_RANGES 256
+#define SILO_GPU_PAIR_SUM_WORDS 5
+#define SILO_GPU_PAIR_SUM_TILE 16
+#define SILO_GPU_PAIR_SUM_POSITION_TILE 16
+#define SILO_GPU_PAIR_SUM_CHUNK 128
+int silo_gpu_table_pair_sums(
+   int alphabet, const uint32_t* counts_dev, uint32_t n_tables, uint32_t n_positions, const uint32_t* ranges, uint32_t n_ranges, uint64_t* out_dev,
+   void* stream
+);
+
 /* The same scan for a batch of filters over one sequence store: every plane row is read once for up to
  * SILO_GPU_MAX_SCAN_BATCH filters per pass (larger batches take several passes), counts_out_dev[q] is
  * accumulated with filters_dev[q].  This is how concurrent Mutations queries share the HBM stream. */

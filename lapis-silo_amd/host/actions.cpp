@@ -1,6 +1,6 @@
 // actions.cpp — Action base (ordering / limit / offset), Aggregated (count), Mutations<SymbolType> and parseAction.  The actions
-// that answer from a small count table (MutationsOverTime, QueriesOverTime, CrossTabulation, Consensus, MutationsComparison) are in
-// table_actions.cpp.
+// that answer from a small count table (MutationsOverTime, QueriesOverTime, CrossTabulation, Consensus, MutationsComparison,
+// MeanDistances) are in table_actions.cpp; the parser of MeanDistances is here.
 // Reference: src/silo/query_engine/actions/{action,aggregated,mutations}.cpp.
 #include <algorithm>
 #include <charconv>
@@ -840,6 +840,78 @@ std::optional<uint32_t> integerField(
    return value.as_uint32();
 }
 
+template <typename SymbolType>
+std::unique_ptr<Action> parseMeanDistances(const json::Value& json) {
+   using Distances = MeanDistances<SymbolType>;
+   const std::string action_name = Distances::actionName();
+   std::optional<std::string> sequence_name = optionalStringField(json, "sequenceName", action_name);
+   CHECK_SILO_QUERY(
+      (std::is_same_v<SymbolType, Nucleotide>) || sequence_name.has_value(), action_name + " action must contain the field sequenceName of type string (a gene)"
+   )
+   std::vector<typename Distances::Group> groups;
+   if (json.contains("groups")) {
+      CHECK_SILO_QUERY(json["groups"].is_array(), action_name + " action: the field groups, if present, must be an array of objects " + GROUP_ENTRY_FORM)
+      const size_t n_groups = json["groups"].items().size();
+      CHECK_SILO_QUERY(
+         n_groups <= Distances::MAX_GROUPS,
+         action_name + " action: the field groups holds " + std::to_string(n_groups) + " groups, more than the limit of " + std::to_string(Distances::MAX_GROUPS)
+      )
+      CHECK_SILO_QUERY(n_groups >= 1, action_name + " action: the field groups, if present, must hold at least one group")
+      for (auto& [group_name, filter] : parseGroupEntries(json["groups"], action_name)) {
+         groups.push_back({std::move(group_name), std::move(filter)});
+      }
+   } else {
+      groups.push_back({std::nullopt, nullptr});  // the query's filter alone
+   }
+   std::vector<typename Distances::Region> regions;
+   if (json.contains("regions")) {
+      const std::string regions_form =
+         action_name + " action: the field regions, if present, must be an array of 1 to " + std::to_string(Distances::MAX_REGIONS) + " objects";
+      const std::string position_form = "an integer from 1 to 2147483647";
+      CHECK_SILO_QUERY(json["regions"].is_array(), regions_form)
+      for (const json::Value& item : json["regions"].items()) {
+         CHECK_SILO_QUERY(item.is_object() && regions.size() < Distances::MAX_REGIONS, regions_form)
+         CHECK_SILO_QUERY(item.contains("name") && item["name"].is_string(), action_name + " action: every region must have the field name of type string")
+         const std::string& name = item["name"].as_string();
+         CHECK_SILO_QUERY(
+            std::none_of(regions.begin(), regions.end(), [&](const typename Distances::Region& other) { return other.name == name; }),
+            action_name + " action: the region '" + name + "' is listed more than once: the names of the regions must be distinct"
+         )
+         // (integerField words its complaints as "<name> action: the field ...": the region's name stands where the action's would)
+         const std::string region_fields = action_name + " action: the region '" + name + "':";
+         const auto position = [&](std::string_view key) {
+            CHECK_SILO_QUERY(item.contains(key), region_fields + " the field " + std::string(key) + " is required")
+            const json::Value& value = item[key];
+            CHECK_SILO_QUERY(
+               value.is_number_unsigned() && value.as_int64() >= 1 && value.as_int64() <= INT32_MAX,
+               region_fields + " the field " + std::string(key) + " must be " + position_form
+            )
+            return value.as_uint32();
+         };
+         const uint32_t position_from = position("positionFrom");
+         const uint32_t position_to = position("positionTo");
+         CHECK_SILO_QUERY(position_from <= position_to, region_fields + " the field positionFrom may not be greater than positionTo")
+         regions.push_back({name, position_from - 1u, position_to});
+      }
+      CHECK_SILO_QUERY(!regions.empty(), regions_form)
+   } else {
+      regions.push_back({std::nullopt, 0, 0});  // the whole sequence: its length is the database's to know
+   }
+   bool between = true;
+   if (json.contains("between")) {
+      CHECK_SILO_QUERY(json["between"].is_boolean(), action_name + " action: the field between, if present, must be of type boolean")
+      between = json["between"].as_bool();
+   }
+   const size_t rows_of_region = between ? groups.size() * (groups.size() + 1) / 2 : groups.size();
+   CHECK_SILO_QUERY(
+      regions.size() * rows_of_region <= Distances::MAX_ROWS,
+      action_name + " action: " + std::to_string(regions.size()) + " regions x " + std::to_string(rows_of_region) +
+         (between ? " pairs of groups are " : " groups are ") + std::to_string(regions.size() * rows_of_region) + " rows, more than the " +
+         std::to_string(Distances::MAX_ROWS) + " a response may hold"
+   )
+   return std::make_unique<Distances>(std::move(sequence_name), std::move(groups), std::move(regions), between);
+}
+
 namespace {
 
 std::vector<std::string> parseFieldList(const json::Value& json, std::string_view field) {
@@ -883,6 +955,8 @@ constexpr std::pair<std::string_view, ActionParser> ACTION_TYPES[] = {
    {"DistinctSequenceCounts", parseDistinctSequenceCounts},
    {"CellCountDistribution", parseCellCountDistribution},
    {"CellCountByRegion", parseCellCountByRegion},
+   {"MeanDistances", parseMeanDistances<Nucleotide>},
+   {"AminoAcidMeanDistances", parseMeanDistances<AminoAcid>},
 };
 
 }  // namespace

@@ -911,6 +911,14 @@ template <typename SymbolType>
 std::unique_ptr<Action> parseConsensus(const json::Value& json);
 template <typename SymbolType>
 std::unique_ptr<Action> parseMutationsComparison(const json::Value& json);
+/// The parser of the sums of pairwise distances within and between groups (actions.cpp; execute in table_actions.cpp).
+template <typename SymbolType>
+std::unique_ptr<Action> parseMeanDistances(const json::Value& json);
+/// An entry of a groups field (Consensus, MutationsComparison, MeanDistances) as the messages show it, and the entries of such a
+/// field (`list`, an array) in request order: objects with a string name that no entry before had and a filterExpression, whose own
+/// complaint comes behind the field and the group (table_actions.cpp).
+extern const std::string GROUP_ENTRY_FORM;
+std::vector<std::pair<std::string, std::unique_ptr<filter_expressions::Expression>>> parseGroupEntries(const json::Value& list, const std::string& action_name);
 /// The parsers of the sequence-comparing actions (distance_actions.cpp).
 std::unique_ptr<Action> parseDistanceMatrix(const json::Value& json);
 std::unique_ptr<Action> parseClusters(const json::Value& json);
@@ -1600,6 +1608,53 @@ class MutationsComparison : public Action {
    std::vector<Group> groups;
    double min_proportion;
    double min_difference;
+
+   void validateOrderByFields(const Database& database) const override;
+   [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;
+};
+
+/// MeanDistances / AminoAcidMeanDistances: the sums of DistanceMatrix's `distance` and `compared` (a position counts when both rows
+/// hold a valid mutation symbol) over every pair of rows within each and between every two of 1 .. MAX_GROUPS groups — the query's
+/// filter AND the group's own expression, per partition, as Consensus resolves them; without groups the filter alone — in each of
+/// 1 .. MAX_REGIONS named regions of one sequence store (without regions the whole sequence), for groups of any size: no row is
+/// compared with a row.  With c a cell of a group's Mutations table and cov the sum of the cells of its position, the pairs of a row
+/// of g and a row of h that differ at the position are cov_g cov_h - sum_s c_g c_h and those compared cov_g cov_h; within a group
+/// (cov^2 - sum_s c^2) / 2 and cov (cov - 1) / 2, the unordered pairs.  One row per region and pair g <= h (g == h only when
+/// `between` is false), in the order region, g, h of the request: region, positionFrom, positionTo (1-based, inclusive), sequenceName,
+/// group, otherGroup, count, otherCount, pairs (n_g n_h, or n (n - 1) / 2), differences, comparedPositions (the three as decimal
+/// strings: they pass 2^53), segregatingSites (g == h: positions with two symbols; else null), fixedDifferences (g < h: positions
+/// where both are covered and share no symbol; else null), meanDistance = differences / pairs, meanCompared = comparedPositions /
+/// pairs, distancePerSite = differences / comparedPositions (each the correctly rounded doubles of the integers, one IEEE division;
+/// null where the divisor is 0).  A row that lies in both g and h forms a pair with itself between them: distance 0, compared.  The
+/// exact Mutations scan of all groups into one table per group, as for Consensus; one call of K24 (silo_gpu_table_pair_sums) and one
+/// fetch of the records: the tables never leave the device.  Every record is checked before it becomes a row.  No counterpart in the
+/// reference.
+template <typename SymbolType>
+class MeanDistances : public Action {
+  public:
+   struct Group {
+      std::optional<std::string> name;                          // none: the one group of a request without groups
+      std::unique_ptr<filter_expressions::Expression> filter;  // null: the query's filter alone
+   };
+   struct Region {
+      std::optional<std::string> name;  // none: the one region of a request without regions, the whole sequence
+      uint32_t first = 0;               // 0-based
+      uint32_t end = 0;                 // past the last position; of the unnamed region: the sequence's length, known at execute
+   };
+   static constexpr uint32_t MAX_GROUPS = SILO_GPU_MAX_PAIR_SUM_TABLES;
+   static constexpr uint32_t MAX_REGIONS = SILO_GPU_MAX_PAIR_SUM_RANGES;
+   static constexpr size_t MAX_ROWS = 65536;       // of a response before limit and offset
+   static_assert(MAX_GROUPS <= MAX_LIVE_FILTERS);  // the bitsets of every group of a partition are alive at a time
+   static std::string actionName() { return std::is_same_v<SymbolType, Nucleotide> ? "MeanDistances" : "AminoAcidMeanDistances"; }
+
+   MeanDistances(std::optional<std::string> sequence_name, std::vector<Group> groups, std::vector<Region> regions, bool between)
+       : sequence_name(std::move(sequence_name)), groups(std::move(groups)), regions(std::move(regions)), between(between) {}
+
+  private:
+   std::optional<std::string> sequence_name;  // none: the default nucleotide sequence
+   std::vector<Group> groups;
+   std::vector<Region> regions;
+   bool between;
 
    void validateOrderByFields(const Database& database) const override;
    [[nodiscard]] QueryResult execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const override;

@@ -1,6 +1,7 @@
 // table_actions.cpp — the actions that answer from one small table of counts filled on the device: MutationsOverTime<SymbolType>
-// (K7), QueriesOverTime (K8) and CrossTabulation (K9), which fetch the table, and Consensus<SymbolType> (K15) and
-// MutationsComparison<SymbolType> (K17), which fetch what a last kernel makes of the tables of their groups, with their parsers.
+// (K7), QueriesOverTime (K8) and CrossTabulation (K9), which fetch the table, and Consensus<SymbolType> (K15),
+// MutationsComparison<SymbolType> (K17) and MeanDistances<SymbolType> (K24), which fetch what a last kernel makes of the tables of their
+// groups, with their parsers (that of MeanDistances: actions.cpp).
 // Each differs in the kernel call of a partition and in the rows it makes of the table; what stands around that — the refusals, the
 // date column, the table's life on the device, the evaluation of labelled sub-expressions, the tables of named groups and what has
 // to stay alive while launches run — is here once.
@@ -832,6 +833,142 @@ QueryResult MutationsComparison<SymbolType>::execute(const Database& database, s
 template class MutationsComparison<Nucleotide>;
 template class MutationsComparison<AminoAcid>;
 
+// ---- MeanDistances -------------------------------------------------------------------------------------------
+// The sums of the pairwise distances within and between up to 64 groups under the query's filter in up to 256 regions of a sequence,
+// from the exact Mutations scan of the groups and the sums over their tables on the device (K24).  No counterpart in the reference.
+namespace {
+
+using Wide = unsigned __int128;  // a sum over pairs of rows and positions: (2^32)^2 pairs x 2^32 positions
+
+std::string decimal(Wide value) {
+   std::string digits;
+   do {
+      digits.push_back(static_cast<char>('0' + static_cast<int>(value % 10)));
+      value /= 10;
+   } while (value != 0);
+   return {digits.rbegin(), digits.rend()};
+}
+
+/// One IEEE division of the correctly rounded doubles of the two integers; null where the divisor is 0.
+JsonValue ratio(Wide dividend, Wide divisor) {
+   if (divisor == 0) {
+      return std::nullopt;
+   }
+   return static_cast<double>(dividend) / static_cast<double>(divisor);
+}
+
+}  // namespace
+
+template <typename SymbolType>
+void MeanDistances<SymbolType>::validateOrderByFields(const Database& /*database*/) const {
+   checkOrderByFields({"region", "positionFrom", "positionTo", "group", "otherGroup", "count", "otherCount", "segregatingSites", "fixedDifferences",
+                       "meanDistance", "meanCompared", "distancePerSite"});
+}
+
+template <typename SymbolType>
+QueryResult MeanDistances<SymbolType>::execute(const Database& database, std::vector<OperatorResult> bitmap_filter) const {
+   const std::string action_name = actionName();
+   requireUnsharded(database, action_name);
+   const auto [name, store] = sequenceStoreOf<SymbolType>(
+      database, sequence_name, "Database does not contain the " + std::string(SymbolType::SYMBOL_NAME_LOWER_CASE) + " sequence with name: "
+   );
+   constexpr size_t record_words = SILO_GPU_PAIR_SUM_WORDS;
+   const auto positions = static_cast<uint32_t>(store.reference_sequence.size());
+   const auto n_groups = static_cast<uint32_t>(groups.size());
+   const size_t n_pairs = static_cast<size_t>(n_groups) * (n_groups + 1) / 2;
+   std::vector<uint32_t> ranges;  // {first, end} of every region, as K24 takes them
+   for (const Region& region : regions) {
+      const uint32_t end = region.name.has_value() ? region.end : positions;
+      CHECK_SILO_QUERY(
+         end <= positions, action_name + ": the region '" + region.name.value_or("") + "': positionTo " + std::to_string(end) +
+                              " is past the end of the sequence '" + name + "' (" + std::to_string(positions) + " positions)"
+      )
+      ranges.insert(ranges.end(), {region.first, end});
+   }
+   std::vector<GroupFilter> group_filters;
+   for (const Group& group : groups) {
+      group_filters.push_back({group.name.value_or(""), group.filter.get()});
+   }
+   // what groups that nobody scanned get: no pair compared anywhere
+   std::vector<uint64_t> records(regions.size() * n_pairs * record_words, 0);
+   // nothing in here returns to the pool before the stream has been waited for: the launches read and write it
+   GroupTables tables;
+   DeviceBuffer device_records;
+   launchAndWait([&] {
+      fillGroupTables<SymbolType>(database, bitmap_filter, name, group_filters, action_name, tables);
+      if (tables.tables) {
+         device_records = database.partitions.front().pool.acquire(records.size() * sizeof(uint64_t));
+         checkGpu(
+            silo_gpu_table_pair_sums(
+               SymbolType::ABI_ALPHABET, tables.tables.as<uint32_t>(), n_groups, positions, ranges.data(), static_cast<uint32_t>(regions.size()),
+               device_records.as<uint64_t>(), queryStream()
+            ),
+            "silo_gpu_table_pair_sums"
+         );
+         const HostFetch fetch(device_records.get(), records.size() * sizeof(uint64_t), queryStream());
+         std::memcpy(records.data(), fetch.wait(), records.size() * sizeof(uint64_t));
+      }
+   });
+   const std::vector<uint32_t>& group_rows = tables.group_rows;
+
+   // what came off the device is checked before it becomes a row: no more differing pairs than compared ones, no more compared ones
+   // than pairs of rows and positions, no more sites than positions
+   const auto broken = [&](const std::string& what) { return std::runtime_error(action_name + ": the device delivered " + what); };
+   const auto nameOf = [](const Group& group) { return group.name.has_value() ? JsonValue{*group.name} : JsonValue{std::nullopt}; };
+   QueryResult results;
+   results.query_result.reserve(regions.size() * (between ? n_pairs : n_groups));
+   for (size_t r = 0; r < regions.size(); ++r) {
+      const uint32_t first = ranges[2 * r];
+      const uint32_t length = ranges[2 * r + 1] - first;
+      const uint64_t* of_region = records.data() + r * n_pairs * record_words;
+      for (uint32_t g = 0; g < n_groups; ++g) {
+         for (uint32_t h = g; h < n_groups; ++h, of_region += record_words) {
+            if (g != h && !between) {
+               continue;
+            }
+            const Wide differences = (static_cast<Wide>(of_region[1]) << 64) | of_region[0];
+            const Wide compared = (static_cast<Wide>(of_region[3]) << 64) | of_region[2];
+            const uint64_t sites = of_region[4];
+            const Wide pairs = g == h ? static_cast<Wide>(group_rows[g]) * (group_rows[g] == 0 ? 0 : group_rows[g] - 1) / 2
+                                      : static_cast<Wide>(group_rows[g]) * group_rows[h];
+            if (differences > compared) {
+               throw broken("more differing pairs than compared ones");
+            }
+            if (compared > pairs * length) {
+               throw broken("more compared pairs than there are pairs of rows and positions");
+            }
+            if (sites > length) {
+               throw broken("more sites than the region has positions");
+            }
+            if (compared == 0 && differences != 0) {
+               throw broken("differences where nothing was compared");
+            }
+            QueryResultEntry& entry = results.query_result.emplace_back();
+            entry.fields.emplace("region", regions[r].name.has_value() ? JsonValue{*regions[r].name} : JsonValue{std::nullopt});
+            entry.fields.emplace("positionFrom", static_cast<int32_t>(first + 1u));
+            entry.fields.emplace("positionTo", static_cast<int32_t>(first + length));
+            entry.fields.emplace("sequenceName", name);
+            entry.fields.emplace("group", nameOf(groups[g]));
+            entry.fields.emplace("otherGroup", nameOf(groups[h]));
+            entry.fields.emplace("count", static_cast<int32_t>(group_rows[g]));
+            entry.fields.emplace("otherCount", static_cast<int32_t>(group_rows[h]));
+            entry.fields.emplace("pairs", decimal(pairs));
+            entry.fields.emplace("differences", decimal(differences));
+            entry.fields.emplace("comparedPositions", decimal(compared));
+            entry.fields.emplace("segregatingSites", g == h ? JsonValue{static_cast<int32_t>(sites)} : JsonValue{std::nullopt});
+            entry.fields.emplace("fixedDifferences", g != h ? JsonValue{static_cast<int32_t>(sites)} : JsonValue{std::nullopt});
+            entry.fields.emplace("meanDistance", ratio(differences, pairs));
+            entry.fields.emplace("meanCompared", ratio(compared, pairs));
+            entry.fields.emplace("distancePerSite", ratio(differences, compared));
+         }
+      }
+   }
+   return results;
+}
+
+template class MeanDistances<Nucleotide>;
+template class MeanDistances<AminoAcid>;
+
 // ---- JSON -> the three actions ---------------------------------------------------------------------------
 namespace {
 
@@ -954,7 +1091,9 @@ struct DistinctFilters {
    }
 };
 
-/// An entry of the groups field of Consensus and MutationsComparison, as the messages show it.
+}  // namespace
+
+/// An entry of the groups field of Consensus, MutationsComparison and MeanDistances, as the messages show it.
 const std::string GROUP_ENTRY_FORM = "{\"name\": string, \"filterExpression\": filter expression}";
 
 /// The entries of a groups field (`list`, an array) in request order: objects with a string name that no entry before had and a
@@ -979,8 +1118,6 @@ std::vector<std::pair<std::string, std::unique_ptr<filter_expressions::Expressio
    }
    return groups;
 }
-
-}  // namespace
 
 template <typename SymbolType>
 std::unique_ptr<Action> parseMutationsOverTime(const json::Value& json) {

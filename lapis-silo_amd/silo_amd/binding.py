@@ -127,6 +127,7 @@ EXPORTED_SYMBOLS = [
     "silo_gpu_distinct_count", "silo_gpu_distinct_classes", "silo_gpu_smallest_keys",
     "silo_gpu_row_cell_counts", "silo_gpu_store_row_cell_counts", "silo_gpu_bitset_from_cell_counts", "silo_gpu_cell_count_histogram",
     "silo_gpu_region_cell_values", "silo_gpu_bitset_from_values", "silo_gpu_count_values",
+    "silo_gpu_table_pair_sums",
 ]
 
 _lib = None
@@ -244,6 +245,7 @@ def load_library():
     lib.silo_gpu_region_cell_values.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
     lib.silo_gpu_bitset_from_values.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_count_values.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
+    lib.silo_gpu_table_pair_sums.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp]
     lib.silo_gpu_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
     lib.silo_gpu_upload_column.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]
     lib.silo_gpu_bitset_from_compare.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -885,6 +887,44 @@ def mutations_compare(alphabet_id, counts, reference_index, min_proportion, min_
         return device_read(out, np.uint32, words, stream), status
     finally:
         for ptr in (counts_dev, reference_dev, out):
+            device_free(ptr)
+
+
+MAX_PAIR_SUM_TABLES = 64       # SILO_GPU_MAX_PAIR_SUM_TABLES: the count tables (groups) of one silo_gpu_table_pair_sums
+MAX_PAIR_SUM_RANGES = 256      # SILO_GPU_MAX_PAIR_SUM_RANGES: its ranges of positions
+PAIR_SUM_WORDS = 5             # SILO_GPU_PAIR_SUM_WORDS: uint64 words of a record: diff_lo, diff_hi, cmp_lo, cmp_hi, sites
+PAIR_SUM_TILE = 16             # SILO_GPU_PAIR_SUM_TILE: a block of K24 owns a tile of 16 x 16 pairs of tables
+PAIR_SUM_POSITION_TILE = 16    # SILO_GPU_PAIR_SUM_POSITION_TILE: the positions it stages through LDS at a time
+PAIR_SUM_CHUNK = 128           # SILO_GPU_PAIR_SUM_CHUNK: the positions of a range that a block owns
+
+
+def table_pair_sums(alphabet_id, counts, ranges, fill=None, guard_bytes=0, calls=1, null=(), n_tables=None, n_positions=None, n_ranges=None, stream=None):
+    """silo_gpu_table_pair_sums (K24) over host counts uint32 [n_tables][n_positions][n_symbols] and ranges [n_ranges][2] (0-based
+    first, end): (out uint64 [n_ranges * G (G + 1) / 2 * 5 + guard_bytes / 8], the status of the last call).  The output is filled
+    with the byte `fill` before the first of `calls` launches, so a test can see what is written, that nothing behind it is, and that
+    a second call gives the same bytes.  A status other than 0 is returned, not raised: the refusals leave the output as it was.
+    null: which of "counts", "ranges", "out" the call gets as NULL.  n_tables / n_positions / n_ranges: what the call is told instead
+    of what there is (fewer, or a number the call refuses)."""
+    lib = load_library()
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    tables, positions = counts.shape[:2]
+    ranges = np.ascontiguousarray(ranges, dtype=np.uint32).reshape(-1, 2)
+    words = len(ranges) * (tables * (tables + 1) // 2) * PAIR_SUM_WORDS + int(guard_bytes) // 8
+    counts_dev = device_malloc(max(counts.nbytes, 4))
+    out = device_malloc(max(words, 1) * 8, fill, stream)
+    try:
+        if counts.nbytes:
+            _check(lib.silo_gpu_memcpy_h2d(counts_dev, _ptr(counts), counts.nbytes, stream))
+        status = 0
+        for _ in range(calls):
+            status = lib.silo_gpu_table_pair_sums(
+                _abi_alphabet(alphabet_id), None if "counts" in null else counts_dev, tables if n_tables is None else int(n_tables),
+                positions if n_positions is None else int(n_positions), None if "ranges" in null or not len(ranges) else _ptr(ranges),
+                len(ranges) if n_ranges is None else int(n_ranges), None if "out" in null else out, stream)
+        _check(lib.silo_gpu_stream_synchronize(stream))
+        return device_read(out, np.uint64, words, stream), status
+    finally:
+        for ptr in (counts_dev, out):
             device_free(ptr)
 
 
